@@ -45,6 +45,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
   per_rank      (N > 1) every rank's own ms/step and its wait at the closing barrier
   rccl          backend, world size, every rank's device index
 --launch graph replays the step as one captured hipGraph (single GPU; pays below ~500 graphs per step).
+--dump-outputs DIR writes what the last timed step returned (logits, mask, gate; rank 0's gathered rows with N > 1) as
+DIR/<name>.npy, float32 / float64, <= 64 MB in all: inputs, weights and sampler noise are seeded, so two builds run with
+the same flags can be compared output for output.
 """
 from __future__ import annotations
 
@@ -106,7 +109,13 @@ def parse(argv=None):
                     help="A/B: lin_edge as its own GEMM + the message-passing kernel streaming e_proj (the round-1 boundary)")
     ap.add_argument("--features", choices=["fp32", "fp16"], default=None,
                     help="storage of the projected rows (default: fp32; fp16 with --workload cfg5 = BASELINE configs[4]'s storage)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (logits, mask, gate; with N > 1 also "
+                         "the gathered rows rank 0 received) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a "
+                         "seeded row sample beyond that): two builds run with the same flags can be compared output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.graphs is None:
         args.graphs = 4096 if args.workload == "cfg2" else 2048
     if args.features is None:
@@ -731,6 +740,35 @@ def cfg5_leg(dev, graphs: int = 2048, steps: int = 10):
             "imbalance_world8_max_over_mean": imb, "steps": steps, "fp32_rows": fp32_rows}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6 - 64 * 1024       # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES, seed: int = 0) -> dict:
+    """Write `arrays` (name -> tensor) as out_dir/<name>.npy: float64 and 32 / 64-bit integer tensors as float64 (exact), every
+    other dtype as float32.  Beyond `budget` bytes in all, every array of more than one row keeps the same fraction of its rows,
+    drawn by a generator seeded with `seed` and kept in order (the same shapes give the same rows in every run).  Returns
+    {name: {"shape", "dtype", "rows_kept"}} of what was written."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)
+        host[name] = t.to(torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, budget / max(total, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in host.items():
+        shape = list(a.shape)
+        if frac < 1.0 and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * frac))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": shape, "dtype": str(a.dtype), "rows_kept": int(a.shape[0]) if a.ndim else None}
+    return info
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
@@ -791,7 +829,7 @@ def main(argv=None):
 
     def step(i: int):
         logits, mask, gate = model(wl, seed=1000 + i, use_hints=not args.no_hints)   # in-kernel Philox noise
-        return pipe.submit(i, logits)
+        return pipe.submit(i, logits), (logits, mask, gate)
 
     def fence():
         drain()
@@ -814,17 +852,18 @@ def main(argv=None):
             cap["plan"] = ops.GraphPlan.build(wl.batch, wl.edge_index, num_graphs=cfg.num_graphs,
                                               max_nodes=wl.max_nodes, max_edges=wl.max_edges)
             noises = {i: _syn.gumbel_noise((cfg.num_graphs, wl.max_nodes), dev) for i in noise_layers}
-            return model(wl, noises=noises, plan=cap["plan"])[0]
+            return model(wl, noises=noises, plan=cap["plan"])
 
     with torch.no_grad():
         if args.launch == "graph":
             for i in range(max(args.warmup, 2)):      # eager: kernel attributes, weight planes, allocator pools, hint check
-                out = body()
+                out = body()[0]
             ops.check_plans()
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = body()
+                last = body()                         # the graph's static outputs: every replay rewrites them
+            out = last[0]
             graph.replay()
             fence()
             progress("step captured as a hipGraph")
@@ -851,7 +890,7 @@ def main(argv=None):
             ops.MP_TIMER = ops.KernelTimer()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                out = step(args.warmup + i)
+                out, last = step(args.warmup + i)
             t_issue = time.perf_counter() - t0      # every step launched; the last all-gather is still in flight
             drain()
             torch.cuda.synchronize()
@@ -861,6 +900,13 @@ def main(argv=None):
             timer, ops.MP_TIMER = ops.MP_TIMER, None
             step_counters = {k: round(v / max(args.steps, 1), 3) for k, v in ops.counters().items()}
     assert torch.isfinite(out).all()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {k: v for k, v in zip(("logits", "mask", "gate"), last) if v is not None}
+        if pipe.active:         # N > 1: what rank 0 received from every rank, shards' padding rows trimmed
+            arrays["gathered_" + args.gather] = torch.cat(pipe.rows(out))
+        dumped = dump_outputs(args.dump_outputs, arrays)
+        progress(f"last timed step's outputs written to {args.dump_outputs}: {dumped}")
 
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
@@ -1017,6 +1063,8 @@ def main(argv=None):
             res["roofline"]["parts"] = parts
             res["roofline"]["unfused_kernel"] = unfused
         res["rccl"] = rccl
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if per_rank is not None:
             res["per_rank"] = per_rank
         # launches per step that left this library's dense kernels (hipBLASLt / torch LayerNorm / torch attention) and extra

@@ -204,3 +204,34 @@ def test_cfg5_workload_lines_name_configs4_and_carry_the_partition():
     assert (args.graphs, args.features) == (2048, "fp16")
     args = bench.parse([])
     assert (args.graphs, args.features, args.workload) == (4096, "fp32", "cfg2")
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows_within_the_budget(tmp_path):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32 (float64 for 64-bit values), whole when it fits; beyond the
+    budget every array keeps the same seeded rows, so two runs (two builds) write the same sample."""
+    import numpy as np
+    import torch
+    import bench
+    logits, mask, ids = torch.randn(300, 7), torch.rand(300) > 0.5, torch.arange(300)
+    info = bench.dump_outputs(str(tmp_path / "all"), {"logits": logits, "mask": mask, "ids": ids})
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in info}
+    assert got["logits"].dtype == np.float32 and np.array_equal(got["logits"], logits.numpy())
+    assert got["mask"].dtype == np.float32 and np.array_equal(got["mask"], mask.float().numpy())
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], ids.double().numpy())
+    budget = 4000
+    for d in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / d), {"logits": logits, "ids": ids}, budget=budget)
+        assert info["logits"]["shape"] == [300, 7] and 0 < info["logits"]["rows_kept"] < 300
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("logits", "ids")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("logits", "ids")}
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    rows = a["ids"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a["logits"], logits.numpy()[rows])
+
+
+def test_steps_sets_the_timed_steps_and_must_be_positive():
+    import bench
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

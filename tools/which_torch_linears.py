@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isubgvqa_amd import ops, synthetic
 from isubgvqa_amd.models import build_model
 dev = torch.device("cuda:0")
