@@ -512,7 +512,7 @@ int isg_linear_bf16x6(const float *a, const uint16_t *w_planes, const float *bia
 
 /* The same Linear for SMALL M (a handful of questions per forward: run_token_coo.py:49-79 evaluates one), where the tile kernels
  * are bound by the latency of their serial k loop (20-36 us per launch whatever the size): the reduction is split over the eight
- * waves of a workgroup, operands go from memory straight into TRUE fp32 MFMAs (v_mfma_f32_32x32x2_f32; no planes, no row scales,
+ * waves of a workgroup, operands go from memory straight into TRUE fp32 MFMAs (v_mfma_f32_16x16x4_f32 on 16 x 16 tiles; no planes, no row scales,
  * no weight preparation), the eight partial tiles are added in wave order -- a row's bits depend on K alone, not on the batch.
  * a fp32 [M,K] (row stride lda); w fp32 [N,K] in torch's Linear layout (row stride ldw); bias fp32 [N] or NULL; d fp32 (row
  * stride ldd); act 0 none, 1 exact GELU, 2 ReLU.  ISG_EUNSUPPORTED unless 4 | K, 4 | lda, 4 | ldw, a and w 16-byte aligned.

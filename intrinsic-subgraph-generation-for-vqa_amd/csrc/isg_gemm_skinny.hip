@@ -94,7 +94,7 @@ __global__ __launch_bounds__(SK_THREADS) void linear_skinny_kernel(const float *
 using namespace isg;
 
 // d[M,N] = act(a[M,K] @ w[N,K]^T + bias), all fp32, w in torch's Linear layout (row stride ldw): see the file header.
-// act 0 none, 1 exact GELU, 2 ReLU.  ISG_EUNSUPPORTED unless 4 | K, 4 | lda, 4 | ldw, a and w 16-byte aligned, M <= 65535 x 32 rows (grid.y).
+// act 0 none, 1 exact GELU, 2 ReLU.  ISG_EUNSUPPORTED unless 4 | K, 4 | lda, 4 | ldw, a and w 16-byte aligned, M <= 65535 x 16 rows (grid.y).
 extern "C" int isg_linear_skinny(const float *a, int32_t lda, const float *w, int32_t ldw, const float *bias, float *d, int32_t ldd,
                                  int64_t M, int32_t N, int32_t K, int32_t act, void *stream) {
   if (M < 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldd < N || act < 0 || act > 2) return ISG_EINVAL;

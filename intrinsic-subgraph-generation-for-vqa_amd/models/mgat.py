@@ -70,7 +70,7 @@ class MGAT(torch.nn.Module):
             return False
         lin, act = seq[0], seq[1]
         return (isinstance(lin, torch.nn.Linear) and isinstance(act, torch.nn.GELU) and act.approximate == "none" and
-                ops.MP_PLANES and ops.h3p_supported(rows, lin.weight.size(0), lin.weight.size(1)))
+                ops.MP_PLANES and ops.reads_planes32(rows, *lin.weight.shape))
 
     def on_tiles(self, plan, in_channels: int, edge_attr) -> bool:
         """Will forward() run its convolutions on the graph-tile kernels for this batch?  (Then a model may send the graphs

@@ -76,17 +76,18 @@ class _MetaLayer(torch.nn.Module):
         w_e = ops.derived_weight("sg_e", (nm[0].weight,), lambda: nm[0].weight[:, nf:].contiguous())
         row, col = edge_index[0].contiguous(), edge_index[1].contiguous()
         P = ops.linear(x, w_nodes, None)                                   # [N, 3C]: W_a x | W_b x | W_x x
-        # [V, C]: W_c emb -- a function of the parameters alone: made once per (weights, switches), not once per forward (it was a
-        # 20 us launch of every forward: 2.5 % of a single question's GPU time)
-        table = ops.derived_weight(("sg_table", hash(ops.CFG)), (embedding.weight, em[0].weight),
+        # [V, C]: W_c emb -- a function of the parameters and of the kernel its Linear runs on alone: made once per (weights,
+        # route), not once per forward (it was a 20 us launch of every forward: 2.5 % of a single question's GPU time)
+        route = ops.linear_route(embedding.weight.size(0), *w_tok.shape)
+        table = ops.derived_weight(("sg_table", route), (embedding.weight, em[0].weight),
                                    lambda: ops.linear(embedding.weight.detach(), w_tok, None))
         E = row.numel()
-        po = ops.GATHER_ADD_PLANES and ops.h3p_supported(E, em[2].weight.size(0), C)   # the Linear behind a gather-add runs on the planes32
+        po = ops.GATHER_ADD_PLANES and ops.reads_planes32(E, em[2].weight.size(0), C)   # the Linear behind a gather-add runs on the planes32
         h = ops.gather_add(P[:, :C], row, P[:, C:2 * C], col, table, edge_tokens, edge_sign, bias=em[0].bias, gelu=True,
                            planes_out=po)                                  # engine: its operand leaves the gather-add as planes
         e_new = ops.linear(h, em[2].weight, em[2].bias)                    # :119-120 second layer
         g = ops.linear(e_new, w_e, None)                                   # W_e e'
-        po = ops.GATHER_ADD_PLANES and ops.h3p_supported(E, nm[2].weight.size(0), nm[2].weight.size(1))
+        po = ops.GATHER_ADD_PLANES and ops.reads_planes32(E, *nm[2].weight.shape)
         h = ops.gather_add(P[:, 2 * C:], row, D=g, bias=nm[0].bias, gelu=True, planes_out=po)
         m = ops.linear(h, nm[2].weight, nm[2].bias)                        # :139-140
         agg = ops.scatter_mean(m, plan)                                    # :141

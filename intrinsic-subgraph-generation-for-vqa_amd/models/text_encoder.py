@@ -60,7 +60,7 @@ def _attention(mha: torch.nn.MultiheadAttention, x_q: Tensor, x_kv: Tensor, B: i
         kv = ops.linear(x_kv, wkv, bkv)                                          # [S*B, 2D]
         k, v = kv[:, :D], kv[:, D:]
     Tq, Tk, H = q.size(0) // B, k.size(0) // B, mha.num_heads
-    if ops.mha_rows_supported(Tq, Tk, H, D // H) and ops.h3p_supported(q.size(0), mha.out_proj.weight.size(0), D):
+    if ops.mha_rows_supported(Tq, Tk, H, D // H) and ops.reads_planes32(q.size(0), mha.out_proj.weight.size(0), D):
         att = ops.mha_small(q, k, v, B, H, key_bias, planes_out=True)            # out_proj's operand leaves the kernel as planes32
     else:
         att = ops.mha_small(q, k, v, B, H, key_bias, want_rowmax=True)           # + max |att| per (row, head)
@@ -76,8 +76,7 @@ def _ln(norm: torch.nn.LayerNorm, x: Tensor, residual: Tensor = None) -> Tensor:
 def _ffn(layer, x: Tensor) -> Tensor:
     # ReLU is the layers' default activation; linear1's epilogue leaves one maximum per 32 columns for linear2's K-chunks
     w1, w2 = layer.linear1.weight, layer.linear2.weight
-    if (ops.H3P_CHAIN and ops.h3p_supported(x.size(0), w1.size(0), w1.size(1)) and ops.h3p_supported(x.size(0), w2.size(0), w2.size(1))
-            and w1.size(0) % 32 == 0):
+    if ops.H3P_CHAIN and ops.reads_planes32(x.size(0), *w1.shape) and ops.reads_planes32(x.size(0), *w2.shape) and w1.size(0) % 32 == 0:
         # the 2048-wide intermediate never exists as fp32 rows: linear1's epilogue writes it as the planes linear2 reads
         h = ops.linear_h3p(x, w1, layer.linear1.bias, relu=True, planes_out=True)
         return ops.linear_h3p(h, w2, layer.linear2.bias)

@@ -32,48 +32,60 @@ MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 # written in place -- and `ops.SPLIT_FORWARD` reads the field; `with ops.configured(split_forward=False): ...` restores it.
 @dataclasses.dataclass(frozen=True)
 class Switches:
-    plan_fused: bool = True
-    bounds_to_host: bool = True
-    mixed_dispatch: bool = True
-    mixed_max_fraction: float = 0.12
+    # graph plan
+    plan_fused: bool = True                # isg_graph_plan_build (6 launches) instead of isg_graph_ptr + isg_csr_build + isg_graph_edge_ptr (14)
+    bounds_to_host: bool = True            # isg_graph_plan_build writes the batch's true bounds into pinned host memory (hint check without a copy)
+    # graphs beyond a tile
+    mixed_dispatch: bool = True            # graphs beyond a tile go to the per-graph kernels, the rest of the batch stays on the tile kernels ...
+    mixed_max_fraction: float = 0.12       # ... while at most this share of the batch's nodes sits in such graphs ...
+    # ... and the batch has at least this many nodes: the big graphs are a chain of ~60 launches of a workgroup or a few each, ~1.8 ms of
+    # HOST time per step whatever the batch.  Measured (profiles/r04_az_split_forward.txt), 4096 graphs + 1 / 8 / 64 big ones:
+    # 1.84-1.91 / 2.00 / 2.12 ms (run_split, sub-batch on its own stream) against 2.35 / 2.49 / 2.63 ms with the per-graph kernels for
+    # everything (1.43 ms without big graphs); 1024 graphs + 1: 1.83 vs 0.89 ms.  Tests and tools lower both to force the mode.
     mixed_min_nodes: int = 60000
-    mp_kernel: str = "graph"
-    fuse_logits: bool = True
-    fuse_logits_wide: bool = True          # ... also at head dimensions / edge widths beyond the tile shapes (C = 300, K = 300: round 5)
-    fuse_tile_conv: bool = True
-    fuse_layer_conv: bool = True
-    split_stream: bool = True
-    split_forward: bool = True
-    fuse_gate: bool = True
-    fuse_dense_tail: bool = True
-    dense_tail_rows: int = 64
-    fuse_readout: bool = True
-    gemm_backend: str = "bf16x6"
-    gemm_kernel: str = "auto"
-    panel_min_n: int = 256
-    embedding_sum: bool = True
-    ln_planes: bool = True
-    mp_planes: bool = True
-    gather_add_planes: bool = True
-    linear_multi: bool = True
-    tile_heavy_first: bool = True
-    mha_rows_planes: bool = True
-    mha_rows_max_tq: int = 16
-
-    f16x3_f16_out: bool = True
-    f16x3_tile: bool = True
-    gemm_f16x3: bool = True
-    h3p: bool = True
-    h3p_min_k: int = 256
-    h3p_chain: bool = True
+    split_stream: bool = True              # run_split's sub-batch on a stream of its own, beside the whole batch's tile kernels
+    split_forward: bool = True             # the graphs beyond a tile run as a batch of their own through the WHOLE model (off: every tile
+                                           # kernel's wrapper fills their rows with the per-graph kernels, layer by layer)
+    # message passing
+    mp_kernel: str = "graph"               # "graph": per-graph LDS-resident kernel; "chunk": node-chunk kernel
+    fuse_logits: bool = True               # lin_edge folded into the attention logits (isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits)
+    fuse_logits_wide: bool = True          # ... also at head dimensions / edge widths beyond the tile shapes (C = 300, K = 300)
+    rows_kernel_min_edges: int = 16384     # below this many edges a wide layer (C = 300 / K = 300) projects its edge rows and runs un-fused
+    fuse_tile_conv: bool = True            # message + softmax + aggregation with lin_edge inside as one launch on graph tiles (isg_gatv2_tile_conv)
+    fuse_layer_conv: bool = True           # ... and lin_l | lin_r inside as well (isg_gatv2_layer_conv): x_l / x_r never exist in memory
+    tile_heavy_first: bool = True          # persistent tile kernels walk the tile list heavy tiles first
+    fuse_gate: bool = True                 # the masked layer's node gate from the layer input's planes, node_nn inside
+    fuse_dense_tail: bool = True           # x_proj + layer tail + next instruction gate as one kernel on graph-aligned tiles
+    dense_tail_rows: int = 64              # nodes per tile of isg_mgat_dense_tail
+    fuse_readout: bool = True              # node_nn + mask + per-graph softmax pooling as one launch on graph-aligned tiles
+    embedding_sum: bool = True             # sum of a node's token embeddings through isg_gather_add instead of gather + reduce
+    # dense projections: which kernel runs a Linear (linear_route)
+    gemm_backend: str = "bf16x6"           # "bf16x6": this library's kernels; "torch": hipBLASLt fp32 through torch
+    gemm_kernel: str = "auto"              # "auto": per shape (linear_route); "panel": isg_linear_panel; "tile": isg_linear_bf16x6
+    panel_min_n: int = 256                 # narrowest Linear the row-panel kernels take
+    gemm_f16x3: bool = True                # K <= 128 panel shapes on the fp16 three-product kernel (isg_linear_f16x3) instead of bf16x6
+    f16x3_f16_out: bool = True             # half-row results (configs[4]) of K <= 128 panel Linears on isg_linear_f16x3_f16 instead of bf16x6
+    f16x3_tile: bool = True                # 128 < K Linears on isg_linear_f16x3_tile where the row maxima come cheap (linear_route)
+    skinny: bool = True                    # Linears over at most skinny_max_m rows (and M N K <= skinny_max_work) on isg_linear_skinny
+    skinny_max_m: int = 1024               # the latency-bound regime: a handful of questions per forward (csrc/isg_gemm_skinny.hip)
+    skinny_max_work: int = 1 << 30         # true fp32 MFMAs run at 1/16 of the fp16 rate: beyond ~1e9 multiply-adds the tile kernels win
+    linear_multi: bool = True              # the layers' bias-free projections of shared rows as one launch (isg_linear_panel_multi)
+    # the planes32 engine (isg_linear_h3p)
+    h3p: bool = True                       # Linears with K >= h3p_min_k over at least h3p_min_m rows on isg_linear_h3p
+    h3p_min_k: int = 256                   # shortest reduction the engine takes
+    # fewest rows the engine takes from a producer that left planes32.  8192 until round 6; swept with the small-batch kernels in place
+    # (tools/time_full_model.py G --set=H3P_MIN_M=...): 2048 is 5-7 % faster at 160-700 graphs
     h3p_min_m: int = 2048
-    h3p_min_m_unsplit: int = 8192
-    h3p_store_policy: int = -1
-    linear_multi_h3p: bool = True
-    skinny: bool = True
-    rows_kernel_min_edges: int = 16384
-    skinny_max_m: int = 1024
-    skinny_max_work: int = 1 << 30
+    h3p_min_m_unsplit: int = 8192          # fewest rows for an input without planes32 (the Linear pays a split pass of its own)
+    h3p_chain: bool = True                 # Linear -> Linear pairs (the Transformer layers' FFN, mlp) through planes: no fp32 intermediate
+    h3p_store_policy: int = -1             # store policy of large engine results: -1 library's / 0 plain / 1 nt / 2 sc0 sc1 nt / "auto" (_h3p_tune)
+    linear_multi_h3p: bool = True          # the layers' lin_edge over the shared edge features as one engine launch
+    ln_planes: bool = True                 # isg_add_layernorm writes its result as planes32 too where Linears on the engine read it
+    mp_planes: bool = True                 # the flat message-passing kernel hands x_proj.0 its operand as segmented planes32
+    gather_add_planes: bool = True         # isg_gather_add hands its rows to the Linear behind it as planes32
+    mha_rows_planes: bool = True           # attention results as planes32 where the all-heads form fits
+    mha_rows_max_tq: int = 16              # ... up to this many query rows per batch item
+
 
 CFG = Switches()
 _SWITCH_FIELDS = {f.name.upper(): f.name for f in dataclasses.fields(Switches)}
@@ -298,17 +310,6 @@ def _f32(t: Tensor) -> Tensor:
 # ------------------------------------------------------------------------------------------------
 # Graph plan
 # ------------------------------------------------------------------------------------------------
-# CFG.plan_fused (ops.PLAN_FUSED): isg_graph_plan_build (6 launches) instead of isg_graph_ptr + isg_csr_build + isg_graph_edge_ptr (14): A/B switch
-# CFG.bounds_to_host (ops.BOUNDS_TO_HOST): isg_graph_plan_build writes the batch's true bounds into pinned host memory (hint check without a copy)
-
-
-# CFG.mixed_dispatch (ops.MIXED_DISPATCH): graphs beyond a tile go to the per-graph kernels, the rest of the batch stays on the tile kernels
-# CFG.mixed_max_fraction (ops.MIXED_MAX_FRACTION): ... while at most this share of the batch's nodes sits in such graphs
-# CFG.mixed_min_nodes (ops.MIXED_MIN_NODES): ... and the batch is large: the big graphs are a chain of ~60 launches of a workgroup or a few each, ~1.8 ms
-                            # of HOST time per step whatever the batch.  Measured (profiles/r04_az_split_forward.txt), 4096
-                            # graphs + 1 / 8 / 64 big ones: 1.84-1.91 / 2.00 / 2.12 ms (run_split, sub-batch on its own stream)
-                            # against 2.35 / 2.49 / 2.63 ms with the per-graph kernels for everything (1.43 ms without big
-                            # graphs); 1024 graphs + 1: 1.83 vs 0.89 ms.  Tests and tools lower both to force the mode.
 
 
 class OversizeGraphs(NamedTuple):
@@ -739,9 +740,6 @@ def node_to_edge_mask(mask: Tensor, edge_index: Tensor, plan: Optional[GraphPlan
     return out.view(E, 1) if mask.dim() == 2 else out
 
 
-# CFG.mp_kernel (ops.MP_KERNEL): "graph": per-graph LDS-resident kernel; "chunk": node-chunk kernel (A/B switch for bench/tests)
-
-
 def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphPlan, heads: int,
              bias: Optional[Tensor] = None, node_mask: Optional[Tensor] = None, edge_mask: Optional[Tensor] = None,
              negative_slope: float = 0.2, kernel: Optional[str] = None, want_rowmax: bool = False,
@@ -837,7 +835,6 @@ def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphP
 
 
 # lin_edge folded into the attention logits (csrc/isg_mp_logits.hip): e_proj [E, H*C] is never written or read
-# CFG.fuse_logits (ops.FUSE_LOGITS): 
 GK_NCAP_L, GK_ECAP_L = 256, 1024      # the per-graph message-passing kernel's largest tables (csrc/isg_mp_graph.hip)
 
 
@@ -1112,7 +1109,6 @@ ISG_EUNSUPPORTED = -2      # include/isg.h
 
 # message + softmax + aggregation with lin_edge inside as ONE launch on graph-aligned tiles (csrc/isg_layer_tile.hip): the
 # head's x_l slice of a tile is staged once in LDS and serves the logit epilogue's row gathers and the aggregation
-# CFG.fuse_tile_conv (ops.FUSE_TILE_CONV): 
 TILE_CONV_NODES, TILE_CONV_EDGES = 64, 256
 
 
@@ -1122,9 +1118,6 @@ def tile_conv_supported(plan: "GraphPlan", heads: int, channels: int, edge_dim: 
     return (CFG.fuse_tile_conv and CFG.fuse_logits and CFG.gemm_backend == "bf16x6" and CFG.gemm_f16x3 and CFG.mp_kernel == "graph" and
             channels == 128 and 0 < edge_dim <= 128 and edge_dim % 4 == 0 and heads <= 64 and plan.B > 0 and
             plan.rowptr is not None and plan.E > 0 and plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) != "none")
-
-
-# CFG.fuse_layer_conv (ops.FUSE_LAYER_CONV): ... and lin_l | lin_r inside as well (csrc/isg_layer_conv.hip): x_l / x_r never exist in memory
 
 
 def layer_conv_supported(plan: "GraphPlan", heads: int, channels: int, in_channels: int, edge_dim: int) -> bool:
@@ -1180,7 +1173,6 @@ def _mixed_sub(plan: "GraphPlan") -> Optional["OversizeGraphs"]:
     return sub
 
 
-# CFG.split_stream (ops.SPLIT_STREAM): ... on a stream of its own, beside the whole batch's tile kernels (A/B switch)
 _side_streams: dict = {}
 
 
@@ -1189,10 +1181,6 @@ def _side_stream(device) -> "torch.cuda.Stream":
     if key not in _side_streams:
         _side_streams[key] = torch.cuda.Stream(device=device)
     return _side_streams[key]
-
-
-# CFG.split_forward (ops.SPLIT_FORWARD): "mixed" batches: the graphs beyond a tile run as a batch of their own through the WHOLE model (A/B switch;
-                          # off: every tile kernel's wrapper fills their rows with the per-graph kernels, layer by layer)
 
 
 def oversize_split(plan: "GraphPlan") -> Optional["OversizeGraphs"]:
@@ -1435,7 +1423,6 @@ def gatv2_tile_conv(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor,
     return out, alpha
 
 
-
 def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
                       plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
                       edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False):
@@ -1600,9 +1587,6 @@ def node_gate(xn: Tensor, q: Tensor, batch: Tensor, double_index: bool, plan: Op
                                  _chk(batch, "batch", torch.int64, (N,)), 1 if double_index else 0, gate.data_ptr(),
                                  N, C, _stream()), "isg_node_gate")
     return gate
-
-
-# CFG.fuse_gate (ops.FUSE_GATE): the masked layer's node gate from the layer input's planes, node_nn inside (A/B switch)
 
 
 def node_gate_planes_supported(node_nn: torch.nn.Sequential, q: Tensor) -> bool:
@@ -1800,10 +1784,6 @@ def mgat_layer_tail(ins: Tensor, c: Tensor, h: Tensor, plan: GraphPlan, weight: 
     return out
 
 
-# CFG.fuse_dense_tail (ops.FUSE_DENSE_TAIL): x_proj + layer tail + next instruction gate as one kernel on graph-aligned tiles (A/B switch)
-# CFG.dense_tail_rows (ops.DENSE_TAIL_ROWS): nodes per tile of isg_mgat_dense_tail
-
-
 def dense_tail_supported(plan: GraphPlan, x_proj: torch.nn.Sequential, width_in: int, channels: int) -> bool:
     """Shape test of isg_mgat_dense_tail (csrc/isg_layer_tile.hip): inference, fp32, Linear(512 -> 256) GELU Linear(256 ->
     128) GELU (MGAT at C = 128, H = 4: BASELINE configs[1]), every graph within one 64-node tile."""
@@ -1882,9 +1862,6 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
     return h_out, xg, xp
 
 
-# CFG.fuse_readout (ops.FUSE_READOUT): node_nn + mask + per-graph softmax pooling as one launch on graph-aligned tiles (A/B switch)
-
-
 def readout_tile_supported(plan: GraphPlan, node_nn: torch.nn.Sequential, width_in: int) -> bool:
     """Shape test of isg_readout_tile: inference, fp32, node_nn = Linear(128 -> 128) GELU Linear(128 -> 128), tiles of 64 nodes."""
     if not (CFG.fuse_readout and CFG.gemm_backend == "bf16x6" and CFG.gemm_f16x3) or torch.is_grad_enabled():
@@ -1952,47 +1929,29 @@ def global_attn_pool(xn: Tensor, q: Tensor, plan: GraphPlan, node_mask: Optional
 # ------------------------------------------------------------------------------------------------
 # Dense projections: fp32 accuracy on the bf16 matrix cores (csrc/isg_gemm.hip)
 # ------------------------------------------------------------------------------------------------
-# CFG.gemm_backend (ops.GEMM_BACKEND): "bf16x6": this library's kernels; "torch": hipBLASLt fp32 through torch (A/B switch)
-_PLANES = {}                 # (id(weight), layout) -> (weakref, version, data_ptr, planes): static weights are split once
-# CFG.f16x3_f16_out (ops.F16X3_F16_OUT): half-row results (configs[4]) of K <= 128 Linears on isg_linear_f16x3_f16 instead of the bf16 six-product
-                             # panel kernel (A/B switch)
-# CFG.gemm_kernel (ops.GEMM_KERNEL): "auto": per shape (below); "panel": isg_linear_panel; "tile": isg_linear_bf16x6 (A/B switch)
+_DERIVED = {}   # (tag, ids of the source tensors) -> ((weakref, version, data_ptr) per source, value, _Ready): tensors derived from parameters
 
 
-# CFG.f16x3_tile (ops.F16X3_TILE): ... and 128 < K <= 1024 when the producer of the input left its row maxima (isg_linear_f16x3_tile)
-# CFG.gemm_f16x3 (ops.GEMM_F16X3): K <= 128 panel shapes on the fp16 three-product kernel (isg_linear_f16x3) instead of bf16x6 (A/B switch)
-
-
-# CFG.panel_min_n (ops.PANEL_MIN_N): narrowest Linear the row-panel kernels take (A/B: tools/ab_step.py)
-
-
-def _use_panel(M: int, N: int, K: int) -> bool:
-    """The row-panel kernel wins where an A panel is split once and serves many columns (K <= 128: lin_edge 182 vs 212 us,
-    lin_l|lin_r 153 vs 166 us) and there are enough 64-row panels to fill the chip; the tile kernel elsewhere
-    (profiles/r02_a_gemm_structures.md)."""
-    if CFG.gemm_kernel != "auto":
-        return CFG.gemm_kernel == "panel"
-    return K <= 128 and N >= CFG.panel_min_n and M >= 32768
-
-
-_DERIVED = {}   # (tag, ids of the source tensors) -> (versions, weakrefs, value): weights re-laid-out once per model
-
-
-def derived_weight(tag: str, sources, build):
-    """Cache of tensors computed from static weights (slices, concatenations): rebuilt when a source was updated in place
-    (tensor._version / data_ptr) or replaced; invalidate_weight_cache() drops it."""
-    key = (tag,) + tuple(id(t) for t in sources)
-    ver = tuple((_ver(t), t.data_ptr()) for t in sources)
+def derived_weight(tag, sources, build):
+    """Cache of tensors computed from static weights (kernel operand layouts, slices, concatenations): rebuilt when a source
+    was updated in place (tensor._version / data_ptr) or replaced; invalidate_weight_cache() drops it."""
+    key = (tag, id(sources[0])) if len(sources) == 1 else (tag, *map(id, sources))
     hit = _DERIVED.get(key)
-    if hit is not None and hit[0] == ver and all(r() is t for r, t in zip(hit[1], sources)):
-        hit[3].wait()               # built on another stream a moment ago (run_split's two passes share this cache)?
-        return hit[2]
+    if hit is not None:
+        # the weak references pin the identities: a freed weight's id (and even its address) can be reused by another model
+        for (r, v, p), t in zip(hit[0], sources):
+            if r() is not t or v != _ver(t) or p != t.data_ptr():
+                break
+        else:
+            hit[2].wait()           # built on another stream a moment ago (run_split's two passes share this cache)?
+            return hit[1]
+    stamps = tuple((weakref.ref(t), _ver(t), t.data_ptr()) for t in sources)
     with torch.no_grad():
         value = build()
     if len(_DERIVED) > 256:
-        for k in [k for k, v in _DERIVED.items() if any(r() is None for r in v[1])]:
+        for k in [k for k, v in _DERIVED.items() if any(r() is None for r, _, _ in v[0])]:
             del _DERIVED[k]
-    _DERIVED[key] = (ver, tuple(weakref.ref(t) for t in sources), value, _Ready(any(t.is_cuda for t in sources)))
+    _DERIVED[key] = (stamps, value, _Ready(any(t.is_cuda for t in sources)))
     return value
 
 
@@ -2038,9 +1997,6 @@ def gather_add(A: Tensor, ia: Tensor, B: Optional[Tensor] = None, ib: Optional[T
     return Planes32(pl, pinv, E, C) if planes_out else out
 
 
-# CFG.embedding_sum (ops.EMBEDDING_SUM): sum of a node's token embeddings through isg_gather_add instead of gather + reduce (A/B switch)
-
-
 def embedding_sum(weight: Tensor, idx: Tensor) -> Tensor:
     """sum_t weight[idx[:, t]] -> [N, C]: torch.sum(embedding(idx), dim=-2) (scene_graph_encoder.py:63-70) without the [N, T, C]
     intermediate -- isg_gather_add adds up to three gathered rows (and a dense term) per launch, so four tokens are two launches
@@ -2063,21 +2019,20 @@ def embedding_sum(weight: Tensor, idx: Tensor) -> Tensor:
 
 
 def invalidate_weight_cache() -> None:
-    """Drop every cached bf16 plane set and fused weight.  The caches are validated by (object identity, tensor._version,
-    data_ptr); a write THROUGH `.data` (weight.data.copy_/mul_, as init / EMA / weight-surgery code does) bumps neither,
-    so such code must call this (Module.load_state_dict goes through copy_ on the Parameter and is safe)."""
-    _PLANES.clear()
-    _CAT.clear()
+    """Drop every cached derivative of a weight (split planes, fused weights).  The cache is validated by (object identity,
+    tensor._version, data_ptr); a write THROUGH `.data` (weight.data.copy_/mul_, as init / EMA / weight-surgery code does) bumps
+    neither, so such code must call this (Module.load_state_dict goes through copy_ on the Parameter and is safe)."""
     _DERIVED.clear()
 
 
 def _weight_planes(weight: Tensor, cache: bool = True, layout: str = "tile") -> Tensor:
-    key = (id(weight), layout)
-    hit = _PLANES.get(key) if cache else None
-    # the weak reference pins the identity: a freed weight's id (and even its address) can be reused by another model
-    if hit is not None and hit[0]() is weight and hit[1] == _ver(weight) and hit[2] == weight.data_ptr():
-        hit[4].wait()
-        return hit[3]
+    """The weight split into the operand layout of one GEMM kernel ("tile": isg_linear_bf16x6, "panel", "f16x3", "f16x3_rows"),
+    once per weight version; cache=False (a weight being trained, or a temporary): split per call."""
+    return derived_weight(("planes", layout), (weight,), lambda: _split_weight(weight, layout)) if cache else \
+        _split_weight(weight, layout)
+
+
+def _split_weight(weight: Tensor, layout: str):
     lib = _lib.load()
     N, K = weight.shape
     w = weight.detach()
@@ -2103,28 +2058,33 @@ def _weight_planes(weight: Tensor, cache: bool = True, layout: str = "tile") -> 
         planes = torch.empty(3 * N * Kp, dtype=torch.int16, device=weight.device)
         _lib.check(lib.isg_split_bf16x3(_chk(w.contiguous(), "weight", torch.float32), N, K, planes.data_ptr(), _stream()),
                    "isg_split_bf16x3")
-    if cache:
-        if len(_PLANES) > 256:
-            for k in [k for k, v in _PLANES.items() if v[0]() is None]:
-                del _PLANES[k]
-        _PLANES[key] = (weakref.ref(weight), _ver(weight), weight.data_ptr(), planes, _Ready(weight.is_cuda))
     return planes
+
+
+def _stamp(x: Tensor):
+    """What a value attached to an activation is valid for: x's version, storage and shape (an in-place write invalidates it)."""
+    return (_ver(x), x.data_ptr(), tuple(x.shape))
+
+
+def _attach(x: Tensor, name: str, value) -> None:
+    setattr(x, name, (_stamp(x), value))
+
+
+def _attached(x: Tensor, name: str):
+    hit = getattr(x, name, None)
+    return hit[1] if hit is not None and hit[0] == _stamp(x) else None
 
 
 def attach_row_maxima(x: Tensor, rowmax: Tensor) -> Tensor:
     """Leave partial row maxima [M, P] (max |x| over P equal column blocks of every row) on `x` for the fp16 three-product
     Linears that read it.  They are tied to x's version counter: an in-place write to x afterwards invalidates them
     (`row_maxima` then returns None and the Linear makes its own pass) -- a stale maximum would mis-scale the fp16 planes."""
-    x._isg_rowmax = rowmax
-    x._isg_rowmax_version = (_ver(x), x.data_ptr(), tuple(x.shape))
+    _attach(x, "_isg_rowmax", rowmax)
     return x
 
 
 def row_maxima(x: Tensor) -> Optional[Tensor]:
-    rm = getattr(x, "_isg_rowmax", None)
-    if rm is None or getattr(x, "_isg_rowmax_version", None) != (_ver(x), x.data_ptr(), tuple(x.shape)):
-        return None
-    return rm
+    return _attached(x, "_isg_rowmax")
 
 
 def carry_row_maxima(dst: Tensor, src: Tensor) -> Tensor:
@@ -2133,10 +2093,9 @@ def carry_row_maxima(dst: Tensor, src: Tensor) -> Tensor:
     rm = row_maxima(src)
     if rm is not None and dst.dim() >= 1:
         attach_row_maxima(dst, rm)
-    hit = getattr(src, "_isg_planes32", None)
-    if hit is not None and hit[0] == (_ver(src), src.data_ptr(), tuple(src.shape)) and dst.data_ptr() == src.data_ptr() \
-            and dst.numel() == src.numel():
-        dst._isg_planes32 = ((_ver(dst), dst.data_ptr(), tuple(dst.shape)), hit[1])
+    pl = _attached(src, "_isg_planes32")
+    if pl is not None and dst.data_ptr() == src.data_ptr() and dst.numel() == src.numel():
+        _attach(dst, "_isg_planes32", pl)
     return dst
 
 
@@ -2170,7 +2129,7 @@ def add_layernorm(x: Tensor, residual: Optional[Tensor], norm: torch.nn.LayerNor
     if rm is not None:
         attach_row_maxima(out, rm)
     if pl is not None:
-        out._isg_planes32 = ((_ver(out), out.data_ptr(), tuple(out.shape)), pl)       # what split_planes32(out) would make
+        _attach(out, "_isg_planes32", pl)       # what split_planes32(out) would make
     return out
 
 
@@ -2180,137 +2139,228 @@ def _linear_torch(x: Tensor, weight: Tensor, bias: Optional[Tensor], gelu: bool,
     return torch.relu(y) if relu else (torch.nn.functional.gelu(y) if gelu else y)
 
 
+def reads_planes32(M: int, N: int, K: int, cfg: Optional[Switches] = None) -> bool:
+    """Does a Linear of shape (M, N, K) read a planes32 operand on the engine (isg_linear_h3p)?  A producer that can write its
+    result as planes32 (the attention and gate kernels, gather_add, a chained Linear) asks this before it does."""
+    cfg = CFG if cfg is None else cfg
+    return (cfg.h3p and cfg.gemm_backend == "bf16x6" and cfg.gemm_kernel == "auto" and cfg.gemm_f16x3 and K >= cfg.h3p_min_k and
+            (K & 3) == 0 and (N & 3) == 0 and M >= cfg.h3p_min_m and M * ((K + 31) // 32) * 128 < (1 << 31) and
+            N * ((K + 31) // 32) * 128 < (1 << 31)
+            and M * ((N + 31) // 32 * 32) * 4 < (1 << 32) - 16)       # the result through a buffer descriptor: 32-bit byte offsets
+
+
+def _k_chunks(K: int):
+    """isg_linear_f16x3_tile's reduction as chains of at most 640 (2.75x an fp32 GEMM's error at 1024-long chains, < 2x here):
+    (number of chunks, columns per chunk)."""
+    nchunk = (K + 639) // 640
+    return nchunk, ((K + nchunk - 1) // nchunk + 31) // 32 * 32
+
+
+def _usable_rowmax(x: Tensor, M: int) -> Optional[Tensor]:
+    rm = row_maxima(x)
+    return None if rm is None or rm.dim() != 2 or rm.size(0) != M or rm.size(1) > 64 or rm.stride(1) != 1 else rm
+
+
+def _rowmax_slices(K: int, P: int) -> bool:
+    """Do the producer's maxima over P column blocks of a row serve every K-chunk (each covers whole columns of ONE chunk)?"""
+    nchunk, step = _k_chunks(K)
+    per = K // P if P > 0 and K % P == 0 else 0
+    return P > 0 and (nchunk == 1 or (per > 0 and step % per == 0))       # one chunk: any partition of the row serves
+
+
+def _use_panel(M: int, N: int, K: int, cfg: Optional[Switches] = None) -> bool:
+    """linear_route's panel rule: an A panel split once serves many columns (K <= 128: lin_edge 182 vs 212 us, lin_l|lin_r 153
+    vs 166 us) with enough 64-row panels to fill the chip; the tile kernels elsewhere (profiles/r02_a_gemm_structures.md)."""
+    cfg = CFG if cfg is None else cfg
+    if cfg.gemm_kernel != "auto":
+        return cfg.gemm_kernel == "panel"
+    return K <= 128 and N >= cfg.panel_min_n and M >= 32768
+
+
+def linear_route(M: int, N: int, K: int, x_dtype=torch.float32, out_dtype=torch.float32, relu: bool = False,
+                 recording: bool = False, planes32: bool = False, carries_planes: bool = False, rowmax_slices: bool = False,
+                 aligned: bool = True, skinny_layout: bool = True, cfg: Optional[Switches] = None) -> str:
+    """The kernel ops.linear runs act(x @ W^T + b) on for x [M, K], W [N, K]: a pure function of plain values.
+
+    recording: autograd records through x, W or b; planes32: x IS a Planes32; carries_planes: x's producer left its planes32 on
+    it; rowmax_slices: x carries partial row maxima that serve every K-chunk of isg_linear_f16x3_tile; aligned: x has contiguous
+    columns, a row stride of 4 | ld and 16-byte alignment; skinny_layout=False: isg_linear_skinny refused the operands' layout.
+    Under the default switches, fp32 rows, inference, the first match of:
+      M == 0                                                         "empty"
+      K % 4 != 0                                                     "torch" (hipBLASLt)
+      M <= 1024, M N K <= 2^30                                       "skinny"
+      K >= 256, 4 | N, M >= 8192 (2048 if the producer left planes32) "h3p"
+      K > 128, the producer's row maxima slice the row, or N >= 256 and M >= 4096
+                                                                     "f16x3_tile"
+      K <= 128, N >= 256, M >= 32768, no ReLU                        "f16x3" ("f16x3_f16": fp16 result)
+      anything else                                                  "bf16x6" ("bf16x6_f16": fp16 rows in or out)
+    A Planes32 meets "h3p"; ReLU under autograd "torch", anything else under autograd "autograd"."""
+    cfg = CFG if cfg is None else cfg
+    if planes32:
+        return "h3p"
+    f16_io = x_dtype == torch.float16 or out_dtype == torch.float16
+    ours = cfg.gemm_backend == "bf16x6" and (K & 3) == 0
+    if relu and (recording or not ours or M == 0):
+        return "torch"
+    if not ours or M == 0:
+        return "empty" if M == 0 else "torch"
+    if recording:
+        return "autograd"
+    if (skinny_layout and cfg.skinny and cfg.gemm_kernel == "auto" and M <= cfg.skinny_max_m and M * N * K <= cfg.skinny_max_work
+            and not f16_io and x_dtype == torch.float32):
+        return "skinny"      # the latency-bound regime: the HOST's time per call is what the forward costs (DESIGN 17.6b)
+    if not f16_io and aligned and (M >= cfg.h3p_min_m_unsplit or carries_planes) and reads_planes32(M, N, K, cfg):
+        # below h3p_min_m_unsplit rows only an input whose PRODUCER left its planes (isg_add_layernorm, the attention kernels,
+        # the gates): an isolated Linear there would pay a split pass of its own and loses to the tile kernels
+        return "h3p"
+    if (cfg.gemm_f16x3 and cfg.f16x3_tile and cfg.gemm_kernel == "auto" and K > 128 and not f16_io and M < (1 << 23) and
+            (rowmax_slices or (N >= 256 and M >= 4096))):   # a pass over x for the row maxima only pays for wide Linears over many rows
+        return "f16x3_tile"
+    if not relu and _use_panel(M, N, K, cfg):
+        if cfg.gemm_f16x3 and K <= 128 and cfg.f16x3_f16_out and x_dtype == torch.float32 and out_dtype == torch.float16:
+            return "f16x3_f16"
+        return "f16x3" if cfg.gemm_f16x3 and K <= 128 and not f16_io else "panel"
+    return "bf16x6_f16" if f16_io else "bf16x6"
+
+
+_ROUTES = {}   # facts of an ops.linear call -> (the CFG they were decided under, route or None, which input facts decide it)
+_INPUT_FACTS = [(c, s, a) for c in (False, True) for s in (False, True) for a in (False, True)]
+
+
+def _route(x: Tensor, M: int, N: int, K: int, out_dtype, relu: bool, rec: bool, skinny_layout: bool = True) -> str:
+    """linear_route, memoised.  Of x's attachments and layout (planes32, row maxima, alignment) only the facts the shape's route
+    depends on are looked at (host time: a one-question forward is ~75 Linears)."""
+    cfg = CFG
+    key = (M, N, K, x.dtype, out_dtype, relu, rec, skinny_layout)
+    hit = _ROUTES.get(key)
+    if hit is None or hit[0] is not cfg:
+        if len(_ROUTES) > 4096:
+            _ROUTES.clear()
+        r = {f: linear_route(M, N, K, x.dtype, out_dtype, relu, rec, False, *f, skinny_layout, cfg) for f in _INPUT_FACTS}
+        need = tuple(any(r[f] != r[f[:i] + (not f[i],) + f[i + 1:]] for f in _INPUT_FACTS) for i in range(3))
+        hit = _ROUTES[key] = (cfg, None if any(need) else r[_INPUT_FACTS[0]], need)
+    if hit[1] is not None:
+        return hit[1]
+    need, rm = hit[2], (_usable_rowmax(x, M) if hit[2][1] else None)       # a fact no route depends on keeps any value
+    key += (need[0] and has_planes32(x), rm is not None and _rowmax_slices(K, rm.size(1)),
+            need[2] and x.stride(1) == 1 and (x.stride(0) & 3) == 0 and (x.data_ptr() & 15) == 0)
+    hit = _ROUTES.get(key)
+    if hit is None or hit[0] is not cfg:
+        hit = _ROUTES[key] = (cfg, linear_route(M, N, K, x.dtype, out_dtype, relu, rec, False, *key[8:], skinny_layout, cfg))
+    return hit[1]
+
+
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gelu: bool = False,
            cache_planes: bool = True, out_dtype=torch.float32, relu: bool = False, want_rowmax: bool = False) -> Tensor:
-    """act(x @ weight^T + bias), x [M,K] fp32, weight [N,K] (torch Linear layout).  Uses the bf16x6 matrix-core kernel
-    when the shape allows it, hipBLASLt through torch otherwise (K not a multiple of 4).  ``cache_planes=False``: the
-    weight is being trained (or is a temporary), so its bf16 planes are split per call instead of cached."""
+    """act(x @ weight^T + bias), x [M,K] fp32 (fp16 rows, a Planes32), weight [N,K] (torch Linear layout), on the kernel
+    linear_route chooses.  ``cache_planes=False``: the weight is being trained (or is a temporary), so its planes are split per
+    call instead of cached.  ``want_rowmax``: isg_linear_f16x3_tile leaves the result's row maxima on it."""
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
     if isinstance(x, Planes32):                    # the producer handed the rows over pre-split (a Linear's planes output)
+        route = linear_route(x.rows, weight.size(0), x.cols, planes32=True)
+    else:
+        M, K = x.shape
+        rec = torch.is_grad_enabled() and _rec(x, weight, bias)
+        if x.dtype == torch.float16 or out_dtype == torch.float16:
+            if CFG.gemm_backend != "bf16x6" or (K & 3) != 0 or rec:
+                raise _lib.IsgError("fp16 feature rows are an inference feature of the bf16x6 kernel (K % 4 == 0, no autograd)")
+            if relu:
+                raise ValueError("relu excludes fp16 rows")
+        N = weight.size(0)
+        hit = _ROUTES.get((M, N, K, x.dtype, out_dtype, relu, rec, True))      # _route's common case inline (host time)
+        route = hit[1] if hit is not None and hit[0] is CFG and hit[1] is not None else _route(x, M, N, K, out_dtype, relu, rec)
+        if route == "skinny":
+            y = linear_skinny(x, weight, bias, gelu=gelu, relu=relu)
+            if y is not None:
+                return y
+            route = _route(x, M, N, K, out_dtype, relu, rec, skinny_layout=False)      # a layout it cannot take
+    return _launch(route, x, weight, bias, gelu, relu, cache_planes, out_dtype, want_rowmax)
+
+
+def _launch(route: str, x, weight: Tensor, bias: Optional[Tensor], gelu: bool, relu: bool, cache_planes: bool, out_dtype,
+            want_rowmax: bool):
+    """One launcher per route but "skinny" (ops.linear runs isg_linear_skinny itself, and takes the route without it where the
+    kernel refuses the operands' layout).  A shape a kernel has no launch for (more than 65535 row tiles) goes to hipBLASLt."""
+    if route == "h3p":
         return linear_h3p(x, weight, bias, gelu=gelu, relu=relu, cache_planes=cache_planes)
-    M, K = x.shape
-    if (M <= CFG.skinny_max_m and out_dtype == torch.float32 and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and skinny_supported(M, weight.size(0), K)):
-        # the latency-bound regime first: at these sizes the HOST's time per call is what the forward costs (DESIGN 17.6b), and
-        # nothing below applies (inference, fp32 rows in and out)
-        y = linear_skinny(x, weight, bias, gelu=gelu, relu=relu)
-        if y is not None:
-            return y
-    f16_io = x.dtype == torch.float16 or out_dtype == torch.float16
-    if f16_io and (CFG.gemm_backend != "bf16x6" or (K & 3) != 0 or _rec(x, weight, bias)):
-        raise _lib.IsgError("fp16 feature rows are an inference feature of the bf16x6 kernel (K % 4 == 0, no autograd)")
-    if relu and (gelu or f16_io):
-        raise ValueError("relu excludes gelu and fp16 rows")
-    if relu and (_rec(x, weight, bias) or CFG.gemm_backend != "bf16x6" or (K & 3) != 0 or M == 0):
-        return _linear_torch(x, weight, bias, False, True)
-    if _rec(x, weight, bias) and CFG.gemm_backend == "bf16x6" and (K & 3) == 0 and M > 0:
+    if route == "torch":
+        return _linear_torch(x, weight, bias, gelu, relu)
+    if route == "empty":
+        return x.new_empty(0, weight.size(0))
+    if route == "autograd":
         from . import autograd
         return autograd.linear(x, weight, bias, gelu)
-    N = weight.size(0)
-    if CFG.gemm_backend != "bf16x6" or (K & 3) != 0 or M == 0:
-        if M == 0:
-            return x.new_empty(0, N)
-        return _linear_torch(x, weight, bias, gelu, False)
-    if skinny_supported(M, N, K) and not f16_io and x.dtype == torch.float32:
-        y = linear_skinny(x, weight, bias, gelu=gelu, relu=relu)
-        if y is not None:
-            return y
-    if (not f16_io and h3p_supported(M, N, K) and (M >= CFG.h3p_min_m_unsplit or has_planes32(x)) and x.stride(1) == 1
-            and (x.stride(0) & 3) == 0 and (x.data_ptr() & 15) == 0):
-        # K >= 256 over many rows: the planes32 engine (csrc/isg_gemm_h3p.hip); the split of x stays attached to x.  Between
-        # CFG.h3p_min_m and CFG.h3p_min_m_unsplit rows only an input whose PRODUCER left its planes (isg_add_layernorm, the attention
-        # kernels, the gates): an isolated Linear there would pay a split pass of its own and loses to the tile kernels
-        return linear_h3p(x, weight, bias, gelu=gelu, relu=relu, cache_planes=cache_planes)
-    lib = _lib.load()
+    lib, (M, K), N = _lib.load(), x.shape, weight.size(0)
     out = torch.empty(M, N, dtype=out_dtype, device=x.device)
-    a_rowmax = row_maxima(x)
-    if a_rowmax is not None and (a_rowmax.dim() != 2 or a_rowmax.size(0) != M or a_rowmax.size(1) > 64 or
-                                 a_rowmax.stride(1) != 1):
-        a_rowmax = None
-    f16x3_tile = CFG.gemm_f16x3 and CFG.f16x3_tile and CFG.gemm_kernel == "auto" and K > 128 and not f16_io and M < (1 << 23)
-    nchunk = (K + 639) // 640              # chains of at most 640: 2.75x an fp32 GEMM's error at 1024-long chains, < 2x here
-    step = (K + nchunk - 1) // nchunk
-    step = (step + 31) // 32 * 32
-    # the producer's partial maxima serve a K-chunk when every partial covers a whole number of columns of ONE chunk
+    if route == "f16x3_tile":
+        return _linear_f16x3_tile(lib, x, weight, bias, gelu, relu, cache_planes, out, want_rowmax, M, N, K)
+    if route in ("f16x3", "f16x3_f16"):        # fp32 rows in; fp32 out, or half rows (configs[4]'s x_l | x_r) rounded once
+        planes, inv = _weight_planes(weight, cache_planes, "f16x3")
+        name = "isg_linear_" + route
+        _lib.check(getattr(lib, name)(_chk(x, "x", torch.float32), planes.data_ptr(), inv.data_ptr(), _bias_ptr(bias, N),
+                                      out.data_ptr(), M, N, K, K, N, 1 if gelu else 0, N, 0, _stream()), name)
+        return out
+    planes = _weight_planes(weight, cache_planes, "panel" if route == "panel" else "tile")
+    if route == "bf16x6":
+        rc = lib.isg_linear_bf16x6(_chk(x, "x", torch.float32), planes.data_ptr(), _bias_ptr(bias, N), out.data_ptr(), M, N, K,
+                                   K, N, 2 if relu else (1 if gelu else 0), _stream())
+        if rc == ISG_EUNSUPPORTED:
+            return _linear_torch(x, weight, bias, gelu, relu)
+        _lib.check(rc, "isg_linear_bf16x6")
+        return out
+    name = "isg_linear_panel" if route == "panel" else "isg_linear_bf16x6_f16"
+    _lib.check(getattr(lib, name)(_chk(x, "x", x.dtype), 1 if x.dtype == torch.float16 else 0, planes.data_ptr(), _bias_ptr(bias, N),
+                                  out.data_ptr(), 1 if out_dtype == torch.float16 else 0, M, N, K, K, N, 1 if gelu else 0,
+                                  _stream()), name)
+    return out
+
+
+def _bias_ptr(bias: Optional[Tensor], N: int) -> int:
+    return _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True)
+
+
+def _linear_f16x3_tile(lib, x: Tensor, weight: Tensor, bias, gelu: bool, relu: bool, cache_planes: bool, out: Tensor,
+                       want_rowmax: bool, M: int, N: int, K: int) -> Tensor:
+    """fp16 three-product tile kernel.  Row scales: the producer's partial maxima (a chunk takes the slice that covers its
+    columns), or one pass over x which is then left on x for its other consumers; reductions longer than 640 run as K-chunks
+    that accumulate into `out` (every chunk its own fp32 chain and its own row scales)."""
+    a_rowmax = _usable_rowmax(x, M)
     P = a_rowmax.size(1) if a_rowmax is not None else 0
-    per = K // P if P and K % P == 0 else 0
-    sliced = P > 0 and (nchunk == 1 or (per > 0 and step % per == 0))      # one chunk: any partition of the row serves
-    if f16x3_tile and not sliced and not (N >= 256 and M >= 4096):
-        f16x3_tile = False         # a pass over x for the row maxima only pays for wide Linears over many rows
-    if f16x3_tile:
-        # fp16 three-product tile kernel.  Row scales: the producer's partial maxima (a chunk takes the slice that covers
-        # its columns), or one pass over x which is then left on x for its other consumers; reductions longer than 640 run
-        # as K-chunks that accumulate into `out` (every chunk its own fp32 chain and its own row scales)
-        planes, inv = _weight_planes(weight, cache_planes, "f16x3_rows")
-        act = 2 if relu else (1 if gelu else 0)
-        bptr = _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True)
-        d_rowmax = torch.empty(M, (N + 31) // 32, dtype=torch.float32, device=x.device) if want_rowmax else None
-        xp = _chk(x, "x", torch.float32)
-        k0, c = 0, 0
-        while k0 < K:
-            kc = min(step, K - k0)
-            last = k0 + kc >= K
-            if sliced and nchunk == 1:
-                rm_ptr, rm_p, rm_ld = a_rowmax.data_ptr(), P, a_rowmax.stride(0)
-            elif sliced:
-                rm_ptr, rm_p, rm_ld = a_rowmax.data_ptr() + 4 * (k0 // per), (kc + per - 1) // per, a_rowmax.stride(0)
-            else:
-                rm = torch.empty(M, 1, dtype=torch.float32, device=x.device)
-                _lib.check(lib.isg_row_absmax(xp + 4 * k0, M, kc, K, rm.data_ptr(), _stream()), "isg_row_absmax")
-                COUNTERS["row_absmax"] += 1
-                if nchunk == 1:
-                    attach_row_maxima(x, rm)          # the next Linear over the same rows does not repeat the pass
-                rm_ptr, rm_p, rm_ld = rm.data_ptr(), 1, 1
-            rc = lib.isg_linear_f16x3_tile(
-                xp + 4 * k0, rm_ptr, rm_p, rm_ld, planes.data_ptr(), inv.data_ptr(), bptr if last else 0,
-                out.data_ptr(), d_rowmax.data_ptr() if (last and d_rowmax is not None) else 0, M, N, kc, K, N,
-                act if last else 0, K, k0, 1 if c > 0 else 0, _stream())
-            if rc == ISG_EUNSUPPORTED and c == 0:       # a shape the kernel has no launch for (> 65535 row tiles): hipBLASLt
-                return _linear_torch(x, weight, bias, gelu, relu)
-            _lib.check(rc, "isg_linear_f16x3_tile")
-            k0 += kc
-            c += 1
-        if d_rowmax is not None:
-            attach_row_maxima(out, d_rowmax)
-        return out
-    if (_use_panel(M, N, K) and not relu and CFG.gemm_f16x3 and K <= 128 and CFG.f16x3_f16_out and x.dtype == torch.float32
-            and out_dtype == torch.float16):
-        # fp32 rows in, half rows out (configs[4]'s x_l | x_r): the three-product kernel with one rounding at its store
-        planes, inv = _weight_planes(weight, cache_planes, "f16x3")
-        _lib.check(lib.isg_linear_f16x3_f16(
-            _chk(x, "x", torch.float32), planes.data_ptr(), inv.data_ptr(),
-            _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True),
-            out.data_ptr(), M, N, K, K, N, 1 if gelu else 0, N, 0, _stream()), "isg_linear_f16x3_f16")
-        return out
-    if _use_panel(M, N, K) and not relu and CFG.gemm_f16x3 and K <= 128 and not f16_io:
-        planes, inv = _weight_planes(weight, cache_planes, "f16x3")
-        _lib.check(lib.isg_linear_f16x3(
-            _chk(x, "x", torch.float32), planes.data_ptr(), inv.data_ptr(),
-            _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True),
-            out.data_ptr(), M, N, K, K, N, 1 if gelu else 0, N, 0, _stream()), "isg_linear_f16x3")
-        return out
-    if _use_panel(M, N, K) and not relu:
-        planes = _weight_planes(weight, cache_planes, "panel")
-        _lib.check(lib.isg_linear_panel(
-            _chk(x, "x", x.dtype), 1 if x.dtype == torch.float16 else 0, planes.data_ptr(),
-            _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True),
-            out.data_ptr(), 1 if out_dtype == torch.float16 else 0, M, N, K, K, N, 1 if gelu else 0, _stream()),
-            "isg_linear_panel")
-        return out
-    planes = _weight_planes(weight, cache_planes)
-    if f16_io:
-        if M > 0:
-            _lib.check(lib.isg_linear_bf16x6_f16(
-                _chk(x, "x", x.dtype), 1 if x.dtype == torch.float16 else 0, planes.data_ptr(),
-                _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True),
-                out.data_ptr(), 1 if out_dtype == torch.float16 else 0, M, N, K, K, N, 1 if gelu else 0, _stream()),
-                "isg_linear_bf16x6_f16")
-        return out
-    rc = lib.isg_linear_bf16x6(_chk(x, "x", torch.float32), planes.data_ptr(),
-                               _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True),
-                               out.data_ptr(), M, N, K, K, N, 2 if relu else (1 if gelu else 0), _stream())
-    if rc == ISG_EUNSUPPORTED:                          # e.g. more than 65535 row tiles: fp32 through hipBLASLt
-        return _linear_torch(x, weight, bias, gelu, relu)
-    _lib.check(rc, "isg_linear_bf16x6")
+    nchunk, step = _k_chunks(K)
+    sliced = _rowmax_slices(K, P)
+    per = K // P if sliced and K % P == 0 else 0
+    planes, inv = _weight_planes(weight, cache_planes, "f16x3_rows")
+    act = 2 if relu else (1 if gelu else 0)
+    bptr = _bias_ptr(bias, N)
+    d_rowmax = torch.empty(M, (N + 31) // 32, dtype=torch.float32, device=x.device) if want_rowmax else None
+    xp = _chk(x, "x", torch.float32)
+    k0, c = 0, 0
+    while k0 < K:
+        kc = min(step, K - k0)
+        last = k0 + kc >= K
+        if sliced and nchunk == 1:
+            rm_ptr, rm_p, rm_ld = a_rowmax.data_ptr(), P, a_rowmax.stride(0)
+        elif sliced:
+            rm_ptr, rm_p, rm_ld = a_rowmax.data_ptr() + 4 * (k0 // per), (kc + per - 1) // per, a_rowmax.stride(0)
+        else:
+            rm = torch.empty(M, 1, dtype=torch.float32, device=x.device)
+            _lib.check(lib.isg_row_absmax(xp + 4 * k0, M, kc, K, rm.data_ptr(), _stream()), "isg_row_absmax")
+            COUNTERS["row_absmax"] += 1
+            if nchunk == 1:
+                attach_row_maxima(x, rm)          # the next Linear over the same rows does not repeat the pass
+            rm_ptr, rm_p, rm_ld = rm.data_ptr(), 1, 1
+        rc = lib.isg_linear_f16x3_tile(
+            xp + 4 * k0, rm_ptr, rm_p, rm_ld, planes.data_ptr(), inv.data_ptr(), bptr if last else 0,
+            out.data_ptr(), d_rowmax.data_ptr() if (last and d_rowmax is not None) else 0, M, N, kc, K, N,
+            act if last else 0, K, k0, 1 if c > 0 else 0, _stream())
+        if rc == ISG_EUNSUPPORTED and c == 0:       # a shape the kernel has no launch for (> 65535 row tiles): hipBLASLt
+            return _linear_torch(x, weight, bias, gelu, relu)
+        _lib.check(rc, "isg_linear_f16x3_tile")
+        k0 += kc
+        c += 1
+    if d_rowmax is not None:
+        attach_row_maxima(out, d_rowmax)
     return out
 
 
@@ -2332,17 +2382,16 @@ class Planes32(NamedTuple):
 
 def has_planes32(x: Tensor) -> bool:
     """Did x's producer leave its planes32 (still valid for x's current version)?"""
-    hit = getattr(x, "_isg_planes32", None)
-    return hit is not None and hit[0] == (_ver(x), x.data_ptr(), tuple(x.shape))
+    return _attached(x, "_isg_planes32") is not None
 
 
 def split_planes32(x: Tensor) -> Planes32:
     """fp32 rows [M, K] -> planes32 (exact row maxima).  The planes stay attached to `x` (tied to its version counter, like
     the row maxima): a second Linear over the same rows (the decoder layers' cross-attention over the encoder memory) does
     not repeat the pass."""
-    hit = getattr(x, "_isg_planes32", None)
-    if hit is not None and hit[0] == (_ver(x), x.data_ptr(), tuple(x.shape)):
-        return hit[1]
+    hit = _attached(x, "_isg_planes32")
+    if hit is not None:
+        return hit
     lib = _lib.load()
     M, K = x.shape
     planes = torch.empty(int(lib.isg_planes32_elems(M, K)), dtype=torch.int16, device=x.device)
@@ -2350,7 +2399,7 @@ def split_planes32(x: Tensor) -> Planes32:
     _lib.check(lib.isg_split_planes32(_chk_rows(x, "x"), M, K, x.stride(0), planes.data_ptr(), inv.data_ptr(), _stream()),
                "isg_split_planes32")
     out = Planes32(planes, inv, M, K)
-    x._isg_planes32 = ((_ver(x), x.data_ptr(), tuple(x.shape)), out)
+    _attach(x, "_isg_planes32", out)
     return out
 
 
@@ -2368,7 +2417,7 @@ def instr_gate_planes32(x: Tensor, instr: Tensor, batch: Tensor, want_rows: bool
                                            planes.data_ptr(), inv.data_ptr(), N, C, _stream()), "isg_instr_gate_planes32")
     pl = Planes32(planes, inv, N, C)
     if rows is not None:
-        rows._isg_planes32 = ((_ver(rows), rows.data_ptr(), tuple(rows.shape)), pl)
+        _attach(rows, "_isg_planes32", pl)
     return rows, pl
 
 
@@ -2393,15 +2442,6 @@ def _h3p_weight(weight: Tensor, bias: Optional[Tensor], cache: bool = True, seg_
         with torch.no_grad():
             return build()
     return derived_weight(f"h3p{seg_cols or ''}", (weight,) if bias is None else (weight, bias), build)
-
-
-# CFG.rows_kernel_min_edges (ops.ROWS_KERNEL_MIN_EDGES): below this many edges a wide layer (C = 300 / K = 300) projects its edge rows and runs un-fused
-# CFG.skinny (ops.SKINNY): Linears over at most CFG.skinny_max_m rows (and M N K <= CFG.skinny_max_work) on isg_linear_skinny (A/B switch)
-# CFG.skinny_max_m (ops.SKINNY_MAX_M): the latency-bound regime: a handful of questions per forward (csrc/isg_gemm_skinny.hip)
-# CFG.skinny_max_work (ops.SKINNY_MAX_WORK): true fp32 MFMAs run at 1/16 of the fp16 rate: beyond ~1e9 multiply-adds the exact-split tile kernels win
-def skinny_supported(M: int, N: int, K: int) -> bool:
-    return (CFG.skinny and CFG.gemm_backend == "bf16x6" and CFG.gemm_kernel == "auto" and 0 < M <= CFG.skinny_max_m and (K & 3) == 0
-            and M * N * K <= CFG.skinny_max_work)
 
 
 def linear_skinny(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gelu: bool = False, relu: bool = False) -> Optional[Tensor]:
@@ -2438,27 +2478,12 @@ def linear_skinny(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gelu
     return out
 
 
-# CFG.h3p (ops.H3P): Linears with K >= CFG.h3p_min_k over at least CFG.h3p_min_m rows on isg_linear_h3p (A/B switch)
-# CFG.h3p_min_k (ops.H3P_MIN_K): CFG.ln_planes (ops.LN_PLANES): isg_add_layernorm writes its result as planes32 too where Linears on the engine read it (A/B switch)
-# CFG.h3p_chain (ops.H3P_CHAIN): linear1 -> linear2 of the Transformer layers through planes (no fp32 intermediate): A/B switch
-# CFG.h3p_min_m_unsplit (ops.H3P_MIN_M_UNSPLIT): ... but a Linear whose input carries no planes from its producer takes the engine from this many rows only
-# CFG.h3p_min_m (ops.H3P_MIN_M): 8192 until round 6; swept with the small-batch kernels in place (tools/time_full_model.py G --set=H3P_MIN_M=...): 2048 is 5-7 % faster at 160-700 graphs
-def h3p_supported(M: int, N: int, K: int) -> bool:
-    return (CFG.h3p and CFG.gemm_backend == "bf16x6" and CFG.gemm_kernel == "auto" and CFG.gemm_f16x3 and K >= CFG.h3p_min_k and (K & 3) == 0 and
-            (N & 3) == 0 and M >= CFG.h3p_min_m and M * ((K + 31) // 32) * 128 < (1 << 31) and N * ((K + 31) // 32) * 128 < (1 << 31)
-            and M * ((N + 31) // 32 * 32) * 4 < (1 << 32) - 16)       # the result through a buffer descriptor: 32-bit byte offsets
-
-
 # The cache policy of a large (>= 128 MB) fp32 result's stores in isg_linear_h3p: -1 (the library's choice: nt at K >= 512, plain
 # below) / 0 plain / 1 nt / 2 sc0 sc1 nt, or "auto" = measured once per process on the box (_h3p_tune).  Results do not depend on
 # it.  In ISOLATION 2 runs the K = 300 projections 15-32 % faster than plain stores on some MI355X boxes and 21 % slower on others
 # (the same way in every process on a box); in the full model, on a box where it wins in isolation, every policy gives the same
 # step (20.09-20.29 ms: profiles/r04_ag_h3p_store_policy.txt) -- what the producer gains by not leaving its result in L2 / the
 # Infinity Cache its consumer loses.  So the default is the library's choice and "auto" stays an experiment.
-# CFG.h3p_store_policy (ops.H3P_STORE_POLICY): 
-# CFG.linear_multi_h3p (ops.LINEAR_MULTI_H3P): the layers' lin_edge over the shared edge features as one engine launch (A/B switch)
-# CFG.mp_planes (ops.MP_PLANES): the flat message-passing kernel hands x_proj.0 its operand as segmented planes32 (A/B switch)
-# CFG.gather_add_planes (ops.GATHER_ADD_PLANES): isg_gather_add hands its rows to the Linear behind it as planes32 (A/B switch)
 _h3p_policy_state = {"chosen": None, "us": None}
 
 
@@ -2521,7 +2546,7 @@ def linear_h3p(x, weight: Tensor, bias: Optional[Tensor] = None, gelu: bool = Fa
     if seg and (not gelu or relu or 2 * seg != K):
         raise ValueError("linear_h3p: a segmented operand (isg_gatv2_mp_fwd_planes) feeds a Linear + GELU over two equal halves")
     wp, winv, bound = _h3p_weight(weight, bias, cache_planes, seg)
-    bptr = _chk(None if bias is None else bias.detach(), "bias", torch.float32, (N,), optional=True)
+    bptr = _bias_ptr(bias, N)
     act = 2 if relu else (1 if gelu else 0)
     dev = xp.planes.device
     ksplit = (seg + 31) // 32 * 32
@@ -2568,9 +2593,6 @@ def planes32_to_rows(p: Planes32) -> Tensor:
     return ((v[:, :, 0] + v[:, :, 1]).reshape(p.rows, KT * 32)[:, :p.cols] * p.inv[:, None]).contiguous()
 
 
-# CFG.linear_multi (ops.LINEAR_MULTI): A/B switch (tools/ab_step.py)
-
-
 def linear_multi(x: Tensor, weights, out_dtype=torch.float32):
     """x @ W_i^T for several bias-free Linears of one shape over the same rows, as ONE launch of the row-panel kernel
     (isg_linear_panel_multi): a tuple of dense [M, n] tensors, or None when the shape is not the panel kernel's (the caller
@@ -2582,22 +2604,24 @@ def linear_multi(x: Tensor, weights, out_dtype=torch.float32):
     if any(tuple(w.shape) != (n, K) for w in weights):
         return None
     if (CFG.linear_multi_h3p and x.dtype == torch.float32 and out_dtype == torch.float32 and (n & 3) == 0 and
-            h3p_supported(M, len(weights) * n, K) and x.stride(1) == 1 and (x.stride(0) & 3) == 0 and (x.data_ptr() & 15) == 0):
+            reads_planes32(M, len(weights) * n, K) and x.stride(1) == 1 and (x.stride(0) & 3) == 0 and (x.data_ptr() & 15) == 0):
         # K >= 256 (the reference's default width): ONE launch of the planes32 engine over the concatenated weights -- the shared
         # rows are read once instead of once per layer (262 MB per layer at 205 k edges); the layers' results are column slices
         cat = derived_weight("linear_multi", tuple(weights), lambda: torch.cat([w.detach() for w in weights], 0).contiguous())
         y = linear_h3p(x, cat, None)
         return tuple(y[:, i * n:(i + 1) * n] for i in range(len(weights)))
-    if (n & 31) or (K & 3) or not _use_panel(M, len(weights) * n, K):
+    if (n & 31) or (K & 3):
+        return None
+    route = linear_route(M, len(weights) * n, K, x.dtype, out_dtype)
+    if route not in ("f16x3", "f16x3_f16", "panel"):      # the row-panel kernels' shapes only
         return None
     lib = _lib.load()
     cat = derived_weight("linear_multi", tuple(weights), lambda: torch.cat([w.detach() for w in weights], 0).contiguous())
     L = len(weights)
     out = torch.empty(L, M, n, dtype=out_dtype, device=x.device)
-    if CFG.gemm_f16x3 and K <= 128 and x.dtype == torch.float32 and (out_dtype == torch.float32 or
-                                                                 (out_dtype == torch.float16 and CFG.f16x3_f16_out)):
+    if route != "panel":
         planes, inv = _weight_planes(cat, True, "f16x3")
-        fn = lib.isg_linear_f16x3 if out_dtype == torch.float32 else lib.isg_linear_f16x3_f16
+        fn = lib.isg_linear_f16x3 if route == "f16x3" else lib.isg_linear_f16x3_f16
         _lib.check(fn(_chk(x, "x", torch.float32), planes.data_ptr(), inv.data_ptr(), 0, out.data_ptr(),
                       M, L * n, K, K, n, 0, n, M * n, _stream()), "isg_linear_f16x3")
         return tuple(out[i] for i in range(L))
@@ -2613,11 +2637,6 @@ def mha_small_supported(t_kv: int, head_dim: int) -> bool:
     V rows (as many queries as keys at most: the callers pass the longer of the two) + score strips within 64 KB of LDS -- at
     head_dim 64 that is 80 keys (CLIP questions: 77).  Callers ask BEFORE choosing the kernel path."""
     return head_dim <= 64 and head_dim % 4 == 0 and t_kv <= 128 and (t_kv * (3 * head_dim + 4) + 4 * 128) * 4 <= 64 * 1024
-
-
-# CFG.tile_heavy_first (ops.TILE_HEAVY_FIRST): persistent tile kernels walk the tile list heavy tiles first (A/B switch)
-# CFG.mha_rows_planes (ops.MHA_ROWS_PLANES): attention results as planes32 where the all-heads form fits (A/B switch)
-# CFG.mha_rows_max_tq (ops.MHA_ROWS_MAX_TQ): ... up to this many query rows per batch item
 
 
 def mha_rows_supported(t_q: int, t_kv: int, heads: int, head_dim: int) -> bool:
@@ -2712,8 +2731,7 @@ def mlp(seq: torch.nn.Sequential, x: Tensor, want_rowmax: bool = False) -> Tenso
             rows_in = x.rows if isinstance(x, Planes32) else x.size(0)
             chain = (more and CFG.h3p_chain and not _rec(m.weight, mods[nxt].weight) and not torch.is_grad_enabled() and
                      (isinstance(x, Planes32) or x.dtype == torch.float32) and
-                     h3p_supported(rows_in, m.weight.size(0), m.weight.size(1)) and
-                     h3p_supported(rows_in, mods[nxt].weight.size(0), mods[nxt].weight.size(1)))
+                     reads_planes32(rows_in, *m.weight.shape) and reads_planes32(rows_in, *mods[nxt].weight.shape))
             if chain:      # this Linear's result as the planes the next Linear reads: no fp32 intermediate, no split pass
                 x = linear_h3p(x, m.weight, m.bias, gelu=fuse, planes_out=True)
             else:
@@ -2725,39 +2743,19 @@ def mlp(seq: torch.nn.Sequential, x: Tensor, want_rowmax: bool = False) -> Tenso
     return x
 
 
-_CAT = {}   # (ids of the weights) -> (versions, concatenated weight, concatenated bias, weakrefs of the weights)
-
-
 def linear_fused(x: Tensor, layers, out_dtype=torch.float32) -> Tuple[Tensor, ...]:
-    """Several Linear layers that share their input as ONE projection (weights concatenated along the output dim, cached);
-    returns one column-slice view of the fused output per layer (row stride = total width)."""
-    if _rec(*([] if isinstance(x, Planes32) else [x]), *[m.weight for m in layers]):      # training: differentiable concatenation, nothing cached
+    """Several Linear layers that share their input as ONE projection (weights concatenated along the output dim, a derived
+    weight); returns one column-slice view of the fused output per layer (row stride = total width)."""
+    biases = [m.bias for m in layers if m.bias is not None]
+
+    def cat():
         w = torch.cat([m.weight for m in layers], dim=0)
-        b = torch.cat([m.bias if m.bias is not None else torch.zeros(m.weight.size(0), device=w.device)
-                       for m in layers]) if any(m.bias is not None for m in layers) else None
-        y = linear(x, w, b)
-        outs, o = [], 0
-        for m in layers:
-            n = m.weight.size(0)
-            outs.append(y[:, o:o + n])
-            o += n
-        return tuple(outs)
-    key = tuple(id(m.weight) for m in layers)
-    ver = tuple((_ver(m.weight), m.weight.data_ptr(), None if m.bias is None else _ver(m.bias)) for m in layers)
-    hit = _CAT.get(key)
-    if hit is None or hit[0] != ver or any(r() is not m.weight for r, m in zip(hit[3], layers)):
-        w = torch.cat([m.weight.detach() for m in layers], dim=0).contiguous()
-        has_b = any(m.bias is not None for m in layers)
-        b = torch.cat([m.bias.detach() if m.bias is not None else torch.zeros(m.weight.size(0), device=w.device)
-                       for m in layers]) if has_b else None
-        if len(_CAT) > 256:
-            for k in [k for k, v in _CAT.items() if any(r() is None for r in v[3])]:
-                del _CAT[k]
-        hit = (ver, w, b, tuple(weakref.ref(m.weight) for m in layers), _Ready(w.is_cuda))
-        _CAT[key] = hit
+        return w, torch.cat([m.bias if m.bias is not None else torch.zeros(m.weight.size(0), device=w.device)
+                             for m in layers]) if biases else None
+    if _rec(*([] if isinstance(x, Planes32) else [x]), *[m.weight for m in layers]):      # training: differentiable, nothing cached
+        y = linear(x, *cat())
     else:
-        hit[4].wait()
-    y = linear(x, hit[1], hit[2], out_dtype=out_dtype)
+        y = linear(x, *derived_weight("linear_fused", [m.weight for m in layers] + biases, cat), out_dtype=out_dtype)
     outs, o = [], 0
     for m in layers:
         n = m.weight.size(0)

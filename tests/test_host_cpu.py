@@ -322,3 +322,83 @@ def test_switches_are_one_frozen_object_swapped_atomically():
     finally:
         ops.CFG = before
     assert ops.CFG is before
+
+
+F16 = torch.float16
+# (M, N, K, linear_route keywords, switch overrides, the kernel ops.linear launched for it before the routing was one function)
+ROUTES = [
+    # thresholds under the default switches, each side
+    (1024, 512, 512, {}, {}, "skinny"), (1025, 512, 512, {}, {}, "bf16x6"),                              # skinny_max_m
+    (1024, 1024, 1024, {}, {}, "skinny"), (1024, 1024, 1028, {}, {}, "bf16x6"),                          # skinny_max_work
+    (2047, 512, 512, {"carries_planes": True}, {}, "bf16x6"), (2048, 512, 512, {"carries_planes": True}, {}, "h3p"),   # h3p_min_m
+    (8191, 512, 512, {}, {}, "f16x3_tile"), (8192, 512, 512, {}, {}, "h3p"),                             # h3p_min_m_unsplit
+    (8191, 512, 512, {"carries_planes": True}, {}, "h3p"), (8192, 512, 512, {"aligned": False}, {}, "f16x3_tile"),
+    (8192, 512, 252, {}, {}, "f16x3_tile"), (8192, 512, 256, {}, {}, "h3p"), (8192, 510, 256, {}, {}, "f16x3_tile"),  # h3p_min_k, 4 | N
+    (32767, 256, 128, {}, {}, "bf16x6"), (32768, 256, 128, {}, {}, "f16x3"),                             # the panel rule: M
+    (32768, 256, 132, {}, {}, "f16x3_tile"), (32768, 255, 128, {}, {}, "bf16x6"),                        # K, N
+    (4095, 256, 300, {}, {}, "bf16x6"), (4096, 256, 300, {}, {}, "f16x3_tile"), (4096, 255, 300, {}, {}, "bf16x6"),   # f16x3_tile
+    (1025, 96, 300, {"rowmax_slices": True}, {}, "f16x3_tile"), (4095, 256, 128, {"rowmax_slices": True}, {}, "bf16x6"),
+    (1 << 23, 256, 300, {"aligned": False}, {}, "bf16x6"),
+    # fp16 rows in / out, ReLU, autograd, no rows, K % 4, a Planes32, isg_linear_skinny refusing the layout
+    (32768, 256, 128, {"x_dtype": F16}, {}, "panel"), (32768, 256, 128, {"out_dtype": F16}, {}, "f16x3_f16"),
+    (12, 512, 512, {"out_dtype": F16}, {}, "bf16x6_f16"), (8192, 512, 512, {"x_dtype": F16}, {}, "bf16x6_f16"),
+    (12, 512, 512, {"relu": True}, {}, "skinny"), (32768, 256, 128, {"relu": True}, {}, "bf16x6"),
+    (12, 512, 512, {"recording": True}, {}, "autograd"), (12, 512, 512, {"recording": True, "relu": True}, {}, "torch"),
+    (0, 512, 512, {}, {}, "empty"), (0, 512, 512, {"relu": True}, {}, "torch"), (0, 512, 512, {"recording": True}, {}, "empty"),
+    (12, 512, 37, {}, {}, "torch"), (12, 512, 37, {"recording": True}, {}, "torch"),
+    (12, 512, 512, {"planes32": True}, {}, "h3p"), (12, 512, 512, {"skinny_layout": False}, {}, "bf16x6"),
+    # the overrides tests and tools use
+    (12, 512, 512, {}, {"gemm_kernel": "panel"}, "panel"), (12, 512, 128, {}, {"gemm_kernel": "panel"}, "f16x3"),
+    (12, 512, 512, {"relu": True}, {"gemm_kernel": "panel"}, "bf16x6"),
+    (32768, 256, 128, {}, {"gemm_kernel": "tile"}, "bf16x6"), (8192, 512, 512, {}, {"gemm_kernel": "tile"}, "bf16x6"),
+    (32768, 256, 128, {}, {"gemm_f16x3": False}, "panel"), (8192, 512, 512, {}, {"gemm_f16x3": False}, "bf16x6"),
+    (32768, 256, 128, {"out_dtype": F16}, {"f16x3_f16_out": False}, "panel"),
+    (12, 512, 512, {}, {"gemm_backend": "torch"}, "torch"), (0, 512, 512, {}, {"gemm_backend": "torch"}, "empty"),
+    (12, 512, 512, {}, {"skinny": False}, "bf16x6"),
+    (12, 512, 512, {"carries_planes": True}, {"h3p_min_m": 1}, "skinny"),
+    (1025, 512, 512, {"carries_planes": True}, {"h3p_min_m": 1}, "h3p"), (1025, 512, 512, {}, {"h3p_min_m": 1}, "bf16x6"),
+    # real shapes.  One question of the full model (C = 300): every Linear on isg_linear_skinny, the [V, C] table aside
+    (1, 1842, 512, {}, {}, "skinny"), (12, 1536, 512, {"rowmax_slices": True}, {}, "skinny"),
+    (12, 2048, 512, {"relu": True, "rowmax_slices": True}, {}, "skinny"), (21, 600, 1200, {}, {}, "skinny"),
+    (45, 1200, 300, {}, {}, "skinny"), (2578, 300, 300, {}, {}, "bf16x6"),
+    # configs[1] (4096 graphs, C = 128)
+    (4096, 128, 128, {}, {}, "bf16x6"), (4096, 1842, 512, {"rowmax_slices": True}, {}, "f16x3_tile"),
+    (4096, 512, 384, {"rowmax_slices": True}, {}, "f16x3_tile"),
+    # the full model at C = 300 over 4096 graphs
+    (16384, 1536, 512, {}, {}, "h3p"), (4096, 300, 2048, {}, {}, "f16x3_tile"), (4096, 300, 300, {}, {}, "f16x3_tile"),
+    (82189, 2400, 300, {"carries_planes": True}, {}, "h3p"), (82189, 32, 16, {}, {}, "bf16x6"), (82189, 300, 332, {}, {}, "h3p"),
+    (204753, 300, 300, {}, {}, "h3p"),
+    # configs[4] (2048 skewed graphs, fp16 rows)
+    (43633, 1024, 128, {"out_dtype": F16}, {}, "f16x3_f16"), (43633, 128, 256, {}, {}, "h3p"),
+    (43633, 256, 512, {"x_dtype": F16}, {}, "bf16x6_f16"), (43633, 128, 128, {}, {}, "bf16x6"),
+]
+
+
+@pytest.mark.parametrize("M,N,K,kw,switches,kernel", ROUTES)
+def test_linear_route_names_the_kernel_a_linear_runs_on(M, N, K, kw, switches, kernel):
+    """ops.linear_route is the whole decision of which kernel runs a Linear (which kernel a row meets depends on the batch's size):
+    each side of every threshold, the switches' overrides, and the Linears of real forwards."""
+    from isubgvqa_amd import ops
+    with ops.configured(**switches):
+        assert ops.linear_route(M, N, K, **kw) == kernel
+    assert ops.linear_route(M, N, K, cfg=ops.Switches(**switches), **kw) == kernel
+
+
+def test_linear_route_memo_follows_the_switches_and_what_the_input_carries():
+    """ops.linear memoises the route per shape and switch object; a changed switch or attachment is seen on the next call."""
+    from isubgvqa_amd import ops
+    x = torch.zeros(2048, 512)
+    assert ops._route(x, 2048, 512, 512, torch.float32, False, False) == "bf16x6"
+    ops._attach(x, "_isg_planes32", object())
+    assert ops._route(x, 2048, 512, 512, torch.float32, False, False) == "h3p"
+    with ops.configured(h3p=False):
+        assert ops._route(x, 2048, 512, 512, torch.float32, False, False) == "bf16x6"
+    x.add_(1.0)                                      # an in-place write invalidates the planes
+    assert ops._route(x, 2048, 512, 512, torch.float32, False, False) == "bf16x6"
+
+
+def test_linear_relu_and_gelu_are_exclusive_at_every_size():
+    from isubgvqa_amd import ops
+    for M in (0, 12, 1024, 5000):
+        with pytest.raises(ValueError):
+            ops.linear(torch.zeros(M, 512), torch.zeros(512, 512), relu=True, gelu=True)
