@@ -120,8 +120,14 @@ def _noises(cfg, wl, seed):
 
 def _run_both(cfg, dev, noise_seed=5):
     from isubgvqa_amd import synthetic
-    from oracle import model as OM
     wl = synthetic.make_workload(cfg)
+    return (wl,) + _run_both_wl(cfg, wl, dev, noise_seed)
+
+
+def _run_both_wl(cfg, wl, dev, noise_seed=5):
+    """(oracle result, GPU result) of cfg's AnswerModel on the host workload `wl`."""
+    from isubgvqa_amd import synthetic
+    from oracle import model as OM
     model = synthetic.build_answer_model(cfg).eval()
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     noises = _noises(cfg, wl, noise_seed)
@@ -130,7 +136,7 @@ def _run_both(cfg, dev, noise_seed=5):
                                     _oracle_cfg(cfg), noises)
         got = model.to(dev)(wl.to(dev), noises={i: n.to(dev) for i, n in noises.items()})
     torch.cuda.synchronize()
-    return wl, ref, tuple(None if t is None else t.cpu() for t in got)
+    return ref, tuple(None if t is None else t.cpu() for t in got)
 
 
 @pytest.mark.parametrize("sampler", ["gumbel", "imle", "aimle"])
@@ -1035,12 +1041,28 @@ def test_oversize_by_edges_only_and_first_and_last_graph(dev):
     cfg = synthetic.WorkloadConfig(num_graphs=len(sizes), sizes=sizes, sampler="gumbel", edges_per_graph=0.0, degree="powerlaw",
                                    seed=17)                      # power-law in-degree: 2 n extra edges, a few hubs
     wl0 = synthetic.make_workload(cfg)
-    e_per_graph = torch.bincount(wl0.batch[wl0.edge_index[1]], minlength=len(sizes))
-    assert int(e_per_graph[41]) <= 256 or True
+    # graph 41 (60 nodes, 180 in-edges from the generator) gets 100 more in-edges: beyond the 256-slot cap by its edges alone
+    gen = torch.Generator().manual_seed(41)
+    off = sum(sizes[:41])
+    more = torch.randint(0, 60, (2, 100), generator=gen) + off
+    ei = torch.cat([wl0.edge_index, more], 1)
+    ea = torch.cat([wl0.edge_attr, torch.randn(100, wl0.edge_attr.size(1), generator=gen)])
+    gs = torch.stack([torch.bincount(wl0.batch, minlength=len(sizes)), torch.bincount(wl0.batch[ei[1]], minlength=len(sizes))])
+    wl = synthetic.Workload(wl0.x, ei, ea, wl0.batch, wl0.instr, wl0.glf, wl0.num_graphs, wl0.max_nodes, int(gs[1].max()), gs)
+    e_per_graph = gs[1]
+    assert sizes[41] <= 64 and int(e_per_graph[41]) > 256
+    big = [g for g in range(len(sizes)) if sizes[g] > 64 or int(e_per_graph[g]) > 256]
+    assert big == [0, 41, 82], big
+    plan = ops.GraphPlan.build(wl.batch.to(dev), wl.edge_index.to(dev), num_graphs=len(sizes))
+    assert _forced_mixed(lambda: plan.tile_mode(64, 256)) == "mixed"
+    assert plan.oversize(64, 256).gids.cpu().tolist() == big            # graph 41 goes to the per-graph kernels
     ops.reset_counters()
-    wl, (rl, rm, rg), (gl, gm, gg) = _forced_mixed(lambda: _run_both(cfg, dev))
+    (rl, rm, rg), (gl, gm, gg) = _forced_mixed(lambda: _run_both_wl(cfg, wl, dev))
     c = ops.counters()
+    n_big = sum(sizes[g] for g in big)
     assert c["oversize_nodes"] > 0 and c["tile_nodes"] > 0
+    # every tile-kernel call counts exactly the nodes of graphs 0, 41 and 82 as the per-graph kernels'
+    assert c["oversize_nodes"] % n_big == 0 and c["tile_nodes"] == (c["oversize_nodes"] // n_big) * (sum(sizes) - n_big), c
     assert torch.equal(gm > 0.5, rm > 0.5)
     assert (gl - rl).abs().max() < LOGIT_TOL, (gl - rl).abs().max()
     assert torch.allclose(gg, rg, atol=1e-5)

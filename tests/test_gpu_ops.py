@@ -1310,7 +1310,7 @@ def _greedy_tiles(sizes, edges, ncap, ecap, chunk=1024):
     return starts + [B]
 
 
-@pytest.mark.parametrize("case", ["cfg2", "tiny", "mixed", "oversize", "one", "edges"])
+@pytest.mark.parametrize("case", ["cfg2", "tiny", "mixed", "oversize", "one", "edges", "dense"])
 def test_tile_plan_is_the_greedy_packing(dev, case):
     from isubgvqa_amd import ops
     gen = torch.Generator().manual_seed(11)
@@ -1324,13 +1324,15 @@ def test_tile_plan_is_the_greedy_packing(dev, case):
         sizes = [5, 70, 3, 64, 1, 200, 2, 2]
     elif case == "one":
         sizes = [17]
+    elif case == "dense":            # ~7 in-edges per node: tiles fill by slots, > 1024 graphs
+        sizes = torch.randint(4, 25, (1500,), generator=gen).tolist()
     else:
         sizes = torch.randint(4, 30, (700,), generator=gen).tolist()
-    batch, ei = _rand_graphs(gen, sizes, extra_per_node=1.5)
+    batch, ei = _rand_graphs(gen, sizes, extra_per_node=6.0 if case == "dense" else 1.5)
     B = len(sizes)
     plan = ops.GraphPlan.build(batch.to(dev), ei.to(dev), num_graphs=B)
     ecount = torch.bincount(batch[ei[1]], minlength=B).tolist()
-    for ncap, ecap in ((64, 0),) + (((64, 160), (48, 96)) if case in ("edges", "cfg2") else ()):
+    for ncap, ecap in ((64, 0),) + (((64, 160), (48, 96), (64, 256)) if case in ("edges", "cfg2", "dense") else ()):
         tile_ptr, ntiles, cap, info = plan.tiles(ncap, ecap)
         want = _greedy_tiles(sizes, ecount, ncap, ecap)
         T = int(ntiles.item())
@@ -1348,17 +1350,20 @@ def test_tile_plan_is_the_greedy_packing(dev, case):
         cls = lambda w: min((w[3] + 31) // 32, 8)
         assert heavy == sorted(want_info, key=lambda w: -cls(w))          # Python's sort is stable: ties keep the tile order
         assert sorted(heavy) == sorted(want_info)
+        if case == "dense" and (ncap, ecap) == (64, 256):      # the shipped caps, filled by slots: the heaviest class (> 224) is reached
+            assert sum(w[3] > 224 for w in want_info) > 0 and sum(w[3] > 192 for w in want_info) > T // 2
 
 
-def _dense_tail_case(dev, sizes, seed, masked, with_next):
-    """The fused dense tail against the un-fused chain on the same inputs, and both against the CPU oracle's layer."""
+def _dense_tail_case(dev, sizes, seed, masked, with_next, topology=None):
+    """The fused dense tail against the un-fused chain on the same inputs, and both against the CPU oracle's layer.  topology:
+    (batch, edge_index) of graphs of these sizes made elsewhere (default: _rand_graphs)."""
     from isubgvqa_amd import ops
     from isubgvqa_amd.models import MGAT
     from oracle import model as OM
     from oracle import primitives as P
     gen = torch.Generator().manual_seed(seed)
     H, C = 4, 128
-    batch, ei = _rand_graphs(gen, sizes, extra_per_node=1.0)
+    batch, ei = _rand_graphs(gen, sizes, extra_per_node=1.0) if topology is None else topology
     N, B = batch.numel(), len(sizes)
     torch.manual_seed(seed)
     m = MGAT(channels=C, num_ins=1, heads=H, use_instr=True, masking_thresholds=[1.0], use_topk=True)
@@ -1575,7 +1580,7 @@ def test_tile_conv_is_bit_identical_to_the_edge_logits_pair(dev, mask, K):
     from oracle import model as OM
     gen = torch.Generator().manual_seed(17)
     H, C = 4, 128
-    for sizes, hub in (([1], None), ([20], None), ([64], None), ([64, 1, 63, 2, 62, 20, 20, 20, 5, 0, 3], (0, 150)),
+    for sizes, hub in (([1], None), ([20], None), ([64], None), ([64, 1, 63, 2, 62, 20, 20, 20, 5, 0, 3], (0, 90)),
                        (torch.randint(8, 34, (300,), generator=gen).tolist(), (7, 60))):
         batch, ei = _rand_graphs(gen, sizes, extra_per_node=1.5, hub=hub)
         N, E, B = batch.numel(), ei.size(1), len(sizes)
@@ -1587,9 +1592,9 @@ def test_tile_conv_is_bit_identical_to_the_edge_logits_pair(dev, mask, K):
         em = (torch.rand(E, generator=gen) < 0.7).float() if mask == "edge" else None
         d = lambda t: None if t is None else t.to(dev)
         plan = ops.GraphPlan.build(batch.to(dev), ei.to(dev), num_graphs=B)
-        assert ops.tile_conv_supported(plan, H, C, K) == (plan.emax <= 256)
-        if not ops.tile_conv_supported(plan, H, C, K):
-            continue
+        assert plan.emax <= 256 and ops.tile_conv_supported(plan, H, C, K), (sizes[:4], plan.emax)    # every case reaches the kernel
+        if hub is not None and hub[0] == 0:
+            assert plan.emax == 250        # graph 0: 64 self-loops, 96 random in-edges, 90 into its hub
         xd = d(x_lr)
         x_l, x_r, wd = xd[:, :H * C], xd[:, H * C:], d(w)
         out_t, al_t = ops.gatv2_tile_conv(x_l, x_r, d(ea), wd, d(att), plan, H, bias=d(bias), node_mask=d(nm), edge_mask=d(em),
@@ -1627,7 +1632,7 @@ def test_layer_conv_is_bit_identical_to_projection_plus_tile_conv(dev, mask, H, 
     with torch.no_grad():
         lin_l.bias.add_(0.1 * torch.randn(H * C, device=dev))
         lin_r.bias.add_(0.1 * torch.randn(H * C, device=dev))
-    cases = (([1], None), ([64], None), ([64, 1, 63, 2, 62, 20, 20, 20, 5, 0, 3], (0, 150)),
+    cases = (([1], None), ([64], None), ([64, 1, 63, 2, 62, 20, 20, 20, 5, 0, 3], (0, 90)),
              (torch.randint(8, 34, (700 if (H, K) == (4, 128) else 150,), generator=gen).tolist(), (7, 60)))
     for sizes, hub in cases:
         batch, ei = _rand_graphs(gen, sizes, extra_per_node=1.5, hub=hub)
@@ -1640,9 +1645,9 @@ def test_layer_conv_is_bit_identical_to_projection_plus_tile_conv(dev, mask, H, 
         em = (torch.rand(E, generator=gen) < 0.7).float() if mask == "edge" else None
         d = lambda t: None if t is None else t.to(dev)
         plan = ops.GraphPlan.build(batch.to(dev), ei.to(dev), num_graphs=B)
-        if not ops.layer_conv_supported(plan, H, C, 128, K):
-            assert plan.emax > 256
-            continue
+        assert plan.emax <= 256 and ops.layer_conv_supported(plan, H, C, 128, K), (sizes[:4], plan.emax)   # every case runs
+        if hub is not None and hub[0] == 0:
+            assert plan.emax == 250        # graph 0: 64 self-loops, 96 random in-edges, 90 into its hub
         xd, ead, wd = d(x), d(ea), d(w)
         with torch.no_grad():
             out_f, al_f = ops.gatv2_layer_conv(xd, lin_l, lin_r, ead, wd, d(att), plan, H, bias=d(bias), node_mask=d(nm),

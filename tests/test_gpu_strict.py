@@ -13,6 +13,7 @@ import torch
 
 from conftest import ROOT
 from test_gpu_ops import _rand_graphs
+from test_gpu_tile_capacity import capacity_batch, device_fill
 
 pytestmark = pytest.mark.gpu
 
@@ -184,3 +185,24 @@ def test_graph_tile_kernels_give_the_strict_builds_bits(dev, both, masked):
     nm = (torch.rand(N, generator=gen) < 0.6).float().to(dev) if masked else None
     fast, strict = both(lambda: ops.gatv2_tile_conv(xl, xr, ea, w, att, plan, H, bias=bias, node_mask=nm, want_rowmax=True))
     _same(fast, strict, "isg_gatv2_tile_conv")
+
+    # tiles filled to 256 slots (tests/test_gpu_tile_capacity.py): the layer kernel's next-tile request then really leads by two
+    # 64-slot chunks, mid-tile
+    from isubgvqa_amd.models.layers import GlorotLinear
+    torch.manual_seed(29)
+    lin_l, lin_r = GlorotLinear(128, H * C, bias=True).to(dev), GlorotLinear(128, H * C, bias=True).to(dev)
+    for name in ("dense", "exact"):
+        graphs, batch, ei, sizes, slots = capacity_batch(name)
+        N, E = batch.numel(), ei.size(1)
+        plan = ops.GraphPlan.build(batch.to(dev), ei.to(dev), num_graphs=len(graphs))
+        print(device_fill(name, plan, sizes, slots))
+        x = (torch.randn(N, 128, generator=gen) * torch.rand(N, 1, generator=gen).mul(3).exp()).to(dev)
+        xl = torch.randn(N, H * C, generator=gen).to(dev)
+        xr = torch.randn(N, H * C, generator=gen).to(dev)
+        ea = torch.randn(E, 128, generator=gen).to(dev)
+        nm = (torch.rand(N, generator=gen) < 0.6).float().to(dev) if masked else None
+        fast, strict = both(lambda: ops.gatv2_layer_conv(x, lin_l, lin_r, ea, w, att, plan, H, bias=bias, node_mask=nm,
+                                                         want_rowmax=True))
+        _same(fast, strict, f"isg_gatv2_layer_conv, {name} batch")
+        fast, strict = both(lambda: ops.gatv2_tile_conv(xl, xr, ea, w, att, plan, H, bias=bias, node_mask=nm, want_rowmax=True))
+        _same(fast, strict, f"isg_gatv2_tile_conv, {name} batch")
