@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the ISubGVQA inference hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 
 N>1 runs one rank per GPU under torch.distributed.run (RCCL).  Started WITHOUT a launcher (WORLD_SIZE unset) the
 script starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>` itself as a CHILD
@@ -19,31 +19,36 @@ north_star / configs[3]; --gather answers moves the arg-max answers instead and 
 --gather-depth (2) of them are in flight on the communicator's stream beside the next steps' kernels (the last ones are
 waited for inside the timed region).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line on rank 0: the headline
+figure (metric, value, unit, higher_is_better, dtype, ms_per_step), the run's config, and what the timed steps gave without
+a launch of their own:
+  summary       headline numbers, flat, at the front of the line (with --full: every leg's as well)
   roofline      the reference's message + aggregate: algorithmic bytes (e_proj included) / mean duration measured
                 with HIP events on the launch stream over the timed region, against the HBM peak.  By default that function
                 runs as TWO launches with lin_edge inside the first (isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits): the
-                bracket covers both, `parts` gives each against its own bytes, `unfused_kernel` the round-1 kernel timed in the
-                same run outside the timed region; --no-fuse-logits times the round-1 boundary as the step.  `traffic` is
+                bracket covers both, `parts` gives each against its own bytes, `unfused_kernel` (--full) the round-1 kernel timed
+                in the same run outside the timed region; --no-fuse-logits times the round-1 boundary as the step.  `traffic` is
                 replayed from the committed PMC summary of exactly those kernels (profiles/*_mp_traffic.json)
-  cpu_baseline  the CPU oracle (oracle/model.py, a port of the reference's PyG CPU path) timed on this host's usable
-                cores on a bounded sample of the same workload; .cfg1 = BASELINE configs[0] exactly
+  fallbacks     launches per step that left this library's dense kernels (0 = none), extra row-maximum passes
+  per_rank      (N > 1) every rank's own ms/step and its wait at the closing barrier
+  rccl          backend, world size, every rank's device index
+With --launch graph the timed region holds no HIP events: roofline and fallbacks come from eager steps that --full runs after it.
+--full (one GPU) then runs, after the timed steps and each on its own inputs, what the headline figure does not need
+(--no-cpu-baseline, --no-cfg5, ... leave single legs out):
+  dense_err_vs_fp32   error of the exact-split dense kernels relative to a plain fp32 GEMM's (vs fp64)
+  sustained     >= 2.5 s of back-to-back configs[1] steps behind the timed burst: ms/step and its ratio to the burst's
   full_model    the configs[2] stand-in (full model at C = 300) timed in the same run; .kernels = its two dominant kernels against
                 their rooflines from HIP events around every launch of three extra steps (isg_linear_h3p: TFLOP/s of fp16
                 products vs the 2.5 PF dense MFMA peak; the message-passing pair -- edge logits + flat kernel from logits --: SURVEY 8(d)'s
                 bytes at H C = 1200 vs HBM)
-  sustained     >= 2.5 s of back-to-back configs[1] steps behind the timed burst: ms/step and its ratio to the burst's
   cfg5          BASELINE configs[4] on one GPU (skewed graphs, AIMLE, fp16 rows): ms/step, MP kernel GB/s on s = 2 bytes, the
                 imbalance of contiguous graph ranges over 8 ranks
-  eval_batch    the reference's evaluation batch (1 024 graphs) on the product path: eager vs its hipGraph option (capture=True)
-  small_batch   the full model at 1 / 8 / 32 questions (run_token_coo.py's batch is one): eager and capture=True
-  summary       the legs' headline numbers, flat, at the front of the line
   mixed         the configs[1] batch with a few graphs beyond a graph tile (what real GQA batches are: the reference caps nothing):
                 ms/step with the tile kernels + the big graphs as a sub-batch (ops.run_split) and with the per-graph kernels for all
-  fallbacks     launches per step that left this library's dense kernels (0 = none), extra row-maximum passes
-  dense_err_vs_fp32   error of the exact-split dense kernels relative to a plain fp32 GEMM's (vs fp64)
-  per_rank      (N > 1) every rank's own ms/step and its wait at the closing barrier
-  rccl          backend, world size, every rank's device index
+  eval_batch    the reference's evaluation batch (1 024 graphs) on the product path: eager vs its hipGraph option (capture=True)
+  small_batch   the full model at 1 / 8 / 32 questions (run_token_coo.py's batch is one): eager and capture=True
+  cpu_baseline  the CPU oracle (oracle/model.py, a port of the reference's PyG CPU path) timed on this host's usable
+                cores on a bounded sample of the same workload; .cfg1 = BASELINE configs[0] exactly (null without --full)
 --launch graph replays the step as one captured hipGraph (single GPU; pays below ~500 graphs per step).
 --dump-outputs DIR writes what the last timed step returned (logits, mask, gate; rank 0's gathered rows with N > 1) as
 DIR/<name>.npy, float32 / float64, <= 64 MB in all: inputs, weights and sampler noise are seeded, so two builds run with
@@ -81,6 +86,10 @@ def parse(argv=None):
                          "fp16 feature rows) sharded into contiguous graph ranges balanced by sum(nodes + edges) "
                          "(distributed.shard_workload(balance=True)); ranks then hold different graph counts and the logits "
                          "all-gather is the ragged GatherPipeline (row counts exchanged once, rows padded to the largest shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the legs below (--no-* "
+                         "switches them off one by one), dense_err_vs_fp32, roofline.unfused_kernel, and with --launch graph "
+                         "the eager steps that give roofline and fallbacks")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the configs[4] leg (skewed graphs, AIMLE, fp16 rows)")
     ap.add_argument("--no-mixed", action="store_true", help="skip the mixed-dispatch leg (configs[1] + a few graphs beyond a tile)")
@@ -445,8 +454,8 @@ def time_unfused_mp(wl, cfg, dev, launches: int = 20):
             "traffic": load_traffic(N, E, "graph"), "launches_timed": len(ts)}
 
 
-# keys of the ONE JSON line (N = 1, default flags); validate_line() runs before the line is printed and in a CPU test over the
-# committed sample (profiles/r03_*bench.json)
+# keys of the ONE JSON line (N = 1, --full, no leg left out); validate_line() runs before the line is printed and in a CPU test
+# over the committed sample (profiles/r06_bench_sample.json)
 LINE_SCHEMA = {
     "": ["metric", "value", "unit", "summary", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
          "dtype", "data", "config", "roofline", "cpu_baseline", "rccl", "fallbacks", "dense_err_vs_fp32", "cfg5", "full_model", "mixed",
@@ -463,17 +472,21 @@ LINE_SCHEMA = {
     "mixed": ["workload", "graphs", "big_graphs", "nodes", "ms_per_step", "host_issue_ms_per_step", "dispatch",
               "tile_kernel_node_share", "per_graph_kernels_ms_per_step"],
 }
+# ... of which every line has these, a plain run's included
+HEADLINE_KEYS = ["metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "summary",
+                 "config", "rccl"]
 
 
 def validate_line(res: dict, full: bool = True) -> None:
-    """Raise if the line lacks a key the contract or VERDICT asks for.  full=False: a run with legs switched off (--no-*)."""
+    """Raise if the line lacks a key the contract or VERDICT asks for.  full=False: a plain run, or a --full run
+    with legs left out (--no-*): only the objects it has are checked."""
     for section, keys in LINE_SCHEMA.items():
         obj = res if section == "" else res.get(section)
         if obj is None:
             if full and section != "":
                 raise KeyError(f"bench line lacks the {section!r} object")
             continue
-        missing = [k for k in keys if k not in obj and (full or section != "")]
+        missing = [k for k in keys if k not in obj and (full or section != "" or k in HEADLINE_KEYS)]
         if missing:
             raise KeyError(f"bench line{' / ' + section if section else ''} lacks {missing}")
     if full and set(res["cfg5"]["imbalance_world8_max_over_mean"]) != {"equal_counts", "balanced"}:
@@ -769,6 +782,105 @@ def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES, se
     return info
 
 
+def mp_kinds(timer):
+    """(fused, tile_conv, layer_conv): which launches the message-passing timer bracketed in every step."""
+    fused = bool(timer.meta) and all(m.get("fused_logits") for m in timer.meta)
+    tile_conv = bool(timer.meta) and all(m.get("tile_conv") for m in timer.meta)
+    return fused, tile_conv, tile_conv and all(m.get("layer_conv") for m in timer.meta)
+
+
+def roofline_figures(timer, N: int, E: int, mp_kernel: str) -> dict:
+    """The `roofline` object from the message-passing launches `timer` bracketed (ops.MP_TIMER) and the committed traffic
+    summary of that kernel and batch shape.  No launches of its own: `unfused_kernel`, where the line has one, is left None
+    for the caller (time_unfused_mp, --full)."""
+    from isubgvqa_amd import ops
+    durs = timer.durations_ms()
+    bytes_l = [ops.mp_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["masked"], m.get("feat_bytes", 4)) for m in timer.meta]
+    mp_ms = sum(durs) / max(len(durs), 1)
+    mp_bytes = sum(bytes_l) / max(len(bytes_l), 1)
+    achieved = mp_bytes / (mp_ms * 1e-3) / 1e9 if durs else 0.0
+    # The reference's message + aggregate runs as TWO launches when lin_edge is folded into the logits
+    # (isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits): the bracket then covers both -- it also contains the lin_edge GEMM,
+    # which the un-fused kernel's bracket did not -- and `achieved` still divides SURVEY 8(d)'s bytes_mp (e_proj included)
+    # by it: a lower bound on what the round-1 definition would give, not comparable with a bracket of the MP kernel alone.
+    fused, tile_conv, layer_conv = mp_kinds(timer)
+    parts = None
+    if fused:
+        split = timer.split_ms()
+        own = [(ops.edge_logits_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["K"], m["masked"], feat_bytes=m.get("feat_bytes", 4)),
+                ops.mp_logits_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["masked"], feat_bytes=m.get("feat_bytes", 4)))
+               for m in timer.meta]
+        n = max(len(split), 1)
+        t0, t1 = sum(a for a, _ in split) / n, sum(b for _, b in split) / n
+        b0, b1 = sum(a for a, _ in own) / n, sum(b for _, b in own) / n
+        parts = [{"kernel": "gatv2_edge_logits_kernel (isg_gatv2_edge_logits: lin_edge GEMM + row gathers -> logits[E,H])",
+                  "avg_launch_us": round(t0 * 1e3, 2), "own_algorithmic_bytes": int(b0),
+                  "own_achieved_GBps": round(b0 / (t0 * 1e-3) / 1e9, 1), "own_frac": round(b0 / (t0 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
+                 {"kernel": "gatv2_mp_graph_kernel<2,1> (isg_gatv2_mp_fwd_logits: softmax + aggregation from logits)",
+                  "avg_launch_us": round(t1 * 1e3, 2), "own_algorithmic_bytes": int(b1),
+                  "own_achieved_GBps": round(b1 / (t1 * 1e-3) / 1e9, 1), "own_frac": round(b1 / (t1 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}]
+    traffic, traffic_src = load_traffic(N, E, "layer_conv" if layer_conv else ("tile_conv" if tile_conv else
+                                                                              ("logits_pair" if fused else mp_kernel)),
+                                        with_source=True)
+    roof = {"bound": "hbm",
+            "kernel": ("gatv2_layer_conv_kernel (isg_gatv2_layer_conv: the reference's message + aggregate WITH lin_edge AND "
+                       "lin_l | lin_r inside as ONE persistent launch on graph-aligned tiles)") if layer_conv else
+                      ("gatv2_tile_conv_kernel (isg_gatv2_tile_conv: the reference's message + aggregate WITH lin_edge "
+                       "inside as ONE persistent launch on graph-aligned tiles)") if tile_conv else
+                      ("isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits (the reference's message + aggregate WITH "
+                       "lin_edge inside: two launches, one bracket)") if fused else
+                      (("gatv2_mp_graph_kernel<2,1>" if mp_kernel == "graph" else "gatv2_mp_kernel<4,2>") + " (isg_gatv2_mp_fwd)"),
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+            "frac_of_measured_copy": round(achieved / HBM_COPY_GBPS, 4),
+            "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": int(mp_bytes),
+            "avg_launch_us": round(mp_ms * 1e3, 2), "launches_timed": len(durs)}
+    if tile_conv:
+        m0 = timer.meta[0]
+        # own minimum: edge planes + (x_l and x_r, or with lin_l | lin_r inside: the gated node rows) in, out + alpha back, CSR
+        own = sum(4 * m["E"] * m["K"] + (4 * m["N"] * m["K_in"] + 4 * m["N"] * m["H"] * m["C"] if m.get("layer_conv") else
+                                          12 * m["N"] * m["H"] * m["C"]) + 4 * m["E"] * m["H"] + 16 * m["E"] +
+                  (4 * m["E"] if m["masked"] else 0) for m in timer.meta) / len(timer.meta)
+        roof["note"] = ("bytes_mp of SURVEY 8(d) (x_l, x_r, e_proj included -- this kernel writes or reads none of them) "
+                        "over the time of the ONE launch that also contains the lin_edge GEMM" +
+                        (" and the lin_l | lin_r GEMM" if layer_conv else "") + ": a lower bound on the round-1 "
+                        "definition, the bracket holds strictly more work; own_* = the kernel against its own minimum "
+                        "traffic")
+        roof["own_algorithmic_bytes"] = int(own)
+        roof["own_achieved_GBps"] = round(own / (mp_ms * 1e-3) / 1e9, 1)
+        roof["own_frac"] = round(own / (mp_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+        flops = 3 * 2.0 * m0["E"] * m0["H"] * m0["C"] * m0["K"]
+        if layer_conv:
+            flops += 3 * 2.0 * m0["N"] * 2 * m0["H"] * m0["C"] * m0["K_in"]
+        roof["mfma_products_TFLOPs"] = round(flops / (mp_ms * 1e-3) / 1e12, 1)
+        # `bound` above is the contract's label for the path (graph / segmented-reduce work prices against HBM); what the
+        # counters say limits THIS kernel is neither of the two rooflines:
+        roof["own_bound"] = {
+            "limit": "issue + barrier lock-step: eight waves pass ~7 barriers per (tile, head), so vector issue, the matrix "
+                     "pipe and LDS add up instead of overlapping",
+            "hbm_frac_on_own_bytes": roof["own_frac"],
+            "mfma_frac_of_dense_fp16_peak": round(flops / (mp_ms * 1e-3) / 1e12 / 2500.0, 4),
+            "evidence": "profiles/r05_q_tile_kernels_sq_counters.txt (round 5: matrix cores 31 % busy, LDS 34 %, SQ_WAIT_ANY / SQ_WAVE_CYCLES = 0.43), "
+                        "profiles/r03_bg_layer_conv_ablation.md (the phases add)"}
+        if layer_conv:     # the launch also IS lin_l | lin_r: the bytes the reference's projection moves beside bytes_mp
+            proj = sum(4 * m["N"] * m["K_in"] + 8 * m["N"] * m["H"] * m["C"] for m in timer.meta) / len(timer.meta)
+            roof["with_projection_bytes"] = {
+                "what": "bytes_mp + the lin_l | lin_r projection's own traffic (x in, x_l and x_r out), the two reference steps "
+                        "this one launch performs; `frac` above counts bytes_mp only",
+                "algorithmic_bytes": int(mp_bytes + proj),
+                "achieved": round((mp_bytes + proj) / (mp_ms * 1e-3) / 1e9, 1),
+                "frac": round((mp_bytes + proj) / (mp_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+        roof["unfused_kernel"] = None
+    if fused:
+        roof["note"] = ("bytes_mp of SURVEY 8(d) (e_proj included, which this pair never writes or reads) over the "
+                        "time of BOTH launches, lin_edge GEMM included: a lower bound, not comparable with the "
+                        "round-1 bracket of the message-passing kernel alone; see parts and unfused_kernel")
+        roof["parts"] = parts
+        roof["unfused_kernel"] = None
+    return roof
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
@@ -873,15 +985,17 @@ def main(argv=None):
             fence()
             dt = time.perf_counter() - t0
             cap["plan"].verify_hints()
-            # kernel durations for the roofline: EAGER steps after the timed region (events cannot sit inside a graph)
-            ops.reset_counters()
-            ops.MP_TIMER = ops.KernelTimer()
-            for i in range(10):
-                step(i)
-            fence()
-            timer, ops.MP_TIMER = ops.MP_TIMER, None
-            # the captured step launches what these eager steps launch: their counters are the step's
-            step_counters = {k: round(v / 10, 3) for k, v in ops.counters().items()}
+            timer = None
+            if args.full:
+                # kernel durations for the roofline: EAGER steps after the timed region (events cannot sit inside a graph)
+                ops.reset_counters()
+                ops.MP_TIMER = ops.KernelTimer()
+                for i in range(10):
+                    step(i)
+                fence()
+                timer, ops.MP_TIMER = ops.MP_TIMER, None
+                # the captured step launches what these eager steps launch: their counters are the step's
+                step_counters = {k: round(v / 10, 3) for k, v in ops.counters().items()}
         else:
             for i in range(args.warmup):
                 step(i)
@@ -944,42 +1058,9 @@ def main(argv=None):
     rccl["gcn_arch"] = getattr(props, "gcnArchName", None)
     rccl["compute_units"] = int(props.multi_processor_count)
 
-    durs = timer.durations_ms()
-    bytes_l = [ops.mp_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["masked"], m.get("feat_bytes", 4)) for m in timer.meta]
-    mp_ms = sum(durs) / max(len(durs), 1)
-    mp_bytes = sum(bytes_l) / max(len(bytes_l), 1)
-    achieved = mp_bytes / (mp_ms * 1e-3) / 1e9 if durs else 0.0
-    # The reference's message + aggregate runs as TWO launches when lin_edge is folded into the logits
-    # (isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits): the bracket then covers both -- it also contains the lin_edge GEMM,
-    # which the un-fused kernel's bracket did not -- and `achieved` still divides SURVEY 8(d)'s bytes_mp (e_proj included)
-    # by it: a lower bound on what the round-1 definition would give, not comparable with a bracket of the MP kernel alone.
-    fused = bool(timer.meta) and all(m.get("fused_logits") for m in timer.meta)
-    tile_conv = bool(timer.meta) and all(m.get("tile_conv") for m in timer.meta)
-    layer_conv = tile_conv and all(m.get("layer_conv") for m in timer.meta)
-    parts = None
-    if fused:
-        split = timer.split_ms()
-        own = [(ops.edge_logits_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["K"], m["masked"], feat_bytes=m.get("feat_bytes", 4)),
-                ops.mp_logits_algorithmic_bytes(m["N"], m["E"], m["H"], m["C"], m["masked"], feat_bytes=m.get("feat_bytes", 4)))
-               for m in timer.meta]
-        n = max(len(split), 1)
-        t0, t1 = sum(a for a, _ in split) / n, sum(b for _, b in split) / n
-        b0, b1 = sum(a for a, _ in own) / n, sum(b for _, b in own) / n
-        parts = [{"kernel": "gatv2_edge_logits_kernel (isg_gatv2_edge_logits: lin_edge GEMM + row gathers -> logits[E,H])",
-                  "avg_launch_us": round(t0 * 1e3, 2), "own_algorithmic_bytes": int(b0),
-                  "own_achieved_GBps": round(b0 / (t0 * 1e-3) / 1e9, 1), "own_frac": round(b0 / (t0 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
-                 {"kernel": "gatv2_mp_graph_kernel<2,1> (isg_gatv2_mp_fwd_logits: softmax + aggregation from logits)",
-                  "avg_launch_us": round(t1 * 1e3, 2), "own_algorithmic_bytes": int(b1),
-                  "own_achieved_GBps": round(b1 / (t1 * 1e-3) / 1e9, 1), "own_frac": round(b1 / (t1 * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}]
-    # continuity with round 1: the UN-fused message-passing kernel on the same batch, timed here outside the timed region
-    unfused = None
-    if (fused or tile_conv) and rank == 0 and not cfg5:
-        unfused = time_unfused_mp(wl, cfg, dev)
+    _, tile_conv, layer_conv = mp_kinds(timer) if timer is not None else (False, False, False)
 
     if rank == 0:
-        traffic, traffic_src = load_traffic(N, E, "layer_conv" if layer_conv else ("tile_conv" if tile_conv else
-                                                                                   ("logits_pair" if fused else args.mp_kernel)),
-                                            with_source=True)
         res = {
             "metric": "GQA questions/sec", "value": round(total_graphs * args.steps / dt, 1),
             "unit": "questions/s",
@@ -1003,65 +1084,14 @@ def main(argv=None):
                        "layers": cfg.layers, "sampler": ("aimle" if cfg5 else "gumbel") + "(in-kernel Philox noise)", "k": cfg.sample_k,
                        "parallelism": (f"dp{world} (graphs sharded, RCCL all-gather of logits" + (", ragged shards" if cfg5 else "") + ")") if world > 1 else "dp1",
                        "feature_rows": args.features,
-                       "launch": "eager" if graph is None else "hipgraph: one captured step (plan build + model) replayed; Gumbel noise from torch's generator inside the graph; the roofline's kernel durations from eager steps after the timed region", "edge_projection": "unfused" if args.no_fuse_logits else ("inside isg_gatv2_layer_conv (with lin_l | lin_r)" if layer_conv else "inside isg_gatv2_tile_conv" if tile_conv else "folded into the logits"), "layer_tail": "isg_mgat_dense_tail (x_proj + instruction attention + GraphNorm + residual + next gate, one launch per layer)" if ops.FUSE_DENSE_TAIL else "un-fused", "dense": ("exact-split fp32 Linears on MFMA: isg_linear_f16x3 / _f16x3_tile (2 fp16 planes, 3 products, per-row scales), isg_linear_bf16x6 for the small ones" if args.gemm == "bf16x6" else "hipBLASLt fp32 via torch")},
-            "roofline": {"bound": "hbm",
-                         "kernel": ("gatv2_layer_conv_kernel (isg_gatv2_layer_conv: the reference's message + aggregate WITH lin_edge AND "
-                                    "lin_l | lin_r inside as ONE persistent launch on graph-aligned tiles)") if layer_conv else
-                                   ("gatv2_tile_conv_kernel (isg_gatv2_tile_conv: the reference's message + aggregate WITH lin_edge "
-                                    "inside as ONE persistent launch on graph-aligned tiles)") if tile_conv else
-                                   ("isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits (the reference's message + aggregate WITH "
-                                    "lin_edge inside: two launches, one bracket)") if fused else
-                                   (("gatv2_mp_graph_kernel<2,1>" if args.mp_kernel == "graph" else "gatv2_mp_kernel<4,2>") + " (isg_gatv2_mp_fwd)"),
-                         "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "frac_of_measured_copy": round(achieved / HBM_COPY_GBPS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": int(mp_bytes),
-                         "avg_launch_us": round(mp_ms * 1e3, 2), "launches_timed": len(durs)},
+                       "launch": "eager" if graph is None else "hipgraph: one captured step (plan build + model) replayed; Gumbel noise from torch's generator inside the graph" + ("; the roofline's kernel durations from eager steps after the timed region" if timer is not None else ""), "edge_projection": "unfused" if args.no_fuse_logits else None if timer is None else ("inside isg_gatv2_layer_conv (with lin_l | lin_r)" if layer_conv else "inside isg_gatv2_tile_conv" if tile_conv else "folded into the logits"), "layer_tail": "isg_mgat_dense_tail (x_proj + instruction attention + GraphNorm + residual + next gate, one launch per layer)" if ops.FUSE_DENSE_TAIL else "un-fused", "dense": ("exact-split fp32 Linears on MFMA: isg_linear_f16x3 / _f16x3_tile (2 fp16 planes, 3 products, per-row scales), isg_linear_bf16x6 for the small ones" if args.gemm == "bf16x6" else "hipBLASLt fp32 via torch")},
         }
-        res["summary"].update(roofline_frac=res["roofline"]["frac"], mp_avg_launch_us=res["roofline"]["avg_launch_us"])
-        if tile_conv:
-            m0 = timer.meta[0]
-            # own minimum: edge planes + (x_l and x_r, or with lin_l | lin_r inside: the gated node rows) in, out + alpha back, CSR
-            own = sum(4 * m["E"] * m["K"] + (4 * m["N"] * m["K_in"] + 4 * m["N"] * m["H"] * m["C"] if m.get("layer_conv") else
-                                              12 * m["N"] * m["H"] * m["C"]) + 4 * m["E"] * m["H"] + 16 * m["E"] +
-                      (4 * m["E"] if m["masked"] else 0) for m in timer.meta) / len(timer.meta)
-            res["roofline"]["note"] = ("bytes_mp of SURVEY 8(d) (x_l, x_r, e_proj included -- this kernel writes or reads none of them) "
-                                       "over the time of the ONE launch that also contains the lin_edge GEMM" +
-                                       (" and the lin_l | lin_r GEMM" if layer_conv else "") + ": a lower bound on the round-1 "
-                                       "definition, the bracket holds strictly more work; own_* = the kernel against its own minimum "
-                                       "traffic")
-            res["roofline"]["own_algorithmic_bytes"] = int(own)
-            res["roofline"]["own_achieved_GBps"] = round(own / (mp_ms * 1e-3) / 1e9, 1)
-            res["roofline"]["own_frac"] = round(own / (mp_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-            flops = 3 * 2.0 * m0["E"] * m0["H"] * m0["C"] * m0["K"]
-            if layer_conv:
-                flops += 3 * 2.0 * m0["N"] * 2 * m0["H"] * m0["C"] * m0["K_in"]
-            res["roofline"]["mfma_products_TFLOPs"] = round(flops / (mp_ms * 1e-3) / 1e12, 1)
-            # `bound` above is the contract's label for the path (graph / segmented-reduce work prices against HBM); what the
-            # counters say limits THIS kernel is neither of the two rooflines:
-            res["roofline"]["own_bound"] = {
-                "limit": "issue + barrier lock-step: eight waves pass ~7 barriers per (tile, head), so vector issue, the matrix "
-                         "pipe and LDS add up instead of overlapping",
-                "hbm_frac_on_own_bytes": res["roofline"]["own_frac"],
-                "mfma_frac_of_dense_fp16_peak": round(flops / (mp_ms * 1e-3) / 1e12 / 2500.0, 4),
-                "evidence": "profiles/r05_q_tile_kernels_sq_counters.txt (round 5: matrix cores 31 % busy, LDS 34 %, SQ_WAIT_ANY / SQ_WAVE_CYCLES = 0.43), "
-                            "profiles/r03_bg_layer_conv_ablation.md (the phases add)"}
-            if layer_conv:     # the launch also IS lin_l | lin_r: the bytes the reference's projection moves beside bytes_mp
-                proj = sum(4 * m["N"] * m["K_in"] + 8 * m["N"] * m["H"] * m["C"] for m in timer.meta) / len(timer.meta)
-                res["roofline"]["with_projection_bytes"] = {
-                    "what": "bytes_mp + the lin_l | lin_r projection's own traffic (x in, x_l and x_r out), the two reference steps "
-                            "this one launch performs; `frac` above counts bytes_mp only",
-                    "algorithmic_bytes": int(mp_bytes + proj),
-                    "achieved": round((mp_bytes + proj) / (mp_ms * 1e-3) / 1e9, 1),
-                    "frac": round((mp_bytes + proj) / (mp_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
-            res["roofline"]["unfused_kernel"] = unfused
-        if fused:
-            res["roofline"]["note"] = ("bytes_mp of SURVEY 8(d) (e_proj included, which this pair never writes or reads) over the "
-                                       "time of BOTH launches, lin_edge GEMM included: a lower bound, not comparable with the "
-                                       "round-1 bracket of the message-passing kernel alone; see parts and unfused_kernel")
-            res["roofline"]["parts"] = parts
-            res["roofline"]["unfused_kernel"] = unfused
+        if timer is not None:
+            res["roofline"] = roofline_figures(timer, N, E, args.mp_kernel)
+            res["summary"].update(roofline_frac=res["roofline"]["frac"], mp_avg_launch_us=res["roofline"]["avg_launch_us"])
+            if args.full and "unfused_kernel" in res["roofline"] and not cfg5:
+                # continuity with round 1: the UN-fused message-passing kernel on the same batch, timed outside the timed region
+                res["roofline"]["unfused_kernel"] = time_unfused_mp(wl, cfg, dev)
         res["rccl"] = rccl
         if dumped is not None:
             res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
@@ -1070,11 +1100,14 @@ def main(argv=None):
         # launches per step that left this library's dense kernels (hipBLASLt / torch LayerNorm / torch attention) and extra
         # row-maximum passes: DESIGN section 1's "no GEMM of the inference path runs on hipBLASLt" as a number
         res["fallbacks"] = step_counters
-        if world == 1:
+        # --full: the legs the headline figure does not need (an accuracy check, other workloads, sizes and precisions, the CPU
+        # baselines), each after the timed steps on its own inputs; a plain run prints its line without them
+        legs = args.full and world == 1
+        if legs:
             progress("dense_err_vs_fp32 leg")
             with torch.no_grad():
                 res["dense_err_vs_fp32"] = dense_err_vs_fp32(dev)
-        if world == 1 and not cfg5 and not args.no_sustained:
+        if legs and not cfg5 and not args.no_sustained:
             # >= 2 s of back-to-back configs[1] steps: the clocks under load, and something the driver's busy sampler can see
             progress("sustained leg (>= 2 s of steps)")
             with torch.no_grad():
@@ -1088,7 +1121,7 @@ def main(argv=None):
             res["sustained"] = {"seconds": round(ds, 3), "steps": n_s, "ms_per_step": round(ds / n_s * 1e3, 4),
                                 "ratio_to_burst": round((ds / n_s) / (dt / args.steps), 4)}
             res["summary"]["sustained_ms_per_step"] = res["sustained"]["ms_per_step"]
-        if world == 1 and not cfg5 and not args.no_full_model:
+        if legs and not cfg5 and not args.no_full_model:
             del model, wl
             torch.cuda.empty_cache()
             progress(f"configs[1] step timed: {dt / args.steps * 1e3:.3f} ms; full model leg ({args.full_model_graphs} graphs)")
@@ -1098,21 +1131,21 @@ def main(argv=None):
                                   full_model_questions_per_s=res["full_model"]["questions_per_s"],
                                   full_model_linear_h3p_frac_of_mfma_peak=fk["linear_h3p"]["frac"],
                                   full_model_mp_pair_frac_of_hbm_peak=fk["gatv2_mp_pair"]["frac"])
-        if world == 1 and not cfg5 and not args.no_cfg5:
+        if legs and not cfg5 and not args.no_cfg5:
             progress("cfg5 leg (skewed graphs, AIMLE, fp16 rows)")
             res["cfg5"] = cfg5_leg(dev)
             res["summary"].update(cfg5_ms_per_step=res["cfg5"]["ms_per_step"], cfg5_mp_frac_of_hbm_peak=res["cfg5"]["mp_frac_of_hbm_peak"])
-        if world == 1 and not cfg5 and not args.no_mixed:
+        if legs and not cfg5 and not args.no_mixed:
             progress("mixed leg (configs[1] + 8 graphs beyond a tile)")
             res["mixed"] = mixed_leg(dev)
             res["summary"].update(mixed_ms_per_step=res["mixed"]["ms_per_step"],
                                   mixed_host_issue_ms_per_step=res["mixed"]["host_issue_ms_per_step"])
-        if world == 1 and not cfg5 and not args.no_mixed:
+        if legs and not cfg5 and not args.no_mixed:
             progress("eval_batch leg (1024 graphs: eager vs the product path's hipGraph option)")
             res["eval_batch"] = eval_batch_leg(dev)
             res["summary"].update(eval_batch_1024_eager_ms=res["eval_batch"]["eager_ms_per_step"],
                                   eval_batch_1024_captured_ms=res["eval_batch"]["captured_ms_per_step"])
-        if world == 1 and not cfg5 and not args.no_full_model:
+        if legs and not cfg5 and not args.no_full_model:
             progress("small_batch leg (full model at 1 / 8 / 32 questions: eager vs capture=True)")
             res["small_batch"] = small_batch_leg(dev)
             sb = res["small_batch"]["sizes"]
@@ -1120,7 +1153,7 @@ def main(argv=None):
                                   full_model_1_question_language_captured_ms=sb["1"]["language_captured_ms"],
                                   full_model_8_questions_captured_ms=sb["8"]["captured_ms"])
         ops.check_plans()           # any understated GraphPlan hint of this run raises here
-        if world == 1 and not cfg5 and not args.no_cpu_baseline:
+        if legs and not cfg5 and not args.no_cpu_baseline:
             progress("cpu_baseline leg (oracle on the host cores)")
             res["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample_graphs, args.cpu_seconds, args.cpu_threads)
             res["cpu_baseline"]["cpu"] = cpu_model_string()
@@ -1130,8 +1163,8 @@ def main(argv=None):
             res["summary"]["cpu_full_model_1_question_ms"] = min(v for k, v in sq.items() if k.endswith("_ms"))
         else:
             res["cpu_baseline"] = None
-        validate_line(res, full=world == 1 and not cfg5 and not (args.no_cpu_baseline or args.no_full_model or args.no_cfg5 or args.no_mixed
-                                                    or args.no_sustained))
+        validate_line(res, full=legs and not cfg5 and not (args.no_cpu_baseline or args.no_full_model or args.no_cfg5 or args.no_mixed
+                                                 or args.no_sustained))
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -128,11 +128,11 @@ def test_traffic_summaries_are_tied_to_kernel_kind_batch_shape_and_kernel_source
     assert bench.load_traffic(N, E, "layer_conv") is not None
 
 
-SAMPLE = "r06_bench_sample.json"        # a default-flag `python bench.py` line of this round, committed under profiles/ by name
+SAMPLE = "r06_bench_sample.json"        # a `python bench.py --full` line of this round, committed under profiles/ by name
 
 
 def test_bench_line_schema_on_the_committed_sample():
-    """The committed default-flag bench line of this round (profiles/r04_bench_sample.json: an explicit file, not "the newest
+    """The committed `--full` bench line of this round (profiles/r06_bench_sample.json: an explicit file, not "the newest
     by name") carries every object the contract and the review ask for: roofline, cpu_baseline (+cfg1), fallbacks,
     dense_err_vs_fp32, cfg5 (with the 8-rank imbalance of both partitions and the fp32-rows leg), full_model; a line without
     one of them must be rejected -- and so must a line whose `fallbacks` is None (what `--launch graph` produced in round 3)."""
@@ -235,3 +235,40 @@ def test_steps_sets_the_timed_steps_and_must_be_positive():
     assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
     with pytest.raises(SystemExit):
         bench.parse(["--steps", "0"])
+
+
+def test_a_plain_run_leaves_every_extra_leg_to_full():
+    """A plain `bench.py --steps N --warmup W` does only what its headline figure needs: every call in main() of a leg that runs
+    launches or CPU passes of its own after the timed steps, and the eager steps a captured run adds for its roofline, sit in the
+    body of an `if` on --full (`args.full`, or `legs` = args.full on one GPU).  --full is off by default."""
+    import ast
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    legs = {"dense_err_vs_fp32", "full_model_rate", "cfg5_leg", "mixed_leg", "eval_batch_leg", "small_batch_leg", "cpu_baseline",
+            "cpu_baseline_cfg1", "cpu_baseline_single_question", "time_unfused_mp"}
+    seen = []
+
+    def visit(node, guarded, in_graph_branch):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name):
+            if node.func.id in legs or (in_graph_branch and node.func.id == "step"):
+                seen.append(node.func.id)
+                assert guarded, f"bench.py:{node.lineno}: {node.func.id}() runs without --full"
+        if isinstance(node, ast.If):
+            test = ast.unparse(node.test)
+            on_full = "args.full" in test or "legs" in test
+            graph = in_graph_branch or test == "args.launch == 'graph'"
+            visit(node.test, guarded, in_graph_branch)
+            for n in node.body:
+                visit(n, guarded or on_full, graph)
+            for n in node.orelse:
+                visit(n, guarded, in_graph_branch)
+            return
+        for child in ast.iter_child_nodes(node):
+            visit(child, guarded, in_graph_branch)
+
+    visit(main, False, False)
+    assert legs <= set(seen) and "step" in seen, sorted(set(seen))
+    assert all(ast.unparse(n.value).startswith("args.full and ") for n in ast.walk(main) if isinstance(n, ast.Assign)
+               and any(isinstance(t, ast.Name) and t.id == "legs" for t in n.targets))
