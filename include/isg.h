@@ -293,7 +293,10 @@ int isg_gatv2_tile_conv(const float *x_l, int32_t ldl, const float *x_r, int32_t
  * stay in LDS: neither tensor exists in memory, the logit epilogue gathers both from LDS.  wn_frag / wn_inv_scale =
  * isg_split_f16x2_frag of cat(lin_l.weight, lin_r.weight) [2*H*C,128]; bn fp32 [2*H*C] = cat of their biases; the remaining
  * operands as isg_gatv2_tile_conv.  Bit-identical to isg_linear_f16x3 + isg_gatv2_tile_conv.  ISG_EUNSUPPORTED unless C == 128,
- * K_in == 128, K_edge <= 128, K_edge % 4 == 0, H <= 16. */
+ * K_in == 128, K_edge <= 128, K_edge % 4 == 0, H <= 16.
+ * Masked launches skip the slots whose mask is +-0 (edge product, logit, aggregation term): with finite inputs their
+ * logit is +0 and their term adds nothing, so the results are unchanged.  A skipped slot whose x_l, x_r or edge projection holds an
+ * Inf or NaN gets the logit +0 where the reference gives NaN.  ISG_LC_DENSE_MASK=1 (read once) walks every slot instead. */
 int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
                          const float *bn,
                          const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,

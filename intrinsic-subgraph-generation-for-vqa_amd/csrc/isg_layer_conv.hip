@@ -39,7 +39,8 @@ constexpr int LC_OFF_A = 2 * LC_ROWS * LC_LDX * 4;                    // panel i
 constexpr int LC_OFF_TAB = LC_OFF_A + 2 * 64 * LC_LDA * 2;
 constexpr int LC_OFF_RAW = LC_OFF_TAB + 2 * (LC_ECAP * 16 + LC_ECAP * 4 + 68 * 4) + LC_ECAP * 4 + 4 * 64 * 4 + 64 * 4 + 3 * LC_C * 4 +
                            4 * LC_C * 4;                              // the next tile's node rows as they come from memory (fp32)
-constexpr int LC_SMEM_BYTES = LC_OFF_RAW + LC_ROWS * LC_K * 4;
+constexpr int LC_OFF_LIVE = LC_OFF_RAW + LC_ROWS * LC_K * 4;          // [2 table sets][4] live-slot bit words (masked layers)
+constexpr int LC_SMEM_BYTES = LC_OFF_LIVE + 2 * 4 * 8;
 static_assert(LC_OFF_RAW % 16 == 0, "16-byte pieces");
 static_assert(LC_SMEM_BYTES <= 160 * 1024, "one workgroup per CU");
 
@@ -61,6 +62,44 @@ struct LcArgs {
   int N, E, H, KSE, NTE, ldo;
   float slope;
 };
+
+// The live slots of a masked tile: bit s of w[s >> 6] is set when slot s carries a mask whose bits are not +-0.  A slot with a
+// zero mask has the logit +0 whatever its inputs (finite ones: z * 0 = +-0 twice over, and fmaf(+-0, att, +0) = +0) and adds
+// fmaf(x_l, +-0, o) = o to its destination, so the edge product, the logit epilogue and the aggregation's products skip it.
+struct LcLive {
+  const unsigned long long *w;      // the four words in LDS
+  int p1, p2, p3, n;                // live slots in words < 1, < 2, < 3, in all
+};
+
+// one table set's words: the prefix counts are wave-uniform (every lane reads the same LDS words)
+__device__ __forceinline__ LcLive lc_live_load(const unsigned long long *sw) {
+  int c[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    c[i] = __builtin_amdgcn_readfirstlane(__popc((unsigned)sw[i]) + __popc((unsigned)(sw[i] >> 32)));
+  return LcLive{sw, c[0], c[0] + c[1], c[0] + c[1] + c[2], c[0] + c[1] + c[2] + c[3]};
+}
+
+// slot of the k-th live slot (0 <= k < L.n): CSR order is kept.  The word is a per-lane LDS read (a select chain over four
+// words in registers is turned into an indexed array in scratch memory).
+__device__ __forceinline__ int lc_nth_live(const LcLive &L, int k) {
+  const int i = (k >= L.p1) + (k >= L.p2) + (k >= L.p3);
+  const unsigned long long w = L.w[i];
+  k -= i == 0 ? 0 : i == 1 ? L.p1 : i == 2 ? L.p2 : L.p3;
+  // halving steps as selects, not branches: the four lookups of a chunk's plane requests then interleave
+  int base = 64 * i;
+  unsigned x = (unsigned)w;
+  int c = __popc(x);
+  bool up = k >= c;
+  x = up ? (unsigned)(w >> 32) : x; base += up ? 32 : 0; k -= up ? c : 0;
+#pragma unroll
+  for (int h = 16; h >= 2; h >>= 1) {
+    c = __popc(x & ((1u << h) - 1u));
+    up = k >= c;
+    x = up ? x >> h : x; base += up ? h : 0; k -= up ? c : 0;
+  }
+  return base + (k >= (int)(x & 1u) ? 1 : 0);
+}
 
 // gelu(x * instr[batch]) -> fp32 rows (optional) + scaled (hi, mid) planes + inverse row scale: 32 lanes x 4 channels per row
 __global__ __launch_bounds__(256) void instr_gate_planes_kernel(const float *__restrict__ x, const float *__restrict__ instr,
@@ -199,7 +238,8 @@ __global__ __launch_bounds__(256, 3) void node_gate_planes_kernel(const _Float16
 // KSE_T: 16-column steps of the edge product when known at compile time (8 = the 128 edge features of the model: no branch between
 // the MFMAs), 0 = read it from the arguments
 // SL01: 0 <= negative_slope <= 1 (the reference's 0.2): leaky_relu(z) = max(z, slope z), one instruction less per value
-template <bool MASKED, int KSE_T, bool SL01>
+// LIVE (masked layers): the chunks walk only the live slots (LcLive); false = every slot (ISG_LC_DENSE_MASK=1)
+template <bool MASKED, int KSE_T, bool SL01, bool LIVE>
 __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
   typedef float (*BufX)[LC_LDX];
@@ -216,6 +256,8 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
   float *s_inv = s_part + 4 * 64;             // inverse row scales of the node planes
   float *s_att = s_inv + 64, *s_weinv = s_att + LC_C;
   float *s_bias = s_weinv + LC_C, *s_bn = s_bias + LC_C, *s_wninv = s_bn + 2 * LC_C;             // [x_l 128 | x_r 128] biases / inverse scales of the head
+  unsigned long long *s_livew = reinterpret_cast<unsigned long long *>(lc_smem + LC_OFF_LIVE);   // [2][4] (LcLive)
+  constexpr bool cmp = MASKED && LIVE;
 
   const int bid = blockIdx.x;
   const int per_xcd = gridDim.x >> 3, jx = bid >> 3;
@@ -304,12 +346,26 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     if (MASKED && tid < min((d).w, LC_ECAP))                                                                         \
       rec_n.w = __float_as_int(a.edge_mask ? a.edge_mask[rec_n.y] : a.node_mask[rec_n.x] * a.node_mask[rec_n.z]);      \
   }
+  // the tile's live slots (compacted walk): waves 0-3 hold slots tid; the masks have landed.  Read behind the next barrier.
+#define LC_BALLOT(d, b)                                                                                              \
+  {                                                                                                                  \
+    if (tid < LC_ECAP) {                                                                                             \
+      const unsigned long long bw = __ballot(tid < min((d).w, LC_ECAP) && (rec_n.w & 0x7fffffff) != 0);              \
+      if (lane == 0) s_livew[(b) * 4 + wave] = bw;                                                                   \
+    }                                                                                                                \
+  }
   // the tile's first chunk of edge planes: requested AFTER the aggregation (16 registers that phase needs), still a node GEMM
-  // ahead of its use
-#define LC_REQUEST_PLANES(d)                                                                                         \
+  // ahead of its use.  Compacted: the chunk's slots are the first 64 live ones of table set `b` (its words are complete).
+#define LC_REQUEST_PLANES(d, b)                                                                                      \
   {                                                                                                                  \
     const int e0n = (d).z, nen = min((d).w, LC_ECAP);                                                                \
-    if (nen > 0) {                                                                                                   \
+    if (cmp) {                                                                                                       \
+      const LcLive lvn = lc_live_load(s_livew + (b) * 4);                                                            \
+      if (lvn.n > 0) {                                                                                               \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                                \
+          ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0n + lc_nth_live(lvn, min(srow + 16 * u, lvn.n - 1))) * 256 + sc4 * 8); \
+      }                                                                                                              \
+    } else if (nen > 0) {                                                                                            \
       _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                                  \
         ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0n + min(srow + 16 * u, nen - 1)) * 256 + sc4 * 8); \
     }                                                                                                                \
@@ -338,11 +394,13 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     float einv_n, xinv_n;
     LC_REQUEST_TILE(desc)
     LC_REQUEST_MASKS(desc)
-    LC_REQUEST_PLANES(desc)
+    if (!cmp) LC_REQUEST_PLANES(desc, 0)
     LC_STORE_TILE(desc, 0)
     LC_PLANES_LANDED()
+    if (cmp) LC_BALLOT(desc, 0)
   }
   __syncthreads();
+  if (cmp) LC_REQUEST_PLANES(desc, 0)      // behind the barrier that completes the live words (once per workgroup)
   LC_STAMP(0)              // first tile's inputs (exposed once per workgroup)
   int cur = 0;             // table set of the tile in hand
 
@@ -356,6 +414,10 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     const int4 *s_tab = s_tab0 + cur * LC_ECAP;
     const float *s_einv = s_einv0 + cur * LC_ECAP;
     const int *s_rp = s_rp0 + cur * 68;
+    // slots the chunks walk: the live ones, or all.  The words are read again where a slot is looked up (LDS broadcast reads):
+    // held in registers over the tile they pushed the kernel into spilling.
+    const int nact = cmp ? lc_live_load(s_livew + cur * 4).n : ne;
+#define LC_LIVE() const LcLive lv = lc_live_load(s_livew + cur * 4);
 
     // ---- node GEMM: [lin_l | lin_r]_head . x^T, this wave's 32 channels x all 64 nodes.  TRANSPOSED like the edge product (W
     // fragment = A operand, node panel = B operand): a lane then holds ONE node and 16 channels of it in four runs of four, which
@@ -392,6 +454,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
       // with the previous tile's slices and tables; the next tile's tables and s_inv are complete.
       __syncthreads();
       LC_STAMP(7)            // hand-over barrier
+      if (cmp && tid < ne) s_lg[tid] = 0.f;        // the skipped slots' logits (the live ones are written over behind barriers)
       float(*dstx)[LC_LDX] = ct < 4 ? sXl : sXr;
       int frl = fr, hhl = hh;          // laundered: the addresses below, hoisted out of the tile loop, were spilled and came back
       asm volatile("" : "+v"(frl), "+v"(hhl));       // from scratch one dependent load at a time (700 cycles per tile)
@@ -414,7 +477,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     LC_STAMP(9)              // node GEMM: epilogue
     // chunk 0's edge planes (requested before the previous tile's aggregation) into the panel image, free since the last chunk's
     // barrier: ONE barrier covers the slices and the first panel
-    if (ne > 0) {
+    if (nact > 0) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) *reinterpret_cast<hf32x4 *>(&sA[sc4 >> 4][srow + 16 * u][(sc4 & 15) * 8]) = ra[u];
     }
@@ -434,7 +497,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     // ---- 64-slot chunks: edge planes -> panel image, transposed product, logit epilogue (isg_mp_logits.hip) --------------------
     // (Running the two 32-slot halves of a chunk one phase apart -- waves 0-3 in chunk c's product while waves 4-7 are in chunk
     // c - 1's epilogue -- did not overlap the matrix and the vector pipe: 304 vs 302 us, profiles/r03_aw_*.)
-    const int nchunk = (ne + 63) >> 6;
+    const int nchunk = (nact + 63) >> 6;
     const int creq = max(nchunk - 2, 0);       // two chunks of lead: one chunk (4 k cycles) did not cover the requests' latency
     const int prow = half * 32 + fr;
     hf32x16 acc;
@@ -444,7 +507,8 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     // 4 chains (one group of reads at a time: all four in flight are 64 registers, which the allocator took from the resident W)
 #define LC_EPILOGUE_(ch, SL01)                                                                                       \
   {                                                                                                                  \
-    const int slot = min(64 * (ch) + prow, ne - 1);                                                                  \
+    int slot = min(64 * (ch) + prow, ne - 1);                                                                        \
+    if (cmp) { LC_LIVE() slot = lc_nth_live(lv, min(64 * (ch) + prow, nact - 1)); }                                  \
     const float sinv = s_einv[slot];                                                                                 \
     int4 rec = s_tab[slot];                                                                                          \
     const float me = own_reg(__int_as_float(rec.w));    /* a scalar: never the high dword of the record's (z, w) pair */  \
@@ -486,13 +550,20 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
       }
       if (c == creq) LC_REQUEST_TILE(desc_n)
       if (c + 1 < nchunk) {      // the next chunk's planes: in flight under this chunk's product and epilogue
+        if (cmp) {
+          LC_LIVE()
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
-          ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0 + min(64 * (c + 1) + srow + 16 * u, ne - 1)) * 256 + sc4 * 8);
+          for (int u = 0; u < 4; ++u)
+            ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0 + lc_nth_live(lv, min(64 * (c + 1) + srow + 16 * u, nact - 1))) * 256 + sc4 * 8);
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0 + min(64 * (c + 1) + srow + 16 * u, ne - 1)) * 256 + sc4 * 8);
+        }
       }
       // a chunk's upper 32 slots are often past the tile's end (its last chunk holds ne mod 64 slots): the four waves of that half
       // then skip product and epilogue, and the other four have their SIMDs to themselves
-      const bool live = half == 0 || 64 * c + 32 < ne;
+      const bool live = half == 0 || 64 * c + 32 < nact;
       if (live) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -520,12 +591,17 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
       if (live) LC_EPILOGUE(c)
       __syncthreads();
       LC_STAMP(4)            // epilogue + barrier
-      if (tid < 64 && 64 * c + tid < ne)     // the tile-waves' partials in a fixed order
-        s_lg[64 * c + tid] = (s_part[tid] + s_part[64 + tid]) + (s_part[128 + tid] + s_part[192 + tid]);
+      if (tid < 64 && 64 * c + tid < nact) {   // the tile-waves' partials in a fixed order
+        int slot = 64 * c + tid;
+        if (cmp) { LC_LIVE() slot = lc_nth_live(lv, slot); }
+        s_lg[slot] = (s_part[tid] + s_part[64 + tid]) + (s_part[128 + tid] + s_part[192 + tid]);
+      }
     }
 #undef LC_EPILOGUE
 #undef LC_EPILOGUE_
+#undef LC_LIVE
     LC_PLANES_LANDED()       // requested two chunks ago
+    if (cmp && nchunk > 0) LC_BALLOT(desc_n, cur ^ 1)
     __syncthreads();
 
     // ---- softmax + aggregation (isg_mp_graph.hip phase C: same operations in the same order) ----------------------------------
@@ -537,10 +613,11 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
       LC_REQUEST_TILE(desc_n)
       LC_REQUEST_MASKS(desc_n)
       LC_PLANES_LANDED()
+      if (cmp) LC_BALLOT(desc_n, cur ^ 1)
       __syncthreads();
     }
     LC_STORE_TILE(desc_n, cur ^ 1)      // panel image and scales are free since the last chunk's barrier; tables: the other set
-    LC_REQUEST_PLANES(desc_n)
+    LC_REQUEST_PLANES(desc_n, cur ^ 1)
     LC_STAMP(5)              // the next tile's planes and tables
     // 8 lanes per node (four 16-byte pieces each, 128 contiguous bytes per instruction): a wave aggregates EIGHT nodes at a time,
     // ONE pass covers the tile.  The phase is issue-bound on its per-node bookkeeping (bounds, records, softmax, stores), which a
@@ -662,6 +739,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
 #undef LC_REQUEST_TILE
 #undef LC_REQUEST_PLANES
 #undef LC_REQUEST_MASKS
+#undef LC_BALLOT
 #undef LC_STORE_TILE
 #undef LC_PLANES_LANDED
   ISG_DIAG_DUMP(g_lc_stamps, bid * 8 + wave, 12, )
@@ -728,6 +806,8 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
       (E > 0 && (!edge_planes || !edge_inv_scale || !eid || !src || !dst || !alpha)) || !we_frag || !we_inv_scale || !att || !rowptr ||
       !tile_info || !ntiles || !out)
     return ISG_EINVAL;
+  // ISG_LC_DENSE_MASK=1: a masked layer walks every slot, as before the live-slot walk (A/B; the same bits either way)
+  static const bool dense_mask = [] { const char *e = getenv("ISG_LC_DENSE_MASK"); return e && atoi(e) != 0; }();
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   LcArgs a = {
       .xp = reinterpret_cast<const _Float16 *>(x_planes), .xinv = x_inv_scale, .Wn = reinterpret_cast<const _Float16 *>(wn_frag),
@@ -746,20 +826,25 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
   if (gpx > need) gpx = (int)need;
   const unsigned grid = 8u * (unsigned)H * (unsigned)gpx;
   hipStream_t st = as_stream(stream);
-#define LC_LAUNCH(M, KT, SL)                                                                                         \
+#define LC_LAUNCH(M, KT, SL, LV)                                                                                     \
   {                                                                                                                  \
-    if (!dyn_lds_ok<&gatv2_layer_conv_kernel<M, KT, SL>>(LC_SMEM_BYTES)) return ISG_EUNSUPPORTED;                    \
-    gatv2_layer_conv_kernel<M, KT, SL><<<grid, LC_THREADS, LC_SMEM_BYTES, st>>>(a);                                  \
+    if (!dyn_lds_ok<&gatv2_layer_conv_kernel<M, KT, SL, LV>>(LC_SMEM_BYTES)) return ISG_EUNSUPPORTED;                \
+    gatv2_layer_conv_kernel<M, KT, SL, LV><<<grid, LC_THREADS, LC_SMEM_BYTES, st>>>(a);                              \
+  }
+#define LC_LAUNCH_M(KT, SL)                                                                                          \
+  {                                                                                                                  \
+    if (dense_mask) LC_LAUNCH(true, KT, SL, false) else LC_LAUNCH(true, KT, SL, true)                                \
   }
   const bool masked = node_mask || edge_mask;
   const bool sl01 = negative_slope >= 0.f && negative_slope <= 1.f;
   if (a.KSE == 8 && sl01) {
-    if (masked) LC_LAUNCH(true, 8, true) else LC_LAUNCH(false, 8, true)
+    if (masked) LC_LAUNCH_M(8, true) else LC_LAUNCH(false, 8, true, false)
   } else if (sl01) {
-    if (masked) LC_LAUNCH(true, 0, true) else LC_LAUNCH(false, 0, true)
+    if (masked) LC_LAUNCH_M(0, true) else LC_LAUNCH(false, 0, true, false)
   } else {
-    if (masked) LC_LAUNCH(true, 0, false) else LC_LAUNCH(false, 0, false)
+    if (masked) LC_LAUNCH_M(0, false) else LC_LAUNCH(false, 0, false, false)
   }
+#undef LC_LAUNCH_M
 #undef LC_LAUNCH
   return check_launch();
 }

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Where does a wave of isg_gatv2_layer_conv spend its cycles?  Uses tools/_build/libisg_dt_stamp.so (tools/stamp_dense_tail.py
---build makes it with -DISG_DIAG)."""
+--build makes it with -DISG_DIAG).
+
+--masked: the masked launch, with the node mask the model's masked layer (BASELINE configs[1]'s third, Gumbel top-k) gives on this
+batch -- taken from one forward of the model -- and, first, how many of each tile's CSR slots that mask leaves live (nonzero)."""
 import ctypes
 import os
 import sys
@@ -35,6 +38,33 @@ out = torch.empty(N, H * C, device=dev)
 alpha = torch.empty(E, H, device=dev)
 rowmax = torch.empty(N, H, device=dev)
 xp = ops.node_planes(x)
+nm_arg = 0
+if "--masked" in sys.argv:
+    seen = []
+    real = ops.gatv2_layer_conv
+
+    def spy(*args, **kw):
+        if kw.get("node_mask") is not None:
+            seen.append(kw["node_mask"].reshape(-1).float().contiguous().clone())
+        return real(*args, **kw)
+
+    ops.gatv2_layer_conv = spy
+    with torch.no_grad():
+        net(wl, seed=1000)
+    ops.gatv2_layer_conv = real
+    assert len(seen) == 1, f"{len(seen)} masked layer_conv launches in one forward"
+    node_mask = seen[0]
+    nm_arg = node_mask.data_ptr()
+    tinfo = tile_info[:int(ntiles.item())].long().cpu()
+    live_slot = ((node_mask[plan.src.long()] * node_mask[plan.dst.long()]) != 0).cpu()
+    cs = torch.cat([torch.zeros(1, dtype=torch.long), live_slot.long().cumsum(0)])
+    ne = tinfo[:, 3].clamp(max=256)
+    live = cs[tinfo[:, 2] + ne] - cs[tinfo[:, 2]]
+    picked = (node_mask != 0).float().sum().item()
+    print(f"masked layer: {picked:.0f} of {N} nodes picked; {int(live.sum())} of {int(ne.sum())} tile slots live "
+          f"({100 * live.sum().item() / max(ne.sum().item(), 1):.2f} %); per tile: slots {ne.float().mean():.1f}, live {live.float().mean():.2f} "
+          f"(max {int(live.max())}); 64-slot chunks per tile: every slot {((ne + 63) // 64).float().mean():.2f}, live slots "
+          f"{((live + 63) // 64).float().mean():.2f}; tiles without a live slot {int((live == 0).sum())} of {len(ne)}")
 buf = torch.zeros(4096 * 8, 16, dtype=torch.int64, device=dev)
 assert stamp.isg_lc_set_stamp_buffer(buf.data_ptr()) == 0
 att = conv.att.detach().reshape(-1).contiguous()
@@ -43,7 +73,7 @@ for rep in range(2):
     rc = stamp.isg_gatv2_layer_conv(xp.planes.data_ptr(), xp.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(),
                                     ep_inv.data_ptr(), we.data_ptr(), we_inv.data_ptr(), att.data_ptr(), conv.bias.data_ptr(),
                                     plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
-                                    tile_info.data_ptr(), ntiles.data_ptr(), cap, 0, 0, out.data_ptr(), H * C, alpha.data_ptr(),
+                                    tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, alpha.data_ptr(),
                                     rowmax.data_ptr(), N, E, H, C, 128, 128, 0.2, torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     torch.cuda.synchronize()
