@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ISG_ABI_VERSION 20
+#define ISG_ABI_VERSION 21
 
 #define ISG_OK 0
 #define ISG_EINVAL (-1)       /* null pointer / negative size / inconsistent sizes          */
@@ -256,7 +256,12 @@ int isg_tile_plan(const int32_t *ptr, const int32_t *eptr, int64_t B, int32_t no
  * intermediate's row scales come from |x_proj.0(a)_ij| <= max_k |a_ik| * y_bound[0] + y_bound[1]); ins / ins_next fp32[B,C]; h, h_out, xg_out fp32[N,C] (h_out must not
  * alias h); batch int64[N].  Arithmetic of the tail: isg_instr_attn_graphnorm_residual's.  ISG_EUNSUPPORTED unless
  * K1 = 512, MID = 256, C = 128 (BASELINE configs[1]); graphs beyond 64 nodes are truncated to the tile (callers test
- * the batch's bound first). */
+ * the batch's bound first).
+ * row_dead (NULL, or uint8 [N,4], 4-byte aligned: what a masked isg_gatv2_layer_conv launch left for conv_out) selects the
+ * live-row form: a workgroup takes `group` (1..4; ignored without row_dead) consecutive tiles, runs x_proj ONCE on their live rows
+ * plus the first dead one -- rows whose four flags are set hold the same 512 floats and the same maxima, and x_proj is local to
+ * a row, so they share one result -- and then the tail of each tile.  A group with more than 64 such rows runs tile by tile.  The
+ * same bits as with row_dead = NULL.  ISG_DT_DENSE_ROWS=1 (read once) ignores row_dead. */
 int isg_mgat_dense_tail(const float *conv_out, int32_t lda, const float *a_rowmax, int32_t P, int32_t ldp,
                         const uint16_t *w1_frag, const float *w1_inv_scale, const float *b1, const float *y_bound,
                         const uint16_t *w2_frag,
@@ -264,8 +269,8 @@ int isg_mgat_dense_tail(const float *conv_out, int32_t lda, const float *a_rowma
                         const float *gn_weight, const float *gn_bias, const float *gn_mean_scale, double eps,
                         const float *node_mask, const float *ins_next, float *h_out, float *xg_out, uint16_t *xp_out,
                         float *xinv_out, const int32_t *ptr, const int64_t *batch, const int32_t *tile_ptr,
-                        const int32_t *tile_info, const int32_t *ntiles, int64_t max_tiles, int64_t N, int32_t K1, int32_t MID,
-                        int32_t C, void *stream);
+                        const int32_t *tile_info, const int32_t *ntiles, int64_t max_tiles, const uint8_t *row_dead,
+                        int32_t group, int64_t N, int32_t K1, int32_t MID, int32_t C, void *stream);
 
 /* MaskingGATv2Conv.message + aggregate with lin_edge inside as ONE launch on graph-aligned tiles (isg_tile_plan with node_cap =
  * 64, edge_cap = 256 and tile_info):   ISubGVQA/models/mgat_v2_conv.py:243-279 (lin_edge :259-261)
@@ -296,15 +301,18 @@ int isg_gatv2_tile_conv(const float *x_l, int32_t ldl, const float *x_r, int32_t
  * K_in == 128, K_edge <= 128, K_edge % 4 == 0, H <= 16.
  * Masked launches skip the slots whose mask is +-0 (edge product, logit, aggregation term): with finite inputs their
  * logit is +0 and their term adds nothing, so the results are unchanged.  A skipped slot whose x_l, x_r or edge projection holds an
- * Inf or NaN gets the logit +0 where the reference gives NaN.  ISG_LC_DENSE_MASK=1 (read once) walks every slot instead. */
+ * Inf or NaN gets the logit +0 where the reference gives NaN.  ISG_LC_DENSE_MASK=1 (read once) walks every slot instead.
+ * row_dead (NULL, or uint8 [N,H], 4-byte aligned; written by masked launches only): 1 when every bit of the (row, head)'s
+ * aggregation accumulators was zero before the bias went in -- the row of `out` is then +0 + bias and its rowmax that vector's,
+ * whatever the inputs were -- else 0.  isg_mgat_dense_tail runs x_proj once for all such rows of a group of tiles. */
 int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
                          const float *bn,
                          const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,
                          const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr,
                          const int32_t *eid, const int32_t *src, const int32_t *dst, const int32_t *tile_info,
                          const int32_t *ntiles, int64_t max_tiles, const float *node_mask, const float *edge_mask, float *out,
-                         int32_t ldo, float *alpha, float *rowmax, int64_t N, int64_t E, int32_t H, int32_t C, int32_t K_in,
-                         int32_t K_edge, float negative_slope, void *stream);
+                         int32_t ldo, float *alpha, float *rowmax, uint8_t *row_dead, int64_t N, int64_t E, int32_t H, int32_t C,
+                         int32_t K_in, int32_t K_edge, float negative_slope, void *stream);
 
 /* GlobalAttention.forward on graph-aligned 64-row tiles as one launch:   ISubGVQA/models/att_pooling.py:57-77
  *   xn = node_nn(x) (Linear GELU Linear) * node_mask;  gate = softmax_g(<xn_n, q_g> / sqrt(C)) (+1e-16);  out_g = sum_n gate_n xn_n

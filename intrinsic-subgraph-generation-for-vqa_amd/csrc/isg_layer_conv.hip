@@ -61,6 +61,8 @@ struct LcArgs {
   float *rowmax;                    // optional
   int N, E, H, KSE, NTE, ldo;
   float slope;
+  unsigned char *row_dead;          // optional, masked launches: [N, H], 1 = every accumulator bit of the (row, head) was zero
+                                    // (last: the fields before it keep the offsets the unmasked instantiations were compiled with)
 };
 
 // The live slots of a masked tile: bit s of w[s >> 6] is set when slot s carries a mask whose bits are not +-0.  A slot with a
@@ -714,6 +716,15 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
             for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[u].x][32 * m + j8 * 4]);
         }
         float rmx = 0.f;
+        // (row, head) is DEAD when no accumulator bit is set: the row written below is then +0 + bias and its maximum that vector's,
+        // whatever the inputs were (a NaN or Inf that came through a masked slot left bits behind: live).  isg_mgat_dense_tail runs
+        // x_proj once for all dead rows of a group of tiles.
+        unsigned zb = 0u;
+        if (MASKED) {
+#pragma unroll
+          for (int m = 0; m < 4; ++m)
+            zb |= __float_as_uint(o[m].x) | __float_as_uint(o[m].y) | __float_as_uint(o[m].z) | __float_as_uint(o[m].w);
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           if (a.bias) {
@@ -727,6 +738,12 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
         if (a.rowmax) {
           rmx = group_max<8>(rmx);
           if (j8 == 0) a.rowmax[(int64_t)(r0 + k) * a.H + hd] = rmx;
+        }
+        if (MASKED && a.row_dead) {
+          zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR1>((int)zb);
+          zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR2>((int)zb);
+          zb |= (unsigned)dpp_mov_i<ISG_DPP_HMIRROR>((int)zb);
+          if (j8 == 0) a.row_dead[(int64_t)(r0 + k) * a.H + hd] = zb == 0u ? 1 : 0;
         }
       }
     }
@@ -794,7 +811,8 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
                                     const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr,
                                     const int32_t *eid, const int32_t *src, const int32_t *dst, const int32_t *tile_info,
                                     const int32_t *ntiles, int64_t max_tiles, const float *node_mask, const float *edge_mask,
-                                    float *out, int32_t ldo, float *alpha, float *rowmax, int64_t N, int64_t E, int32_t H,
+                                    float *out, int32_t ldo, float *alpha, float *rowmax, uint8_t *row_dead, int64_t N, int64_t E,
+                                    int32_t H,
                                     int32_t C, int32_t K_in, int32_t K_edge, float negative_slope, void *stream) {
   if (N < 0 || E < 0 || H <= 0 || C <= 0 || K_in <= 0 || K_edge <= 0 || max_tiles < 0 || ldo < H * C) return ISG_EINVAL;
   auto mis = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
@@ -815,7 +833,7 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
       .We = reinterpret_cast<const _Float16 *>(we_frag), .we_inv = we_inv_scale, .att = att, .bias = bias, .rowptr = rowptr,
       .eid = eid, .src = src, .dst = dst, .ntiles = ntiles, .tile_info = reinterpret_cast<const int4 *>(tile_info),
       .edge_mask = edge_mask, .node_mask = node_mask, .out = out, .alpha = alpha, .rowmax = rowmax, .N = (int)N, .E = (int)E,
-      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope};
+      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead};
   if (!a.xp || !a.xinv || !a.Wn || !a.wn_inv || !a.bn || (a.E > 0 && (!a.ep || !a.ep_inv || !a.eid || !a.src || !a.dst || !a.alpha)) ||
       !a.We || !a.we_inv || !a.att || !a.rowptr || !a.tile_info || !a.ntiles || !a.out)
     return ISG_EINVAL;                         // the struct the kernel dereferences, not the parameters it was filled from

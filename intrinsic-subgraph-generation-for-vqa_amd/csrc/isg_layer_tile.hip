@@ -19,13 +19,17 @@
 //   rows: wave per node for <ins_g, c_n> / sqrt(C), wave per graph for the softmax, thread per channel walking a graph's
 //   nodes IN ORDER with unfused mul + add (the CPU scatter kernels' order and roundings), + h, * mask; the result and, when
 //   a next layer exists, gelu(result * ins_next[g]) are written out.
-// HBM traffic per layer at configs[1]: conv_out 168 MB + h 42 MB in, h' and x' 84 MB out (un-fused chain: ~590 MB).
+// HBM traffic per layer at configs[1]: conv_out 168 MB + h 42 MB in, h' and x' 84 MB out (un-fused chain: ~590 MB).  The masked
+// layer's launch (live-row form below) reads the rows a live slot reached plus one dead row per three tiles:
+// conv_out 24 MB of the 168, the flags 0.3 MB.
 #include "isg_f16x3.hpp"
 
 #include "isg_diag.hpp"
 
+#include <type_traits>
+
 ISG_DIAG_BUFFER(g_dt_stamps)            // -DISG_DIAG builds only (tools/stamp_dense_tail.py, stamp_tile_conv.py): [tile * 4 + wave][16] int64
-#define DT_STAMP(i) ISG_DIAG_SET(i)     // the dense tail: one pass per launch
+#define DT_STAMP(i) ISG_DIAG_ADD(i)     // the dense tail: one pass per launch, or (live-row form) summed over a group's tiles
 #define TC_STAMP(i) ISG_DIAG_ADD(i)     // the tile convolution: persistent, accumulated over its tiles
 
 namespace isg {
@@ -208,6 +212,10 @@ constexpr int DT_GST = 8;                        // graphs of a tile whose instr
 constexpr int DT_SMEM_BYTES = DT_BUF_BYTES + (3 * 64 + 4 * 64 + 64 + 64 + 64 + 2 * DT_GST * DT_C + DT_GPC + 4) * 4;      // 80,912
 static_assert(2 * DT_ROWS * DT_LDY * 2 <= DT_BUF_BYTES && DT_ROWS * DT_LDC * 4 + 2 * 32 * DT_C * 4 <= DT_BUF_BYTES, "aliases must fit");
 static_assert(2 * DT_SMEM_BYTES <= 160 * 1024, "two workgroups per CU");
+// the live-row form adds the row list [64], the map group row -> compact row [256 bytes] and eight wave counts
+constexpr int DT_GROUP_MAX = 4;
+constexpr int DT_LIVE_SMEM_BYTES = DT_SMEM_BYTES + (DT_ROWS + DT_GROUP_MAX * DT_ROWS / 4 + 8) * 4;                        // 81,456
+static_assert(2 * DT_LIVE_SMEM_BYTES <= 160 * 1024, "two workgroups per CU");
 
 struct DtArgs {
   const float *a;          // conv output [N, 512], row stride lda
@@ -228,8 +236,20 @@ struct DtArgs {
   const long long *batch;
   int N, lda, P, ldp;
   float eps, denom;
+  // the live-row form's (last: the fields before them keep the offsets the other form was compiled with)
+  const unsigned *row_dead;  // [N] words of four flag bytes (isg_gatv2_layer_conv's row_dead at H = 4); NULL in the other form
+  int group, max_tiles;      // tiles per workgroup, entries of tile_info
 };
 
+// Two pieces: x_proj (header scales, staging, GEMM1, epilogue 1, GEMM2, epilogue 2: everything in it is local to a row -- the panel
+// is the MFMAs' B operand, so a lane's results belong to one row, and equal input rows give bit-equal rows of c wherever they sit)
+// and the tail of one tile (phases A, B, C: these mix the rows of a graph).
+// LIVE = false: one tile per workgroup, x_proj over the tile's rows r0 + row.
+// LIVE = true (the conv output of a masked layer, with its dead-row flags): a workgroup takes a.group consecutive tiles, lists
+// their live rows and the FIRST dead one (every dead row holds the same 512 floats and maxima: +0 + bias), runs x_proj once over
+// the list -- its second 32-row block only when the list is longer than 32 -- and then each tile's tail, which reads c through the
+// map group row -> list position.  A group whose list would pass 64 rows runs x_proj per tile with the identity list.
+template <bool LIVE>
 __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dt_smem[];
   typedef _Float16 (*BufA)[2][DT_ROWS][DT_LDA];       // [buffer][plane][row][k]
@@ -244,46 +264,119 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
   float *s_mask = s_f + 576;
   float *s_ins = s_f + 640, *s_insn = s_f + 640 + DT_GST * DT_C;       // [DT_GST][C] each
 
-  const int t = blockIdx.x;
-  const int4 tinfo = a.tile_info[t];        // requested together with the count (entries beyond it are never used)
-  if (t >= *a.ntiles) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  ISG_DIAG_BEGIN()
-  const int fr = lane & 31, hh = lane >> 5, fk = hh * 8;
-  const int r0 = tinfo.x;
-  const int nrows = min(tinfo.y, DT_ROWS);
-  if (nrows <= 0) return;
-  const int g0 = a.tile_ptr[t], g1 = a.tile_ptr[t + 1];      // needed by the tail only: off the rows' critical path
+  int *s_gp = reinterpret_cast<int *>(s_f + 2688);      // node offsets of the tile's first DT_GPC graphs: the tail's loops read these
+  int *s_list = reinterpret_cast<int *>(s_f + 2820);                        // LIVE: list position -> global row
+  unsigned char *s_cpos = reinterpret_cast<unsigned char *>(s_f + 2884);    // LIVE: row of the group -> list position
+  int *s_w = reinterpret_cast<int *>(s_f + 2948);                           // LIVE: live rows / first dead row per wave
 
-  // ---- staging map: 8 float4 per thread and chunk; the 32 lanes of a half-wave hold one 512-byte row piece -----------------
-  const int srow = tid >> 5, sc4 = tid & 31;          // rows srow + 8 u
+  // (not const: the live-row form derives them again per tile of its group, DT_LANE_IDS below)
+  int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int fr = lane & 31, hh = lane >> 5, fk = hh * 8;
+  int srow = tid >> 5, sc4 = tid & 31;                // staging map: rows srow + 8 u, float4 sc4 of a 128-wide chunk
+  int gi = tid >> 5, c4 = tid & 31;
+  int voff = lane * 16;
+  // the tile of the tail (LIVE: the current one of the group) and the rows of x_proj
+  int t = blockIdx.x, r0 = 0, nrows = 0, g0 = 0, g1 = 0, ng = 0, L = 0, tb = 0, t0 = 0, gt = 1;
+  bool grouped = false;
+  if constexpr (!LIVE) {
+    const int4 tinfo = a.tile_info[t];        // requested together with the count (entries beyond it are never used)
+    if (t >= *a.ntiles) return;
+    r0 = tinfo.x;
+    nrows = min(tinfo.y, DT_ROWS);
+    if (nrows <= 0) return;
+    L = nrows;
+    g0 = a.tile_ptr[t], g1 = a.tile_ptr[t + 1];      // needed by the tail only: off the rows' critical path
+    ng = g1 - g0;
+  } else {
+    // ---- the group's rows, one thread each: flags -> live rows compacted in row order, then the first dead row ---------------
+    t0 = blockIdx.x * a.group;
+    int4 ti[DT_GROUP_MAX];
+#pragma unroll
+    for (int k = 0; k < DT_GROUP_MAX; ++k) ti[k] = a.tile_info[min(t0 + k, a.max_tiles - 1)];
+    const int nt = *a.ntiles;
+    if (t0 >= nt) return;
+    gt = min(a.group, nt - t0);
+    int bk[DT_GROUP_MAX + 1];
+    bk[0] = 0;
+#pragma unroll
+    for (int k = 0; k < DT_GROUP_MAX; ++k) bk[k + 1] = bk[k] + (k < gt ? max(min(ti[k].y, DT_ROWS), 0) : 0);
+    const int total = bk[DT_GROUP_MAX];
+    if (total == 0) return;
+    int gr = ti[0].x + tid;
+#pragma unroll
+    for (int k = 1; k < DT_GROUP_MAX; ++k)
+      if (tid >= bk[k]) gr = ti[k].x + tid - bk[k];
+    const bool has = tid < total;
+    gr = min(max(gr, 0), a.N - 1);
+    const bool dead = has && a.row_dead[gr] == 0x01010101u;
+    const bool live = has && !dead;
+    const unsigned long long lb = __ballot(live), db = __ballot(dead);
+    if (lane == 0) {
+      s_w[wave] = __popcll(lb);
+      s_w[4 + wave] = db ? wave * 64 + (int)__builtin_ctzll(db) : 256;
+    }
+    __syncthreads();
+    int before = 0, nlive = 0, fd = 256;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_w[w];
+      if (w < wave) before += c;
+      nlive += c;
+      fd = min(fd, s_w[4 + w]);
+    }
+    nlive = __builtin_amdgcn_readfirstlane(nlive);
+    fd = __builtin_amdgcn_readfirstlane(fd);
+    const int Lg = nlive + (fd < 256 ? 1 : 0);
+    grouped = Lg <= DT_ROWS;
+    if (grouped) {
+      L = Lg;
+      const int pos = before + __popcll(lb & ((1ull << lane) - 1ull));
+      if (live) { s_list[pos] = gr; s_cpos[tid] = (unsigned char)pos; }
+      if (dead) s_cpos[tid] = (unsigned char)nlive;
+      if (tid == fd) s_list[nlive] = gr;      // the representative is read like any other row: nothing here assumes `bias`
+    }
+  }
+  ISG_DIAG_BEGIN()
+  hf32x4 rh[8];              // the tile's residual rows (LIVE = false: in flight under GEMM2), used by the last pass of the tail
+  // what the tail's header requests and files: the tile's graph ids, masks, node offsets, instruction rows
+  int h_gid = 0, h_gp = 0;
+  float h_mask = 1.f;
+  float4 h_ins = make_float4(0.f, 0.f, 0.f, 0.f), h_insn = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  // x's row at position `row` of x_proj's panel
+#define DT_ROW(row) (LIVE ? s_list[min(row, L - 1)] : min(r0 + min(row, nrows - 1), a.N - 1))
+  auto x_proj = [&](auto ni_c) __attribute__((always_inline)) {
+  constexpr int NI = decltype(ni_c)::value;      // 32-row blocks of the panel: 2, or 1 when the list fits the first
+  constexpr int NU = 4 * NI;
+  if constexpr (LIVE) __syncthreads();           // the list is filed; the previous tile's tail is done with the buffers
+  // ---- staging: NU float4 per thread and chunk; the 32 lanes of a half-wave hold one 512-byte row piece ----------------------
 #define DT_LOAD_CHUNK(c)                                                                                         \
-  _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                                \
+  _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                               \
     const int row = srow + 8 * u;                                                                                \
-    const int gr = min(r0 + min(row, nrows - 1), a.N - 1);                                                       \
+    const int gr = DT_ROW(row);                                                                                  \
     { const hf32x4 t_ = __builtin_nontemporal_load(reinterpret_cast<const hf32x4 *>(a.a + (int64_t)gr * a.lda + (c) * DT_KC + sc4 * 4)); ra[u] = make_float4(t_[0], t_[1], t_[2], t_[3]); } \
   }
-  float4 ra[8];
+  float4 ra[NU];
   DT_LOAD_CHUNK(0)               // in flight under the tile's bookkeeping
   // Every other input of the header is requested HERE, unconditionally (clamped indices), before anything is used: a load inside
   // `if (tid < 64) { ... s_x[tid] = p[i]; }` is waited for inside its branch, and the header was eight such round trips in a row
   // (9 900 cycles of a workgroup's 90 000: profiles/r03_g_dense_tail_stamps.txt); now it is the one behind tile_info / tile_ptr.
-  const int ng = g1 - g0;
-  const int hrow = min(r0 + min(tid, nrows - 1), a.N - 1);          // the row whose scales thread tid < DT_ROWS files
+  const int hrow = DT_ROW(tid);          // the row whose scales thread tid < DT_ROWS files
   const float *rm = a.a_rowmax + (int64_t)hrow * a.ldp;
   float rmv[4];
 #pragma unroll
   for (int p = 0; p < 4; ++p) rmv[p] = rm[min(p, a.P - 1)];
-  const int h_gid = (int)a.batch[hrow];
-  float h_mask = 1.f;
-  if (a.node_mask) h_mask = a.node_mask[hrow];                      // (wave-uniform: the pointer is a kernel argument)
-  const int h_gp = a.ptr[g0 + min(tid, ng)];
-  const int gi = tid >> 5, c4 = tid & 31;
-  const int gi_c = min(gi, max(min(ng, DT_GST) - 1, 0));
-  const float4 h_ins = *reinterpret_cast<const float4 *>(a.ins + (int64_t)(g0 + gi_c) * DT_C + c4 * 4);
-  float4 h_insn = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (a.ins_next) h_insn = *reinterpret_cast<const float4 *>(a.ins_next + (int64_t)(g0 + gi_c) * DT_C + c4 * 4);
+#define DT_TAIL_REQUEST(trow)                                                                                    \
+  h_gid = (int)a.batch[trow];                                                                                    \
+  if (a.node_mask) h_mask = a.node_mask[trow];                      /* (wave-uniform: the pointer is a kernel argument) */ \
+  h_gp = a.ptr[g0 + min(tid, ng)];                                                                               \
+  {                                                                                                              \
+    const int gi_c = min(gi, max(min(ng, DT_GST) - 1, 0));                                                       \
+    h_ins = *reinterpret_cast<const float4 *>(a.ins + (int64_t)(g0 + gi_c) * DT_C + c4 * 4);                     \
+    if (a.ins_next) h_insn = *reinterpret_cast<const float4 *>(a.ins_next + (int64_t)(g0 + gi_c) * DT_C + c4 * 4); \
+  }
+  if constexpr (!LIVE) { DT_TAIL_REQUEST(hrow) }
   if (tid < DT_ROWS) {     // the row's scale from the producer's partial maxima: one round of loads per tile
     float mx = fmaxf(fmaxf(rmv[0], rmv[1]), fmaxf(rmv[2], rmv[3]));      // (P < 4: the clamped reads repeat the last one)
     for (int p = 4; p < a.P; ++p) mx = fmaxf(mx, rm[p]);
@@ -297,25 +390,28 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
     h3_scale(fmaf(mx, a.y_bound[0], a.y_bound[1]), s, inv);
     s_scale2[tid] = s;
     s_inv2[tid] = inv;
-    s_gid[tid] = h_gid;
-    s_mask[tid] = h_mask;
+    if constexpr (!LIVE) {
+      s_gid[tid] = h_gid;
+      s_mask[tid] = h_mask;
+    }
   }
-  int *s_gp = reinterpret_cast<int *>(s_f + 2688);      // node offsets of the tile's first DT_GPC graphs: the tail's loops read these
-  if (tid <= min(ng, DT_GPC)) s_gp[tid] = h_gp - r0;
-  // the instruction rows of the tile's first DT_GST graphs (this layer's and the next one's): 32 lanes per row
-  if (gi < min(ng, DT_GST)) {
-    *reinterpret_cast<float4 *>(&s_ins[gi * DT_C + c4 * 4]) = h_ins;
-    if (a.ins_next) *reinterpret_cast<float4 *>(&s_insn[gi * DT_C + c4 * 4]) = h_insn;
+  // node offsets; the instruction rows of the tile's first DT_GST graphs (this layer's and the next one's): 32 lanes per row
+#define DT_TAIL_FILE()                                                                                           \
+  if (tid <= min(ng, DT_GPC)) s_gp[tid] = h_gp - r0;                                                             \
+  if (gi < min(ng, DT_GST)) {                                                                                    \
+    *reinterpret_cast<float4 *>(&s_ins[gi * DT_C + c4 * 4]) = h_ins;                                             \
+    if (a.ins_next) *reinterpret_cast<float4 *>(&s_insn[gi * DT_C + c4 * 4]) = h_insn;                           \
   }
+  if constexpr (!LIVE) { DT_TAIL_FILE() }
   __syncthreads();
-  float sa[8];
+  float sa[NU];
 #pragma unroll
-  for (int u = 0; u < 8; ++u) sa[u] = s_rmax[srow + 8 * u];
+  for (int u = 0; u < NU; ++u) sa[u] = s_rmax[srow + 8 * u];
 #define DT_WRITE_CHUNK(b)                                                                                        \
-  _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                                \
+  _Pragma("unroll") for (int u = 0; u < NU; ++u) {                                                               \
     const int row = srow + 8 * u;                                                                                \
     float4 v = ra[u];                                                                                            \
-    if (row >= nrows) v = make_float4(0.f, 0.f, 0.f, 0.f);                                                       \
+    if (row >= L) v = make_float4(0.f, 0.f, 0.f, 0.f);                                                           \
     v.x *= sa[u]; v.y *= sa[u]; v.z *= sa[u]; v.w *= sa[u];                                                      \
     hf16x4 hi = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};                                    \
     hf16x4 mid = {(_Float16)(v.x - (float)hi[0]), (_Float16)(v.y - (float)hi[1]), (_Float16)(v.z - (float)hi[2]), \
@@ -331,33 +427,32 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
   constexpr unsigned plane1 = (unsigned)(DT_MID / 32) * DT_KS1 * 1024u;
   const __amdgpu_buffer_rsrc_t wr1 =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.w1f), 0, (int)(2u * plane1), 0x00020000);
-  const int voff = lane * 16;
-  hf32x16 acc[2][2];
+  hf32x16 acc[NI][2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  hf16x8 wq[4][2][2], af[2][2];      // W fragments three k-steps ahead; ONE set of panel fragments: a step's LDS reads are
+  hf16x8 wq[4][2][2], af[NI][2];      // W fragments three k-steps ahead; ONE set of panel fragments: a step's LDS reads are
                                      // issued behind the previous step's twelve MFMAs (384 cycles of matrix-core work)
 #define DT_LOADW1(st, s)                                                                                         \
   _Pragma("unroll") for (int j = 0; j < 2; ++j) _Pragma("unroll") for (int q = 0; q < 2; ++q)                    \
       wq[st][j][q] = __builtin_bit_cast(hf16x8, __builtin_amdgcn_raw_buffer_load_b128(                           \
           wr1, voff, (int)(((unsigned)(2 * wave + j) * DT_KS1 + (unsigned)(s)) * 1024u + q * plane1), 0));
 #define DT_LOADA1(b, ksl)                                                                                        \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int q = 0; q < 2; ++q)                    \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int q = 0; q < 2; ++q)                   \
       af[i][q] = *reinterpret_cast<const hf16x8 *>(&bufA[b][q][i * 32 + fr][(ksl) * 16 + fk]);
   // small terms first; the four accumulators take turns so that dependent MFMAs are four issues apart.  TRANSPOSED (W fragment =
   // the MFMA's A operand, the panel fragment its B operand; the fragments are the same either way): a lane then holds ONE row and
   // 16 columns of it in four runs of four, so the epilogue writes 8-byte plane pieces and reads a row's scales once -- with the
   // panel as the A operand a lane holds one column of 16 rows: 128 two-byte LDS stores and 64 scale reads per lane
 #define DT_MMA1(A, W)                                                                                            \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                    \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                   \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[j][1], A[i][0], acc[i][j], 0, 0, 0);                  \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                    \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                   \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[j][0], A[i][1], acc[i][j], 0, 0, 0);                  \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                    \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                   \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(W[j][0], A[i][0], acc[i][j], 0, 0, 0);
   DT_LOADW1(0, 0)
   DT_LOADW1(1, 1)
@@ -379,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
       DT_STAMP(2 + c)          // chunk c computed, chunk c + 1 staged
     }
   }
-  ISG_DIAG_KEEP2(acc[0][0][0], acc[1][1][15])
+  ISG_DIAG_KEEP2(acc[0][0][0], acc[NI - 1][1][15])
   DT_STAMP(5)                  // last chunk computed
 #undef DT_LOADW1
 #undef DT_LOADA1
@@ -401,7 +496,7 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
       }
     __syncthreads();          // every wave is done with the A buffers: the planes may overwrite them
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NI; ++i) {
       const int row = i * 32 + fr;
       const float si = s_inv1[row], s2 = s_scale2[row];
 #pragma unroll
@@ -429,27 +524,27 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
   constexpr unsigned plane2 = (unsigned)(DT_C / 32) * DT_KS2 * 1024u;
   const __amdgpu_buffer_rsrc_t wr2 =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.w2f), 0, (int)(2u * plane2), 0x00020000);
-  hf32x4 rh[8];              // the tile's residual rows: in flight under GEMM2, used by the last pass of the tail
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int gr = min(r0 + min(srow + 8 * u, nrows - 1), a.N - 1);
-    rh[u] = __builtin_nontemporal_load(reinterpret_cast<const hf32x4 *>(a.h + (int64_t)gr * DT_C + sc4 * 4));      // read once
+#define DT_LOAD_H()                                                                                              \
+  _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                                \
+    const int gr = min(r0 + min(srow + 8 * u, nrows - 1), a.N - 1);                                              \
+    rh[u] = __builtin_nontemporal_load(reinterpret_cast<const hf32x4 *>(a.h + (int64_t)gr * DT_C + sc4 * 4));      /* read once */ \
   }
-  hf32x16 acc2[2][2];        // [k half][row block]
+  if constexpr (!LIVE) { DT_LOAD_H() }
+  hf32x16 acc2[2][NI];       // [k half][row block]
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NI; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.f;
   {
-    hf16x8 w2[4][2], a2[2][2][2];
+    hf16x8 w2[4][2], a2[2][NI][2];
 #define DT_LOADW2(st, s)                                                                                         \
   _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                  \
       w2[st][q] = __builtin_bit_cast(hf16x8, __builtin_amdgcn_raw_buffer_load_b128(                              \
           wr2, voff, (int)(((unsigned)wave * DT_KS2 + (unsigned)(s)) * 1024u + q * plane2), 0));
 #define DT_LOADA2(st, s)                                                                                         \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int q = 0; q < 2; ++q)                    \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int q = 0; q < 2; ++q)                   \
       a2[st][i][q] = *reinterpret_cast<const hf16x8 *>(&sY[q][i * 32 + fr][(s) * 16 + fk]);
     DT_LOADW2(0, 0)
     DT_LOADW2(1, 1)
@@ -462,13 +557,13 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
       if (s + 1 < DT_KS2) { DT_LOADA2((s + 1) & 1, s + 1) }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < NI; ++i)
         acc2[kh][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[s & 3][1], a2[s & 1][i][0], acc2[kh][i], 0, 0, 0);       // transposed,
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < NI; ++i)
         acc2[kh][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[s & 3][0], a2[s & 1][i][1], acc2[kh][i], 0, 0, 0);       // as GEMM1
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < NI; ++i)
         acc2[kh][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[s & 3][0], a2[s & 1][i][0], acc2[kh][i], 0, 0, 0);
     }
 #undef DT_LOADW2
@@ -480,11 +575,11 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
     wi2[g] = *reinterpret_cast<const hf32x4 *>(a.w2_inv + wave * 32 + 8 * g + 4 * hh);
     bv2[g] = *reinterpret_cast<const hf32x4 *>(a.b2 + wave * 32 + 8 * g + 4 * hh);
   }
-  ISG_DIAG_KEEP2(acc2[0][0][0], acc2[1][1][15])
+  ISG_DIAG_KEEP2(acc2[0][0][0], acc2[1][NI - 1][15])
   DT_STAMP(7)                  // GEMM2
   __syncthreads();          // every wave is done with the planes of the intermediate: c may overwrite them
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < NI; ++i) {
     const int row = i * 32 + fr;
     const float si2 = s_inv2[row];
 #pragma unroll
@@ -498,7 +593,23 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
   }
   __syncthreads();
   DT_STAMP(8)                  // epilogue 2
+  };      // x_proj
 
+  // c's row of tile row k
+  auto crow = [&](int k) __attribute__((always_inline)) { if constexpr (LIVE) return (int)s_cpos[tb + k]; else return k; };
+  auto tail = [&]() __attribute__((always_inline)) {
+  if constexpr (LIVE) {      // this tile's header (LIVE = false: requested and filed under x_proj's)
+    const int trow = min(r0 + min(tid, nrows - 1), a.N - 1);
+    DT_TAIL_REQUEST(trow)
+    DT_LOAD_H()
+    if (tid < DT_ROWS) {
+      s_gid[tid] = h_gid;
+      s_mask[tid] = h_mask;
+    }
+    DT_TAIL_FILE()
+    __syncthreads();
+    DT_STAMP(15)               // LIVE: the tiles' headers
+  }
   // ---- the layer tail on the tile's graphs (isg_norm_pool.hip::graph_tail_kernel<2>, same arithmetic, rows from LDS) --------
   // phase A: a_n = <ins_g, c_n> / sqrt(C).  A half-wave per node, one float4 per lane, the 32-lane butterfly -- the same bits as
   // graph_tail_kernel's 64-lane wave_sum, whose upper half adds zeros; eight nodes per wave and iteration (independent chains)
@@ -510,7 +621,7 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
       const int gi = s_gid[k] - g0;
       const float4 q = gi < DT_GST ? *reinterpret_cast<const float4 *>(&s_ins[gi * DT_C + fr * 4])
                                    : *reinterpret_cast<const float4 *>(a.ins + (int64_t)(g0 + gi) * DT_C + fr * 4);
-      const float4 v = *reinterpret_cast<const float4 *>(&sC[k][fr * 4]);
+      const float4 v = *reinterpret_cast<const float4 *>(&sC[crow(k)][fr * 4]);
       part[u] = 0.f + dot4_rn(v, q);
     }
 #pragma unroll
@@ -558,12 +669,12 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
         const float cnt = (float)n;
         float sum = 0.f;
 #pragma unroll 4
-        for (int k = 0; k < n; ++k) sum = add_rn(sum, mul_rn(s_a[nb + k], sC[nb + k][ch]));
+        for (int k = 0; k < n; ++k) sum = add_rn(sum, mul_rn(s_a[nb + k], sC[crow(nb + k)][ch]));
         const float mean_ms = mul_rn(sum / cnt, ms);
         float sq = 0.f;
 #pragma unroll 4
         for (int k = 0; k < n; ++k) {
-          const float o = sub_rn(mul_rn(s_a[nb + k], sC[nb + k][ch]), mean_ms);
+          const float o = sub_rn(mul_rn(s_a[nb + k], sC[crow(nb + k)][ch]), mean_ms);
           sq = add_rn(sq, mul_rn(o, o));
         }
         s_mean[gi - gb][ch] = mean_ms;
@@ -580,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
         const int gi = s_gid[min(row, nrows - 1)] - g0;
         if (row >= nrows || gi < gb || gi >= ge) continue;
         const float an = s_a[row], mk = s_mask[row];
-        const float4 c4 = *reinterpret_cast<const float4 *>(&sC[row][sc4 * 4]);
+        const float4 c4 = *reinterpret_cast<const float4 *>(&sC[crow(row)][sc4 * 4]);
         const float4 m4 = *reinterpret_cast<const float4 *>(&s_mean[gi - gb][sc4 * 4]);
         const float4 d4 = *reinterpret_cast<const float4 *>(&s_std[gi - gb][sc4 * 4]);
         float4 x4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -623,7 +734,49 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
     if (gb + 32 < ng) __syncthreads();
   }
   DT_STAMP(11)                 // phase C
-  ISG_DIAG_DUMP(g_dt_stamps, t * 4 + wave, 12, st_acc[13] = nrows; st_acc[14] = ng;)
+  };      // tail
+#undef DT_ROW
+#undef DT_TAIL_REQUEST
+#undef DT_TAIL_FILE
+#undef DT_LOAD_H
+
+  if constexpr (!LIVE) {
+    x_proj(std::integral_constant<int, 2>{});
+    tail();
+    ISG_DIAG_DUMP(g_dt_stamps, t * 4 + wave, 12, st_acc[13] = nrows; st_acc[14] = ng;)
+  } else {
+    bool have_c = false;
+#pragma unroll 1
+    for (int it = 0; it < gt; ++it) {
+      // The lane's indices are made again from an opaque copy of the thread id: hoisted out of this loop, the addresses derived
+      // from them stay live across x_proj, which has no register to spare (the kernel sits at 256), and spill.
+      asm volatile("" : "+v"(tid));
+      lane = tid & 63, fr = lane & 31, hh = lane >> 5, fk = hh * 8, srow = tid >> 5, sc4 = tid & 31, gi = srow, c4 = sc4, voff = lane * 16;
+      t = t0 + it;
+      const int4 tinfo = a.tile_info[t];
+      r0 = tinfo.x;
+      nrows = min(tinfo.y, DT_ROWS);
+      if (nrows <= 0) continue;      // a hole of a mixed plan (uniform)
+      g0 = a.tile_ptr[t], g1 = a.tile_ptr[t + 1];
+      ng = g1 - g0;
+      if (!grouped) {                // today's walk: the tile's own rows, in place (x_proj opens with a barrier)
+        L = nrows;
+        if (tid < nrows) {
+          s_list[tid] = min(r0 + tid, a.N - 1);
+          s_cpos[tb + tid] = (unsigned char)tid;
+        }
+      }
+      if (!grouped || !have_c) {
+        if (L > 32) x_proj(std::integral_constant<int, 2>{}); else x_proj(std::integral_constant<int, 1>{});
+        have_c = true;
+      } else {
+        __syncthreads();             // the previous tile's tail is done with its tables
+      }
+      tail();
+      tb += nrows;
+    }
+    ISG_DIAG_DUMP(g_dt_stamps, blockIdx.x * 4 + wave, 12, st_acc[13] = L; st_acc[14] = gt;)
+  }
 }
 
 }  // namespace isg
@@ -662,7 +815,8 @@ extern "C" int isg_mgat_dense_tail(const float *conv_out, int32_t lda, const flo
                                    double eps, const float *node_mask, const float *ins_next, float *h_out, float *xg_out,
                                    uint16_t *xp_out, float *xinv_out, const int32_t *ptr, const int64_t *batch,
                                    const int32_t *tile_ptr, const int32_t *tile_info, const int32_t *ntiles, int64_t max_tiles,
-                                   int64_t N, int32_t K1, int32_t MID, int32_t C, void *stream) {
+                                   const uint8_t *row_dead, int32_t group, int64_t N, int32_t K1, int32_t MID, int32_t C,
+                                   void *stream) {
   if (N < 0 || max_tiles < 0 || lda < K1 || P <= 0 || ldp < P) return ISG_EINVAL;
   if (K1 != DT_K1 || MID != DT_MID || C != DT_C || (lda & 3) != 0 || N >= (1ll << 31) || max_tiles >= (1ll << 31) ||
       (reinterpret_cast<uintptr_t>(conv_out) & 15) != 0 || (reinterpret_cast<uintptr_t>(ins) & 15) != 0 ||
@@ -674,7 +828,12 @@ extern "C" int isg_mgat_dense_tail(const float *conv_out, int32_t lda, const flo
       !gn_weight || !gn_bias || !gn_mean_scale || !h_out || !ptr || !batch || !tile_ptr || !tile_info || !ntiles ||
       ((xg_out || xp_out) && !ins_next) || (xp_out && !xinv_out))
     return ISG_EINVAL;
-  if (!dyn_lds_ok<&mgat_dense_tail_kernel>(DT_SMEM_BYTES)) return ISG_EUNSUPPORTED;
+  // ISG_DT_DENSE_ROWS=1: x_proj over every row of every tile whatever the flags say (A/B; the same bits either way)
+  static const bool dense_rows = [] { const char *e = getenv("ISG_DT_DENSE_ROWS"); return e && atoi(e) != 0; }();
+  if (dense_rows) row_dead = nullptr;
+  if (row_dead && (group < 1 || group > DT_GROUP_MAX || (reinterpret_cast<uintptr_t>(row_dead) & 3) != 0)) return ISG_EINVAL;
+  if (!(row_dead ? dyn_lds_ok<&mgat_dense_tail_kernel<true>>(DT_LIVE_SMEM_BYTES) : dyn_lds_ok<&mgat_dense_tail_kernel<false>>(DT_SMEM_BYTES)))
+    return ISG_EUNSUPPORTED;
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   DtArgs a = {
       .a = conv_out, .a_rowmax = a_rowmax, .w1f = reinterpret_cast<const _Float16 *>(w1_frag), .w1_inv = w1_inv_scale, .b1 = b1,
@@ -682,12 +841,16 @@ extern "C" int isg_mgat_dense_tail(const float *conv_out, int32_t lda, const flo
       .gn_w = gn_weight, .gn_b = gn_bias, .gn_ms = gn_mean_scale, .node_mask = node_mask, .ins_next = ins_next, .h_out = h_out,
       .xg_out = xg_out, .xinv_out = xinv_out, .xp_out = reinterpret_cast<_Float16 *>(xp_out), .ptr = ptr, .tile_ptr = tile_ptr,
       .ntiles = ntiles, .tile_info = reinterpret_cast<const int4 *>(tile_info), .batch = reinterpret_cast<const long long *>(batch),
-      .N = (int)N, .lda = lda, .P = P, .ldp = ldp, .eps = (float)eps, .denom = (float)sqrt((double)DT_C)};
+      .N = (int)N, .lda = lda, .P = P, .ldp = ldp, .eps = (float)eps, .denom = (float)sqrt((double)DT_C),
+      .row_dead = reinterpret_cast<const unsigned *>(row_dead), .group = row_dead ? group : 1, .max_tiles = (int)max_tiles};
   if (!a.a || !a.a_rowmax || !a.w1f || !a.w1_inv || !a.b1 || !a.y_bound || !a.w2f || !a.w2_inv || !a.b2 || !a.ins || !a.h || !a.gn_w ||
       !a.gn_b || !a.gn_ms || !a.h_out || !a.ptr || !a.tile_ptr || !a.ntiles || !a.tile_info || !a.batch ||
       ((a.xg_out || a.xp_out) && !a.ins_next) || (a.xp_out && !a.xinv_out))
     return ISG_EINVAL;                         // the struct the kernel dereferences, not the parameters it was filled from
-  mgat_dense_tail_kernel<<<(unsigned)max_tiles, 256, DT_SMEM_BYTES, as_stream(stream)>>>(a);
+  if (row_dead)
+    mgat_dense_tail_kernel<true><<<(unsigned)((max_tiles + group - 1) / group), 256, DT_LIVE_SMEM_BYTES, as_stream(stream)>>>(a);
+  else
+    mgat_dense_tail_kernel<false><<<(unsigned)max_tiles, 256, DT_SMEM_BYTES, as_stream(stream)>>>(a);
   return check_launch();
 }
 

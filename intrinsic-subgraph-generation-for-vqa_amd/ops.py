@@ -1334,6 +1334,12 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
     out = torch.empty(N, HC, dtype=torch.float32, device=dev)
     alpha = torch.empty(E, H, dtype=torch.float32, device=dev)
     rowmax = torch.empty(N, H, dtype=torch.float32, device=dev) if want_rowmax else None
+    # a masked launch also says which (row, head) kept all-zero accumulators: those rows of `out` are +0 + bias, all alike, and
+    # mgat_dense_tail runs x_proj once for them.  Rows of a mixed plan's oversize graphs are written elsewhere: never flagged.
+    row_dead = None
+    if rowmax is not None and (node_mask is not None or edge_mask is not None):
+        whole = plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) == "tiles"
+        row_dead = (torch.empty if whole else torch.zeros)(N, H, dtype=torch.uint8, device=dev)
     timer = MP_TIMER
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "K": K, "masked": node_mask is not None or edge_mask is not None,
@@ -1347,8 +1353,8 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
         ntiles.data_ptr(), cap,
         _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
         _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr(), N, E, H, C, K_in, K,
-        float(negative_slope), _stream())
+        out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr(),
+        0 if row_dead is None else row_dead.data_ptr(), N, E, H, C, K_in, K, float(negative_slope), _stream())
     if rc == ISG_EUNSUPPORTED:
         if timer is not None:
             timer.drop_last()
@@ -1366,6 +1372,8 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
                        out, alpha, rowmax)
     if rowmax is not None:
         attach_row_maxima(out, rowmax)
+    if row_dead is not None:
+        attach_dead_rows(out, row_dead)
     return out, alpha
 
 
@@ -1802,13 +1810,15 @@ def dense_tail_supported(plan: GraphPlan, x_proj: torch.nn.Sequential, width_in:
 
 def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, h: Tensor, plan: GraphPlan, weight: Tensor,
                     bias: Tensor, mean_scale: Tensor, eps: float = 1e-5, node_mask: Optional[Tensor] = None,
-                    ins_next: Optional[Tensor] = None, want_rows: bool = True, want_planes: bool = False
-                    ) -> Optional[Tuple[Tensor, Optional[Tensor], Optional["NodePlanes"]]]:
+                    ins_next: Optional[Tensor] = None, want_rows: bool = True, want_planes: bool = False,
+                    group: Optional[int] = None) -> Optional[Tuple[Tensor, Optional[Tensor], Optional["NodePlanes"]]]:
     """mgat.py:156-177 after the convolution, plus the next layer's instruction gate (mgat_v2_conv.py:156-157), as one launch:
     x_proj (Linear GELU Linear GELU) -> scatter attention -> GraphNorm -> + h [-> * mask] -> (h', xg, xg planes) with
     xg = gelu(h' * ins_next[batch]) as fp32 rows (want_rows) and / or as NodePlanes for gatv2_layer_conv (want_planes).
     conv_out must carry its row maxima (the message-passing kernels leave them); returns None when it does not (the caller
-    runs the un-fused chain).  The caller checks dense_tail_supported() first."""
+    runs the un-fused chain).  The caller checks dense_tail_supported() first.
+    When conv_out also carries the dead-row flags of a masked gatv2_layer_conv launch, the kernel's live-row form runs x_proj once
+    per `group` tiles, on their live rows plus one dead row; group = None: dense_tail_group's rule."""
     lib = _lib.load()
     N, K1 = conv_out.shape
     rm = row_maxima(conv_out)
@@ -1823,6 +1833,11 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
     # one tile plan per batch: the convolution's (64 nodes / 256 slots) serves this kernel too when it exists
     # one tile plan per batch, the convolution's (64 nodes / 256 slots): the same graphs are "oversize" for every tile kernel
     tile_ptr, ntiles, cap, tile_info = plan.tiles(CFG.dense_tail_rows, TILE_CONV_EDGES if plan.rowptr is not None else 0)
+    dead = dead_rows(conv_out)
+    if dead is not None and (tuple(dead.shape) != (N, 4) or dead.dtype != torch.uint8 or not dead.is_contiguous()):
+        dead = None
+    if dead is not None and group is None:
+        group = dense_tail_group(N, plan.E if plan.rowptr is not None else 0, h.device)
     h_out = torch.empty_like(h)
     xg = torch.empty_like(h) if ins_next is not None and want_rows else None
     xp = None
@@ -1840,7 +1855,8 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
         _chk(ins_next, "ins_next", torch.float32, (plan.B, C), optional=True), h_out.data_ptr(),
         0 if xg is None else xg.data_ptr(), 0 if xp is None else xp.planes.data_ptr(), 0 if xp is None else xp.inv.data_ptr(),
         plan.ptr.data_ptr(), _chk(plan.batch, "batch", torch.int64, (N,)),
-        tile_ptr.data_ptr(), tile_info.data_ptr(), ntiles.data_ptr(), cap, N, K1, l0.weight.size(0), C, _stream())
+        tile_ptr.data_ptr(), tile_info.data_ptr(), ntiles.data_ptr(), cap, 0 if dead is None else dead.data_ptr(),
+        1 if dead is None else int(group), N, K1, l0.weight.size(0), C, _stream())
     if rc == ISG_EUNSUPPORTED:
         return None
     _lib.check(rc, "isg_mgat_dense_tail")
@@ -2085,6 +2101,32 @@ def attach_row_maxima(x: Tensor, rowmax: Tensor) -> Tensor:
 
 def row_maxima(x: Tensor) -> Optional[Tensor]:
     return _attached(x, "_isg_rowmax")
+
+
+def attach_dead_rows(x: Tensor, row_dead: Tensor) -> Tensor:
+    """Leave on `x` (the output of a masked gatv2_layer_conv launch) the uint8 flags [N, H] of the (row, head) pairs whose
+    accumulators stayed all-zero bits: rows with every flag set are `+0 + bias`, one and the same vector.  Tied to x's version
+    like the row maxima."""
+    _attach(x, "_isg_row_dead", row_dead)
+    return x
+
+
+def dead_rows(x: Tensor) -> Optional[Tensor]:
+    return _attached(x, "_isg_row_dead")
+
+
+_CUS = {}
+
+
+def dense_tail_group(N: int, E: int, device) -> int:
+    """Tiles per workgroup of the dense tail's live-row form: as many as make the launch ONE round of workgroups at two per CU,
+    at most 4.  The tile count stays on the device; N / 64 and E / 256 (what fills a tile) bound it from below and are within
+    a fifth of it on the batches the tile kernels take (BASELINE configs[1]: 1 286 against 1 514 tiles -> 3)."""
+    idx = torch.device(device).index or 0
+    if idx not in _CUS:
+        _CUS[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
+    est = max(-(-N // TILE_CONV_NODES), -(-E // TILE_CONV_EDGES), 1)
+    return max(1, min(4, -(-est // (2 * _CUS[idx]))))
 
 
 def carry_row_maxima(dst: Tensor, src: Tensor) -> Tensor:

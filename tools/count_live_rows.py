@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""DESIGN.md 17.10's count, on the CPU: the rows of x_proj per group of G tiles in the dense tail's live-row form at BASELINE
+configs[1] -- live rows of the masked layer (a destination with an in-slot whose two ends are both picked) plus one for the group's
+dead rows -- from synthetic.make_workload, the model's CPU path (its mask indices are bit-exact with the GPU's) and isg_tile_plan's
+packing rule (64 nodes / 256 slots, consecutive graphs, 1024-graph chunks).       python3 tools/count_live_rows.py [graphs]"""
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from isubgvqa_amd import synthetic  # noqa: E402
+from oracle import model as OM  # noqa: E402
+from oracle import samplers as OS  # noqa: E402
+
+graphs = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+cfg = synthetic.WorkloadConfig(**{**synthetic.CFG2.__dict__, "num_graphs": graphs})
+wl = synthetic.make_workload(cfg)
+model = synthetic.build_answer_model(cfg).eval()
+sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+ocfg = OM.PathConfig(heads=cfg.heads, masking_thresholds=list(cfg.masks), use_topk=True, sampler_type=cfg.sampler, sample_k=cfg.sample_k)
+gen = torch.Generator().manual_seed(1)
+noises = {i: OS.uniform_to_gumbel(torch.rand(graphs, wl.max_nodes, generator=gen)) for i, t in enumerate(cfg.masks) if t != 1.0}
+torch.set_num_threads(min(16, os.cpu_count() or 1))
+with torch.no_grad():
+    mask = OM.mgat_pool_classify(sd, wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf, ocfg, noises)[1].reshape(-1)
+picked = mask != 0
+src, dst = wl.edge_index
+N, B = wl.x.size(0), graphs
+live = torch.bincount(dst, weights=(picked[src] & picked[dst]).double(), minlength=N) > 0
+sizes = torch.bincount(wl.batch, minlength=B).tolist()
+slots = torch.bincount(wl.batch[dst], minlength=B).tolist()
+tiles, g, r = [], 0, 0
+while g < B:
+    end = min((g // 1024 + 1) * 1024, B)
+    n, s, k = sizes[g], slots[g], g + 1
+    while k < end and n + sizes[k] <= 64 and s + slots[k] <= 256:
+        n += sizes[k]; s += slots[k]; k += 1
+    tiles.append((r, n))
+    r += n
+    g = k
+print(f"{N} nodes, {int(picked.sum())} picked, {int(live.sum())} live rows ({100 * live.double().mean().item():.1f} %), {len(tiles)} tiles")
+print("| G | groups | mean | <= 8 | 9-16 | 17-32 | 33-64 | > 64 | max |")
+print("|---|---|---|---|---|---|---|---|---|")
+for G in (1, 2, 3, 4):
+    rows = []
+    for t0 in range(0, len(tiles), G):
+        a, b = tiles[t0][0], tiles[min(t0 + G, len(tiles)) - 1]
+        seg = live[a:b[0] + b[1]]
+        rows.append(int(seg.sum()) + int((~seg).any()))
+    v = torch.tensor(rows)
+    share = lambda lo, hi: f"{100 * ((v >= lo) & (v <= hi)).double().mean().item():.1f} %"
+    print(f"| {G} | {len(rows)} | {v.double().mean().item():.1f} | {share(0, 8)} | {share(9, 16)} | {share(17, 32)} | {share(33, 64)} | "
+          f"{share(65, 10 ** 9)} | {int(v.max())} |")
