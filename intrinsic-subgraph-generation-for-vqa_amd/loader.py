@@ -10,41 +10,28 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import c_char_p, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_int64, c_void_p
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import Tensor
 
-ABI_VERSION = 1
+from ._lib import bind, read_header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ISG_LOADER_LIB: an alternative build of the same library (the sanitizer build of tools/asan_loader.sh)
 LIB_PATH = os.environ.get("ISG_LOADER_LIB") or os.path.join(_HERE, "csrc", "libisg_loader.so")
 
-SIGNATURES = {
-    "isg_loader_abi_version": (c_int, []),
-    "isg_sg_last_error": (c_char_p, []),
-    "isg_sg_vocab_build": (c_int, [c_void_p, c_int64, c_void_p]),
-    "isg_sg_vocab_size": (c_int64, [c_void_p]),
-    "isg_sg_vocab_lookup": (c_int64, [c_void_p, c_char_p]),
-    "isg_sg_vocab_free": (None, [c_void_p]),
-    "isg_sg_store_create": (c_int, [c_void_p, c_void_p]),
-    "isg_sg_store_add_json": (c_int, [c_void_p, c_char_p, c_int64]),
-    "isg_sg_store_add_json_file": (c_int, [c_void_p, c_char_p]),
-    "isg_sg_store_num_graphs": (c_int64, [c_void_p]),
-    "isg_sg_store_find": (c_int64, [c_void_p, c_char_p]),
-    "isg_sg_store_free": (None, [c_void_p]),
-    "isg_sg_store_find_many": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "isg_sg_collate_sizes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "isg_sg_collate": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 8 + [ctypes.c_int32]),
-}
-
-_lib = None
-
 
 class LoaderError(RuntimeError):
     pass
+
+
+# name -> (restype, argtypes) of every symbol include/isg_loader.h declares; ISG_LOADER_ABI_VERSION
+SIGNATURES, ABI_VERSION = read_header(os.path.join(os.path.dirname(_HERE), "include", "isg_loader.h"), LoaderError)
+
+_lib = None
 
 
 def load():
@@ -54,10 +41,7 @@ def load():
         return _lib
     if not os.path.exists(LIB_PATH):
         raise LoaderError(f"{LIB_PATH} is missing: run `python __graft_entry__.py` (build()) first")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
+    lib = bind(ctypes.CDLL(LIB_PATH), SIGNATURES)
     if lib.isg_loader_abi_version() != ABI_VERSION:
         raise LoaderError(f"libisg_loader.so ABI {lib.isg_loader_abi_version()}, binding expects {ABI_VERSION}")
     _lib = lib

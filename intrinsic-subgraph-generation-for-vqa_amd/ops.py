@@ -369,26 +369,22 @@ class GraphPlan:
         operand of isg_gatv2_tile_conv.  Every layer and head reads the same edge features (mgat.py:144-148), so the split is
         made once per batch and kept on the plan (keyed by the tensor's identity, storage and version)."""
         self.require_csr()
-        key = (id(edge_attr), edge_attr.data_ptr(), _ver(edge_attr), tuple(edge_attr.shape))
-        hit = self._edge_planes
-        if hit is None or hit[0] != key or (len(hit) > 3 and hit[3]() is not edge_attr):    # the id of a freed tensor can be reused
+        hit = _if_from_tensor(self._edge_planes, edge_attr)
+        if hit is None:
             lib = _lib.load()
             E, K = edge_attr.shape
-            planes = torch.empty(max(E, 1), 2, 128, dtype=torch.int16, device=edge_attr.device)
-            inv = torch.empty(max(E, 1), dtype=torch.float32, device=edge_attr.device)
+            hit = _empty_node_planes(E, edge_attr.device)
             _lib.check(lib.isg_edge_planes(_chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), self.eid.data_ptr(), E, K,
-                                           planes.data_ptr(), inv.data_ptr(), _stream()), "isg_edge_planes")
-            hit = (key, planes, inv, weakref.ref(edge_attr))
-            self._edge_planes = hit
-        return hit[1], hit[2]
+                                           hit.planes.data_ptr(), hit.inv.data_ptr(), _stream()), "isg_edge_planes")
+            self._edge_planes = _from_tensor(edge_attr, hit)
+        return hit.planes, hit.inv
 
     def tiles_and_edge_planes(self, edge_attr: Tensor, node_cap: int, edge_cap: int):
         """(tiles(node_cap, edge_cap), edge_planes(edge_attr)); when neither exists yet they are made by ONE launch
         (isg_tile_plan_edge_planes: the one-workgroup tile plan runs beside the row split instead of alone on the chip)."""
         key = (int(node_cap), int(edge_cap))
-        ekey = (id(edge_attr), edge_attr.data_ptr(), _ver(edge_attr), tuple(edge_attr.shape))
         have_t = self._tiles is not None and key in self._tiles
-        have_e = self._edge_planes is not None and self._edge_planes[0] == ekey
+        have_e = _if_from_tensor(self._edge_planes, edge_attr) is not None
         if CFG.plan_fused and not have_t and not have_e and edge_cap > 0 and edge_attr.dim() == 2 and edge_attr.size(1) <= 128 \
                 and edge_attr.size(1) % 4 == 0 and edge_attr.dtype == torch.float32:
             lib = _lib.load()
@@ -397,18 +393,17 @@ class GraphPlan:
             cap = int(lib.isg_tile_plan_capacity(self.N, self.E, self.B, key[0], key[1]))
             buf = torch.empty(9 * cap + 8, dtype=torch.int32, device=self.ptr.device)     # info first: 16-byte aligned
             info, heavy, tp, nt = buf[:4 * cap], buf[4 * cap:8 * cap], buf[8 * cap + 4:9 * cap + 5], buf[9 * cap + 5:9 * cap + 6]
-            planes = torch.empty(max(E, 1), 2, 128, dtype=torch.int16, device=edge_attr.device)
-            inv = torch.empty(max(E, 1), dtype=torch.float32, device=edge_attr.device)
+            ep = _empty_node_planes(E, edge_attr.device)
             rc = lib.isg_tile_plan_edge_planes(self.ptr.data_ptr(), self.eptr.data_ptr(), self.B, key[0], key[1], tp.data_ptr(),
                                                nt.data_ptr(), info.data_ptr(), cap, heavy.data_ptr(), _chk_rows(edge_attr, "edge_attr"),
-                                               edge_attr.stride(0), self.eid.data_ptr(), E, K, planes.data_ptr(), inv.data_ptr(),
-                                               _stream())
+                                               edge_attr.stride(0), self.eid.data_ptr(), E, K, ep.planes.data_ptr(),
+                                               ep.inv.data_ptr(), _stream())
             if rc != ISG_EUNSUPPORTED:
                 _lib.check(rc, "isg_tile_plan_edge_planes")
                 if self._tiles is None:
                     self._tiles = {}
                 self._tiles[key] = (tp, nt, cap, info.view(cap, 4), heavy.view(cap, 4))
-                self._edge_planes = (ekey, planes, inv, weakref.ref(edge_attr))
+                self._edge_planes = _from_tensor(edge_attr, ep)
         return self.tiles(node_cap, edge_cap), self.edge_planes(edge_attr)
 
     def tiles_heavy_first(self, node_cap: int = 64, edge_cap: int = 0) -> Tensor:
@@ -740,6 +735,38 @@ def node_to_edge_mask(mask: Tensor, edge_index: Tensor, plan: Optional[GraphPlan
     return out.view(E, 1) if mask.dim() == 2 else out
 
 
+def _mp_operands(att: Tensor, bias: Optional[Tensor], node_mask: Optional[Tensor], edge_mask: Optional[Tensor], N: int, E: int,
+                 HC: int) -> Tuple[int, int, int, int]:
+    """(att, bias, node_mask, edge_mask) as every kernel of the message-passing family takes them: flattened and checked, once per
+    call of a wrapper however many entry points it tries; an optional one that is absent is a null pointer."""
+    return (_chk(att.reshape(-1), "att", torch.float32, (HC,)),
+            _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
+            _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
+            _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True))
+
+
+def _launched(rc: int, what: str, timer: Optional[KernelTimer], event) -> bool:
+    """The status of a launch inside an MP_TIMER bracket.  ISG_EUNSUPPORTED: the kernel has no launch for this shape and the
+    caller takes another path (False, the bracket dropped).  Any other status is checked, and `event` recorded behind the launch."""
+    if rc == ISG_EUNSUPPORTED:
+        if timer is not None:
+            timer.drop_last()
+        return False
+    _lib.check(rc, what)
+    if timer is not None:
+        event.record()
+    return True
+
+
+def _segmented_planes32(N: int, H: int, C: int, device):
+    """The unwritten SEGMENTED Planes32 result [N, H*C] of the flat per-graph kernel (H = 4: two segments of 2 * C columns, each
+    under its own row scale), and the two pointers the kernel writes through: the planes, the inverse scales [2, N]."""
+    seg = 2 * C
+    pl = torch.empty(N * 2 * ((seg + 31) // 32) * 64, dtype=torch.int16, device=device)
+    pinv = torch.empty(2, N, dtype=torch.float32, device=device)
+    return Planes32(pl, pinv[1], N, H * C, pinv[0], seg), pl.data_ptr(), pinv.data_ptr()
+
+
 def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphPlan, heads: int,
              bias: Optional[Tensor] = None, node_mask: Optional[Tensor] = None, edge_mask: Optional[Tensor] = None,
              negative_slope: float = 0.2, kernel: Optional[str] = None, want_rowmax: bool = False,
@@ -773,62 +800,38 @@ def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphP
     use_graph = (kernel or CFG.mp_kernel) == "graph" and plan.B > 0 and plan.nmax > 0
     if fdt == torch.float16 and not use_graph:
         raise _lib.IsgError("fp16 feature rows need the per-graph kernel (a GraphPlan built with edge_index)")
+    # every entry point takes `ins`, its results, `dims`; the per-graph arrays are handed over only where that kernel may run
+    attp, biasp, nm, em = _mp_operands(att, bias, node_mask, edge_mask, N, E, HC)
+    ins = (_chk_rows(x_l, "x_l", fdt), _chk_rows(x_r, "x_r", fdt), _chk_rows(e_proj, "e_proj", fdt) if E > 0 else 0, attp, biasp,
+           plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), nm, em)
+    dims = (N, E, H, C, float(negative_slope), plan.ptr.data_ptr() if use_graph else 0, plan.eptr.data_ptr() if use_graph else 0,
+            plan.dst.data_ptr() if use_graph else 0, plan.B, plan.nmax if use_graph else 0, plan.emax if use_graph else 0,
+            ld_l, ld_r, ld_e, _stream())
     timer = MP_TIMER
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "masked": node_mask is not None or edge_mask is not None,
                                   "feat_bytes": 2 if fdt == torch.float16 else 4})
         ev0.record()
+    # the richer result first; ISG_EUNSUPPORTED = this batch / width takes another kernel: the next form, inside the same bracket
     if want_planes and CFG.mp_planes and use_graph and fdt == torch.float32 and E > 0 and H == 4 and C % 4 == 0:
-        seg = 2 * C
-        st = (seg + 31) // 32
-        pl = torch.empty(N * 2 * st * 64, dtype=torch.int16, device=x_l.device)
-        pinv = torch.empty(2, N, dtype=torch.float32, device=x_l.device)
-        rc = lib.isg_gatv2_mp_fwd_planes(
-            _chk_rows(x_l, "x_l", fdt), _chk_rows(x_r, "x_r", fdt), _chk_rows(e_proj, "e_proj", fdt),
-            _chk(att.reshape(-1), "att", torch.float32, (HC,)),
-            _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-            plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
-            _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-            _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-            pl.data_ptr(), pinv.data_ptr(), alpha.data_ptr(), N, E, H, C, float(negative_slope), plan.ptr.data_ptr(),
-            plan.eptr.data_ptr(), plan.dst.data_ptr(), plan.B, plan.nmax, plan.emax, ld_l, ld_r, ld_e, _stream())
+        planes, pl, pinv = _segmented_planes32(N, H, C, x_l.device)
+        rc = lib.isg_gatv2_mp_fwd_planes(*ins, pl, pinv, alpha.data_ptr(), *dims)
         if rc != ISG_EUNSUPPORTED:
             _lib.check(rc, "isg_gatv2_mp_fwd_planes")
             if timer is not None:
                 ev1.record()
-            return Planes32(pl, pinv[1], N, HC, pinv[0], seg), alpha
-    rowmax = None
+            return planes, alpha
     if want_rowmax and use_graph and fdt == torch.float32 and E > 0:
         rowmax = torch.empty(N, H, dtype=torch.float32, device=x_l.device)
-        rc = lib.isg_gatv2_mp_fwd_rowmax(
-            _chk_rows(x_l, "x_l", fdt), _chk_rows(x_r, "x_r", fdt), _chk_rows(e_proj, "e_proj", fdt),
-            _chk(att.reshape(-1), "att", torch.float32, (HC,)),
-            _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-            plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
-            _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-            _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-            out.data_ptr(), alpha.data_ptr(), rowmax.data_ptr(), N, E, H, C, float(negative_slope), plan.ptr.data_ptr(),
-            plan.eptr.data_ptr(), plan.dst.data_ptr(), plan.B, plan.nmax, plan.emax, ld_l, ld_r, ld_e, _stream())
-        if rc == ISG_EUNSUPPORTED:
-            rowmax = None              # this batch / width takes another kernel: plain call below
-        else:
+        rc = lib.isg_gatv2_mp_fwd_rowmax(*ins, out.data_ptr(), alpha.data_ptr(), rowmax.data_ptr(), *dims)
+        if rc != ISG_EUNSUPPORTED:
             _lib.check(rc, "isg_gatv2_mp_fwd_rowmax")
             if timer is not None:
                 ev1.record()
             attach_row_maxima(out, rowmax)
             return out, alpha
     entry = lib.isg_gatv2_mp_fwd if fdt == torch.float32 else lib.isg_gatv2_mp_fwd_f16
-    _lib.check(entry(
-        _chk_rows(x_l, "x_l", fdt), _chk_rows(x_r, "x_r", fdt),
-        _chk_rows(e_proj, "e_proj", fdt) if E > 0 else 0, _chk(att.reshape(-1), "att", torch.float32, (HC,)),
-        _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        out.data_ptr(), alpha.data_ptr(), N, E, H, C, float(negative_slope),
-        plan.ptr.data_ptr() if use_graph else 0, plan.eptr.data_ptr() if use_graph else 0,
-        plan.dst.data_ptr() if use_graph else 0, plan.B,
-        plan.nmax if use_graph else 0, plan.emax if use_graph else 0, ld_l, ld_r, ld_e, _stream()), "isg_gatv2_mp_fwd")
+    _lib.check(entry(*ins, out.data_ptr(), alpha.data_ptr(), *dims), "isg_gatv2_mp_fwd")
     if timer is not None:
         ev1.record()
     return out, alpha
@@ -870,6 +873,22 @@ def _edge_logits_weight(w_edge: Tensor, heads: int):
     return _weight_planes(derived_weight(f"edge_logits_pad{heads}", (w_edge,), build), True, "f16x3")
 
 
+def _edge_logits(lib, x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_planes, attp: int, nm: int, em: int, plan: "GraphPlan", H: int,
+                 C: int, negative_slope: float, timer: Optional[KernelTimer] = None, event=None) -> Optional[Tensor]:
+    """isg_gatv2_edge_logits (fp32 rows) or its _f16 twin (half rows: BASELINE configs[4]'s storage, K >= 128) on checked
+    operands: logits fp32 [E, H] in CSR SLOT order (slot t = edge plan.eid[t]), or None when the kernel has no launch."""
+    E, K = edge_attr.shape
+    fdt = x_l.dtype
+    logits = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
+    entry, what = (lib.isg_gatv2_edge_logits, "isg_gatv2_edge_logits") if fdt == torch.float32 else \
+        (lib.isg_gatv2_edge_logits_f16, "isg_gatv2_edge_logits_f16")
+    rc = entry(_chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), w_planes[0].data_ptr(), w_planes[1].data_ptr(),
+               _chk_rows(x_l, "x_l", fdt), x_l.stride(0), 0, _chk_rows(x_r, "x_r", fdt), x_r.stride(0), 0, attp,
+               plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), em, nm, logits.data_ptr(), E, H, C, K,
+               float(negative_slope), _stream())
+    return logits if _launched(rc, what, timer, event) else None
+
+
 def gatv2_edge_logits(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor, att: Tensor, plan: "GraphPlan", heads: int,
                       node_mask: Optional[Tensor] = None, edge_mask: Optional[Tensor] = None,
                       negative_slope: float = 0.2) -> Optional[Tensor]:
@@ -878,22 +897,8 @@ def gatv2_edge_logits(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tenso
     plan.require_csr()
     N, HC = x_l.shape
     H = int(heads)
-    E, K = edge_attr.shape
-    planes, inv = _edge_logits_weight(w_edge, H)
-    logits = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
-    fdt = x_l.dtype                      # fp32 rows, or half rows (isg_gatv2_edge_logits_f16: BASELINE configs[4]'s storage, K >= 128)
-    entry = lib.isg_gatv2_edge_logits if fdt == torch.float32 else lib.isg_gatv2_edge_logits_f16
-    rc = entry(
-        _chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), planes.data_ptr(), inv.data_ptr(),
-        _chk_rows(x_l, "x_l", fdt), x_l.stride(0), 0, _chk_rows(x_r, "x_r", fdt), x_r.stride(0), 0,
-        _chk(att.reshape(-1), "att", torch.float32, (HC,)), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        logits.data_ptr(), E, H, HC // H, K, float(negative_slope), _stream())
-    if rc == ISG_EUNSUPPORTED:
-        return None
-    _lib.check(rc, "isg_gatv2_edge_logits")
-    return logits
+    attp, _, nm, em = _mp_operands(att, None, node_mask, edge_mask, N, edge_attr.size(0), HC)
+    return _edge_logits(lib, x_l, x_r, edge_attr, _edge_logits_weight(w_edge, H), attp, nm, em, plan, H, HC // H, negative_slope)
 
 
 def gatv2_mp_edge_logits(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor, att: Tensor, plan: "GraphPlan",
@@ -916,108 +921,50 @@ def gatv2_mp_edge_logits(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Te
         raise TypeError("gatv2_mp_edge_logits: x_l / x_r as fp32 or fp16 rows, fp32 edge rows")
     if tuple(x_r.shape) != (N, HC) or x_r.dtype != x_l.dtype:
         raise ValueError("gatv2_mp_edge_logits: x_r must be [N, H*C] of x_l's type")
-    planes, inv = _edge_logits_weight(w_edge, H)
-    if x_l.dtype == torch.float16:
-        # BASELINE configs[4]'s storage (fp16 feature rows, fp32 arithmetic): the rows kernel gathers half rows and rounds the edge
-        # projection to half as the un-fused path stores it; the result row leaves as half.  K >= 128 (the rows kernel only).
-        if K < 128:
-            return None
-        logits = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
-        alpha = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
-        out = torch.empty(N, HC, dtype=torch.float16, device=x_l.device)
-        nm = _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True)
-        em = _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True)
-        attp = _chk(att.reshape(-1), "att", torch.float32, (HC,))
-        timer = MP_TIMER
-        if timer is not None:
-            ev0, evm, ev1 = timer.bracket3({"N": N, "E": E, "H": H, "C": C, "K": K,
-                                            "masked": node_mask is not None or edge_mask is not None, "feat_bytes": 2,
-                                            "fused_logits": True})
-            ev0.record()
-        rc = lib.isg_gatv2_edge_logits_f16(
-            _chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), planes.data_ptr(), inv.data_ptr(),
-            _chk_rows(x_l, "x_l", torch.float16), x_l.stride(0), 0, _chk_rows(x_r, "x_r", torch.float16), x_r.stride(0), 0, attp,
-            plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), em, nm, logits.data_ptr(), E, H, C, K,
-            float(negative_slope), _stream())
-        if rc == ISG_EUNSUPPORTED:
-            if timer is not None:
-                timer.drop_last()
-            return None
-        _lib.check(rc, "isg_gatv2_edge_logits_f16")
-        if timer is not None:
-            evm.record()
-        rc = lib.isg_gatv2_mp_fwd_logits_f16(
-            _chk_rows(x_l, "x_l", torch.float16), logits.data_ptr(), attp,
-            _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-            plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), nm, em, out.data_ptr(), alpha.data_ptr(),
-            N, E, H, C, float(negative_slope), plan.ptr.data_ptr(), plan.eptr.data_ptr(), plan.dst.data_ptr(),
-            plan.B, plan.nmax, plan.emax, x_l.stride(0), _stream())
-        if rc == ISG_EUNSUPPORTED:
-            if timer is not None:
-                timer.drop_last()
-            return None
-        _lib.check(rc, "isg_gatv2_mp_fwd_logits_f16")
-        if timer is not None:
-            ev1.record()
-        return out, alpha
-    logits = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
+    w_planes = _edge_logits_weight(w_edge, H)
+    # BASELINE configs[4]'s storage (fp16 feature rows, fp32 arithmetic): the rows kernel gathers half rows and rounds the edge
+    # projection to half as the un-fused path stores it; the result row leaves as half.  K >= 128 (the rows kernel only).
+    half = x_l.dtype == torch.float16
+    if half and K < 128:
+        return None
     alpha = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
-    # the result as the segmented planes32 operand of x_proj.0 (the flat kernel, H = 4: the reference's C = 300) -- or fp32 rows
-    as_planes = bool(want_planes and CFG.mp_planes and H == 4 and C % 32 != 0)
-    out = None if as_planes else torch.empty(N, HC, dtype=torch.float32, device=x_l.device)
-    rowmax = torch.empty(N, H, dtype=torch.float32, device=x_l.device) if want_rowmax and not as_planes and C % 32 == 0 else None
-    nm = _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True)
-    em = _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True)
-    attp = _chk(att.reshape(-1), "att", torch.float32, (HC,))
-    timer = MP_TIMER
+    # the result as the segmented planes32 operand of x_proj.0 (the flat kernel, H = 4: the reference's C = 300) -- or rows
+    as_planes = bool(not half and want_planes and CFG.mp_planes and H == 4 and C % 32 != 0)
+    out = None if as_planes else torch.empty(N, HC, dtype=x_l.dtype, device=x_l.device)
+    rowmax = None
+    if not half and want_rowmax and not as_planes and C % 32 == 0:
+        rowmax = torch.empty(N, H, dtype=torch.float32, device=x_l.device)
+    attp, biasp, nm, em = _mp_operands(att, bias, node_mask, edge_mask, N, E, HC)
+    timer, evm, ev1 = MP_TIMER, None, None
     if timer is not None:   # bench.py: ONE bracket around both launches -- together they are the reference's message +
         # aggregate (plus lin_edge); the roofline keeps the un-fused algorithmic bytes of SURVEY 8(d)
         ev0, evm, ev1 = timer.bracket3({"N": N, "E": E, "H": H, "C": C, "K": K,
-                                        "masked": node_mask is not None or edge_mask is not None, "feat_bytes": 4,
-                                        "fused_logits": True})
+                                        "masked": node_mask is not None or edge_mask is not None,
+                                        "feat_bytes": 2 if half else 4, "fused_logits": True})
         ev0.record()
-    rc = lib.isg_gatv2_edge_logits(
-        _chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), planes.data_ptr(), inv.data_ptr(),
-        _chk_rows(x_l, "x_l"), x_l.stride(0), 0, _chk_rows(x_r, "x_r"), x_r.stride(0), 0, attp,
-        plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), em, nm, logits.data_ptr(), E, H, C, K,
-        float(negative_slope), _stream())
-    if rc == ISG_EUNSUPPORTED:
-        if timer is not None:
-            timer.drop_last()
+    logits = _edge_logits(lib, x_l, x_r, edge_attr, w_planes, attp, nm, em, plan, H, C, negative_slope, timer, evm)
+    if logits is None:
         return None
-    _lib.check(rc, "isg_gatv2_edge_logits")
-    if timer is not None:
-        evm.record()
+    # the three softmax + aggregation entry points take `ins`, their results, `dims` (x_l: checked by _edge_logits)
+    ins = (x_l.data_ptr(), logits.data_ptr(), attp, biasp, plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), nm, em)
+    dims = (N, E, H, C, float(negative_slope), plan.ptr.data_ptr(), plan.eptr.data_ptr(), plan.dst.data_ptr(), plan.B, plan.nmax,
+            plan.emax, x_l.stride(0), _stream())
     if as_planes:
-        seg = 2 * C
-        st = (seg + 31) // 32
-        pl = torch.empty(N * 2 * st * 64, dtype=torch.int16, device=x_l.device)
-        pinv = torch.empty(2, N, dtype=torch.float32, device=x_l.device)
-        rc = lib.isg_gatv2_mp_fwd_logits_planes(
-            _chk_rows(x_l, "x_l"), logits.data_ptr(), attp,
-            _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-            plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), nm, em, pl.data_ptr(), pinv.data_ptr(),
-            alpha.data_ptr(), N, E, H, C, float(negative_slope), plan.ptr.data_ptr(), plan.eptr.data_ptr(), plan.dst.data_ptr(),
-            plan.B, plan.nmax, plan.emax, x_l.stride(0), _stream())
+        planes, pl, pinv = _segmented_planes32(N, H, C, x_l.device)
+        rc = lib.isg_gatv2_mp_fwd_logits_planes(*ins, pl, pinv, alpha.data_ptr(), *dims)
         if rc != ISG_EUNSUPPORTED:
             _lib.check(rc, "isg_gatv2_mp_fwd_logits_planes")
             if timer is not None:
                 ev1.record()
-            return Planes32(pl, pinv[1], N, HC, pinv[0], seg), alpha
+            return planes, alpha
         out = torch.empty(N, HC, dtype=torch.float32, device=x_l.device)
-    rc = lib.isg_gatv2_mp_fwd_logits(
-        _chk_rows(x_l, "x_l"), logits.data_ptr(), attp,
-        _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), nm, em, out.data_ptr(), alpha.data_ptr(),
-        0 if rowmax is None else rowmax.data_ptr(), N, E, H, C, float(negative_slope), plan.ptr.data_ptr(),
-        plan.eptr.data_ptr(), plan.dst.data_ptr(), plan.B, plan.nmax, plan.emax, x_l.stride(0), _stream())
-    if rc == ISG_EUNSUPPORTED:
-        if timer is not None:
-            timer.drop_last()
+    if half:
+        rc, what = lib.isg_gatv2_mp_fwd_logits_f16(*ins, out.data_ptr(), alpha.data_ptr(), *dims), "isg_gatv2_mp_fwd_logits_f16"
+    else:
+        rc, what = lib.isg_gatv2_mp_fwd_logits(*ins, out.data_ptr(), alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr(),
+                                               *dims), "isg_gatv2_mp_fwd_logits"
+    if not _launched(rc, what, timer, ev1):
         return None
-    _lib.check(rc, "isg_gatv2_mp_fwd_logits")
-    if timer is not None:
-        ev1.record()
     if rowmax is not None:
         attach_row_maxima(out, rowmax)
     return out, alpha
@@ -1132,15 +1079,21 @@ class NodePlanes(NamedTuple):
     inv: Tensor
 
 
+def _empty_node_planes(rows: int, device) -> NodePlanes:
+    """Unwritten planes for the kernel that fills them (edge rows take the same form); one row at least, so that an empty batch
+    still hands its kernel a pointer."""
+    return NodePlanes(torch.empty(max(rows, 1), 2, 128, dtype=torch.int16, device=device),
+                      torch.empty(max(rows, 1), dtype=torch.float32, device=device))
+
+
 def node_planes(x: Tensor) -> NodePlanes:
     """fp32 rows [N, 128] -> NodePlanes (isg_edge_planes in row order): for callers that hold the gated rows only as fp32."""
     lib = _lib.load()
     N, K = x.shape
-    planes = torch.empty(max(N, 1), 2, 128, dtype=torch.int16, device=x.device)
-    inv = torch.empty(max(N, 1), dtype=torch.float32, device=x.device)
-    _lib.check(lib.isg_edge_planes(_chk_rows(x, "x"), x.stride(0), 0, N, K, planes.data_ptr(), inv.data_ptr(), _stream()),
+    out = _empty_node_planes(N, x.device)
+    _lib.check(lib.isg_edge_planes(_chk_rows(x, "x"), x.stride(0), 0, N, K, out.planes.data_ptr(), out.inv.data_ptr(), _stream()),
                "isg_edge_planes")
-    return NodePlanes(planes, inv)
+    return out
 
 
 def instr_gate_planes(x: Tensor, instr: Tensor, batch: Tensor, want_rows: bool = False) -> Tuple[Optional[Tensor], NodePlanes]:
@@ -1149,12 +1102,11 @@ def instr_gate_planes(x: Tensor, instr: Tensor, batch: Tensor, want_rows: bool =
     lib = _lib.load()
     N, C = x.shape
     rows = torch.empty_like(x) if want_rows else None
-    planes = torch.empty(max(N, 1), 2, 128, dtype=torch.int16, device=x.device)
-    inv = torch.empty(max(N, 1), dtype=torch.float32, device=x.device)
+    out = _empty_node_planes(N, x.device)
     _lib.check(lib.isg_instr_gate_planes(_chk(x, "x", torch.float32), _chk(instr, "instr", torch.float32, (instr.size(0), C)),
                                          _chk(batch, "batch", torch.int64, (N,)), 0 if rows is None else rows.data_ptr(),
-                                         planes.data_ptr(), inv.data_ptr(), N, C, _stream()), "isg_instr_gate_planes")
-    return rows, NodePlanes(planes, inv)
+                                         out.planes.data_ptr(), out.inv.data_ptr(), N, C, _stream()), "isg_instr_gate_planes")
+    return rows, out
 
 
 def _count_tile_nodes(plan: "GraphPlan", sub: Optional["OversizeGraphs"]) -> None:
@@ -1277,12 +1229,11 @@ def _oversize_conv(sub: "OversizeGraphs", x_l: Tensor, x_r: Tensor, edge_attr: T
     """Message passing of the graphs the tile kernels passed over (mgat_v2_conv.py:215-279 on the sub-batch): lin_edge +
     the per-graph kernel (256-node / 1024-edge tables, or node chunks beyond), written into the rows / edges of `out` /
     `alpha` / `rowmax` that belong to those graphs."""
-    key = (id(edge_attr), edge_attr.data_ptr(), _ver(edge_attr))          # every layer reads the same edge features
-    hit = getattr(sub.plan, "_parent_edge_rows", None)
-    if hit is None or hit[0] != key:
-        hit = (key, edge_attr.index_select(0, sub.edges))
-        sub.plan._parent_edge_rows = hit
-    e_proj = linear(hit[1], w_edge)
+    rows = _if_from_tensor(getattr(sub.plan, "_parent_edge_rows", None), edge_attr)      # every layer reads the same edge features
+    if rows is None:
+        rows = edge_attr.index_select(0, sub.edges)
+        sub.plan._parent_edge_rows = _from_tensor(edge_attr, rows)
+    e_proj = linear(rows, w_edge)
     nm = None if node_mask is None else node_mask.reshape(-1).index_select(0, sub.nodes)
     em = None if edge_mask is None else edge_mask.reshape(-1).index_select(0, sub.edges)
     o, a = gatv2_mp(x_l, x_r, e_proj, att, sub.plan, heads, bias=bias, node_mask=nm, edge_mask=em,
@@ -1294,6 +1245,21 @@ def _oversize_conv(sub: "OversizeGraphs", x_l: Tensor, x_r: Tensor, edge_attr: T
         if rm is None:                                  # the node-chunk kernel leaves none: one pass over the few rows
             rm = o.view(o.size(0), heads, -1).abs().amax(dim=2)
         rowmax.index_copy_(0, sub.nodes, rm)
+
+
+def _tile_conv_operands(plan: "GraphPlan", ntiles: Tensor, cap: int, att: Tensor, bias, node_mask, edge_mask, H: int, HC: int,
+                        want_rowmax: bool, device):
+    """What isg_gatv2_layer_conv and isg_gatv2_tile_conv take alike, in the order both take it -- att, bias, the CSR, the tile list,
+    the masks, out, its row stride, alpha, rowmax -- and the three result tensors (rowmax: None unless wanted)."""
+    N, E = plan.N, plan.E
+    tile_info = plan.tiles_heavy_first(TILE_CONV_NODES, TILE_CONV_EDGES)        # a persistent kernel: balanced rounds
+    out = torch.empty(N, HC, dtype=torch.float32, device=device)
+    alpha = torch.empty(E, H, dtype=torch.float32, device=device)
+    rowmax = torch.empty(N, H, dtype=torch.float32, device=device) if want_rowmax else None
+    attp, biasp, nm, em = _mp_operands(att, bias, node_mask, edge_mask, N, E, HC)
+    shared = (attp, biasp, plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), tile_info.data_ptr(),
+              ntiles.data_ptr(), cap, nm, em, out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr())
+    return shared, out, alpha, rowmax
 
 
 def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Tensor, plan: "GraphPlan", heads: int,
@@ -1330,38 +1296,24 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
     wn, wn_inv = _weight_planes(cat_w, True, "f16x3")
     we, we_inv = _weight_planes(w_edge, True, "f16x3")
     (_, ntiles, cap, _), (ep, ep_inv) = plan.tiles_and_edge_planes(edge_attr, TILE_CONV_NODES, TILE_CONV_EDGES)
-    tile_info = plan.tiles_heavy_first(TILE_CONV_NODES, TILE_CONV_EDGES)        # a persistent kernel: balanced rounds
-    out = torch.empty(N, HC, dtype=torch.float32, device=dev)
-    alpha = torch.empty(E, H, dtype=torch.float32, device=dev)
-    rowmax = torch.empty(N, H, dtype=torch.float32, device=dev) if want_rowmax else None
+    shared, out, alpha, rowmax = _tile_conv_operands(plan, ntiles, cap, att, bias, node_mask, edge_mask, H, HC, want_rowmax, dev)
     # a masked launch also says which (row, head) kept all-zero accumulators: those rows of `out` are +0 + bias, all alike, and
     # mgat_dense_tail runs x_proj once for them.  Rows of a mixed plan's oversize graphs are written elsewhere: never flagged.
     row_dead = None
     if rowmax is not None and (node_mask is not None or edge_mask is not None):
         whole = plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) == "tiles"
         row_dead = (torch.empty if whole else torch.zeros)(N, H, dtype=torch.uint8, device=dev)
-    timer = MP_TIMER
+    timer, ev1 = MP_TIMER, None
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "K": K, "masked": node_mask is not None or edge_mask is not None,
                                   "feat_bytes": 4, "tile_conv": True, "layer_conv": True, "K_in": K_in})
         ev0.record()
     rc = lib.isg_gatv2_layer_conv(
         x.planes.data_ptr(), x.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(), ep_inv.data_ptr(),
-        we.data_ptr(), we_inv.data_ptr(), _chk(att.reshape(-1), "att", torch.float32, (HC,)),
-        _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), tile_info.data_ptr(),
-        ntiles.data_ptr(), cap,
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr(),
-        0 if row_dead is None else row_dead.data_ptr(), N, E, H, C, K_in, K, float(negative_slope), _stream())
-    if rc == ISG_EUNSUPPORTED:
-        if timer is not None:
-            timer.drop_last()
+        we.data_ptr(), we_inv.data_ptr(), *shared, 0 if row_dead is None else row_dead.data_ptr(), N, E, H, C, K_in, K,
+        float(negative_slope), _stream())
+    if not _launched(rc, "isg_gatv2_layer_conv", timer, ev1):
         return None
-    _lib.check(rc, "isg_gatv2_layer_conv")
-    if timer is not None:
-        ev1.record()
     sub = _mixed_sub(plan)
     if sub is not None:
         # the gated rows of those graphs out of the SAME planes the tile kernel read (hi + mid, exact), projected per node
@@ -1393,35 +1345,21 @@ def gatv2_tile_conv(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor,
         raise ValueError("gatv2_tile_conv: operand shapes do not match the plan")
     if x_l.dtype != torch.float32 or x_r.dtype != torch.float32 or edge_attr.dtype != torch.float32:
         raise TypeError("gatv2_tile_conv: fp32 rows")
-    planes, inv = _weight_planes(w_edge, True, "f16x3")
+    we, we_inv = _weight_planes(w_edge, True, "f16x3")
     ep, ep_inv = plan.edge_planes(edge_attr)
     _, ntiles, cap, _ = plan.tiles(TILE_CONV_NODES, TILE_CONV_EDGES)
-    tile_info = plan.tiles_heavy_first(TILE_CONV_NODES, TILE_CONV_EDGES)        # a persistent kernel: balanced rounds
-    out = torch.empty(N, HC, dtype=torch.float32, device=x_l.device)
-    alpha = torch.empty(E, H, dtype=torch.float32, device=x_l.device)
-    rowmax = torch.empty(N, H, dtype=torch.float32, device=x_l.device) if want_rowmax else None
-    timer = MP_TIMER
+    shared, out, alpha, rowmax = _tile_conv_operands(plan, ntiles, cap, att, bias, node_mask, edge_mask, H, HC, want_rowmax,
+                                                     x_l.device)
+    xlp, xrp = _chk_rows(x_l, "x_l"), _chk_rows(x_r, "x_r")
+    timer, ev1 = MP_TIMER, None
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "K": K, "masked": node_mask is not None or edge_mask is not None,
                                   "feat_bytes": 4, "tile_conv": True})
         ev0.record()
-    rc = lib.isg_gatv2_tile_conv(
-        _chk_rows(x_l, "x_l"), x_l.stride(0), _chk_rows(x_r, "x_r"), x_r.stride(0), ep.data_ptr(), ep_inv.data_ptr(),
-        planes.data_ptr(), inv.data_ptr(), _chk(att.reshape(-1), "att", torch.float32, (HC,)),
-        _chk(None if bias is None else bias.reshape(-1), "bias", torch.float32, (HC,), optional=True),
-        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), tile_info.data_ptr(),
-        ntiles.data_ptr(), cap,
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr(), N, E, H, C, K,
-        float(negative_slope), _stream())
-    if rc == ISG_EUNSUPPORTED:
-        if timer is not None:
-            timer.drop_last()
+    rc = lib.isg_gatv2_tile_conv(xlp, x_l.stride(0), xrp, x_r.stride(0), ep.data_ptr(), ep_inv.data_ptr(), we.data_ptr(),
+                                 we_inv.data_ptr(), *shared, N, E, H, C, K, float(negative_slope), _stream())
+    if not _launched(rc, "isg_gatv2_tile_conv", timer, ev1):
         return None
-    _lib.check(rc, "isg_gatv2_tile_conv")
-    if timer is not None:
-        ev1.record()
     sub = _mixed_sub(plan)
     if sub is not None:
         _oversize_conv(sub, x_l.index_select(0, sub.nodes), x_r.index_select(0, sub.nodes), edge_attr, w_edge, att, H, bias,
@@ -1840,10 +1778,7 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
         group = dense_tail_group(N, plan.E if plan.rowptr is not None else 0, h.device)
     h_out = torch.empty_like(h)
     xg = torch.empty_like(h) if ins_next is not None and want_rows else None
-    xp = None
-    if ins_next is not None and want_planes:
-        xp = NodePlanes(torch.empty(max(N, 1), 2, 128, dtype=torch.int16, device=h.device),
-                        torch.empty(max(N, 1), dtype=torch.float32, device=h.device))
+    xp = _empty_node_planes(N, h.device) if ins_next is not None and want_planes else None
     rc = lib.isg_mgat_dense_tail(
         _chk_rows(conv_out, "conv_out"), conv_out.stride(0), rm.data_ptr(), rm.size(1), rm.stride(0),
         p1.data_ptr(), inv1.data_ptr(), _chk(l0.bias.detach(), "x_proj.0.bias", torch.float32, (l0.weight.size(0),)),
@@ -2080,6 +2015,18 @@ def _split_weight(weight: Tensor, layout: str):
 def _stamp(x: Tensor):
     """What a value attached to an activation is valid for: x's version, storage and shape (an in-place write invalidates it)."""
     return (_ver(x), x.data_ptr(), tuple(x.shape))
+
+
+def _from_tensor(t: Tensor, value) -> tuple:
+    """A cache entry for a value made from this very tensor (a plan's edge planes, the edge rows of its oversize graphs): valid
+    while `t` is the same object -- a weak reference, since the id of a freed tensor can be reused -- with the same version,
+    storage and shape."""
+    return (weakref.ref(t), _stamp(t), value)
+
+
+def _if_from_tensor(entry: Optional[tuple], t: Tensor):
+    """The value of a _make_from entry if it was made from `t` as it is now, else None."""
+    return entry[2] if entry is not None and entry[0]() is t and entry[1] == _stamp(t) else None
 
 
 def _attach(x: Tensor, name: str, value) -> None:

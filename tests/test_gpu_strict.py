@@ -47,10 +47,7 @@ def both():
     from isubgvqa_amd import _lib
     assert os.path.exists(STRICT), "csrc/libisg_hip_strict.so is missing: __graft_entry__.build() makes it beside the library"
     fast = _lib.load()
-    strict = ctypes.CDLL(STRICT)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(strict, name)
-        fn.restype, fn.argtypes = res, args
+    strict = _lib.bind(ctypes.CDLL(STRICT))
     assert strict.isg_abi_version() == _lib.ABI_VERSION
 
     def run(fn):

@@ -26,6 +26,98 @@ def test_library_exports_every_symbol_in_header():
     assert lib.isg_csr_workspace_bytes(10, 7) == (2 * 11 + 7 + 2) * 4
 
 
+def test_binding_is_derived_from_the_header_rule_by_rule():
+    """_lib.parse_header on small headers: every mapping rule of the two real headers, and nothing a comment says."""
+    import ctypes as ct
+    from isubgvqa_amd import _lib
+    sigs, abi = _lib.parse_header("""
+        #include <stdint.h>
+        #define ISG_ABI_VERSION 7
+        /* not a declaration: int isg_in_comment(int64_t n);  nor this call: isg_called( x ) */
+        // nor this one: float isg_line_comment(void);
+        typedef struct isg_thing isg_thing;
+        int isg_a(void);
+        const char *isg_b(int status);
+        void isg_c(isg_thing *t);
+        size_t isg_d(int64_t n, int32_t c, uint64_t seed, size_t bytes, float slope, double eps);
+        int64_t isg_e(const float *x, int32_t *const out, void *stream, const char *path,
+                      const char *const *names, isg_thing **made);
+        """)
+    assert abi == 7
+    assert list(sigs) == ["isg_a", "isg_b", "isg_c", "isg_d", "isg_e"]
+    assert sigs["isg_a"] == (ct.c_int, [])
+    assert sigs["isg_b"] == (ct.c_char_p, [ct.c_int])
+    assert sigs["isg_c"] == (None, [ct.c_void_p])
+    assert sigs["isg_d"] == (ct.c_size_t, [ct.c_int64, ct.c_int32, ct.c_uint64, ct.c_size_t, ct.c_float, ct.c_double])
+    assert sigs["isg_e"] == (ct.c_int64, [ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_char_p, ct.c_void_p, ct.c_void_p])
+    # the real headers: the library's own answers are bound as the header types them
+    assert _lib.SIGNATURES["isg_csr_workspace_bytes"] == (ct.c_size_t, [ct.c_int64, ct.c_int64])
+    assert _lib.SIGNATURES["isg_status_string"] == (ct.c_char_p, [ct.c_int])
+    from isubgvqa_amd import loader
+    assert loader.SIGNATURES["isg_sg_vocab_free"] == (None, [ct.c_void_p])
+    assert loader.SIGNATURES["isg_sg_vocab_lookup"] == (ct.c_int64, [ct.c_void_p, ct.c_char_p])
+
+
+@pytest.mark.parametrize("decl, says", [
+    ("int isg_x(long n);", "type `long`"),                                   # a type word the headers do not use
+    ("int isg_x(unsigned int n);", "type `unsigned int`"),
+    ("bool isg_x(int n);", "type `bool`"),                                   # ... as a return type
+    ("ISG_API int isg_x(int n);", "type `ISG_API int`"),
+    ("int isg_x(const float x[4], int n);", "array, function-pointer or variadic"),
+    ("int isg_x(void (*done)(int), int n);", "array, function-pointer or variadic"),
+    ("int isg_x(const char *fmt, ...);", "array, function-pointer or variadic"),
+    ("int isg_x(int64_t, int32_t c);", "has no name"),
+    ("int isg_x(const float *, int32_t c);", "has no name"),
+    ("int isg_x(void v);", "parameter `void v`"),
+    ("static inline int isg_x(int n) { return n; } int isg_y(void);", "not a plain function declaration"),
+    ("int isg_x(int n), isg_y(int n);", "array, function-pointer or variadic"),
+    ("*isg_x(int n);", "type `*`"),
+    ("const isg_x(int n);", "type `const`"),
+    ("int isg_x(int * n, float *const *p, const *q);", "type `const *`"),
+    ("int isg_x(int n); int isg_x(int64_t n);", "declared twice"),
+])
+def test_binding_refuses_a_declaration_it_does_not_understand(decl, says):
+    """A declaration that was skipped or half-understood would be a symbol bound with the wrong registers: each raises, with
+    the declaration's text."""
+    from isubgvqa_amd import _lib
+    with pytest.raises(ValueError, match="isg_x") as err:
+        _lib.parse_header("#define ISG_ABI_VERSION 1\nint isg_ok(void);\n" + decl)
+    assert says in str(err.value), str(err.value)
+
+
+def test_binding_counts_the_declarations_it_skipped():
+    """Every `isg_name(` of the comment-stripped header has to be a declaration that was parsed: one that was passed over (no `;`
+    behind it) is named instead of silently left unbound."""
+    from isubgvqa_amd import _lib
+    with pytest.raises(ValueError, match=r"not understood: \['isg_skipped'\]"):
+        _lib.parse_header("#define ISG_ABI_VERSION 1\nint isg_ok(void);\nint isg_skipped(int n)\n")
+    for text in ("int isg_ok(void);", "#define ISG_ABI_VERSION 1\n#define ISG_LOADER_ABI_VERSION 2\nint isg_ok(void);"):
+        with pytest.raises(ValueError, match="ABI_VERSION"):
+            _lib.parse_header(text)
+    with pytest.raises(_lib.IsgError, match="no_such_dir/isg.h"):
+        _lib.read_header(os.path.join(ROOT, "no_such_dir/isg.h"))
+
+
+def test_cache_entry_made_from_a_tensor_holds_for_that_tensor_only():
+    """The plan's edge planes and the oversize graphs' edge rows are kept "for this very edge_attr": the same object (held
+    weakly -- a freed tensor's id and address can be handed to the next one), version, storage and shape."""
+    import gc
+    from isubgvqa_amd import ops
+    t = torch.zeros(6, 4)
+    entry = ops._from_tensor(t, "made")
+    assert ops._if_from_tensor(entry, t) == "made" and ops._if_from_tensor(None, t) is None
+    assert ops._if_from_tensor(entry, t.view(6, 4)) is None          # same storage, version and shape: another object
+    assert ops._if_from_tensor(entry, t.clone()) is None
+    t.add_(1.0)
+    assert ops._if_from_tensor(entry, t) is None                     # written in place since
+    entry = ops._from_tensor(t, "made")
+    ref = entry[0]
+    del t
+    gc.collect()
+    assert ref() is None                                             # the entry does not keep the tensor alive ...
+    assert ops._if_from_tensor(entry, torch.zeros(6, 4)) is None     # ... and no later tensor is taken for it
+
+
 def test_product_path_fails_loudly_on_cpu_tensors():
     from isubgvqa_amd import _lib, ops
     with pytest.raises(_lib.IsgError):
@@ -208,6 +300,22 @@ def test_docs_quote_the_headers_symbol_count_and_abi_version():
         for q in re.findall(r"(\d+) (?:`extern \"C\"` )?symbols", text) + re.findall(r"for all (\d+)\b", text):
             if 30 <= int(q) <= 200:      # counts of the device library (the loader's 15 are quoted too)
                 assert int(q) == n_sym, f"{name} quotes {q} symbols, include/isg.h declares {n_sym}"
+    # INTEGRATION.md's binding stubs: the argtypes / restype lines a maintainer would copy are hand-written and reviewed; the
+    # binding derived from the header has to agree with each of them
+    import ctypes
+    from isubgvqa_amd import _lib
+    names = dict(zip(("P", "I64", "I32", "F32"), (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float)), ctypes=ctypes)
+    text = open(os.path.join(root, "INTEGRATION.md")).read()
+    assert "P, I64, I32, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float" in text
+    quoted = re.findall(r"^_lib\.(isg_\w+)\.(restype|argtypes) = ([^#\n]+)", text, flags=re.M)
+    assert {(n, k) for n, k, _ in quoted} == {
+        ("isg_graph_ptr", "argtypes"), ("isg_csr_workspace_bytes", "restype"), ("isg_csr_workspace_bytes", "argtypes"),
+        ("isg_csr_build", "argtypes"), ("isg_gatv2_mp_fwd", "argtypes"), ("isg_planes32_elems", "restype"),
+        ("isg_planes32_elems", "argtypes"), ("isg_split_planes32", "argtypes"), ("isg_linear_h3p", "argtypes")}, quoted
+    for sym, kind, value in quoted:
+        restype, argtypes = _lib.SIGNATURES[sym]
+        got = eval(value, dict(names))
+        assert got == (argtypes if kind == "argtypes" else restype), f"INTEGRATION.md: {sym}.{kind} = {value.strip()}, header: {(restype, argtypes)}"
 
 
 def test_library_holds_no_cross_selecting_packed_fp32_operation():

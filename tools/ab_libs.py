@@ -18,10 +18,7 @@ variant_path = [a for a in sys.argv[1:] if a.endswith(".so")][0]
 graphs = int(sys.argv[sys.argv.index("--graphs") + 1]) if "--graphs" in sys.argv else 4096
 dev = torch.device("cuda:0")
 shipped = _lib.load()
-variant = ctypes.CDLL(os.path.join(ROOT, variant_path) if not os.path.isabs(variant_path) else variant_path)
-for name, (res, args) in _lib.SIGNATURES.items():
-    fn = getattr(variant, name)
-    fn.restype, fn.argtypes = res, args
+variant = _lib.bind(ctypes.CDLL(os.path.join(ROOT, variant_path) if not os.path.isabs(variant_path) else variant_path))
 assert variant.isg_abi_version() == _lib.ABI_VERSION
 
 if "--full" in sys.argv:

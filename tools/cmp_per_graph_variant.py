@@ -13,10 +13,7 @@ from isubgvqa_amd import _lib, ops
 
 dev = torch.device("cuda:0")
 shipped = _lib.load()
-variant = ctypes.CDLL(os.path.join(ROOT, sys.argv[1]))
-for name, (res, args) in _lib.SIGNATURES.items():
-    fn = getattr(variant, name)
-    fn.restype, fn.argtypes = res, args
+variant = _lib.bind(ctypes.CDLL(os.path.join(ROOT, sys.argv[1])))
 gen = torch.Generator().manual_seed(5)
 for C in (128, 300, 20):
     sizes = torch.randint(1, 200, (300,), generator=gen)

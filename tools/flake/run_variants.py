@@ -50,10 +50,7 @@ def use(path):
     if path is None:
         _lib._lib = shipped
         return
-    variant = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(variant, name)
-        fn.restype, fn.argtypes = res, args
+    variant = _lib.bind(ctypes.CDLL(os.path.abspath(path)))
     _lib._lib = variant
 
 

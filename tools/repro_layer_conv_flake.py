@@ -18,10 +18,7 @@ lib_arg = [a for a in sys.argv[1:] if a.endswith(".so")]
 if lib_arg:             # a variant build of the library (tools/_build/...) in place of the shipped one
     import ctypes
     from isubgvqa_amd import _lib
-    variant = ctypes.CDLL(os.path.abspath(lib_arg[0]))
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(variant, name)
-        fn.restype, fn.argtypes = res, args
+    variant = _lib.bind(ctypes.CDLL(os.path.abspath(lib_arg[0])))
     _lib.load()
     _lib._lib = variant
     print("library:", lib_arg[0])
