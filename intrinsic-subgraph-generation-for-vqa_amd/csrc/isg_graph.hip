@@ -142,15 +142,25 @@ __global__ void csr_fill_kernel(const int64_t *__restrict__ dst, int E, int N, c
   eid_tmp[rowptr[d] + slot] = e;
 }
 
+// The plan's last launch hands bound i (final by then) to the host: as it is, or -- bounds_max given -- as the largest value of
+// every call since the caller zeroed bounds_max[i] (device memory: a read of the pinned host word would cost a bus round trip).
+__device__ __forceinline__ void publish_bound(int *bounds_host, int *bounds_max, int i, int v) {
+  if (bounds_max) {
+    v = max(v, bounds_max[i]);
+    bounds_max[i] = v;
+  }
+  bounds_host[i] = v;
+}
+
 // The atomic fill leaves each segment in arrival order; rank every slot by its edge id inside its
 // segment so the final order is ascending edge id (= torch_scatter's CPU accumulation order).
 __global__ void csr_rank_kernel(const int64_t *__restrict__ edge_index, int E, int N,
                                 const int *__restrict__ rowptr, const int *__restrict__ eid_tmp,
                                 int *__restrict__ eid, int *__restrict__ src, int *__restrict__ dst,
-                                const int *__restrict__ bounds = nullptr, int *bounds_host = nullptr) {
+                                const int *__restrict__ bounds = nullptr, int *bounds_host = nullptr, int *bounds_max = nullptr) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (bounds_host && t < 2) {           // the plan's last launch: the bounds are final (isg_graph_plan_build)
-    bounds_host[t] = bounds[t];
+    publish_bound(bounds_host, bounds_max, t, bounds[t]);
     __threadfence_system();
   }
   int total = rowptr[N];
@@ -173,8 +183,8 @@ __global__ void csr_rank_kernel(const int64_t *__restrict__ edge_index, int E, i
 // (2) in-degree histogram + largest graph, (3) per-chunk degree sums, (4) scan: every workgroup adds up the chunk sums before
 // its own (at most a few hundred values) instead of a separate one-workgroup scan, (5) atomic fill + per-graph slot ranges and
 // the largest edge count, (6) rank by edge id inside each segment.  (7) is the tile plan (isg_tile_plan).
-__global__ void copy_bounds_kernel(const int *__restrict__ bounds, int *bounds_host) {
-  if (threadIdx.x < 2) bounds_host[threadIdx.x] = bounds[threadIdx.x];
+__global__ void copy_bounds_kernel(const int *__restrict__ bounds, int *bounds_host, int *bounds_max) {
+  if (threadIdx.x < 2) publish_bound(bounds_host, bounds_max, threadIdx.x, bounds[threadIdx.x]);
   __threadfence_system();
 }
 __global__ void plan_init_kernel(const int64_t *__restrict__ batch, int N, int B, int *__restrict__ ptr, int *__restrict__ zero,
@@ -274,7 +284,7 @@ __global__ void plan_fill_kernel(const int64_t *__restrict__ dst, int E, int N, 
 constexpr int PS_THREADS = 1024, PS_MAX_N = 2048, PS_MAX_E = 8192;
 __global__ __launch_bounds__(PS_THREADS) void plan_small_kernel(const int64_t *__restrict__ batch, const int64_t *__restrict__ edge_index,
                                                                 int N, int E, int B, int *__restrict__ ptr, int *__restrict__ bounds,
-                                                                int *bounds_host, int *__restrict__ rowptr, int *__restrict__ eid,
+                                                                int *bounds_host, int *bounds_max, int *__restrict__ rowptr, int *__restrict__ eid,
                                                                 int *__restrict__ src, int *__restrict__ dst, int *__restrict__ eptr,
                                                                 int *__restrict__ deg, int *__restrict__ cursor, int *__restrict__ eid_tmp) {
   __shared__ int s_scan[PS_THREADS];
@@ -352,7 +362,7 @@ __global__ __launch_bounds__(PS_THREADS) void plan_small_kernel(const int64_t *_
   if (tid < 2) {
     bounds[tid] = s_max[tid];
     if (bounds_host) {
-      bounds_host[tid] = s_max[tid];
+      publish_bound(bounds_host, bounds_max, tid, s_max[tid]);
       __threadfence_system();
     }
   }
@@ -449,8 +459,11 @@ extern "C" int isg_graph_edge_ptr(const int32_t *ptr, const int32_t *rowptr, int
 // ptr / nmax, CSR by destination, per-graph slot ranges and the largest edge count in six launches (the tile plan is the
 // seventh): what isg_graph_ptr + isg_csr_build + isg_graph_edge_ptr compute in fourteen.  bounds int32[2] receives {largest node
 // count, largest edge count of a graph}; the other outputs as in those three; workspace: isg_csr_workspace_bytes(N, E).
+// bounds_host (optional, pinned host memory the device can address) receives the same two values from the last launch -- or, with
+// bounds_max (optional, device int32[2] the caller zeroed), the largest values of every call since: a caller who replays this call
+// from a hipGraph and looks at bounds_host only now and then misses no replay's bounds.
 extern "C" int isg_graph_plan_build(const int64_t *batch, const int64_t *edge_index, int64_t N, int64_t E, int64_t B,
-                                    int32_t *ptr, int32_t *bounds, int32_t *bounds_host, int32_t *rowptr, int32_t *eid,
+                                    int32_t *ptr, int32_t *bounds, int32_t *bounds_host, int32_t *bounds_max, int32_t *rowptr, int32_t *eid,
                                     int32_t *src, int32_t *dst, int32_t *eptr, void *workspace, size_t workspace_bytes,
                                     void *stream) {
   if (N < 0 || E < 0 || B < 0 || !ptr || !bounds || !rowptr || !eptr || (N > 0 && !batch) || (E > 0 && (!edge_index || !eid || !src)))
@@ -465,7 +478,7 @@ extern "C" int isg_graph_plan_build(const int64_t *batch, const int64_t *edge_in
   const int n = (int)N, e = (int)E, b = (int)B;
   static const bool small_ok = [] { const char *f = getenv("ISG_PLAN_SMALL"); return !f || atoi(f) != 0; }();
   if (small_ok && n <= PS_MAX_N && e <= PS_MAX_E && b <= PS_MAX_N && e > 0) {      // a handful of graphs: one workgroup, one launch
-    plan_small_kernel<<<1, PS_THREADS, 0, st>>>(batch, edge_index, n, e, b, ptr, bounds, bounds_host, rowptr, eid, src, dst, eptr, deg,
+    plan_small_kernel<<<1, PS_THREADS, 0, st>>>(batch, edge_index, n, e, b, ptr, bounds, bounds_host, bounds_max, rowptr, eid, src, dst, eptr, deg,
                                                cursor, eid_tmp);
     return check_launch();
   }
@@ -483,8 +496,8 @@ extern "C" int isg_graph_plan_build(const int64_t *batch, const int64_t *edge_in
   const int span3 = std::max(e, b + 1);
   plan_fill_kernel<<<(span3 + 255) / 256, 256, 0, st>>>(edge_index + E, e, n, rowptr, cursor, eid_tmp, ptr, b, eptr, bounds + 1);
   if (e > 0)
-    csr_rank_kernel<<<(e + 255) / 256, 256, 0, st>>>(edge_index, e, n, rowptr, eid_tmp, eid, src, dst, bounds, bounds_host);
+    csr_rank_kernel<<<(e + 255) / 256, 256, 0, st>>>(edge_index, e, n, rowptr, eid_tmp, eid, src, dst, bounds, bounds_host, bounds_max);
   else if (bounds_host)
-    copy_bounds_kernel<<<1, 64, 0, st>>>(bounds, bounds_host);
+    copy_bounds_kernel<<<1, 64, 0, st>>>(bounds, bounds_host, bounds_max);
   return check_launch();
 }

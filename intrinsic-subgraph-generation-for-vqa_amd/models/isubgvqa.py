@@ -114,7 +114,8 @@ class ISubGVQA(torch.nn.Module):
         batches are launch-bound (run_token_coo.py:49-79 evaluates one question at a time; datasets/build.py:59-62 four times the
         training batch).  Needs the collate's per-graph bounds on `scene_graphs` (max_nodes / max_edges: loader.SceneGraphBatch
         carries them); sampler noise from `noises` or from torch's generator inside the graph; a `seed` is refused (it would be
-        frozen into the graph).  Returns the graph's static output tensors: valid until the next call with the same shapes."""
+        frozen into the graph).  Returns the graph's static output tensors: valid until the next call with the same shapes.  The
+        capture is stamped with the module's weights (ops.WeightsWatch): after an update it is captured again, not replayed."""
         if seed is not None:
             raise ValueError("capture=True: a seed is a kernel argument and would repeat in every replay; pass `noises` or neither")
         if plan is not None or explainer or explainer_stage:
@@ -127,6 +128,9 @@ class ISubGVQA(torch.nn.Module):
         cap = self.__dict__.get("_step_capture")
         if cap is None:
             cap = self.__dict__["_step_capture"] = ops.StepCapture()
+        watch = self.__dict__.get("_weights_watch")
+        if watch is None:
+            watch = self.__dict__["_weights_watch"] = ops.WeightsWatch(self)
         keys = sorted(noises) if noises else []
         x_bbox, sym = scene_graphs.x_bbox, scene_graphs.added_sym_edge
 
@@ -139,7 +143,7 @@ class ISubGVQA(torch.nn.Module):
 
         tensors = [node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, x_bbox, sym, text_uniform] + \
                   [noises[k] for k in keys]
-        return cap.run(fn, tensors, key_extra=("isubgvqa", int(mn), int(me), tuple(keys), self.training))
+        return cap.run(fn, tensors, key_extra=("isubgvqa", int(mn), int(me), tuple(keys), self.training), stamp=watch.stamp())
 
     def _captured_language(self, questions, qsts_att_mask, text_uniform, seed):
         """language_features() -- question encoder, program decoder, the two reductions: ~65 of a forward's ~110 launches -- as a
@@ -153,8 +157,23 @@ class ISubGVQA(torch.nn.Module):
         cap = self.__dict__.get("_language_capture")
         if cap is None:
             cap = self.__dict__["_language_capture"] = ops.StepCapture(max_entries=64)
-        return cap.run(lambda q, m, tu: (self.language_features(q, m, tu, None), None), [questions, qsts_att_mask, text_uniform],
-                       key_extra=("language", self.training))
+        watch = self.__dict__.get("_language_watch")
+        if watch is None:      # the modules language_features() runs: the scene-graph side's weights are read eagerly behind the replay
+            mods = [self.question_encoder, self.program_decoder, self.qsts_reduction, self.instr_reduction]
+            if self.text_sampling:
+                mods += [self.qsts_att_keys, self.qsts_att_query]
+            watch = self.__dict__["_language_watch"] = ops.WeightsWatch(*mods)
+
+        def fn(q, m, tu):       # mask_text is an OUTPUT of the graph: module state belongs to whichever call wrote it last
+            glf, instr = self.language_features(q, m, tu, None)
+            return (glf, instr, self.last_mask_text), None
+
+        glf, instr, mask_text = cap.run(fn, [questions, qsts_att_mask, text_uniform], key_extra=("language", self.training),
+                                        stamp=watch.stamp())
+        # (static tensors of the replayed graph: the graph side reads glf / instr behind it on the same stream; mask_text leaves
+        # forward(), so the caller gets a copy of its own)
+        self.last_mask_text = mask_text = None if mask_text is None else mask_text.clone()
+        return glf, instr, mask_text
 
     def forward(self, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask,
                 return_masks=False, explainer=False, explainer_stage=False, expl_bypass_x=False, scene_graphs=None,
@@ -168,15 +187,13 @@ class ISubGVQA(torch.nn.Module):
             return self._captured(node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, explainer,
                                   explainer_stage, scene_graphs, noises, seed, plan, text_uniform)
         if capture == "language":
-            glf, instr_vectors = self._captured_language(questions, qsts_att_mask, text_uniform, seed)
+            glf, instr_vectors, mask_text = self._captured_language(questions, qsts_att_mask, text_uniform, seed)
         elif capture:
             raise ValueError(f"capture = {capture!r}: True (the whole forward), 'language' (the question side only) or False")
         else:
             glf, instr_vectors = self.language_features(questions, qsts_att_mask, text_uniform,
                                                         None if seed is None else seed + 7919)
-        mask_text = self.last_mask_text
-        if capture == "language" and mask_text is not None:
-            mask_text = mask_text.clone()                  # (a static tensor of the replayed graph: the caller gets its own)
+            mask_text = self.last_mask_text
         if explainer and explainer_stage > 0:                                            # :249-253
             node_embeddings, expl_bypass_x = expl_bypass_x, node_embeddings.clone()
         if plan is None:   # a loader.SceneGraphBatch carries the per-graph bounds: the plan is then built without a sync

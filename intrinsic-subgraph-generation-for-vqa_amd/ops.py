@@ -11,6 +11,7 @@ from __future__ import annotations
 import contextlib
 import copy
 import dataclasses
+import operator
 import sys
 import types
 import weakref
@@ -269,7 +270,7 @@ _PENDING_HINTS = []      # (event, pinned int32[2] = true [max nodes, max edges]
 _PENDING_SIZES = []      # (event, pinned int64[2 or 3] = graphs beyond a tile / their nodes / their edges counted on the device, the hint's counts)
 
 
-_CAPTURE_BOUNDS = []     # StepCapture: the pinned int32[2] a plan built inside the capture in progress hands its last kernel
+_CAPTURE_BOUNDS = []     # StepCapture: the (pinned int32[2], device int32[2]) a plan built inside the capture in progress hands its last kernel
 
 
 def check_plans(block: bool = True) -> None:
@@ -589,7 +590,7 @@ class GraphPlan:
             if graph_sizes.device.type != "cpu" or graph_sizes.dim() != 2 or tuple(graph_sizes.shape) != (2, B):
                 raise ValueError("graph_sizes: a HOST tensor [2, num_graphs] (nodes, in-edges per graph)")
             plan.sizes_host = graph_sizes.long()
-        host_bounds = None
+        host_bounds = bounds_max = None
         if edge_index is not None:
             _chk(edge_index, "edge_index", torch.int64)
             if edge_index.dim() != 2 or edge_index.size(0) != 2:
@@ -610,10 +611,11 @@ class GraphPlan:
                 if max_nodes is not None and max_edges is not None and CFG.bounds_to_host:
                     if not torch.cuda.is_current_stream_capturing():
                         host_bounds = torch.empty(2, dtype=torch.int32, pin_memory=True)
-                    elif _CAPTURE_BOUNDS:          # StepCapture: pinned memory allocated BEFORE the capture; every replay rewrites it
-                        host_bounds = _CAPTURE_BOUNDS[-1]
+                    elif _CAPTURE_BOUNDS:          # StepCapture: pinned memory allocated BEFORE the capture, and a device int32[2]
+                        host_bounds, bounds_max = _CAPTURE_BOUNDS[-1]      # in which the replays keep their running maximum
                 _lib.check(lib.isg_graph_plan_build(batch.data_ptr(), edge_index.data_ptr(), N, E, B, ptr.data_ptr(),
                                                     bounds.data_ptr(), 0 if host_bounds is None else host_bounds.data_ptr(),
+                                                    0 if bounds_max is None else bounds_max.data_ptr(),
                                                     plan.rowptr.data_ptr(), plan.eid.data_ptr(),
                                                     plan.src.data_ptr(), plan.dst.data_ptr(), plan.eptr.data_ptr(), ws.data_ptr(),
                                                     ws_bytes, _stream()), "isg_graph_plan_build")
@@ -977,10 +979,14 @@ class StepCapture:
     per KEY = (shape / dtype / device of every input, the caller's hints and options, the module's switches): the first call of a key
     runs `fn` eagerly on private static copies of the inputs (kernel attributes, derived weights, allocator pools; the plan's hints
     are checked), captures it once, and every call replays it after copying the caller's tensors into the static ones (a tensor
-    that already IS the static one is not copied).  `fn(*tensors) -> (outputs, plan)`: the GraphPlan must be built INSIDE fn from
-    host-side bounds (no device-to-host read is possible in a capture); its true bounds are written to pinned host memory by the
-    plan's own last kernel on every replay and compared with the hints at the next call -- a batch whose graphs exceed the hints
-    raises IsgError one call late, exactly like an eager hinted build (check_plans).  Outputs are the graph's static tensors: valid
+    that already IS the static one is not copied).  A capture bakes in the tensors derived_weight() made from the weights at capture
+    time, so the caller hands over `stamp=WeightsWatch(module).stamp()`: an entry whose stamp differs from the call's (a weight or buffer
+    written in place, replaced or loaded; invalidate_weight_cache()) is retired and captured again in its place -- a replay never
+    runs on derived weights older than the live ones.  `fn(*tensors) -> (outputs, plan)`: the GraphPlan must be built INSIDE fn
+    from host-side bounds (no device-to-host read is possible in a capture); the plan's own last kernel hands the largest true
+    bounds of ALL the entry's replays (kept on the device) to pinned host memory, compared with the hints at the next call that finds the last replay
+    finished, when the entry is retired or evicted, and in verify() -- a batch whose graphs exceed the hints raises IsgError at one
+    of those, however far the host runs ahead of the device in between.  Outputs are the graph's static tensors: valid
     until the next call with the same key.  Nothing here is a fallback: a forward that cannot be captured raises."""
 
     def __init__(self, max_entries: int = 8):
@@ -997,29 +1003,46 @@ class StepCapture:
     def _check_bounds(self, ent) -> None:
         plan, host = ent["plan"], ent["host"]
         if plan is None or host is None or not ent["event"].query():
-            return                                      # the last replay has not finished: look again at the next call
-        n_true, e_true = int(host[0]), int(host[1])
+            return                                      # the last replay has not finished: its bounds stay in the running maximum
+        n_true, e_true = int(host[0]), int(host[1])     # the largest of every replay since the capture (or the last raise)
         hn, he = plan._hints
         if n_true > hn or (he is not None and e_true > he):
+            ent["max"].zero_()                          # reported once: the running maximum starts over (in stream order; no
+            host.zero_()                                # replay is in flight: the event has completed)
             raise _lib.IsgError(f"GraphPlan hints understate the batch: max_nodes={hn} / max_edges={he} given, but a graph of a "
-                                f"recent replay has {n_true} nodes / {e_true} edges; results of that replay are invalid")
+                                f"recent replay has {n_true} nodes / {e_true} edges; results of that replay are invalid "
+                                f"(the capture of {ent['what']!r})")
 
-    def run(self, fn, tensors, key_extra=(), warm: int = 2):
+    def _retire(self, key) -> None:
+        """Drop an entry (its hipGraph and private allocator pool); its replays' bounds are compared first, none is lost: this
+        waits for the entry's last replay (an eviction or a stale stamp is followed by a capture, which synchronises anyway)."""
+        ent = self.entries.pop(key)
+        ent["event"].synchronize()
+        self._check_bounds(ent)
+
+    def run(self, fn, tensors, key_extra=(), warm: int = 2, stamp=None):
         if torch.is_grad_enabled():
             raise RuntimeError("StepCapture: inference only (wrap the call in torch.no_grad() / inference_mode())")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("StepCapture: already inside a capture")
         key = (tuple(self._sig(t) for t in tensors), key_extra, CFG)
         ent = self.entries.get(key)
+        if ent is not None and ent["stamp"] != stamp:
+            self._retire(key)                          # captured from other weights: freed before its successor is captured
+            ent = None
         if ent is None:
+            while len(self.entries) >= self.max_entries > 0:     # room first: an evicted entry's bounds are compared (and may raise)
+                self._retire(next(iter(self.entries)))           # before anything new is captured
             static = [None if t is None else t.clone() for t in tensors]
             for _ in range(max(1, warm)):
                 fn(*static)
             check_plans()                              # the eager runs' hints: a wrong one raises HERE, before anything is captured
             torch.cuda.synchronize()
+            # outside the capture: memory of the graph's own pool would be zeroed again by every replay
             host = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+            running = torch.zeros(2, dtype=torch.int32, device=torch.cuda.current_device())
             graph = torch.cuda.CUDAGraph()
-            _CAPTURE_BOUNDS.append(host)
+            _CAPTURE_BOUNDS.append((host, running))
             try:
                 with torch.cuda.graph(graph):
                     outs, plan = fn(*static)
@@ -1027,11 +1050,10 @@ class StepCapture:
                 _CAPTURE_BOUNDS.pop()
             if plan is not None and getattr(plan, "_bounds_host", None) is None:
                 host = None                            # (a plan without an edge list / without both hints keeps its bounds on the device)
-            ent = {"graph": graph, "static": static, "outs": outs, "plan": plan, "host": host, "event": torch.cuda.Event()}
+            ent = {"graph": graph, "static": static, "outs": outs, "plan": plan, "host": host, "max": running, "event": torch.cuda.Event(),
+                   "stamp": stamp, "what": key_extra}
             self.entries[key] = ent
             self.captures += 1
-            while len(self.entries) > self.max_entries:
-                self.entries.popitem(last=False)
         else:
             self.entries.move_to_end(key)
             self._check_bounds(ent)
@@ -1044,7 +1066,7 @@ class StepCapture:
         return ent["outs"]
 
     def verify(self) -> None:
-        """Synchronise and check every entry's last replay (tests; the end of an evaluation loop)."""
+        """Synchronise and check every entry's replays (tests; the end of an evaluation loop)."""
         torch.cuda.synchronize()
         for ent in self.entries.values():
             self._check_bounds(ent)
@@ -1969,11 +1991,64 @@ def embedding_sum(weight: Tensor, idx: Tensor) -> Tensor:
     return out
 
 
+_WEIGHTS_GENERATION = 0      # invalidate_weight_cache() counts up: part of every weights_stamp()
+
+
 def invalidate_weight_cache() -> None:
-    """Drop every cached derivative of a weight (split planes, fused weights).  The cache is validated by (object identity,
+    """Drop every cached derivative of a weight (split planes, fused weights) and make every StepCapture entry stale (each holds
+    such derivatives inside its hipGraph; it is captured again at its next call).  The cache is validated by (object identity,
     tensor._version, data_ptr); a write THROUGH `.data` (weight.data.copy_/mul_, as init / EMA / weight-surgery code does) bumps
     neither, so such code must call this (Module.load_state_dict goes through copy_ on the Parameter and is safe)."""
+    global _WEIGHTS_GENERATION
+    _WEIGHTS_GENERATION += 1
     _DERIVED.clear()
+
+
+class WeightsWatch:
+    """Stamp of the weights of one or more modules, cheap enough to take before every captured call (StepCapture.run's `stamp`):
+    two stamps are equal when nothing in between could have changed what a forward computes from the parameters and buffers.
+    stamp() = (walk number, every tensor's _version, every tensor's data_ptr) -- what derived_weight() validates its cache by,
+    so a captured and an eager forward notice the same events: an in-place write (optimizer.step(), p.add_(), load_state_dict's
+    copy_, BatchNorm's running statistics) changes a version; `p.data = other` (Module.to(dtype) / .half(), weight swaps) an
+    address; a Parameter or buffer OBJECT that was replaced is noticed by identity (the modules' own `_parameters` / `_buffers`
+    dicts are read at every call) and invalidate_weight_cache() by its generation: both walk the module tree again, which starts
+    a new walk number.  Host work only; the tree itself is walked once.  Timed with perf_counter loops on a CPU-only build host
+    (not on the GPU host): 27-37 us per stamp() over the 147 tensors of ISubGVQA's question side before data_ptr was added
+    (~0.2 us per tensor and attribute), against 330 us for list(Module.modules()) of the 251-module ISubGVQA alone.
+    Blind spots, each answered by invalidate_weight_cache(): a WRITE through `.data` (p.data.mul_(): neither version, address nor
+    identity moves -- derived_weight() cannot see it either), a submodule exchanged for another, a tensor registered on a
+    module that had none when the tree was walked.  Tensors made under torch.inference_mode() have no version (_ver): identity
+    and address stand for them."""
+    _WALKS = 0
+
+    def __init__(self, *modules):
+        self.modules = modules
+        self._generation = None
+
+    def _walk(self) -> None:
+        WeightsWatch._WALKS += 1
+        self._generation, self._number = _WEIGHTS_GENERATION, WeightsWatch._WALKS
+        seen, dicts = set(), []
+        for root in self.modules:
+            for m in root.modules():
+                if id(m) not in seen:
+                    seen.add(id(m))
+                    dicts += [d for d in (m._parameters, m._buffers) if d]
+        self._dicts = dicts
+        self._tensors = [t for d in dicts for t in d.values()]          # (None for an absent bias: compared by identity too)
+        self._present = [t for t in self._tensors if t is not None]
+        self._versioned = [t for t in self._present if not t.is_inference()]
+
+    def stamp(self):
+        if self._generation != _WEIGHTS_GENERATION:
+            self._walk()
+        now = [t for d in self._dicts for t in d.values()]
+        if len(now) != len(self._tensors) or not all(map(operator.is_, now, self._tensors)):
+            self._walk()
+        return (self._number, *map(_VERSION_OF, self._versioned), *map(_DATA_PTR_OF, self._present))
+
+
+_VERSION_OF, _DATA_PTR_OF = operator.attrgetter("_version"), operator.methodcaller("data_ptr")
 
 
 def _weight_planes(weight: Tensor, cache: bool = True, layout: str = "tile") -> Tensor:

@@ -193,6 +193,9 @@ class AnswerModel(torch.nn.Module):
         cap = self.__dict__.get("_step_capture")
         if cap is None:
             cap = self.__dict__["_step_capture"] = ops.StepCapture()
+        watch = self.__dict__.get("_weights_watch")
+        if watch is None:
+            watch = self.__dict__["_weights_watch"] = ops.WeightsWatch(self)
         keys = sorted(noises) if noises else []
         hints = (int(wl.max_nodes), int(wl.max_edges))
 
@@ -202,7 +205,7 @@ class AnswerModel(torch.nn.Module):
             return out, p
 
         tensors = [wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf] + [noises[k] for k in keys]
-        return cap.run(fn, tensors, key_extra=("answer", hints, tuple(keys), self.training))
+        return cap.run(fn, tensors, key_extra=("answer", hints, tuple(keys), self.training), stamp=watch.stamp())
 
     def _answer(self, x, edge_index, edge_attr, batch, instr, glf, plan, noises, seed, gate_feats):
         from . import ops as _ops

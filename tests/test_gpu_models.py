@@ -988,6 +988,7 @@ def test_capture_of_the_question_side_alone(dev):
             got = model(wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.questions, wl.att_mask, return_masks=True, scene_graphs=sg,
                         capture="language")
             assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2])
+            assert (got[4] is None and ref[4] is None) or torch.equal(got[4], ref[4])      # (None without --text_sampling)
         cap = model._language_capture
         assert len(shapes) >= 3, "the batches were meant to differ in their graphs' sizes"
         assert (cap.captures, cap.replays) == (2, 4)

@@ -510,3 +510,85 @@ def test_linear_relu_and_gelu_are_exclusive_at_every_size():
     for M in (0, 12, 1024, 5000):
         with pytest.raises(ValueError):
             ops.linear(torch.zeros(M, 512), torch.zeros(512, 512), relu=True, gelu=True)
+
+
+def _watched_module():
+    torch.manual_seed(0)
+    return torch.nn.Sequential(torch.nn.Linear(8, 8), torch.nn.BatchNorm1d(8), torch.nn.Sequential(torch.nn.Linear(8, 4, bias=False)))
+
+
+def test_weights_watch_stamp_is_stable_while_nothing_is_written():
+    """ops.WeightsWatch.stamp() -- what a StepCapture entry is stamped with: equal between two calls with nothing in between, a
+    forward in eval mode included, and equal for two watches' own repeated stamps; one tree walk serves them all."""
+    from isubgvqa_amd import ops
+    m = _watched_module().eval()
+    w = ops.WeightsWatch(m)
+    s0, walks = w.stamp(), ops.WeightsWatch._WALKS
+    with torch.no_grad():
+        m(torch.zeros(3, 8))
+    assert w.stamp() == s0 and w.stamp() == s0
+    assert ops.WeightsWatch._WALKS == walks, "the module tree was walked again although nothing changed"
+    # the walk number; versions of five parameters (the absent bias has none) and BatchNorm's three buffers; their eight addresses
+    assert len(s0) == 1 + (5 + 3) + (5 + 3)
+
+
+@pytest.mark.parametrize("write", ["parameter_in_place", "optimizer_step", "buffer_in_place", "batchnorm_in_training", "load_state_dict",
+                                   "parameter_replaced", "buffer_replaced", "bias_added", "data_assigned", "invalidate_weight_cache"])
+def test_weights_watch_stamp_changes_with_every_write_it_promises_to_see(write):
+    """Each way the weights of a module change between two captured calls changes the stamp -- and the stamp is stable again
+    afterwards.  Documented blind spots, stated rather than asserted away: a WRITE through `.data` moves neither a version, an address
+    nor an identity (the derived-weight cache cannot see it either), a submodule exchanged for another and a tensor
+    registered on a module that had none are not looked for per call; all three are answered by ops.invalidate_weight_cache(),
+    the last case here."""
+    from isubgvqa_amd import ops
+    m = _watched_module().eval()
+    w = ops.WeightsWatch(m)
+    s0 = w.stamp()
+    if write == "parameter_in_place":
+        with torch.no_grad():
+            m[2][0].weight.add_(1.0)
+    elif write == "optimizer_step":
+        m[0].bias.grad = torch.ones(8)
+        torch.optim.SGD([m[0].bias], lr=0.1).step()
+    elif write == "buffer_in_place":
+        m[1].running_var.mul_(2.0)
+    elif write == "batchnorm_in_training":
+        m.train()(torch.randn(5, 8))
+    elif write == "load_state_dict":
+        m.load_state_dict({k: v + 1 for k, v in m.state_dict().items()})
+    elif write == "parameter_replaced":
+        m[0].weight = torch.nn.Parameter(m[0].weight.detach().clone())
+    elif write == "buffer_replaced":
+        m[1].running_mean = torch.ones(8)
+    elif write == "data_assigned":
+        m[0].weight.data = m[0].weight.data.clone()                 # what Module.to(dtype) does: same object, same version, new address
+    elif write == "bias_added":
+        m[2][0].bias = torch.nn.Parameter(torch.zeros(4))           # (the slot existed, holding None)
+    else:
+        m[0].weight.data.mul_(2.0)
+        assert w.stamp() == s0, "a write through .data is the documented blind spot; if it is seen now, say so in the docstrings"
+        ops.invalidate_weight_cache()
+    s1 = w.stamp()
+    assert s1 != s0
+    assert w.stamp() == s1
+
+
+def test_weights_watch_over_inference_tensors_and_several_modules():
+    """Tensors made under torch.inference_mode() have no version counter (ops._ver answers -1; reading `._version` raises): the stamp
+    must not raise, and identity still stands for them.  A watch over several modules (the question side of ISubGVQA) sees each."""
+    from isubgvqa_amd import ops
+    with torch.inference_mode():
+        a = torch.nn.Linear(4, 4)
+    b = torch.nn.Linear(4, 4)
+    w = ops.WeightsWatch(a, b)
+    s0 = w.stamp()
+    assert w.stamp() == s0 and len(s0) == 1 + 2 + 4        # the walk number, b's two versions, four addresses
+    with torch.inference_mode():
+        a.weight.add_(1.0)                                 # invisible (no version), as for the derived-weight cache
+    assert w.stamp() == s0
+    a.weight = torch.nn.Parameter(torch.zeros(4, 4))
+    s1 = w.stamp()
+    assert s1 != s0
+    with torch.no_grad():
+        b.bias.add_(1.0)
+    assert w.stamp() != s1
