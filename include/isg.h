@@ -305,6 +305,10 @@ int isg_gatv2_tile_conv(const float *x_l, int32_t ldl, const float *x_r, int32_t
  * Masked launches skip the slots whose mask is +-0 (edge product, logit, aggregation term): with finite inputs their
  * logit is +0 and their term adds nothing, so the results are unchanged.  A skipped slot whose x_l, x_r or edge projection holds an
  * Inf or NaN gets the logit +0 where the reference gives NaN.  ISG_LC_DENSE_MASK=1 (read once) walks every slot instead.
+ * They also work on groups of tiles: x_l / x_r are formed once per group, and only for the rows that a live slot of
+ * the group names.  Same bits for finite inputs; an Inf or NaN in a row that no live slot names reaches nothing any more, and a dead
+ * term's +-0 product may carry another row's sign, which shows only where an accumulator is exactly -0.  ISG_LC_GROUP=n (read once)
+ * forces the tiles per group, 1 = one tile per work item as before.
  * row_dead (NULL, or uint8 [N,H], 4-byte aligned; written by masked launches only): 1 when every bit of the (row, head)'s
  * aggregation accumulators was zero before the bias went in -- the row of `out` is then +0 + bias and its rowmax that vector's,
  * whatever the inputs were -- else 0.  isg_mgat_dense_tail runs x_proj once for all such rows of a group of tiles. */

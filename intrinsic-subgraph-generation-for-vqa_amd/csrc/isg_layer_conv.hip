@@ -63,6 +63,7 @@ struct LcArgs {
   float slope;
   unsigned char *row_dead;          // optional, masked launches: [N, H], 1 = every accumulator bit of the (row, head) was zero
                                     // (last: the fields before it keep the offsets the unmasked instantiations were compiled with)
+  int G;                            // tiles per group of gatv2_layer_conv_groups_kernel (the per-tile kernel does not read it)
 };
 
 // The live slots of a masked tile: bit s of w[s >> 6] is set when slot s carries a mask whose bits are not +-0.  A slot with a
@@ -236,6 +237,163 @@ __global__ __launch_bounds__(256, 3) void node_gate_planes_kernel(const _Float16
     if (n < nrows && l == 0) gate[r0 + n] = gelu_libm(dot / denom);
   }
 }
+
+// logit epilogue of a chunk, behind the lookup of the lane's slot (sinv = its edge planes' inverse scale, me = its mask, XS / XD =
+// the rows of its source in sXl and of its destination in sXr): shared text of the per-tile kernel and the grouped one
+#define LC_EPILOGUE_ARITH(SL01, XS, XD)                                                                              \
+    float part[4];                                                                                                   \
+    int cb = tw * 32 + 4 * hh;       /* laundered: hoisted out of the chunk loop, the 16 addresses below cost 16 registers */ \
+    asm volatile("" : "+v"(cb));                                                                                     \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                  \
+      const int cc = cb + 8 * g;                                                                                     \
+      const float4 xl4 = *reinterpret_cast<const float4 *>(&sXl[XS][cc]);                                            \
+      const float4 xr4 = *reinterpret_cast<const float4 *>(&sXr[XD][cc]);                                            \
+      const float4 at4 = *reinterpret_cast<const float4 *>(&s_att[cc]);                                              \
+      const float4 wi4 = *reinterpret_cast<const float4 *>(&s_weinv[cc]);                                            \
+      const float lv[4] = {xl4.x, xl4.y, xl4.z, xl4.w}, rv[4] = {xr4.x, xr4.y, xr4.z, xr4.w};                        \
+      const float atv[4] = {at4.x, at4.y, at4.z, at4.w}, wiv[4] = {wi4.x, wi4.y, wi4.z, wi4.w};                      \
+      part[g] = 0.f;                                                                                                 \
+      _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                                                             \
+        const float e = (acc[g * 4 + jj] * sinv) * wiv[jj];                                                          \
+        float z = (rv[jj] + lv[jj]) + e;                                                                             \
+        if (MASKED) z *= me;                                                                                         \
+        z = (SL01) ? fmaxf(z, z * slope) : (z > 0.f ? z : z * slope);   /* 0 <= slope <= 1: max(z, slope z), same bits */ \
+        if (MASKED) z *= me;                                                                                         \
+        part[g] = fmaf(z, atv[jj], part[g]);                                                                         \
+      }                                                                                                              \
+      if (g < 3) __builtin_amdgcn_sched_barrier(0);                                                                  \
+    }                                                                                                                \
+    const float mine = (part[0] + part[1]) + (part[2] + part[3]);                                                    \
+    const float tot = mine + __shfl_xor(mine, 32);                                                                   \
+    if (hh == 0) s_part[tw * 64 + prow] = tot;
+
+// Softmax + aggregation of one tile (isg_mp_graph.hip phase C: same operations in the same order), as text shared by the per-tile
+// kernel and the grouped one (a macro like the request macros below, for their reason; as an inline function the per-tile
+// kernel compiled to other instructions and one spill more).  REC(slot) = the slot's {x_l row in sXl, edge id, -, mask bits}.
+#define LC_AGGREGATE(REC)                                                                                                                  \
+  {                                                                                                                                        \
+    const int q8 = lane >> 3, j8 = lane & 7;                                                                                               \
+    const int k = 8 * wave + q8;                                                                                                           \
+    if (k < nrows) {                                                                                                                       \
+      const int rb = s_rp[k], re = min(s_rp[k + 1], ne);                                                                                   \
+      float lg4[4], e4[4];                                                                                                                 \
+      int4 rc4[4];                                                                                                                         \
+    _Pragma("unroll")                                                                                                                      \
+      for (int u = 0; u < 4; ++u) {                                                                                                        \
+        const int idx = max(min(rb + u, re - 1), 0);                                                                                       \
+        lg4[u] = s_lg[idx];                                                                                                                \
+        rc4[u] = REC(idx);                                                                                                                 \
+      }                                                                                                                                    \
+      float4 u2[2][4];          /* the rows of two in-edges at a time (four would be 64 registers) */                                      \
+    _Pragma("unroll")                                                                                                                      \
+      for (int u = 0; u < 2; ++u)                                                                                                          \
+    _Pragma("unroll")                                                                                                                      \
+        for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[u].x][32 * m + j8 * 4]);                         \
+      float mx = fmaxf(fmaxf(-INFINITY, lg4[0]), fmaxf(fmaxf(lg4[1], lg4[2]), lg4[3]));                                                    \
+    _Pragma("unroll 1")                                                                                                                    \
+      for (int s = rb + 4; s < re; s += 4) {                                                                                               \
+        const float v0 = s_lg[s], v1 = s_lg[min(s + 1, re - 1)], v2 = s_lg[min(s + 2, re - 1)], v3 = s_lg[min(s + 3, re - 1)];             \
+        mx = fmaxf(fmaxf(mx, v0), fmaxf(fmaxf(v1, v2), v3));                                                                               \
+      }                                                                                                                                    \
+      float den = 0.f;          /* in slot order, like the per-edge loop of the kernels this replaces */                                   \
+    _Pragma("unroll")                                                                                                                      \
+      for (int u = 0; u < 4; ++u) {                                                                                                        \
+        e4[u] = __builtin_amdgcn_exp2f((lg4[u] - mx) * 1.4426950408889634f);                                                               \
+        den += rb + u < re ? e4[u] : 0.f;                                                                                                  \
+      }                                                                                                                                    \
+    _Pragma("unroll 1")                                                                                                                    \
+      for (int s = rb + 4; s < re; s += 4) {                                                                                               \
+        const float v0 = s_lg[s], v1 = s_lg[min(s + 1, re - 1)], v2 = s_lg[min(s + 2, re - 1)], v3 = s_lg[min(s + 3, re - 1)];             \
+        const float e0 = __builtin_amdgcn_exp2f((v0 - mx) * 1.4426950408889634f);                                                          \
+        const float e1 = __builtin_amdgcn_exp2f((v1 - mx) * 1.4426950408889634f);                                                          \
+        const float e2 = __builtin_amdgcn_exp2f((v2 - mx) * 1.4426950408889634f);                                                          \
+        const float e3 = __builtin_amdgcn_exp2f((v3 - mx) * 1.4426950408889634f);                                                          \
+        den += e0;                                                                                                                         \
+        den += s + 1 < re ? e1 : 0.f;                                                                                                      \
+        den += s + 2 < re ? e2 : 0.f;                                                                                                      \
+        den += s + 3 < re ? e3 : 0.f;                                                                                                      \
+      }                                                                                                                                    \
+      const float rden = __builtin_amdgcn_rcpf(den + 1e-16f);                                                                              \
+      float4 o[4];                                                                                                                         \
+    _Pragma("unroll")                                                                                                                      \
+      for (int m = 0; m < 4; ++m) o[m] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                  \
+      int s = rb;                                                                                                                          \
+    _Pragma("unroll 1")                                                                                                                    \
+      while (true) {          /* four in-edges per round (two and two), edge-id order, one fma per term like every kernel of the family */ \
+        {     /* alpha: ONE store instruction per round, lane u of a node's eight writes in-edge u */                                      \
+          const float wsel = (j8 & 2) ? ((j8 & 1) ? e4[3] : e4[2]) : ((j8 & 1) ? e4[1] : e4[0]);                                           \
+          const int esel = (j8 & 2) ? ((j8 & 1) ? rc4[3].y : rc4[2].y) : ((j8 & 1) ? rc4[1].y : rc4[0].y);                                 \
+          if (j8 < 4 && s + j8 < re) a.alpha[(int64_t)esel * a.H + hd] = wsel * rden;                                                      \
+        }                                                                                                                                  \
+    _Pragma("unroll")                                                                                                                      \
+        for (int hp = 0; hp < 2; ++hp) {                                                                                                   \
+          if (hp == 1) {      /* the second pair's rows: only when some node of the wave has a third in-edge in this round */              \
+            if (!__any(s + 2 < re)) break;                                                                                                 \
+    _Pragma("unroll")                                                                                                                      \
+            for (int u = 0; u < 2; ++u)                                                                                                    \
+    _Pragma("unroll")                                                                                                                      \
+              for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[2 + u].x][32 * m + j8 * 4]);               \
+          }                                                                                                                                \
+    _Pragma("unroll")                                                                                                                      \
+          for (int u = 0; u < 2; ++u) {                                                                                                    \
+            /* slots past the segment's end carry weight 0 instead of a branch each: their rows are copies of the last slot's */           \
+            /* (finite), and x + 0 * r = x exactly */                                                                                      \
+            const float w = s + 2 * hp + u < re ? e4[2 * hp + u] * rden : 0.f;                                                             \
+            const float wm = MASKED ? mul_rn(w, __int_as_float(rc4[2 * hp + u].w)) : w;                                                    \
+    _Pragma("unroll")                                                                                                                      \
+            for (int m = 0; m < 4; ++m) {                                                                                                  \
+              o[m].x = fmaf(u2[u][m].x, wm, o[m].x);                                                                                       \
+              o[m].y = fmaf(u2[u][m].y, wm, o[m].y);                                                                                       \
+              o[m].z = fmaf(u2[u][m].z, wm, o[m].z);                                                                                       \
+              o[m].w = fmaf(u2[u][m].w, wm, o[m].w);                                                                                       \
+            }                                                                                                                              \
+          }                                                                                                                                \
+        }                                                                                                                                  \
+        s += 4;                                                                                                                            \
+        if (s >= re) break;                                                                                                                \
+    _Pragma("unroll")                                                                                                                      \
+        for (int u = 0; u < 4; ++u) {                                                                                                      \
+          const int idx = min(s + u, re - 1);                                                                                              \
+          e4[u] = __builtin_amdgcn_exp2f((s_lg[idx] - mx) * 1.4426950408889634f);                                                          \
+          rc4[u] = REC(idx);                                                                                                               \
+        }                                                                                                                                  \
+    _Pragma("unroll")                                                                                                                      \
+        for (int u = 0; u < 2; ++u)                                                                                                        \
+    _Pragma("unroll")                                                                                                                      \
+          for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[u].x][32 * m + j8 * 4]);                       \
+      }                                                                                                                                    \
+      float rmx = 0.f;                                                                                                                     \
+      /* (row, head) is DEAD when no accumulator bit is set: the row written below is then +0 + bias and its maximum that vector's, */     \
+      /* whatever the inputs were (a NaN or Inf that came through a masked slot left bits behind: live).  isg_mgat_dense_tail runs */      \
+      /* x_proj once for all dead rows of a group of tiles. */                                                                             \
+      unsigned zb = 0u;                                                                                                                    \
+      if (MASKED) {                                                                                                                        \
+    _Pragma("unroll")                                                                                                                      \
+        for (int m = 0; m < 4; ++m)                                                                                                        \
+          zb |= __float_as_uint(o[m].x) | __float_as_uint(o[m].y) | __float_as_uint(o[m].z) | __float_as_uint(o[m].w);                     \
+      }                                                                                                                                    \
+    _Pragma("unroll")                                                                                                                      \
+      for (int m = 0; m < 4; ++m) {                                                                                                        \
+        if (a.bias) {                                                                                                                      \
+          const float4 b4 = *reinterpret_cast<const float4 *>(&s_bias[32 * m + j8 * 4]);                                                   \
+          o[m].x += b4.x; o[m].y += b4.y; o[m].z += b4.z; o[m].w += b4.w;                                                                  \
+        }                                                                                                                                  \
+        hf32x4 o4 = {o[m].x, o[m].y, o[m].z, o[m].w};                                                                                      \
+        __builtin_nontemporal_store(o4, reinterpret_cast<hf32x4 *>(a.out + (int64_t)(r0 + k) * a.ldo + hoff + 32 * m + j8 * 4));           \
+        rmx = fmaxf(rmx, fmaxf(fmaxf(fabsf(o[m].x), fabsf(o[m].y)), fmaxf(fabsf(o[m].z), fabsf(o[m].w))));                                 \
+      }                                                                                                                                    \
+      if (a.rowmax) {                                                                                                                      \
+        rmx = group_max<8>(rmx);                                                                                                           \
+        if (j8 == 0) a.rowmax[(int64_t)(r0 + k) * a.H + hd] = rmx;                                                                         \
+      }                                                                                                                                    \
+      if (MASKED && a.row_dead) {                                                                                                          \
+        zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR1>((int)zb);                                                                                  \
+        zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR2>((int)zb);                                                                                  \
+        zb |= (unsigned)dpp_mov_i<ISG_DPP_HMIRROR>((int)zb);                                                                               \
+        if (j8 == 0) a.row_dead[(int64_t)(r0 + k) * a.H + hd] = zb == 0u ? 1 : 0;                                                          \
+      }                                                                                                                                    \
+    }                                                                                                                                      \
+  }
 
 // KSE_T: 16-column steps of the edge product when known at compile time (8 = the 128 edge features of the model: no branch between
 // the MFMAs), 0 = read it from the arguments
@@ -514,31 +672,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     const float sinv = s_einv[slot];                                                                                 \
     int4 rec = s_tab[slot];                                                                                          \
     const float me = own_reg(__int_as_float(rec.w));    /* a scalar: never the high dword of the record's (z, w) pair */  \
-    float part[4];                                                                                                   \
-    int cb = tw * 32 + 4 * hh;       /* laundered: hoisted out of the chunk loop, the 16 addresses below cost 16 registers */ \
-    asm volatile("" : "+v"(cb));                                                                                     \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                  \
-      const int cc = cb + 8 * g;                                                                                     \
-      const float4 xl4 = *reinterpret_cast<const float4 *>(&sXl[rec.x][cc]);                                         \
-      const float4 xr4 = *reinterpret_cast<const float4 *>(&sXr[rec.z][cc]);                                         \
-      const float4 at4 = *reinterpret_cast<const float4 *>(&s_att[cc]);                                              \
-      const float4 wi4 = *reinterpret_cast<const float4 *>(&s_weinv[cc]);                                            \
-      const float lv[4] = {xl4.x, xl4.y, xl4.z, xl4.w}, rv[4] = {xr4.x, xr4.y, xr4.z, xr4.w};                        \
-      const float atv[4] = {at4.x, at4.y, at4.z, at4.w}, wiv[4] = {wi4.x, wi4.y, wi4.z, wi4.w};                      \
-      part[g] = 0.f;                                                                                                 \
-      _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) {                                                             \
-        const float e = (acc[g * 4 + jj] * sinv) * wiv[jj];                                                          \
-        float z = (rv[jj] + lv[jj]) + e;                                                                             \
-        if (MASKED) z *= me;                                                                                         \
-        z = (SL01) ? fmaxf(z, z * slope) : (z > 0.f ? z : z * slope);   /* 0 <= slope <= 1: max(z, slope z), same bits */ \
-        if (MASKED) z *= me;                                                                                         \
-        part[g] = fmaf(z, atv[jj], part[g]);                                                                         \
-      }                                                                                                              \
-      if (g < 3) __builtin_amdgcn_sched_barrier(0);                                                                  \
-    }                                                                                                                \
-    const float mine = (part[0] + part[1]) + (part[2] + part[3]);                                                    \
-    const float tot = mine + __shfl_xor(mine, 32);                                                                   \
-    if (hh == 0) s_part[tw * 64 + prow] = tot;                                                                       \
+    LC_EPILOGUE_ARITH(SL01, rec.x, rec.z)                                                                            \
   }
 #define LC_EPILOGUE(ch) LC_EPILOGUE_(ch, SL01)
 #pragma unroll 1
@@ -624,129 +758,9 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
     // 8 lanes per node (four 16-byte pieces each, 128 contiguous bytes per instruction): a wave aggregates EIGHT nodes at a time,
     // ONE pass covers the tile.  The phase is issue-bound on its per-node bookkeeping (bounds, records, softmax, stores), which a
     // pass does once per instruction whatever the lane count per node: 16 lanes per node needed two passes, 32 lanes four.
-    {
-      const int q8 = lane >> 3, j8 = lane & 7;
-      const int k = 8 * wave + q8;
-      if (k < nrows) {
-        const int rb = s_rp[k], re = min(s_rp[k + 1], ne);
-        float lg4[4], e4[4];
-        int4 rc4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int idx = max(min(rb + u, re - 1), 0);
-          lg4[u] = s_lg[idx];
-          rc4[u] = s_tab[idx];
-        }
-        float4 u2[2][4];          // the rows of two in-edges at a time (four would be 64 registers)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[u].x][32 * m + j8 * 4]);
-        float mx = fmaxf(fmaxf(-INFINITY, lg4[0]), fmaxf(fmaxf(lg4[1], lg4[2]), lg4[3]));
-#pragma unroll 1
-        for (int s = rb + 4; s < re; s += 4) {
-          const float v0 = s_lg[s], v1 = s_lg[min(s + 1, re - 1)], v2 = s_lg[min(s + 2, re - 1)], v3 = s_lg[min(s + 3, re - 1)];
-          mx = fmaxf(fmaxf(mx, v0), fmaxf(fmaxf(v1, v2), v3));
-        }
-        float den = 0.f;          // in slot order, like the per-edge loop of the kernels this replaces
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          e4[u] = __builtin_amdgcn_exp2f((lg4[u] - mx) * 1.4426950408889634f);
-          den += rb + u < re ? e4[u] : 0.f;
-        }
-#pragma unroll 1
-        for (int s = rb + 4; s < re; s += 4) {
-          const float v0 = s_lg[s], v1 = s_lg[min(s + 1, re - 1)], v2 = s_lg[min(s + 2, re - 1)], v3 = s_lg[min(s + 3, re - 1)];
-          const float e0 = __builtin_amdgcn_exp2f((v0 - mx) * 1.4426950408889634f);
-          const float e1 = __builtin_amdgcn_exp2f((v1 - mx) * 1.4426950408889634f);
-          const float e2 = __builtin_amdgcn_exp2f((v2 - mx) * 1.4426950408889634f);
-          const float e3 = __builtin_amdgcn_exp2f((v3 - mx) * 1.4426950408889634f);
-          den += e0;
-          den += s + 1 < re ? e1 : 0.f;
-          den += s + 2 < re ? e2 : 0.f;
-          den += s + 3 < re ? e3 : 0.f;
-        }
-        const float rden = __builtin_amdgcn_rcpf(den + 1e-16f);
-        float4 o[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) o[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-        int s = rb;
-#pragma unroll 1
-        while (true) {          // four in-edges per round (two and two), edge-id order, one fma per term like every kernel of the family
-          {     // alpha: ONE store instruction per round, lane u of a node's eight writes in-edge u
-            const float wsel = (j8 & 2) ? ((j8 & 1) ? e4[3] : e4[2]) : ((j8 & 1) ? e4[1] : e4[0]);
-            const int esel = (j8 & 2) ? ((j8 & 1) ? rc4[3].y : rc4[2].y) : ((j8 & 1) ? rc4[1].y : rc4[0].y);
-            if (j8 < 4 && s + j8 < re) a.alpha[(int64_t)esel * a.H + hd] = wsel * rden;
-          }
-#pragma unroll
-          for (int hp = 0; hp < 2; ++hp) {
-            if (hp == 1) {      // the second pair's rows: only when some node of the wave has a third in-edge in this round
-              if (!__any(s + 2 < re)) break;
-#pragma unroll
-              for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[2 + u].x][32 * m + j8 * 4]);
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              // slots past the segment's end carry weight 0 instead of a branch each: their rows are copies of the last slot's
-              // (finite), and x + 0 * r = x exactly
-              const float w = s + 2 * hp + u < re ? e4[2 * hp + u] * rden : 0.f;
-              const float wm = MASKED ? mul_rn(w, __int_as_float(rc4[2 * hp + u].w)) : w;
-#pragma unroll
-              for (int m = 0; m < 4; ++m) {
-                o[m].x = fmaf(u2[u][m].x, wm, o[m].x);
-                o[m].y = fmaf(u2[u][m].y, wm, o[m].y);
-                o[m].z = fmaf(u2[u][m].z, wm, o[m].z);
-                o[m].w = fmaf(u2[u][m].w, wm, o[m].w);
-              }
-            }
-          }
-          s += 4;
-          if (s >= re) break;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int idx = min(s + u, re - 1);
-            e4[u] = __builtin_amdgcn_exp2f((s_lg[idx] - mx) * 1.4426950408889634f);
-            rc4[u] = s_tab[idx];
-          }
-#pragma unroll
-          for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) u2[u][m] = *reinterpret_cast<const float4 *>(&sXl[rc4[u].x][32 * m + j8 * 4]);
-        }
-        float rmx = 0.f;
-        // (row, head) is DEAD when no accumulator bit is set: the row written below is then +0 + bias and its maximum that vector's,
-        // whatever the inputs were (a NaN or Inf that came through a masked slot left bits behind: live).  isg_mgat_dense_tail runs
-        // x_proj once for all dead rows of a group of tiles.
-        unsigned zb = 0u;
-        if (MASKED) {
-#pragma unroll
-          for (int m = 0; m < 4; ++m)
-            zb |= __float_as_uint(o[m].x) | __float_as_uint(o[m].y) | __float_as_uint(o[m].z) | __float_as_uint(o[m].w);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          if (a.bias) {
-            const float4 b4 = *reinterpret_cast<const float4 *>(&s_bias[32 * m + j8 * 4]);
-            o[m].x += b4.x; o[m].y += b4.y; o[m].z += b4.z; o[m].w += b4.w;
-          }
-          hf32x4 o4 = {o[m].x, o[m].y, o[m].z, o[m].w};
-          __builtin_nontemporal_store(o4, reinterpret_cast<hf32x4 *>(a.out + (int64_t)(r0 + k) * a.ldo + hoff + 32 * m + j8 * 4));
-          rmx = fmaxf(rmx, fmaxf(fmaxf(fabsf(o[m].x), fabsf(o[m].y)), fmaxf(fabsf(o[m].z), fabsf(o[m].w))));
-        }
-        if (a.rowmax) {
-          rmx = group_max<8>(rmx);
-          if (j8 == 0) a.rowmax[(int64_t)(r0 + k) * a.H + hd] = rmx;
-        }
-        if (MASKED && a.row_dead) {
-          zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR1>((int)zb);
-          zb |= (unsigned)dpp_mov_i<ISG_DPP_XOR2>((int)zb);
-          zb |= (unsigned)dpp_mov_i<ISG_DPP_HMIRROR>((int)zb);
-          if (j8 == 0) a.row_dead[(int64_t)(r0 + k) * a.H + hd] = zb == 0u ? 1 : 0;
-        }
-      }
-    }
+#define LC_REC_TAB(i) s_tab[i]
+    LC_AGGREGATE(LC_REC_TAB)
+#undef LC_REC_TAB
     LC_STAMP(6)              // softmax + aggregation, stores
     if (!has_next) break;
     desc = desc_n;           // (no barrier here: it waits behind the next tile's node products)
@@ -761,6 +775,397 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
 #undef LC_PLANES_LANDED
   ISG_DIAG_DUMP(g_lc_stamps, bid * 8 + wave, 12, )
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The masked, live form on GROUPS of tiles.  A top-k mask leaves a tile about 7 nodes that a live slot touches
+// and 9 live slots; the kernel above still pushes 64 node columns and 64 slot columns through the matrix cores for them, per
+// (tile, head).  Here the persistent workgroup's work item is a group of up to a.G entries of its tile sequence:
+//   scan     every tile's src / dst / eid / masks as above -> per-tile tables in LDS, the live slots' ballots, and per tile the 64-bit
+//            set of rows that a live slot's source or destination names (from the slots: the edge_mask form has no node mask)
+//   compact  the named rows in (tile, row) order -> the group's node list (s_nodes) and a per-tile byte map row -> list position;
+//            the live slots in (tile, CSR slot) order -> per-tile lists of slot numbers
+//   node product ONCE for the listed rows (a gather: the LDS-DMA's source address is per lane), the second 32-row block only for
+//            a list longer than 32; edge product once per 64 live slots of the group, logits to their (tile, slot) places
+//   per tile softmax + aggregation over EVERY in-edge as above (LC_AGGREGATE): a dead slot's source maps to list position 0 (any
+//            finite row: its weight is +-0), its logit is the +0 the scan wrote
+// A product element depends on its own row's planes, the W fragments, the MFMA shape and the k order, not on the column its row
+// sits in, so out / alpha / rowmax / row_dead are the per-tile kernel's bits for finite inputs.  A group whose list would pass 64
+// rows runs its tiles one by one through the same code.  The panel of node planes and the edge panel image share their LDS here
+// (nothing of the next group is in flight under a product), which pays for the G table sets.
+constexpr int LG_MAXG = 6, LC_GROUP_DEFAULT = 4;
+constexpr int LG_T_LG = LC_ECAP * 8, LG_T_SP = LG_T_LG + LC_ECAP * 4, LG_T_DR = LG_T_SP + LC_ECAP, LG_T_LV = LG_T_DR + LC_ECAP,
+              LG_T_RP = LG_T_LV + LC_ECAP, LG_T_POS = LG_T_RP + 68 * 4, LG_TILE_BYTES = LG_T_POS + 64;
+constexpr int LG_OFF_T = LC_OFF_A + 2 * 64 * LC_LDA * 2;
+constexpr int LG_OFF_MISC = LG_OFF_T + LG_MAXG * LG_TILE_BYTES;
+constexpr int LG_MISC_FLOATS = 4 * 64 + 3 * LC_C + 4 * LC_C + 64;       // s_part, att / we_inv / bias, bn / wn_inv, s_nodes
+constexpr int LG_SMEM_BYTES = LG_OFF_MISC + LG_MISC_FLOATS * 4 + LG_MAXG * 16 + LG_MAXG * 8 + LG_MAXG * 4 * 8;
+static_assert(LG_TILE_BYTES % 16 == 0 && LG_OFF_MISC % 16 == 0, "16-byte pieces");
+static_assert(64 * 512 <= 2 * 64 * LC_LDA * 2, "the node planes fit the panel image they share LDS with");
+static_assert(LG_SMEM_BYTES <= 160 * 1024, "one workgroup per CU");
+
+template <int KSE_T, bool SL01>
+__global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(LcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
+  typedef float (*BufX)[LC_LDX];
+  typedef _Float16 (*BufP)[64][LC_LDA];
+  constexpr bool MASKED = true;
+  BufX sXl = reinterpret_cast<BufX>(lc_smem);
+  BufX sXr = reinterpret_cast<BufX>(lc_smem + LC_OFF_XR);
+  BufP sA = reinterpret_cast<BufP>(lc_smem + LC_OFF_A);
+  unsigned char *s_tiles = lc_smem + LG_OFF_T;      // [LG_MAXG] table sets:
+#define LG_EM(j) reinterpret_cast<int2 *>(s_tiles + (j) * LG_TILE_BYTES)                       /* [256] {eid, mask bits} */
+#define LG_LG(j) reinterpret_cast<float *>(s_tiles + (j) * LG_TILE_BYTES + LG_T_LG)            /* [256] logits; until a live slot's is written, its edge planes' inverse scale */
+#define LG_SP(j) (s_tiles + (j) * LG_TILE_BYTES + LG_T_SP)                                     /* [256] source: tile row, then list position */
+#define LG_DR(j) (s_tiles + (j) * LG_TILE_BYTES + LG_T_DR)                                     /* [256] destination: tile row */
+#define LG_LV(j) (s_tiles + (j) * LG_TILE_BYTES + LG_T_LV)                                     /* [256] the tile's live slots in CSR order */
+#define LG_RP(j) reinterpret_cast<int *>(s_tiles + (j) * LG_TILE_BYTES + LG_T_RP)              /* [68] row pointers relative to the tile's first slot */
+#define LG_POS(j) (s_tiles + (j) * LG_TILE_BYTES + LG_T_POS)                                   /* [64] tile row -> list position (0: not listed) */
+  float *s_part = reinterpret_cast<float *>(lc_smem + LG_OFF_MISC);        // [4 tile-waves][64 slots]
+  float *s_att = s_part + 4 * 64, *s_weinv = s_att + LC_C;
+  float *s_bias = s_weinv + LC_C, *s_bn = s_bias + LC_C, *s_wninv = s_bn + 2 * LC_C;
+  int *s_nodes = reinterpret_cast<int *>(s_wninv + 2 * LC_C);                // [64] list position -> node
+  int4 *s_desc = reinterpret_cast<int4 *>(s_nodes + 64);                     // [LG_MAXG] the group's {r0, nrows, e0, ne}
+  unsigned long long *s_touch = reinterpret_cast<unsigned long long *>(s_desc + LG_MAXG);      // [LG_MAXG] rows a live slot names
+  unsigned long long *s_livew = s_touch + LG_MAXG;                           // [LG_MAXG][4] live-slot bit words
+
+  const int bid = blockIdx.x;
+  const int per_xcd = gridDim.x >> 3, jx = bid >> 3;
+  const int hd = jx % a.H;
+  const int ngrp = gridDim.x / a.H;
+  const int t = (bid & 7) * (per_xcd / a.H) + jx / a.H;
+  const int T = *a.ntiles;
+  if (t >= T) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = wave >> 2, tw = wave & 3;
+  ISG_DIAG_BEGIN()
+  const int fr = lane & 31, hh = lane >> 5, fk = hh * 8;
+  const int hoff = hd * LC_C;
+  const int srow = tid >> 5, sc4 = tid & 31;
+  const int G = min(max(a.G, 1), LG_MAXG);
+
+  // ---- resident W fragments, the head's vectors: as above ------------------------------------------------------------------
+  const int KSE = KSE_T ? KSE_T : a.KSE;
+  const unsigned plane_e = (unsigned)a.NTE * (unsigned)KSE * 1024u;
+  const __amdgpu_buffer_rsrc_t wrs_e =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.We), 0, (int)(2u * plane_e), 0x00020000);
+  const unsigned wb_e = (unsigned)(hd * (LC_C / 32) + tw) * (unsigned)KSE * 1024u;
+  const int NTN = 2 * a.H * (LC_C / 32);
+  const unsigned plane_n = (unsigned)NTN * 8u * 1024u;
+  const __amdgpu_buffer_rsrc_t wrs_n =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.Wn), 0, (int)(2u * plane_n), 0x00020000);
+  const int ct = wave;
+  const unsigned wb_n = (unsigned)((ct >> 2) * a.H * (LC_C / 32) + hd * (LC_C / 32) + (ct & 3)) * 8u * 1024u;
+  hf16x8 wq_e[8][2], wq_n[8][2];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      wq_n[ks][q] = __builtin_bit_cast(hf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                   wrs_n, lane * 16, (int)(wb_n + q * plane_n + (unsigned)ks * 1024u), 0));
+      wq_e[ks][q] = hf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (ks < KSE)
+        wq_e[ks][q] = __builtin_bit_cast(hf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                     wrs_e, lane * 16, (int)(wb_e + q * plane_e + (unsigned)ks * 1024u), 0));
+    }
+  if (tid < LC_C) {
+    s_att[tid] = a.att[hoff + tid];
+    s_weinv[tid] = a.we_inv[hoff + tid];
+    s_bias[tid] = a.bias ? a.bias[hoff + tid] : 0.f;
+    sXl[0][tid] = 0.f;           // list position 0, which dead slots read, is finite before the first product writes it
+  } else if (tid < 3 * LC_C) {
+    const int c = tid - LC_C;
+    const int src_col = (c >> 7) * a.H * LC_C + hoff + (c & 127);
+    s_bn[c] = a.bn[src_col];
+    s_wninv[c] = a.wn_inv[src_col];
+  }
+  const float slope = a.slope;
+  const int prow = half * 32 + fr;
+
+#pragma unroll 1
+  for (int tg = t; tg < T; tg += G * ngrp) {
+    // ---- scan: descriptors, then every tile's raw tables (LC_REQUEST_TILE / LC_REQUEST_MASKS, one slot per thread of waves 0-3) ----
+    int tl = tid, ll = lane;      // laundered: what the scan derives from them is not hoisted out of the group loop and spilled
+    asm volatile("" : "+v"(tl), "+v"(ll));
+    int4 dsc[LG_MAXG];
+    int ng = 0;
+#pragma unroll
+    for (int j = 0; j < LG_MAXG; ++j) {
+      const int tj = tg + j * ngrp;
+      const bool on = j < G && tj < T;
+      const int4 d = a.tile_info[min(tj, T - 1)];
+      dsc[j] = make_int4(on ? __builtin_amdgcn_readfirstlane(d.x) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.y), LC_ROWS) : 0,
+                         on ? __builtin_amdgcn_readfirstlane(d.z) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.w), LC_ECAP) : 0);
+      ng += on ? 1 : 0;
+    }
+    int srcv[LG_MAXG], eidv[LG_MAXG], dstv[LG_MAXG], rpv[LG_MAXG];
+    float einvv[LG_MAXG], mskv[LG_MAXG];
+#pragma unroll
+    for (int j = 0; j < LG_MAXG; ++j) {
+      srcv[j] = eidv[j] = dstv[j] = rpv[j] = 0;
+      einvv[j] = 1.f;
+      if (j < ng) {
+        if (tl <= dsc[j].y) rpv[j] = a.rowptr[dsc[j].x + tl];
+        if (tl < dsc[j].w) {
+          srcv[j] = a.src[dsc[j].z + tl];
+          eidv[j] = a.eid[dsc[j].z + tl];
+          dstv[j] = a.dst[dsc[j].z + tl];
+          einvv[j] = a.ep_inv[dsc[j].z + tl];
+        }
+      }
+    }
+    if (tl < LG_MAXG) s_touch[tl] = 0ull;      // (read last before the previous group's compaction barrier)
+    __syncthreads();         // every wave is done with the previous group's tables and slices; the row sets are empty
+#pragma unroll
+    for (int j = 0; j < LG_MAXG; ++j) {
+      mskv[j] = 1.f;
+      if (j < ng && tl < dsc[j].w)
+        mskv[j] = a.edge_mask ? a.edge_mask[eidv[j]] : a.node_mask[srcv[j]] * a.node_mask[dstv[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < LG_MAXG; ++j) {
+      if (j < ng) {
+        const int r0n = dsc[j].x, nrn = dsc[j].y, e0n = dsc[j].z, nen = dsc[j].w;
+        if (tl <= nrn) LG_RP(j)[tl] = rpv[j] - e0n;
+        if (tl == 0) s_desc[j] = dsc[j];
+        if (tl < LC_ECAP) {                          /* a source outside its tile is clamped into it */
+          const int sx = min(max(srcv[j] - r0n, 0), max(nrn - 1, 0));
+          const int dz = min(max(dstv[j] - r0n, 0), max(nrn - 1, 0));
+          const bool lv = tl < nen && (__float_as_int(mskv[j]) & 0x7fffffff) != 0;        // LC_BALLOT's test
+          const unsigned long long bw = __ballot(lv);
+          if (ll == 0) s_livew[j * 4 + wave] = bw;
+          if (lv) atomicOr(&s_touch[j], (1ull << sx) | (1ull << dz));
+          LG_EM(j)[tl] = make_int2(eidv[j], __float_as_int(mskv[j]));
+          LG_LG(j)[tl] = lv ? einvv[j] : 0.f;        // a dead slot's logit is +0
+          LG_SP(j)[tl] = (unsigned char)sx;
+          LG_DR(j)[tl] = (unsigned char)dz;
+        }
+      }
+    }
+    __syncthreads();
+    LC_STAMP(0)              // scan: requests, tables, ballots
+
+    int ntot = 0;
+#pragma unroll
+    for (int j = 0; j < LG_MAXG; ++j) ntot += j < ng ? __builtin_amdgcn_readfirstlane(__popcll(s_touch[j])) : 0;
+    // a list that would pass 64 rows: the group's tiles one by one through the same code
+    const int step = ntot <= LC_ROWS ? ng : 1;
+#pragma unroll 1
+    for (int ja = 0; ja < ng; ja += step) {
+      const int jb = min(ja + step, ng);
+      // ---- compact: node list + row maps, live lists; cum[j] = live slots of the sub-group's tiles up to and including j ----
+      int cum[LG_MAXG];
+      int nl = 0, nlive = 0;
+#pragma unroll
+      for (int j = 0; j < LG_MAXG; ++j) {
+        if (j >= ja && j < jb) {
+          const unsigned long long m = s_touch[j];
+          if (tl < LC_ROWS) {
+            const bool on = (m >> tl) & 1ull;
+            const int p = nl + __popcll(m & ((1ull << tl) - 1ull));
+            LG_POS(j)[tl] = (unsigned char)(on ? p : 0);
+            if (on) s_nodes[p] = s_desc[j].x + tl;
+          }
+          int c[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned long long w = s_livew[j * 4 + i];
+            c[i] = __builtin_amdgcn_readfirstlane(__popc((unsigned)w) + __popc((unsigned)(w >> 32)));
+          }
+          if (tl < LC_ECAP) {
+            const unsigned long long w = s_livew[j * 4 + wave];
+            const int pre = (wave > 0 ? c[0] : 0) + (wave > 1 ? c[1] : 0) + (wave > 2 ? c[2] : 0);
+            if ((w >> ll) & 1ull) LG_LV(j)[pre + __popcll(w & ((1ull << ll) - 1ull))] = (unsigned char)tl;
+          }
+          nl += __builtin_amdgcn_readfirstlane(__popcll(m));
+          nlive += (c[0] + c[1]) + (c[2] + c[3]);
+        }
+        cum[j] = nlive;
+      }
+      // the k-th live slot of the sub-group (0 <= k < nlive): its tile jj, slot and the tile's first slot e0
+#define LG_FIND(k, jj, slot, e0v)                                                                                    \
+  int jj = 0, slot, e0v;                                                                                             \
+  {                                                                                                                  \
+    int base_ = 0;                                                                                                   \
+    _Pragma("unroll") for (int j_ = 0; j_ < LG_MAXG - 1; ++j_) {                                                     \
+      const bool up_ = (k) >= cum[j_];                                                                               \
+      jj += up_ ? 1 : 0;                                                                                             \
+      base_ = up_ ? cum[j_] : base_;                                                                                 \
+    }                                                                                                                \
+    slot = LG_LV(jj)[(k) - base_];                                                                                   \
+    e0v = s_desc[jj].z;                                                                                              \
+  }
+      __syncthreads();       // maps, lists and s_nodes complete
+      LC_STAMP(1)            // compaction
+#pragma unroll
+      for (int j = 0; j < LG_MAXG; ++j)
+        if (j >= ja && j < jb && tid < LC_ECAP) LG_SP(j)[tid] = LG_POS(j)[LG_SP(j)[tid]];
+      if (nlive == 0) {
+        __syncthreads();     // no live slot: no product; the sources' positions (all 0) are complete
+      } else {
+        const bool two = nl > 32;
+        // ---- node planes of the listed rows -> panel (LDS-DMA, swizzled on the source address as above); chunk 0's edge planes ----
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (u < 2 || two) {
+            const int lrow = srow + 16 * u;
+            const int row = min(s_nodes[min(lrow, nl - 1)], a.N - 1);
+            const int piece = (sc4 & 15) ^ (lrow & 15);
+            __builtin_amdgcn_global_load_lds((lc_glb_t *)(a.xp + (int64_t)row * 256 + (sc4 >> 4) * 128 + piece * 8),
+                                             (lc_lds_t *)(lc_smem + LC_OFF_A + (2 * wave + 16 * u) * 512), 16, 0, 0);
+          }
+        }
+        float si2[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) si2[i] = a.xinv[min(s_nodes[min(i * 32 + fr, nl - 1)], a.N - 1)];
+        hf32x4 ra[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          LG_FIND(min(srow + 16 * u, nlive - 1), jj, slot, e0v)
+          ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0v + slot) * 256 + sc4 * 8);
+        }
+        ISG_WAIT(0x0F70);    // vmcnt(0): this wave's node planes have landed
+        __syncthreads();
+        LC_STAMP(2)          // gather: node planes, first edge planes
+        // ---- node product: [lin_l | lin_r]_head . x^T, this wave's 32 channels x the listed rows (one or two 32-row blocks) ----
+        {
+          hf32x16 accn[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) accn[i][r] = 0.f;
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            if (i == 0 || two) {
+              hf16x8 an[2];
+              hf32x16 c = accn[i];
+#pragma unroll
+              for (int ks = 0; ks < 8; ++ks) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+                  an[q] = *reinterpret_cast<const hf16x8 *>(lc_smem + LC_OFF_A + (i * 32 + fr) * 512 + q * 256 + (((ks * 2 + hh) ^ (fr & 15)) << 4));
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_n[ks][1], an[0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_n[ks][0], an[1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_n[ks][0], an[0], c, 0, 0, 0);
+              }
+              accn[i] = c;
+            }
+          }
+          ISG_DIAG_KEEP2(accn[0][0], accn[1][15])
+          LC_STAMP(8)        // node product: k loop
+          __syncthreads();   // every wave is done with the node planes: the panel image may take chunk 0
+          float(*dstx)[LC_LDX] = ct < 4 ? sXl : sXr;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int cc = ct * 32 + 4 * hh + 8 * g;                 // column of [x_l 128 | x_r 128]
+            const float4 wi4 = *reinterpret_cast<const float4 *>(&s_wninv[cc]);
+            const float4 bv4 = *reinterpret_cast<const float4 *>(&s_bn[cc]);
+            const float wiv[4] = {wi4.x, wi4.y, wi4.z, wi4.w}, bvv[4] = {bv4.x, bv4.y, bv4.z, bv4.w};
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              if (i == 0 || two) {
+                hf32x4 o;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) o[jj] = (accn[i][g * 4 + jj] * si2[i]) * wiv[jj] + bvv[jj];     // both scales are powers of two
+                *reinterpret_cast<hf32x4 *>(&dstx[i * 32 + fr][(ct & 3) * 32 + 4 * hh + 8 * g]) = o;
+              }
+            }
+          }
+        }
+        LC_STAMP(9)          // node product: epilogue
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<hf32x4 *>(&sA[sc4 >> 4][srow + 16 * u][(sc4 & 15) * 8]) = ra[u];
+        __syncthreads();     // x_l / x_r slices and chunk 0's panel complete
+        LC_STAMP(10)         // panel staging + barrier
+
+        // ---- 64-slot chunks over the sub-group's live slots: the per-tile kernel's product and epilogue -------------------------
+        const int nchunk = (nlive + 63) >> 6;
+        hf32x16 acc;
+#pragma unroll 1
+        for (int c = 0; c < nchunk; ++c) {
+          if (c > 0) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) *reinterpret_cast<hf32x4 *>(&sA[sc4 >> 4][srow + 16 * u][(sc4 & 15) * 8]) = ra[u];
+            __syncthreads();
+            LC_STAMP(10)
+          }
+          if (c + 1 < nchunk) {      // the next chunk's planes: in flight under this chunk's product and epilogue
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              LG_FIND(min(64 * (c + 1) + srow + 16 * u, nlive - 1), jj, slot, e0v)
+              ra[u] = *reinterpret_cast<const hf32x4 *>(a.ep + (int64_t)(e0v + slot) * 256 + sc4 * 8);
+            }
+          }
+          const bool live = half == 0 || 64 * c + 32 < nlive;
+          if (live) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            hf16x8 af[2][2];          // [stage][plane]
+#pragma unroll
+            for (int q = 0; q < 2; ++q) af[0][q] = *reinterpret_cast<const hf16x8 *>(&sA[q][prow][fk]);
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+              if (ks < KSE) {
+                if (ks + 1 < 8) {
+#pragma unroll
+                  for (int q = 0; q < 2; ++q)
+                    af[(ks + 1) & 1][q] = *reinterpret_cast<const hf16x8 *>(&sA[q][prow][(ks + 1) * 16 + fk]);
+                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_e[ks][0], af[ks & 1][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_e[ks][1], af[ks & 1][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq_e[ks][0], af[ks & 1][0], acc, 0, 0, 0);
+              }
+            }
+            ISG_DIAG_KEEP2(acc[0], acc[15])
+            LC_STAMP(3)      // chunk: k loop
+            LG_FIND(min(64 * c + prow, nlive - 1), jj, slot, e0v)
+            (void)e0v;
+            const float sinv = LG_LG(jj)[slot];
+            const int2 em = LG_EM(jj)[slot];
+            const int xs = LG_SP(jj)[slot], xd = LG_POS(jj)[LG_DR(jj)[slot]];
+            const float me = own_reg(__int_as_float(em.y));
+            LC_EPILOGUE_ARITH(SL01, xs, xd)
+          }
+          __syncthreads();
+          LC_STAMP(4)        // chunk: epilogue + barrier
+          if (tid < 64 && 64 * c + tid < nlive) {   // the tile-waves' partials in a fixed order, to the slot's (tile, slot) place
+            LG_FIND(64 * c + tid, jj, slot, e0v)
+            (void)e0v;
+            LG_LG(jj)[slot] = (s_part[tid] + s_part[64 + tid]) + (s_part[128 + tid] + s_part[192 + tid]);
+          }
+        }
+        __syncthreads();
+        LC_STAMP(11)         // last logit sums + barrier
+      }
+#undef LG_FIND
+      // ---- per tile: softmax + aggregation over every in-edge, out / alpha / rowmax / row_dead for every row ---------------------
+#pragma unroll 1
+      for (int j = ja; j < jb; ++j) {
+        const int4 dj = s_desc[j];
+        const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
+                  ne = __builtin_amdgcn_readfirstlane(dj.w);
+        const float *s_lg = LG_LG(j);
+        const int *s_rp = LG_RP(j);
+        const int2 *s_em = LG_EM(j);
+        const unsigned char *s_sp = LG_SP(j);
+#define LG_REC(i) make_int4((int)s_sp[i], s_em[i].x, 0, s_em[i].y)
+        LC_AGGREGATE(LG_REC)
+#undef LG_REC
+      }
+      LC_STAMP(6)            // per tile: softmax + aggregation, stores
+    }
+  }
+#undef LG_EM
+#undef LG_LG
+#undef LG_SP
+#undef LG_DR
+#undef LG_LV
+#undef LG_RP
+#undef LG_POS
+  ISG_DIAG_DUMP(g_lc_stamps, bid * 8 + wave, 12, )
+}
+#undef LC_AGGREGATE
+#undef LC_EPILOGUE_ARITH
 
 }  // namespace isg
 
@@ -833,7 +1238,7 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
       .We = reinterpret_cast<const _Float16 *>(we_frag), .we_inv = we_inv_scale, .att = att, .bias = bias, .rowptr = rowptr,
       .eid = eid, .src = src, .dst = dst, .ntiles = ntiles, .tile_info = reinterpret_cast<const int4 *>(tile_info),
       .edge_mask = edge_mask, .node_mask = node_mask, .out = out, .alpha = alpha, .rowmax = rowmax, .N = (int)N, .E = (int)E,
-      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead};
+      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead, .G = 1};
   if (!a.xp || !a.xinv || !a.Wn || !a.wn_inv || !a.bn || (a.E > 0 && (!a.ep || !a.ep_inv || !a.eid || !a.src || !a.dst || !a.alpha)) ||
       !a.We || !a.we_inv || !a.att || !a.rowptr || !a.tile_info || !a.ntiles || !a.out)
     return ISG_EINVAL;                         // the struct the kernel dereferences, not the parameters it was filled from
@@ -844,6 +1249,19 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
   if (gpx > need) gpx = (int)need;
   const unsigned grid = 8u * (unsigned)H * (unsigned)gpx;
   hipStream_t st = as_stream(stream);
+  // Tiles per group of the masked, live form.  ISG_LC_GROUP=n forces it (1 = the per-tile kernel, as before);
+  // otherwise LC_GROUP_DEFAULT where a workgroup's tile sequence is that long, by the estimate ops.dense_tail_group uses.
+  static const int force_group = [] { const char *e = getenv("ISG_LC_GROUP"); return e ? atoi(e) : 0; }();
+  {
+    const long long tiles = std::max((N + LC_ROWS - 1) / LC_ROWS, (E + LC_ECAP - 1) / LC_ECAP);
+    const long long per_wg = (std::min<long long>(tiles, max_tiles) + 8 * gpx - 1) / (8 * gpx);
+    a.G = force_group > 0 ? std::min(force_group, LG_MAXG) : (int)std::max<long long>(1, std::min<long long>(LC_GROUP_DEFAULT, per_wg));
+  }
+#define LC_LAUNCH_G(KT, SL)                                                                                          \
+  {                                                                                                                  \
+    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;                \
+    gatv2_layer_conv_groups_kernel<KT, SL><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                              \
+  }
 #define LC_LAUNCH(M, KT, SL, LV)                                                                                     \
   {                                                                                                                  \
     if (!dyn_lds_ok<&gatv2_layer_conv_kernel<M, KT, SL, LV>>(LC_SMEM_BYTES)) return ISG_EUNSUPPORTED;                \
@@ -851,7 +1269,7 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
   }
 #define LC_LAUNCH_M(KT, SL)                                                                                          \
   {                                                                                                                  \
-    if (dense_mask) LC_LAUNCH(true, KT, SL, false) else LC_LAUNCH(true, KT, SL, true)                                \
+    if (dense_mask) LC_LAUNCH(true, KT, SL, false) else if (a.G > 1) LC_LAUNCH_G(KT, SL) else LC_LAUNCH(true, KT, SL, true) \
   }
   const bool masked = node_mask || edge_mask;
   const bool sl01 = negative_slope >= 0.f && negative_slope <= 1.f;
@@ -863,6 +1281,7 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
     if (masked) LC_LAUNCH_M(0, false) else LC_LAUNCH(false, 0, false, false)
   }
 #undef LC_LAUNCH_M
+#undef LC_LAUNCH_G
 #undef LC_LAUNCH
   return check_launch();
 }

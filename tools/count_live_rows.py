@@ -2,7 +2,9 @@
 """DESIGN.md 17.10's count, on the CPU: the rows of x_proj per group of G tiles in the dense tail's live-row form at BASELINE
 configs[1] -- live rows of the masked layer (a destination with an in-slot whose two ends are both picked) plus one for the group's
 dead rows -- from synthetic.make_workload, the model's CPU path (its mask indices are bit-exact with the GPU's) and isg_tile_plan's
-packing rule (64 nodes / 256 slots, consecutive graphs, 1024-graph chunks).       python3 tools/count_live_rows.py [graphs]"""
+packing rule (64 nodes / 256 slots, consecutive graphs, 1024-graph chunks).       python3 tools/count_live_rows.py [graphs]
+Then DESIGN.md 17.12's count: per group of G tiles of the masked layer kernel's grouped form, the nodes that a live slot names and
+the live slots, in the order the kernel walks (heavy-first list, a workgroup takes every 64th entry: 256 CUs, 4 heads)."""
 import os
 import sys
 
@@ -36,7 +38,7 @@ while g < B:
     n, s, k = sizes[g], slots[g], g + 1
     while k < end and n + sizes[k] <= 64 and s + slots[k] <= 256:
         n += sizes[k]; s += slots[k]; k += 1
-    tiles.append((r, n))
+    tiles.append((r, n, s))
     r += n
     g = k
 print(f"{N} nodes, {int(picked.sum())} picked, {int(live.sum())} live rows ({100 * live.double().mean().item():.1f} %), {len(tiles)} tiles")
@@ -45,10 +47,36 @@ print("|---|---|---|---|---|---|---|---|---|")
 for G in (1, 2, 3, 4):
     rows = []
     for t0 in range(0, len(tiles), G):
-        a, b = tiles[t0][0], tiles[min(t0 + G, len(tiles)) - 1]
+        a, b = tiles[t0][0], tiles[min(t0 + G, len(tiles)) - 1][:2]
         seg = live[a:b[0] + b[1]]
         rows.append(int(seg.sum()) + int((~seg).any()))
     v = torch.tensor(rows)
     share = lambda lo, hi: f"{100 * ((v >= lo) & (v <= hi)).double().mean().item():.1f} %"
     print(f"| {G} | {len(rows)} | {v.double().mean().item():.1f} | {share(0, 8)} | {share(9, 16)} | {share(17, 32)} | {share(33, 64)} | "
           f"{share(65, 10 ** 9)} | {int(v.max())} |")
+
+# ---- 17.12: the layer kernel's groups.  A slot (in-edge) is live when both ends are picked; the nodes it names are its ends.
+live_slot = picked[src] & picked[dst]
+named = torch.zeros(N, dtype=torch.bool)
+named[src[live_slot]] = True
+named[dst[live_slot]] = True
+slots_at = torch.bincount(dst[live_slot], minlength=N)
+cs_named = torch.cat([torch.zeros(1, dtype=torch.long), named.long().cumsum(0)])
+cs_slots = torch.cat([torch.zeros(1, dtype=torch.long), slots_at.cumsum(0)])
+heavy = sorted(range(len(tiles)), key=lambda t: -min((tiles[t][2] + 31) // 32, 8))      # stable: ties keep the tile order
+NGRP = 64
+print(f"\n{int(named.sum())} of {N} nodes are named by a live slot; {int(live_slot.sum())} of {src.numel()} slots are live")
+print("| tiles per group G | groups | named nodes mean / max | groups > 32 nodes | groups > 64 nodes | live slots mean / max | groups > 64 slots |")
+print("|---|---|---|---|---|---|---|")
+for G in (1, 2, 3, 4, 5, 6):
+    nn, ns = [], []
+    for w in range(min(NGRP, len(heavy))):
+        seq = heavy[w::NGRP]
+        for i in range(0, len(seq), G):
+            grp = [tiles[t] for t in seq[i:i + G]]
+            nn.append(sum(int(cs_named[a + n] - cs_named[a]) for a, n, _ in grp))
+            ns.append(sum(int(cs_slots[a + n] - cs_slots[a]) for a, n, _ in grp))
+    nn, ns = torch.tensor(nn), torch.tensor(ns)
+    pc = lambda m: f"{100 * m.double().mean().item():.1f} %"
+    print(f"| {G} | {len(nn)} | {nn.double().mean().item():.1f} / {int(nn.max())} | {pc(nn > 32)} | {pc(nn > 64)} | "
+          f"{ns.double().mean().item():.1f} / {int(ns.max())} | {pc(ns > 64)} |")

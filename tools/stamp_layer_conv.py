@@ -3,7 +3,8 @@
 --build makes it with -DISG_DIAG).
 
 --masked: the masked launch, with the node mask the model's masked layer (BASELINE configs[1]'s third, Gumbel top-k) gives on this
-batch -- taken from one forward of the model -- and, first, how many of each tile's CSR slots that mask leaves live (nonzero)."""
+batch -- taken from one forward of the model -- and, first, how many of each tile's CSR slots that mask leaves live (nonzero).
+The masked launch is the grouped form unless ISG_LC_GROUP=1 is set: its phases carry their own labels."""
 import ctypes
 import os
 import sys
@@ -74,7 +75,7 @@ for rep in range(2):
                                     ep_inv.data_ptr(), we.data_ptr(), we_inv.data_ptr(), att.data_ptr(), conv.bias.data_ptr(),
                                     plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
                                     tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, alpha.data_ptr(),
-                                    rowmax.data_ptr(), N, E, H, C, 128, 128, 0.2, torch.cuda.current_stream().cuda_stream)
+                                    rowmax.data_ptr(), 0, N, E, H, C, 128, 128, 0.2, torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     torch.cuda.synchronize()
 s = buf.double().cpu()
@@ -82,6 +83,12 @@ s = s[s[:, 12] > 0]
 names = ["first tile's inputs (once)", "node GEMM: barrier", "chunks: staging barrier", "chunks: k loops",
          "chunks: epilogue + barrier", "next tile: rows -> planes, tables", "softmax + aggregation per node, stores",
          "hand-over barrier", "node GEMM: k loop", "node GEMM: epilogue (LDS writes)", "chunks: wait for the planes, LDS writes", "last logit sums + barrier", "(total)", "(probe) other", "(probe) exposed latency of a chunk request"]
+if nm_arg and os.environ.get("ISG_LC_GROUP") != "1" and os.environ.get("ISG_LC_DENSE_MASK", "0") == "0":
+    # gatv2_layer_conv_groups_kernel's stamps (per group of tiles; 3, 4, 10 per chunk; 6 covers the group's tiles)
+    names = ["scan: requests, tables, ballots (per group)", "compaction: node list, maps, live lists", "gather: node planes, first edge planes (wait)",
+             "group chunks: k loops", "group chunks: epilogue + barrier", "-", "per tile: softmax + aggregation, stores (all tiles of the group)",
+             "-", "group node product: k loop", "group node product: barrier + epilogue (LDS writes)", "panel staging + barrier",
+             "last logit sums + barrier", "(total)"]
 tot = s[:, 12].mean().item()
 nwg = s.size(0) // 8
 print(f"{T} tiles x {H} heads on {nwg} persistent workgroups of 8 waves; a wave lives {tot:.0f} cycles = {tot * nwg / max(T * H, 1):.0f} per (tile, head)")
