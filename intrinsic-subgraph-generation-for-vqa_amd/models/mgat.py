@@ -75,9 +75,7 @@ class MGAT(torch.nn.Module):
     def on_tiles(self, plan, in_channels: int, edge_attr) -> bool:
         """Will forward() run its convolutions on the graph-tile kernels for this batch?  (Then a model may send the graphs
         beyond a tile through ops.run_split instead of having every layer fill their rows.)"""
-        if plan is None or edge_attr is None or edge_attr.dim() != 2 or torch.is_grad_enabled():
-            return False
-        return self.convs[0].dispatch(plan, in_channels, edge_attr.float()) in ("layer_conv", "tile_conv")
+        return self.convs[0].route(plan, in_channels, edge_attr).conv in ("layer_conv", "tile_conv")
 
     def forward(self, x, edge_index, instr_vectors, global_language_feats, edge_attr, batch, return_masks=False,
                 explainer=False, explainer_stage=False, expl_bypass_x=False, plan: Optional[ops.GraphPlan] = None,
@@ -93,17 +91,18 @@ class MGAT(torch.nn.Module):
         mask = None
         global_mask = None
         edge_attns = []
+        gate_u = glf if gate_feats is None else gate_feats.contiguous()
+        # how every layer runs on this batch (ops.conv_route), asked once: the layers are handed their answer, the dense tail reads
+        # the next layer's
+        routes = [conv.route(plan, h.size(1), edge_attr, imle_att=gate_u) for conv in self.convs]
+        assert all(r.e_proj == routes[0].e_proj for r in routes), routes
         # every layer projects the SAME edge features (mgat.py:144-148): one launch splits each 64-row panel of
         # edge_attr into its bf16 planes once and writes one dense [E, H*C] tensor per layer (isg_linear_panel_multi)
         e_projs = None
-        fdt = self.convs[0].rows_dtype(plan)
-        fused = (edge_attr.dim() == 2 and not torch.is_grad_enabled()
-                 and (fdt == torch.float32 or (fdt == torch.float16 and edge_attr.size(1) >= 128))       # MaskingGATv2Conv.dispatch
-                 and ops.fused_logits_supported(plan, self.heads, self.convs[0].out_channels, edge_attr.size(1)))
-        if (not fused and not torch.is_grad_enabled() and all(c.lin_edge is not None for c in self.convs)
+        if (routes[0].e_proj and not torch.is_grad_enabled() and all(c.lin_edge is not None for c in self.convs)
                 and edge_attr.dim() == 2):
             e_projs = ops.linear_multi(edge_attr, [c.lin_edge.weight for c in self.convs],
-                                       out_dtype=fdt)
+                                       out_dtype=self.convs[0].rows_dtype(plan))
         L = len(self.convs)
         wide = self.heads * self.convs[0].out_channels
         x_gated = x_planes = None     # gelu(h * ins_i[batch]) when the previous layer's fused tail has written it: fp32 rows, planes
@@ -114,8 +113,8 @@ class MGAT(torch.nn.Module):
                 x_gated = x_planes = None
             conv_res, mask, edge_att = self.convs[i](
                 x=h, edge_index=edge_index, edge_attr=edge_attr, instruction=ins, batch=batch,
-                return_masks=return_masks, return_attention_weights=True, imle_att=glf if gate_feats is None else gate_feats.contiguous(),
-                gate_rows_given=gate_feats is not None, all_instrs=instr_vectors,
+                return_masks=return_masks, return_attention_weights=True, imle_att=gate_u,
+                gate_rows_given=gate_feats is not None, all_instrs=instr_vectors, route=routes[i],
                 plan=plan, noise=None if noises is None else noises.get(i),
                 seed=None if seed is None else seed + i,
                 e_proj=None if e_projs is None else e_projs[i], x_gated=x_gated, x_planes=x_planes,
@@ -137,14 +136,10 @@ class MGAT(torch.nn.Module):
                 nxt = instr_vectors[i + 1].contiguous() if i + 1 < L and self.convs[i + 1].use_instr else None
                 # the next layer's gated input: as planes when it runs as isg_gatv2_layer_conv, as fp32 rows when anything else
                 # reads it (a masked layer's node gate, the un-fused convolution)
-                want_planes = want_rows = False
-                if nxt is not None:
-                    cn = self.convs[i + 1]
-                    want_planes = cn.layer_conv_ready(plan, h.size(1), edge_attr,
-                                                      None if e_projs is None else e_projs[i + 1])
-                    want_rows = cn.needs_rows(plan, h.size(1), edge_attr, None if e_projs is None else e_projs[i + 1], glf)
+                nr = routes[i + 1] if nxt is not None else None
                 res = ops.mgat_dense_tail(conv_res, self.x_proj[i], ins, h, plan, bn.weight, bn.bias, bn.mean_scale, bn.eps,
-                                          node_mask=tail_mask, ins_next=nxt, want_rows=want_rows, want_planes=want_planes)
+                                          node_mask=tail_mask, ins_next=nxt, want_rows=nr is not None and nr.gate_rows,
+                                          want_planes=nr is not None and nr.conv == "layer_conv")
                 if res is not None:
                     h, x_gated, x_planes = res
                     continue

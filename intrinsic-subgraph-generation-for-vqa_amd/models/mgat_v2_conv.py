@@ -9,6 +9,9 @@ Device work per call:
   three dense projections        lin_l, lin_r (C -> H*C, +bias), lin_edge (no bias)     (:177,181,259)
   isg_gatv2_mp_fwd               message + segment softmax + aggregate + bias, with the node->edge
                                  mask product of NodeMaskToEdgeMask fused in            (:169-171,215-232,243-279)
+Which of these launches a layer makes on a batch -- message passing as one persistent launch on graph tiles, with lin_l | lin_r
+inside or before it, as the edge-logits pair, or un-fused; what the gate writes -- is decided by ops.conv_route, nowhere else:
+route() asks it once per forward, forward() follows the answer.
 The reference stashes alpha on the module between message() and forward() (:223-224,274); here it
 is a local, so the module is re-entrant.
 """
@@ -86,59 +89,41 @@ class MaskingGATv2Conv(torch.nn.Module):
             return torch.float32
         return fdt
 
-    def dispatch(self, plan, in_channels: int, edge_attr, e_proj=None) -> str:
-        """Which kernels run this layer's message passing -- the ONE place that decides (forward, layer_conv_ready and
-        needs_rows all ask here):
-          "layer_conv"  lin_l | lin_r, lin_edge, logits, softmax, aggregation as one persistent launch on graph tiles
-          "tile_conv"   the same with x_l / x_r projected before it (a layer input that is not 128 wide)
-          "pair"        lin_edge folded into the logits, softmax + aggregation from them (two launches, per-graph kernel; also on
-                        fp16 feature rows when the edge width is one the rows kernel takes)
-          "unfused"     lin_edge as a Linear (e_proj in memory) + the message-passing kernel (any width, narrow fp16 rows, training)"""
-        if (e_proj is not None or edge_attr is None or self.lin_edge is None or edge_attr.dim() != 2
-                or torch.is_grad_enabled() or plan is None):
-            return "unfused"
-        # forward, layer_conv_ready and needs_rows of this layer and MGAT's look-ahead ask ~6 times per layer and step: the answer
-        # depends on the plan, the widths, the storage type and the switches only, and is kept on the plan (host time: 0.15 ms per step)
-        memo = plan.memo()
-        key = ("dispatch", id(self), in_channels, edge_attr.size(1), self.rows_dtype(plan), self.share_weights)
+    def route(self, plan, in_channels: int, edge_attr, e_proj=None, imle_att=None) -> "ops.ConvRoute":
+        """ops.conv_route for this layer on this batch, kept on the plan.  GraphPlan.tile_mode can cost a device-to-host sync: it is
+        asked only when the route depends on it."""
+        masked = self.mask.masking_threshold != 1.0
+        facts = dict(heads=self.heads, channels=self.out_channels, in_channels=in_channels,
+                     edge_dim=edge_attr.size(1) if edge_attr is not None and edge_attr.dim() == 2 else None,
+                     rows_dtype=self.rows_dtype(plan), share_weights=self.share_weights, use_instr=self.use_instr, masked=masked,
+                     gate_on_planes=masked and self.mask.planes_ready(imle_att), grad=torch.is_grad_enabled(),
+                     e_proj_given=e_proj is not None, has_edge_lin=self.lin_edge is not None)
+        if plan is None:
+            return ops.conv_route(N=0, B=0, E=0, nmax=0, has_csr=False, tile_mode="none", **facts)
+        memo, key = plan.memo(), ("route", id(self), *facts.values())
         hit = memo.get(key)
-        if hit is not None and hit[0] is ops.CFG:
-            return hit[1]
-        how = self._dispatch(plan, in_channels, edge_attr)
-        memo[key] = (ops.CFG, how)
-        return how
+        if hit is None or hit[0] is not ops.CFG:
+            facts.update(N=plan.N, B=plan.B, E=plan.E, nmax=plan.nmax, has_csr=plan.rowptr is not None)
+            route = ops.conv_route(tile_mode="tiles", **facts)
+            if route.conv in ("layer_conv", "tile_conv"):
+                mode = plan.tile_mode(ops.TILE_CONV_NODES, ops.TILE_CONV_EDGES)
+                if mode != "tiles":
+                    route = ops.conv_route(tile_mode=mode, **facts)
+            hit = memo[key] = (ops.CFG, route)
+        return hit[1]
 
-    def _dispatch(self, plan, in_channels: int, edge_attr) -> str:
-        H, C = self.heads, self.out_channels
-        if not ops.fused_logits_supported(plan, H, C, edge_attr.size(1)):
-            return "unfused"
-        if self.rows_dtype(plan) != torch.float32:
-            # fp16 feature rows (BASELINE configs[4]): the pair exists on the rows kernel (K >= 128), the tile kernels do not
-            return "pair" if self.feature_dtype == torch.float16 and edge_attr.size(1) >= 128 else "unfused"
-        if not self.share_weights and ops.layer_conv_supported(plan, H, C, in_channels, edge_attr.size(1)):
-            return "layer_conv"
-        if ops.tile_conv_supported(plan, H, C, edge_attr.size(1)):
-            return "tile_conv"
-        return "pair"
-
-    def layer_conv_ready(self, plan, in_channels: int, edge_attr, e_proj=None) -> bool:
-        """Will forward() run this layer as isg_gatv2_layer_conv?  (Then its gated input is wanted as ops.NodePlanes: MGAT asks
-        before it lets the previous layer's fused tail write them.)"""
-        return self.dispatch(plan, in_channels, edge_attr, e_proj) == "layer_conv"
-
-    def needs_rows(self, plan, in_channels: int, edge_attr, e_proj=None, imle_att=None) -> bool:
-        """Does forward() read the gated layer input as fp32 ROWS (beside, or instead of, its planes)?  Everything but the
-        layer kernel does, and so does a node gate that cannot run on the planes."""
-        if self.dispatch(plan, in_channels, edge_attr, e_proj) != "layer_conv":
-            return True
-        return self.mask.masking_threshold != 1.0 and not self.mask.planes_ready(imle_att)
+    def dispatch(self, plan, in_channels: int, edge_attr, e_proj=None) -> str:
+        """Which kernels run this layer's message passing: ops.ConvRoute.conv."""
+        return self.route(plan, in_channels, edge_attr, e_proj).conv
 
     def forward(self, x: Tensor, edge_index: Tensor, batch: Tensor, edge_attr: Optional[Tensor] = None,
                 instruction: Optional[Tensor] = None, imle_att: Optional[Tensor] = None,
                 return_attention_weights: bool = None, return_masks: bool = None, all_instrs=None,
                 plan: Optional[ops.GraphPlan] = None, noise: Optional[Tensor] = None, seed: Optional[int] = None,
                 e_proj: Optional[Tensor] = None, x_gated: Optional[Tensor] = None,
-                x_planes: Optional["ops.NodePlanes"] = None, out_planes: bool = False, gate_rows_given: bool = False):
+                x_planes: Optional["ops.NodePlanes"] = None, out_planes: bool = False, gate_rows_given: bool = False,
+                route: Optional["ops.ConvRoute"] = None):
+        # route: self.route(...) of this call, from a caller that has asked already (MGAT)
         # gate_rows_given: imle_att[g] already IS the row the node gate of graph g reads (ops.run_split's sub-batch: the reference's
         # double index batch[batch[n]], quirk Q3, refers to positions in the batch the graphs were taken from)
         # out_planes (inference): the caller feeds the result to a Linear + GELU on the planes32 engine (MGAT's x_proj.0) and
@@ -151,29 +136,28 @@ class MaskingGATv2Conv(torch.nn.Module):
         if plan is None:
             plan = ops.GraphPlan.build(batch, edge_index,
                                        num_graphs=None if instruction is None else instruction.size(0))
-        how = self.dispatch(plan, x.size(1), edge_attr, e_proj)
-        need_rows = self.needs_rows(plan, x.size(1), edge_attr, e_proj, imle_att)
+        if route is None:
+            route = self.route(plan, x.size(1), edge_attr, e_proj, imle_att)
+        how, masked = route.conv, self.mask.masking_threshold != 1.0
         planes = None          # gelu(x * instruction[batch]) as the planes isg_gatv2_layer_conv reads (fp32 rows only where needed)
         if (x_gated is not None or x_planes is not None) and self.use_instr:
             # gelu(x * instruction[batch]) was already written by the previous layer's fused tail (isg_mgat_dense_tail)
             x, planes = x_gated, x_planes
-            if x is None and need_rows:
+            if x is None and route.gate_rows:
                 raise RuntimeError("the previous layer's tail left no fp32 rows of the gated input, and this layer needs them")
         else:
             x = x.float().contiguous()
-            if self.use_instr and how == "layer_conv":
-                x, planes = ops.instr_gate_planes(x, instruction.contiguous(), batch, want_rows=need_rows)   # :156-157
-            elif self.use_instr and not torch.is_grad_enabled() and self.rows_dtype(plan) == torch.float32 and \
-                    ops.reads_planes32(x.size(0), (1 if self.share_weights else 2) * H * C, x.size(1)):
+            if route.gate == "planes":
+                x, planes = ops.instr_gate_planes(x, instruction.contiguous(), batch, want_rows=route.gate_rows)   # :156-157
+            elif route.gate == "planes32":
                 # the projection runs on the planes32 engine: the gate writes its operand (and fp32 rows only for a node gate)
-                masked = self.mask.masking_threshold != 1.0
                 rows, xp = ops.instr_gate_planes32(x, instruction.contiguous(), batch, want_rows=masked)   # :156-157
                 x = rows if masked else xp
-            elif self.use_instr:
+            elif route.gate == "rows":
                 x = ops.instr_gate(x, instruction.contiguous(), batch, plan=plan)        # :156-157
 
         mask = None
-        if self.mask.masking_threshold != 1.0:                                           # :161
+        if masked:                                                                       # :161
             mask = self.mask(x, imle_att, batch, edge_index, use_all_instrs=False, plan=plan, noise=noise,
                              seed=seed, u_is_per_graph=not gate_rows_given, x_planes=planes)             # :166-168
 
@@ -192,7 +176,7 @@ class MaskingGATv2Conv(torch.nn.Module):
             if res is not None:
                 return done(*res)
             if x is None:
-                raise RuntimeError("isg_gatv2_layer_conv refused a shape layer_conv_supported() accepted, and the gated input "
+                raise RuntimeError("isg_gatv2_layer_conv refused a shape ops.conv_route accepted, and the gated input "
                                    "exists only as planes")
             how = "tile_conv"
         if self.share_weights:

@@ -357,7 +357,7 @@ class GraphPlan:
     graph_ids: Optional[Tensor] = None            # int32 [B]: this plan's graphs are a CUT of a larger batch and these are their numbers
                                                   # there -- the samplers' in-kernel noise is keyed by them (ops._gid_ptr)
     holes: Optional["OversizeGraphs"] = None      # set by run_split: the tile kernels pass over these graphs and NOTHING fills their rows
-    _memo: Optional[dict] = None                  # answers that depend on the plan and the switches only (tile_mode, a layer's dispatch):
+    _memo: Optional[dict] = None                  # answers that depend on the plan and the switches only (tile_mode, a layer's route):
                                                   # asked ~17 times per step by the layers, computed once (shared by run_split's copy)
 
     def memo(self) -> dict:
@@ -843,18 +843,23 @@ def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphP
 GK_NCAP_L, GK_ECAP_L = 256, 1024      # the per-graph message-passing kernel's largest tables (csrc/isg_mp_graph.hip)
 
 
-def fused_logits_supported(plan: "GraphPlan", heads: int, channels: int, edge_dim: int) -> bool:
-    """Shape test of isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits (inference, fp32 rows, per-graph kernel)."""
+def _fused_logits_ok(heads: int, channels: int, edge_dim: int, B: int, E: int, nmax: int, has_csr: bool, cfg: Switches) -> bool:
+    """fused_logits_supported over plain values (conv_route)."""
     cp = (channels + 31) // 32 * 32       # round 5: heads padded to whole 32-channel tiles (the reference's C = 300 -> 320), K <= 304
     wide = channels % 32 != 0 or edge_dim > 128
-    if wide and plan.E < CFG.rows_kernel_min_edges:
+    if wide and E < cfg.rows_kernel_min_edges:
         # the rows kernel streams all of lin_edge's tiles through its three-slot ring whatever the number of slots: ~94 us for 400
         # edges as for 50 000 (40 tiles x one DMA round trip each).  A small batch projects its few edge rows (isg_linear_skinny, ~5 us)
         # and runs the flat kernel on e_proj instead
         return False
-    return (CFG.fuse_logits and (CFG.fuse_logits_wide or not wide) and CFG.gemm_backend == "bf16x6" and CFG.gemm_f16x3 and
-            CFG.mp_kernel == "graph" and channels % 4 == 0 and heads * cp <= 2048 and 0 < edge_dim <= 304 and edge_dim % 4 == 0 and
-            plan.B > 0 and plan.nmax > 0 and plan.rowptr is not None and plan.E > 0)
+    return (cfg.fuse_logits and (cfg.fuse_logits_wide or not wide) and cfg.gemm_backend == "bf16x6" and cfg.gemm_f16x3 and
+            cfg.mp_kernel == "graph" and channels % 4 == 0 and heads * cp <= 2048 and 0 < edge_dim <= 304 and edge_dim % 4 == 0 and
+            B > 0 and nmax > 0 and has_csr and E > 0)
+
+
+def fused_logits_supported(plan: "GraphPlan", heads: int, channels: int, edge_dim: int) -> bool:
+    """Shape test of isg_gatv2_edge_logits + isg_gatv2_mp_fwd_logits (inference, fp32 rows, per-graph kernel)."""
+    return _fused_logits_ok(heads, channels, edge_dim, plan.B, plan.E, plan.nmax, plan.rowptr is not None, CFG)
 
 
 def _edge_logits_weight(w_edge: Tensor, heads: int):
@@ -1081,17 +1086,32 @@ ISG_EUNSUPPORTED = -2      # include/isg.h
 TILE_CONV_NODES, TILE_CONV_EDGES = 64, 256
 
 
+def _tile_conv_ok(heads: int, channels: int, edge_dim: int, B: int, E: int, has_csr: bool, tile_mode: str, cfg: Switches) -> bool:
+    """tile_conv_supported over plain values (conv_route); tile_mode is GraphPlan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES)."""
+    return (cfg.fuse_tile_conv and cfg.fuse_logits and cfg.gemm_backend == "bf16x6" and cfg.gemm_f16x3 and cfg.mp_kernel == "graph" and
+            channels == 128 and 0 < edge_dim <= 128 and edge_dim % 4 == 0 and heads <= 64 and B > 0 and has_csr and E > 0 and
+            tile_mode != "none")
+
+
+def _layer_conv_ok(heads: int, channels: int, in_channels: int, edge_dim: int, B: int, E: int, has_csr: bool, tile_mode: str,
+                   cfg: Switches) -> bool:
+    """layer_conv_supported over plain values (conv_route)."""
+    return (cfg.fuse_layer_conv and in_channels == 128 and heads <= 16 and
+            _tile_conv_ok(heads, channels, edge_dim, B, E, has_csr, tile_mode, cfg))
+
+
+# the plan-taking forms ask GraphPlan.tile_mode LAST, only when everything cheaper has passed: it can cost a device-to-host sync
 def tile_conv_supported(plan: "GraphPlan", heads: int, channels: int, edge_dim: int) -> bool:
     """Shape test of isg_gatv2_tile_conv (inference, fp32 rows): C = 128, edge features <= 128 wide, every graph within one
     64-node / 256-slot tile -- or all but a few (GraphPlan.tile_mode: those go to the per-graph kernels)."""
-    return (CFG.fuse_tile_conv and CFG.fuse_logits and CFG.gemm_backend == "bf16x6" and CFG.gemm_f16x3 and CFG.mp_kernel == "graph" and
-            channels == 128 and 0 < edge_dim <= 128 and edge_dim % 4 == 0 and heads <= 64 and plan.B > 0 and
-            plan.rowptr is not None and plan.E > 0 and plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) != "none")
+    return (_tile_conv_ok(heads, channels, edge_dim, plan.B, plan.E, plan.rowptr is not None, "tiles", CFG) and
+            plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) != "none")
 
 
 def layer_conv_supported(plan: "GraphPlan", heads: int, channels: int, in_channels: int, edge_dim: int) -> bool:
     """Shape test of isg_gatv2_layer_conv: isg_gatv2_tile_conv's, and a 128-wide layer input."""
-    return CFG.fuse_layer_conv and in_channels == 128 and heads <= 16 and tile_conv_supported(plan, heads, channels, edge_dim)
+    return (_layer_conv_ok(heads, channels, in_channels, edge_dim, plan.B, plan.E, plan.rowptr is not None, "tiles", CFG) and
+            plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) != "none")
 
 
 class NodePlanes(NamedTuple):
@@ -1202,7 +1222,7 @@ def run_split(plan: "GraphPlan", sub: "OversizeGraphs", core, x: Tensor, edge_in
         plan.memo()
         holed = copy.copy(plan)
         holed.holes = sub
-        holed._memo = {}               # (a layer's dispatch depends on `holes`: the holed plan answers for itself)
+        holed._memo = {}               # (a layer's route depends on `holes`: the holed plan answers for itself)
         res = core(x, edge_index, edge_attr, batch, instr, glf, holed, noises, seed, None)
         plan._edge_planes = holed._edge_planes          # (a tuple, not a container: handed back)
         return res
@@ -2285,6 +2305,69 @@ def linear_route(M: int, N: int, K: int, x_dtype=torch.float32, out_dtype=torch.
             return "f16x3_f16"
         return "f16x3" if cfg.gemm_f16x3 and K <= 128 and not f16_io else "panel"
     return "bf16x6_f16" if f16_io else "bf16x6"
+
+
+class ConvRoute(NamedTuple):
+    """How one MaskingGATv2Conv layer runs (conv_route)."""
+    conv: str          # "layer_conv" | "tile_conv" | "pair" | "unfused": the kernels of the message passing
+    gate: str          # "planes" | "planes32" | "rows" | "none": what gelu(x * instruction[batch]) is written as when the layer gates itself
+    gate_rows: bool    # the layer reads fp32 ROWS of its gated input (beside, or instead of, the planes)
+    e_proj: bool       # lin_edge runs as a Linear: the kernel reads e_proj [E, H*C] from memory
+
+
+def conv_route(*, heads: int, channels: int, in_channels: int, edge_dim: Optional[int], N: int, B: int, E: int, nmax: int,
+               has_csr: bool, tile_mode: str, rows_dtype=torch.float32, share_weights: bool = False,
+               use_instr: bool = True, masked: bool = False, gate_on_planes: bool = False, grad: bool = False,
+               e_proj_given: bool = False, has_edge_lin: bool = True, cfg: Optional[Switches] = None) -> ConvRoute:
+    """How a MaskingGATv2Conv layer (in_channels -> heads x channels, edge features edge_dim wide) runs on a batch of B graphs, N
+    nodes (at most nmax per graph) and E edges: a pure function of plain values, the ONE place that decides.
+
+    edge_dim: None without 2-D edge features; has_csr: the plan holds the CSR by destination; tile_mode: GraphPlan.tile_mode of the
+    64-node / 256-slot tiles; rows_dtype: MaskingGATv2Conv.rows_dtype(plan); masked: the layer has a node gate (masking_threshold
+    != 1), gate_on_planes: which can run on the input's planes (MaskingModel.planes_ready); grad: autograd is recording;
+    e_proj_given: the caller hands e_proj in; has_edge_lin: the layer has a lin_edge.
+    conv, the first match of (under the default switches):
+      e_proj given, no edge features or lin_edge, autograd                   "unfused"  lin_edge as a Linear + the message-passing kernel
+      4 !| C, H ceil32(C) > 2048, K = 0, K > 304, 4 !| K, nothing to do (B, E, nmax = 0), no CSR,
+        or a wide layer (32 !| C or K > 128) under 16 384 edges              "unfused"
+      fp16 rows                                                              "pair" when K >= 128, else "unfused"
+      other half rows                                                        "unfused"
+      the next rule's shape, lin_l and lin_r distinct, in_channels = 128,    "layer_conv"  lin_l | lin_r, lin_edge, logits, softmax and
+        H <= 16                                                                            aggregation as one persistent launch on tiles
+      C = 128, K <= 128, H <= 64, tile_mode not "none"                       "tile_conv"   the same with x_l / x_r projected before it
+      anything else                                                          "pair"        lin_edge folded into the logits, softmax +
+                                                                                           aggregation from them (per-graph kernel)
+    gate, the first match of:
+      no instruction gate                                                    "none"
+      conv is "layer_conv"                                                   "planes"    ops.NodePlanes (+ fp32 rows if gate_rows)
+      inference, fp32 rows, the lin_l | lin_r projection reads planes32      "planes32"  its operand (+ fp32 rows for a node gate)
+      anything else                                                          "rows"
+    gate_rows: everything but "layer_conv" reads rows, and so does a node gate that cannot run on the planes.  e_proj: conv is
+    "unfused" (a stack of layers then projects every layer's edge rows in one launch)."""
+    cfg = CFG if cfg is None else cfg
+    if e_proj_given or edge_dim is None or not has_edge_lin or grad:
+        conv = "unfused"
+    elif not _fused_logits_ok(heads, channels, edge_dim, B, E, nmax, has_csr, cfg):
+        conv = "unfused"
+    elif rows_dtype != torch.float32:
+        # fp16 feature rows (BASELINE configs[4]): the pair exists on the rows kernel (K >= 128), the tile kernels do not
+        conv = "pair" if rows_dtype == torch.float16 and edge_dim >= 128 else "unfused"
+    elif not share_weights and _layer_conv_ok(heads, channels, in_channels, edge_dim, B, E, has_csr, tile_mode, cfg):
+        conv = "layer_conv"
+    elif _tile_conv_ok(heads, channels, edge_dim, B, E, has_csr, tile_mode, cfg):
+        conv = "tile_conv"
+    else:
+        conv = "pair"
+    if not use_instr:
+        gate = "none"
+    elif conv == "layer_conv":
+        gate = "planes"
+    elif (not grad and rows_dtype == torch.float32 and
+          reads_planes32(N, (1 if share_weights else 2) * heads * channels, in_channels, cfg)):
+        gate = "planes32"
+    else:
+        gate = "rows"
+    return ConvRoute(conv, gate, conv != "layer_conv" or (masked and not gate_on_planes), conv == "unfused")
 
 
 _ROUTES = {}   # facts of an ops.linear call -> (the CFG they were decided under, route or None, which input facts decide it)

@@ -327,7 +327,7 @@ def test_results_are_per_graph_independent_without_sampling(dev):
 ENGINE = pytest.mark.parametrize("engine", [False, True], ids=["shipped_thresholds", "engine_dispatch"])
 
 
-def _dispatch(engine):
+def _engine_switches(engine):
     """engine=True: `ops.configured(h3p_min_m=1)` -- every K >= 256 Linear of the full model on isg_linear_h3p with its planes32
     producers / consumers (instr_gate_planes32, gather_add planes, add_layernorm planes, mha planes, the flat message-passing
     kernel's segmented planes into x_proj.0): the dispatch bench.py's `full_model` leg times at 49 152 question rows, here at the
@@ -397,7 +397,7 @@ def test_full_isubgvqa_model_matches_oracle(dev, sampler, engine):
         model = model.to(dev)
         sgd = argparse.Namespace(x_bbox=x_bbox.to(dev), added_sym_edge=sym.to(dev))
         from isubgvqa_amd import ops
-        with _dispatch(engine):
+        with _engine_switches(engine):
             ops.reset_counters()
             gl, gm, gg, extra, mt = model(x.to(dev), ei.to(dev), edge_attr.to(dev), batch.to(dev), q.to(dev),
                                           qmask.to(dev), return_masks=True, scene_graphs=sgd,
@@ -535,7 +535,7 @@ def test_full_model_matches_the_reference_forward_golden(dev, ci, engine):
     sg = argparse.Namespace(x_bbox=t("x_bbox"), added_sym_edge=t("added_sym_edge"))
     noises = {i: n.to(dev) for i, n in case["noises"].items()} or None
     from isubgvqa_amd import ops
-    with torch.no_grad(), _dispatch(engine):
+    with torch.no_grad(), _engine_switches(engine):
         x_enc, e_enc = model.scene_graph_encoder(t("x"), edge_index=t("edge_index"), edge_attr=t("edge_attr"),
                                                  batch=t("batch"), gt_scene_graphs=sg)
         enc = model.question_encoder(t("questions"), mask=t("att_mask"))
@@ -615,7 +615,7 @@ def test_reference_layout_checkpoint_to_hip_forward_matches_the_reference_golden
     sg = argparse.Namespace(x_bbox=t("x_bbox"), added_sym_edge=t("added_sym_edge"))
     noises = {i: n.to(dev) for i, n in case["noises"].items()} or None
     from isubgvqa_amd import ops
-    with torch.no_grad(), _dispatch(engine):
+    with torch.no_grad(), _engine_switches(engine):
         ops.reset_counters()
         logits, mask, gate, _, _ = model(t("x"), t("edge_index"), t("edge_attr"), t("batch"), t("questions"),
                                          t("att_mask"), return_masks=True, scene_graphs=sg, noises=noises)

@@ -505,6 +505,137 @@ def test_linear_route_memo_follows_the_switches_and_what_the_input_carries():
     assert ops._route(x, 2048, 512, 512, torch.float32, False, False) == "bf16x6"
 
 
+# facts of BASELINE configs[1]'s batch (4096 graphs) and layer (C = 128, H = 4, every width 128): what CONV_ROUTES' rows override
+_CONV = dict(heads=4, channels=128, in_channels=128, edge_dim=128, N=82189, B=4096, E=204753, nmax=40, has_csr=True, tile_mode="tiles")
+_C300 = dict(channels=300, in_channels=300, edge_dim=300)
+_SMALL = dict(N=5000, B=200, E=16383)
+UNFUSED = ("unfused", "rows", True, True)
+# (conv_route keywords over _CONV, switch overrides, (conv, gate, gate_rows, e_proj))
+CONV_ROUTES = [
+    ({}, {}, ("layer_conv", "planes", False, False)),
+    # the layer kernel: a 128-wide input, lin_l and lin_r distinct, H <= 16 (H x ceil32(C) <= 2048 ends the fused logits at C = 128)
+    ({"in_channels": 300}, {}, ("tile_conv", "planes32", True, False)), ({"in_channels": 64}, {}, ("tile_conv", "rows", True, False)),
+    ({"share_weights": True}, {}, ("tile_conv", "rows", True, False)),
+    ({"heads": 16}, {}, ("layer_conv", "planes", False, False)), ({"heads": 17}, {}, UNFUSED),
+    ({"heads": 64, "channels": 32}, {}, ("pair", "rows", True, False)), ({"heads": 65, "channels": 32}, {}, UNFUSED),
+    # edge widths: the tile kernels to 128, the rows kernel to 304, multiples of 4
+    ({"edge_dim": 64}, {}, ("layer_conv", "planes", False, False)), ({"edge_dim": 132}, {}, ("pair", "rows", True, False)),
+    ({"edge_dim": 304}, {}, ("pair", "rows", True, False)), ({"edge_dim": 308}, {}, UNFUSED), ({"edge_dim": 130}, {}, UNFUSED),
+    ({"edge_dim": None}, {}, UNFUSED),
+    # head dimensions: C = 128 on tiles, 32 | C or not (wide) on the per-graph pair, 4 !| C nowhere
+    ({"channels": 96}, {}, ("pair", "rows", True, False)), (_C300, {}, ("pair", "planes32", True, False)),
+    ({"channels": 130}, {}, UNFUSED),
+    # a wide layer on each side of rows_kernel_min_edges; a narrow one does not care
+    ({**_C300, **_SMALL}, {}, ("unfused", "planes32", True, True)), ({**_C300, **_SMALL, "E": 16384}, {}, ("pair", "planes32", True, False)),
+    ({**_SMALL, "edge_dim": 132}, {}, UNFUSED), (_SMALL, {}, ("layer_conv", "planes", False, False)),
+    ({**_C300, **_SMALL}, {"rows_kernel_min_edges": 1000}, ("pair", "planes32", True, False)),
+    # nothing to do, no CSR
+    ({"N": 100, "B": 5, "E": 0}, {}, UNFUSED), ({"N": 0, "B": 0, "E": 0, "nmax": 0}, {}, UNFUSED), ({"has_csr": False}, {}, UNFUSED),
+    # half rows (configs[4]): the pair on the rows kernel from K = 128; an oversize batch keeps fp32 rows and is beyond the tiles too
+    ({"rows_dtype": F16, "edge_dim": 64}, {}, UNFUSED), ({"rows_dtype": F16}, {}, ("pair", "rows", True, False)),
+    ({"rows_dtype": torch.bfloat16}, {}, UNFUSED),
+    ({"rows_dtype": torch.float32, "nmax": 300, "tile_mode": "none"}, {}, ("pair", "rows", True, False)),
+    # autograd, an e_proj handed in, no lin_edge
+    ({"grad": True}, {}, UNFUSED), ({"grad": True, "in_channels": 300}, {}, UNFUSED), ({"e_proj_given": True}, {}, UNFUSED),
+    ({"has_edge_lin": False}, {}, UNFUSED),
+    # graphs beyond a tile
+    ({"tile_mode": "tiles"}, {}, ("layer_conv", "planes", False, False)), ({"tile_mode": "mixed"}, {}, ("layer_conv", "planes", False, False)),
+    ({"tile_mode": "none"}, {}, ("pair", "rows", True, False)), ({"tile_mode": "mixed", "in_channels": 300}, {}, ("tile_conv", "planes32", True, False)),
+    ({"tile_mode": "none", "in_channels": 300}, {}, ("pair", "planes32", True, False)),
+    # the gate: planes with and without rows (a node gate that cannot run on the planes reads rows), planes32 from h3p_min_m rows
+    ({"masked": True, "gate_on_planes": True}, {}, ("layer_conv", "planes", False, False)),
+    ({"masked": True, "gate_on_planes": False}, {}, ("layer_conv", "planes", True, False)),
+    ({"masked": True, "gate_on_planes": True, "share_weights": True}, {}, ("tile_conv", "rows", True, False)),
+    ({"in_channels": 300, "N": 2047, "B": 90, "E": 5000}, {}, ("tile_conv", "rows", True, False)),
+    ({"in_channels": 300, "N": 2048, "B": 90, "E": 5000}, {}, ("tile_conv", "planes32", True, False)),
+    ({"in_channels": 300, "N": 2048, "B": 90, "E": 5000, "masked": True}, {}, ("tile_conv", "planes32", True, False)),
+    ({"in_channels": 300, "rows_dtype": F16}, {}, ("pair", "rows", True, False)),
+    ({"use_instr": False}, {}, ("layer_conv", "none", False, False)), ({"use_instr": False, "in_channels": 300}, {}, ("tile_conv", "none", True, False)),
+    # the overrides tests and tools use
+    ({}, {"fuse_layer_conv": False}, ("tile_conv", "rows", True, False)), ({}, {"fuse_tile_conv": False}, ("pair", "rows", True, False)),
+    ({}, {"fuse_logits": False}, UNFUSED), ({}, {"fuse_logits_wide": False}, ("layer_conv", "planes", False, False)),
+    (_C300, {"fuse_logits_wide": False}, ("unfused", "planes32", True, True)),
+    ({}, {"gemm_backend": "torch"}, UNFUSED), (_C300, {"gemm_backend": "torch"}, UNFUSED), ({}, {"gemm_f16x3": False}, UNFUSED),
+    ({}, {"mp_kernel": "chunk"}, UNFUSED), ({"in_channels": 300}, {"h3p": False}, ("tile_conv", "rows", True, False)),
+    ({}, {"h3p_min_k": 128, "fuse_layer_conv": False}, ("tile_conv", "planes32", True, False)),
+    # real forwards.  configs[1]: two plain layers and the masked last one; with a few graphs beyond a tile
+    ({}, {}, ("layer_conv", "planes", False, False)), ({"masked": True, "gate_on_planes": True}, {}, ("layer_conv", "planes", False, False)),
+    ({"nmax": 100, "tile_mode": "mixed", "masked": True, "gate_on_planes": True}, {}, ("layer_conv", "planes", False, False)),
+    # the full model at C = 300 over 4096 graphs, and over one question
+    ({**_C300, "masked": True}, {}, ("pair", "planes32", True, False)),
+    ({**_C300, "N": 17, "B": 1, "E": 40, "nmax": 17}, {}, UNFUSED), ({"N": 17, "B": 1, "E": 40, "nmax": 17}, {}, ("layer_conv", "planes", False, False)),
+    # configs[4] (2048 skewed graphs, fp16 rows)
+    ({"rows_dtype": F16, "N": 43633, "B": 2048, "E": 110000, "nmax": 180, "tile_mode": "none", "masked": True}, {}, ("pair", "rows", True, False)),
+]
+
+
+@pytest.mark.parametrize("facts,switches,route", CONV_ROUTES)
+def test_conv_route_names_how_a_gatv2_layer_runs(facts, switches, route):
+    """ops.conv_route is the whole decision of how a MaskingGATv2Conv layer runs -- its message-passing kernels, what its
+    instruction gate writes, whether fp32 rows of the gated input are read, whether e_proj exists in memory: each side of every
+    rule, the switches' overrides, and the layers of real forwards."""
+    from isubgvqa_amd import ops
+    with ops.configured(**switches):
+        assert ops.conv_route(**{**_CONV, **facts}) == route
+    assert ops.conv_route(cfg=ops.Switches(**switches), **{**_CONV, **facts}) == route
+
+
+class _StubPlan:
+    """What MaskingGATv2Conv.route reads of an ops.GraphPlan (which only a GPU can build); counts the calls of tile_mode."""
+    def __init__(self, N=82189, B=4096, E=204753, nmax=40, emax=100, mode="tiles"):
+        self.N, self.B, self.E, self.nmax, self.emax, self.rowptr = N, B, E, nmax, emax, object()
+        self.mode, self.asked, self._memo = mode, 0, {}
+
+    def memo(self):
+        return self._memo
+
+    def tile_mode(self, node_cap=64, edge_cap=256):
+        self.asked += 1
+        return self.mode
+
+
+def _conv_layer(in_channels=128, channels=128, **kw):
+    from isubgvqa_amd.models.mgat_v2_conv import MaskingGATv2Conv
+    return MaskingGATv2Conv(in_channels, channels, heads=4, edge_dim=channels, add_self_loops=False, masking_threshold=1.0,
+                            use_instr=True, **kw)
+
+
+def test_conv_route_asks_the_plans_tile_mode_only_when_the_route_depends_on_it():
+    """GraphPlan.tile_mode can cost a device-to-host sync (a big batch with a graph beyond a tile): a layer that cannot run on the
+    tile kernels whatever it says -- the C = 300 full model, fuse_tile_conv off -- never asks; one that can asks once per plan."""
+    from isubgvqa_amd import ops
+    with torch.no_grad():
+        wide, plan = _conv_layer(300, 300), _StubPlan(nmax=100, mode="none")
+        assert wide.route(plan, 300, torch.empty(0, 300)) == ("pair", "planes32", True, False) and plan.asked == 0
+        assert not ops.layer_conv_supported(plan, 4, 300, 128, 300) and not ops.tile_conv_supported(plan, 4, 300, 300) and plan.asked == 0
+        conv, ea = _conv_layer(), torch.empty(0, 128)
+        with ops.configured(fuse_tile_conv=False):
+            assert conv.route(plan, 128, ea) == ("pair", "rows", True, False) and conv.dispatch(plan, 128, ea) == "pair"
+            assert not ops.layer_conv_supported(plan, 4, 128, 128, 128) and plan.asked == 0
+        for mode, route in (("none", ("pair", "rows", True, False)), ("mixed", ("layer_conv", "planes", False, False)),
+                            ("tiles", ("layer_conv", "planes", False, False))):
+            plan = _StubPlan(nmax=100, mode=mode)
+            assert conv.route(plan, 128, ea) == route and conv.dispatch(plan, 128, ea) == route[0] and plan.asked == 1, mode
+            assert ops.layer_conv_supported(plan, 4, 128, 128, 128) == (mode != "none") and plan.asked == 2
+    assert conv.route(plan, 128, ea) == UNFUSED and conv.route(None, 128, ea, None) == UNFUSED and plan.asked == 2      # autograd; no plan
+
+
+def test_conv_route_memo_is_per_plan_and_follows_the_switches():
+    """MaskingGATv2Conv.route keeps its answer on the plan, per layer, facts and switch object; a changed switch is seen on the next call."""
+    from isubgvqa_amd import ops
+    conv, other, plan, ea = _conv_layer(), _conv_layer(share_weights=True), _StubPlan(), torch.empty(0, 128)
+    with torch.no_grad():
+        first = conv.route(plan, 128, ea)
+        assert first == ("layer_conv", "planes", False, False) and conv.route(plan, 128, ea) is first and plan.asked == 1
+        assert other.route(plan, 128, ea).conv == "tile_conv" and conv.route(plan, 300, ea).conv == "tile_conv"
+        assert conv.route(plan, 128, ea, e_proj=ea) == UNFUSED and conv.route(plan, 128, ea) is first
+        with ops.configured(fuse_layer_conv=False):
+            assert conv.route(plan, 128, ea).conv == "tile_conv" and conv.dispatch(plan, 128, ea) == "tile_conv"
+        again = conv.route(plan, 128, ea)                      # the switches are a new object again: decided again
+        assert again == first and again is not first
+        assert conv.route(_StubPlan(mode="none"), 128, ea).conv == "pair" and conv.route(plan, 128, ea) is again
+
+
 def test_linear_relu_and_gelu_are_exclusive_at_every_size():
     from isubgvqa_amd import ops
     for M in (0, 12, 1024, 5000):
