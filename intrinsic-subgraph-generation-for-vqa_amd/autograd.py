@@ -223,6 +223,15 @@ def scatter_mean(msg, plan):
 # ------------------------------------------------------------------------------------------------
 # Dense projection
 # ------------------------------------------------------------------------------------------------
+# g^T x through torch sums the rows of one output in a single fp32 chain: its error against float64 grows like
+# sqrt(M) * 3.7e-8 of the largest entry (measured: 1.1e-6 at M = 2047, 2.3e-6 at 4095, 3.6e-6 at 16383 -- six to ten times the
+# blocked fp32 sum of a CPU BLAS) and passes 2e-6 near M = 3000.  The split-M kernel sums M / splits rows per chain (32 at a time on the
+# matrix core) and stays at 3e-7 to 6e-7 at every M.  Its time against hipBLASLt between 2 k and 16 k rows is NOT measured yet
+# (`tools/time_wgrad.py --mid` times that range; at 4096 x 1842 x 512 it is 26 us slower, profiles/r01_o_wgrad_vs_hipblaslt.txt): the
+# switch sits here for the error, not for the time.
+WGRAD_MIN_ROWS = 2048
+
+
 class _Linear(torch.autograd.Function):
     """y = act(x W^T + b): forward on isg_linear_bf16x6 (pre-activation kept when act = GELU), backward as fp32 GEMMs."""
 
@@ -246,7 +255,7 @@ class _Linear(torch.autograd.Function):
                   if (g.size(1) & 3) == 0 else g @ weight)
         dw = None
         if ctx.needs_input_grad[1]:   # long-and-thin reductions on the split-M kernel; short ones are hipBLASLt's home turf
-            dw = ops.linear_wgrad(g, x.contiguous()) if g.size(0) >= 16384 else g.t() @ x
+            dw = ops.linear_wgrad(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db, None
 

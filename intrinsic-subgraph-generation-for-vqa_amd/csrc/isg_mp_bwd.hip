@@ -4,7 +4,11 @@
 //   s = x_r[i] + x_l[j] + ep[e];  u = leaky(s*m)*m;  a_e = <u, att_h>;  alpha = softmax_i(a);  out_i = sum_e alpha_e m_e x_l[j]
 // Given g = d out_i:
 //   dalpha_e = m_e <g, x_l[j]>
-//   da_e     = alpha_e (dalpha_e - sum_e' alpha_e' dalpha_e')                      (softmax; the +1e-16 is below fp32 resolution)
+//   da_e     = alpha_e (dalpha_e - S),  S = sum_e' alpha_e' dalpha_e' / sum_e' alpha_e'  (softmax; the +1e-16 is below fp32
+//              resolution).  The stored alpha of a destination sum to 1 only up to the rounding of the forward's fp32
+//              denominator (a few 1e-6 at 1000 in-edges); without the division that residue times S reaches every da_e with
+//              one sign and survives the cancelling sums d x_r and d mask.  Both sums of S are kept in fp64: their own fp32
+//              rounding over a long row would put the same kind of residue back.
 //   ds_e     = da_e * att_h * m_e^2 * (s*m > 0 ? 1 : slope)
 //   d att_h += da_e * u_e          d x_r[i] += ds_e          d ep[e] = ds_e
 //   d x_l[j] += ds_e + alpha_e m_e g                                               (a scatter by SOURCE)
@@ -82,8 +86,8 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
     }
     const float mi = mode == 1 ? a.node_mask[i] : 1.f;
 
-    // pass 1: dalpha_e = m_e <g, x_l[j]> and S = sum alpha_e dalpha_e (edge order)
-    float S = 0.f;
+    // pass 1: dalpha_e = m_e <g, x_l[j]> and S = sum alpha_e dalpha_e / sum alpha_e (edge order)
+    double sum_ad = 0.0, sum_a = 0.0;
     for (int t = rb; t < re; ++t) {
       const int rel = t - e0;
       int j, e;
@@ -98,7 +102,9 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
         if (ok[p]) part += dot4(g4[p], xl[off[p]]);
       const float raw = group_sum<G>(part);
       const float dal = raw * me;
-      S += a.alpha[(size_t)e * H + g] * dal;
+      const float al = a.alpha[(size_t)e * H + g];
+      sum_ad += (double)al * (double)dal;
+      sum_a += (double)al;
       const int slot = t - rb;
       if (l == 0) {
         if (slot < MP_LCAP) {
@@ -111,6 +117,7 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
         }
       }
     }
+    const float S = sum_a > 0.0 ? (float)(sum_ad / sum_a) : 0.f;
     __builtin_amdgcn_wave_barrier();
 
     // pass 2: da_e, then everything that flows through the logit
