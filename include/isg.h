@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ISG_ABI_VERSION 22
+#define ISG_ABI_VERSION 23
 
 #define ISG_OK 0
 #define ISG_EINVAL (-1)       /* null pointer / negative size / inconsistent sizes          */
@@ -683,6 +683,38 @@ int isg_mha_small(const float *q, int32_t ldq, const float *k, int32_t ldk, cons
 int isg_add_layernorm(const float *x, int32_t ldx, const float *r, int32_t ldr, const float *gamma, const float *beta,
                       float eps, float *out, int32_t ldo, float *rowmax, int64_t M, int32_t D, uint16_t *planes,
                       float *planes_inv, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The sampled subgraph as a graph
+ * ------------------------------------------------------------------------------------------- */
+
+/* Induced-subgraph cut of a batch by a node mask, on the device: what the reference's evaluation does one question per forward
+ * on the host, with one .item() per node (run_token_coo.py:65-173, utils/token_coo_fns.py, utils/graph_vis.py:27-41).  All
+ * integer and exact:
+ *   keep[n]  = (node_mask[n] > threshold) != (complement != 0)       (a NaN compares false: dropped by a keep-cut, kept by a
+ *              complement-cut);  edge e = (s, d) is kept iff 0 <= s, d < N and keep[s] && keep[d]
+ *   node_new int32 [N]   rank of n among the kept nodes in ascending n, or -1
+ *   edge_new int32 [E]   rank of e among the kept edges in ORIGINAL edge order (the list need not be sorted by graph), or -1
+ *   node_id int64 [N], edge_id int64 [E]: the kept ids, ascending, in entries [0, N') / [0, E')
+ *   edge_index_out int64 [2, E] (row stride E): columns [0, E') hold node_new[edge_index[:, edge_id]]
+ *   batch_out int64 [N]: entries [0, N') = batch[node_id]
+ *   ptr_out int32 [B+1]: node range per graph in the cut = kept nodes before ptr[g]; graph numbers are kept, graphs may come out
+ *              empty
+ *   sel int32 [B, table_k] (skipped, and may be NULL, when table_k == 0): row g = the LOCAL indices n - ptr[g] of graph g's
+ *              first table_k kept nodes, ascending, then -1 -- for a top-k mask with table_k = k the whole explanation
+ *   counts int32 [2] = {N', E'}, on the device.  Entries of the capacity-sized outputs beyond N' / E' are unspecified.
+ * node_mask fp32 [N]; edge_index int64 [2, E]; batch int64 [N]; ptr int32 [B+1] (isg_graph_ptr).  Three launches at most, no
+ * atomics, a grid sized from N, E, B and table_k alone: the same inputs give the same bits on any device.  SUBGRAPH_BLOCK = 1024
+ * consecutive elements are ranked by one workgroup.
+ * isg_subgraph_workspace_bytes(N, E) = 4 * (ceil(N / 1024) + ceil(E / 1024) + (N + 1) + 1): the kept elements of every block,
+ * the kept nodes before every node, E'.  Host-only; 0 for a negative size.
+ * ISG_EINVAL for a null required pointer or a negative size, before any HIP call; ISG_EUNSUPPORTED when N, E, B or B * table_k
+ * does not fit int32; ISG_EWORKSPACE for a workspace that is null or too small. */
+size_t isg_subgraph_workspace_bytes(int64_t N, int64_t E);
+int isg_subgraph_cut(const float *node_mask, float threshold, int32_t complement, const int64_t *edge_index, const int64_t *batch,
+                     const int32_t *ptr, int64_t N, int64_t E, int64_t B, int32_t *node_new, int32_t *edge_new, int64_t *node_id,
+                     int64_t *edge_id, int64_t *edge_index_out, int64_t *batch_out, int32_t *ptr_out, int32_t *sel,
+                     int32_t table_k, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -704,6 +704,129 @@ class GraphPlan:
 
 
 # ------------------------------------------------------------------------------------------------
+# The sampled subgraph as a graph
+# ------------------------------------------------------------------------------------------------
+SUBGRAPH_BLOCK = 1024      # consecutive elements one workgroup of isg_subgraph_cut ranks (SG_BLOCK in csrc/isg_subgraph.hip)
+
+
+class SubgraphCut:
+    """What isg_subgraph_cut left on the device: the induced subgraph of a node mask, renumbered.  The tensors below have the
+    parent's capacity (N / E entries); `.sizes()` copies the two counts to the host -- once, the operator's only device-to-host
+    copy -- and the trimmed views go through it.
+
+    node_new int32 [N] / edge_new int32 [E]: new id of every node / edge, -1 where it was cut; ptr int32 [B + 1]: node range per
+    graph in the cut (graph numbers are the parent's; a graph may be empty); sel int32 [B, table_k] or None: local indices of
+    every graph's first table_k kept nodes, then -1; counts int32 [2] = (N', E') on the device."""
+
+    def __init__(self, parent: "GraphPlan", node_new, edge_new, node_id, edge_id, edge_index, batch, ptr, sel, counts):
+        self.parent = parent
+        self.node_new, self.edge_new, self.ptr, self.sel, self.counts = node_new, edge_new, ptr, sel, counts
+        self._node_id, self._edge_id, self._edge_index, self._batch = node_id, edge_id, edge_index, batch
+        self._sizes = None
+        self._trim = {}
+
+    def sizes(self) -> Tuple[int, int]:
+        """(N', E'): nodes and edges of the cut."""
+        if self._sizes is None:
+            n, e = self.counts.tolist()
+            self._sizes = (int(n), int(e))
+        return self._sizes
+
+    def _trimmed(self, name: str) -> Tensor:
+        if name not in self._trim:
+            n, e = self.sizes()
+            self._trim[name] = {"node_id": lambda: self._node_id[:n], "edge_id": lambda: self._edge_id[:e],
+                                "edge_index": lambda: self._edge_index[:, :e].contiguous(),
+                                "batch": lambda: self._batch[:n]}[name]()
+        return self._trim[name]
+
+    @property
+    def node_id(self) -> Tensor:
+        """int64 [N']: the kept nodes, ascending."""
+        return self._trimmed("node_id")
+
+    @property
+    def edge_id(self) -> Tensor:
+        """int64 [E']: the kept edges, in their original order."""
+        return self._trimmed("edge_id")
+
+    @property
+    def edge_index(self) -> Tensor:
+        """int64 [2, E']: the kept edges between the cut's node numbers."""
+        return self._trimmed("edge_index")
+
+    @property
+    def batch(self) -> Tensor:
+        """int64 [N']: graph of every kept node."""
+        return self._trimmed("batch")
+
+    def gather_nodes(self, t: Tensor) -> Tensor:
+        """t[node_id] for a tensor with one row per node of the parent batch."""
+        return t.index_select(0, self.node_id)
+
+    def gather_edges(self, t: Tensor) -> Tensor:
+        """t[edge_id] for a tensor with one row per edge of the parent batch."""
+        return t.index_select(0, self.edge_id)
+
+    def remap_edge_positions(self, positions: Tensor) -> Tensor:
+        """Positions in the parent's GLOBAL edge list (the scene graphs' added_sym_edge as the encoder applies it, quirk Q6) as
+        positions in the cut's edge list; those of cut edges, and those beyond the list, are dropped."""
+        E = self.edge_new.numel()
+        p = positions.long()
+        p = p[(p >= 0) & (p < E)]
+        new = self.edge_new.long().index_select(0, p)
+        return new[new >= 0]
+
+    def plan(self) -> "GraphPlan":
+        """The GraphPlan of the cut.  A subgraph's graphs are no larger than the parent's, so the parent's bounds serve as hints
+        and the build costs no device-to-host sync."""
+        if "plan" not in self._trim:
+            self._trim["plan"] = GraphPlan.build(self.batch, self.edge_index, num_graphs=self.parent.B, max_nodes=self.parent.nmax,
+                                                 max_edges=self.parent.emax)
+        return self._trim["plan"]
+
+
+def subgraph_cut(node_mask: Tensor, edge_index: Tensor, plan: "GraphPlan", threshold: float = 0.0, complement: bool = False,
+                 table_k: int = 0) -> SubgraphCut:
+    """The induced subgraph of the nodes with node_mask > threshold (complement: of the others) as a graph, cut on the device
+    (isg_subgraph_cut: three launches, no sync).  node_mask fp32 [N] or [N, 1] (a forward's imle_mask), edge_index int64 [2, E],
+    plan the batch's GraphPlan; table_k > 0 also fills SubgraphCut.sel."""
+    lib = _lib.load()
+    if node_mask.dim() == 2 and node_mask.size(1) == 1:
+        node_mask = node_mask.squeeze(1)
+    p_mask = _chk(node_mask, "node_mask", torch.float32)
+    p_ei = _chk(edge_index, "edge_index", torch.int64)
+    N, B, k = plan.N, plan.B, int(table_k)
+    if tuple(node_mask.shape) != (N,):
+        raise ValueError(f"node_mask: expected [{N}] or [{N}, 1], got {tuple(node_mask.shape)}")
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"edge_index must be [2,E], got {tuple(edge_index.shape)}")
+    if plan.batch is None:
+        raise ValueError("subgraph_cut needs a GraphPlan built from the batch vector")
+    p_batch = _chk(plan.batch, "plan.batch", torch.int64, (N,))
+    if k < 0:
+        raise ValueError(f"table_k must be >= 0, got {table_k}")
+    E = edge_index.size(1)
+    dev = node_mask.device
+    # one allocation per element width; pointers are taken from the buffers (an EMPTY view's data_ptr() is null)
+    ws_bytes = lib.isg_subgraph_workspace_bytes(N, E)
+    n32 = N + E + (B + 1) + B * k + 2
+    i32 = torch.empty(n32 + (ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    i64 = torch.empty(max(2 * N + 3 * E, 1), dtype=torch.int64, device=dev)
+    o_nn, o_en, o_ptr, o_sel, o_cnt = 0, N, N + E, N + E + B + 1, N + E + B + 1 + B * k
+    o_nid, o_eid, o_ei, o_b = 0, N, N + E, N + 3 * E
+    b32, b64 = i32.data_ptr(), i64.data_ptr()
+    _lib.check(lib.isg_subgraph_cut(p_mask, float(threshold), 1 if complement else 0, p_ei, p_batch,
+                                    _chk(plan.ptr, "plan.ptr", torch.int32, (B + 1,)), N, E, B, b32 + 4 * o_nn, b32 + 4 * o_en,
+                                    b64 + 8 * o_nid, b64 + 8 * o_eid, b64 + 8 * o_ei, b64 + 8 * o_b, b32 + 4 * o_ptr,
+                                    b32 + 4 * o_sel if k else 0, k, b32 + 4 * o_cnt, b32 + 4 * n32, ws_bytes, _stream()),
+               "isg_subgraph_cut")
+    return SubgraphCut(plan, i32[o_nn:o_nn + N], i32[o_en:o_en + E], i64[o_nid:o_nid + N], i64[o_eid:o_eid + E],
+                       i64[o_ei:o_ei + 2 * E].view(2, E), i64[o_b:o_b + N], i32[o_ptr:o_ptr + B + 1],
+                       i32[o_sel:o_sel + B * k].view(B, k) if k else None, i32[o_cnt:o_cnt + 2])
+
+
+# ------------------------------------------------------------------------------------------------
 # Message passing
 # ------------------------------------------------------------------------------------------------
 def instr_gate(x: Tensor, instr: Tensor, batch: Tensor, plan: Optional["GraphPlan"] = None) -> Tensor:
