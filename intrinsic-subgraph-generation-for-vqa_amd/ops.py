@@ -9,13 +9,12 @@ without a backward refuses such an operand loudly.
 from __future__ import annotations
 
 import contextlib
-import copy
 import dataclasses
 import operator
 import sys
 import types
 import weakref
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -273,6 +272,15 @@ _PENDING_SIZES = []      # (event, pinned int64[2 or 3] = graphs beyond a tile /
 _CAPTURE_BOUNDS = []     # StepCapture: the (pinned int32[2], device int32[2]) a plan built inside the capture in progress hands its last kernel
 
 
+def _hint_error(true, hints, of: str) -> Optional[Exception]:
+    """The IsgError for true (nodes, edges) beyond the hinted (max_nodes, max_edges or None), else None; `of`: what ran under them."""
+    (n_true, e_true), (hn, he) = true, hints
+    if n_true <= hn and (he is None or e_true <= he):
+        return None
+    return _lib.IsgError(f"GraphPlan hints understate the batch: max_nodes={hn} / max_edges={he} given, but a graph has "
+                         f"{n_true} nodes / {e_true} edges; results of {of} are invalid")
+
+
 def check_plans(block: bool = True) -> None:
     """Raise IsgError if a GraphPlan was built with hints smaller than the batch's true per-graph bounds.
     block=False only looks at copies that have already completed."""
@@ -282,9 +290,7 @@ def check_plans(block: bool = True) -> None:
             keep.append((ev, host, hn, he))
             continue
         ev.synchronize()
-        n_true, e_true = int(host[0]), int(host[1])
-        if n_true > hn or (he is not None and e_true > he):
-            bad = bad or (n_true, e_true, hn, he)
+        bad = bad or _hint_error((int(host[0]), int(host[1])), (hn, he), "that batch")
     _PENDING_HINTS[:] = keep
     keep_s, bad_s = [], None
     for ev, host, expect in _PENDING_SIZES:       # graph_sizes hints (GraphPlan._oversize_stats): counted on the device as well
@@ -300,8 +306,7 @@ def check_plans(block: bool = True) -> None:
         raise _lib.IsgError(f"GraphPlan graph_sizes disagree with the batch: graphs beyond a tile / their nodes / their edges "
                             f"counted on the device {bad_s[0]}, from the hint {bad_s[1]}; results of that batch are invalid")
     if bad is not None:
-        raise _lib.IsgError(f"GraphPlan hints understate the batch: max_nodes={bad[2]} / max_edges={bad[3]} given, "
-                            f"but a graph has {bad[0]} nodes / {bad[1]} edges; results of that batch are invalid")
+        raise bad
 
 
 def _f32(t: Tensor) -> Tensor:
@@ -323,7 +328,39 @@ class OversizeGraphs(NamedTuple):
     plan: "GraphPlan"
 
 
-@dataclass
+class TilePlan(NamedTuple):
+    """One packing of a batch's graphs into tiles (GraphPlan.tiles): five views of one int32 buffer."""
+    tile_ptr: Tensor             # int32 [cap + 1] first graph of every tile
+    ntiles: Tensor               # int32 [1], on the device
+    cap: int                     # upper bound of the tile count: what the kernels are launched with
+    info: Tensor                 # int32 [cap, 4] (first node, nodes, first CSR slot, CSR slots) in tile order
+    heavy: Tensor                # int32 [cap, 4] the same entries by descending CSR-slot count (tiles_heavy_first)
+
+
+class _PlanCache:
+    """Everything a GraphPlan builds lazily, each on first use.  One object per plan, shared by the views made of it
+    (GraphPlan.with_holes): what one of them builds, all of them find."""
+    __slots__ = ("tiles", "edge_planes", "oversize_stats", "oversize", "by_src", "slots", "parent_edge_rows")
+
+    def __init__(self):
+        self.tiles = {}                   # (node_cap, edge_cap) -> TilePlan
+        self.edge_planes = None           # _from_tensor(edge_attr, NodePlanes)
+        self.oversize_stats = {}          # (node_cap, edge_cap) -> dict or None (GraphPlan._oversize_stats)
+        self.oversize = {}                # (node_cap, edge_cap) -> OversizeGraphs or None
+        self.by_src = None                # (rowptr_s, eid_s, dst_s)
+        self.slots = None                 # int64 [N]
+        self.parent_edge_rows = None      # on the plan of a batch's oversize graphs: _from_tensor(the batch's edge_attr, their rows)
+
+
+def _csr_build(lib, edge_index: Tensor, N: int, E: int, rowptr: Tensor, eid: Tensor, src: Tensor, dst: Optional[Tensor]) -> None:
+    """CSR by destination of edge_index into the given int32 arrays (isg_csr_build and its workspace)."""
+    ws_bytes = lib.isg_csr_workspace_bytes(N, E)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=edge_index.device)
+    _lib.check(lib.isg_csr_build(edge_index.data_ptr(), N, E, rowptr.data_ptr(), eid.data_ptr(), src.data_ptr(),
+                                 0 if dst is None else dst.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "isg_csr_build")
+
+
+@dataclass(slots=True)
 class GraphPlan:
     """What every layer needs to know about one PyG Batch, computed once on the device.
 
@@ -346,75 +383,78 @@ class GraphPlan:
     eptr: Optional[Tensor] = None
     batch: Optional[Tensor] = None           # kept for the backward restatements (autograd.py)
     edge_index: Optional[Tensor] = None      # kept for the lazily built CSR by source (backward only)
-    _by_src: Optional[Tuple[Tensor, Tensor, Tensor]] = None
-    _slots: Optional[Tensor] = None
-    _tiles: Optional[dict] = None
-    _edge_planes: Optional[tuple] = None
-    _oversize: Optional[dict] = None
     sizes_host: Optional[Tensor] = None           # HOST int64 [2, B] nodes / in-edges per graph when the caller's collate gave them (a hint
                                                   # like max_nodes / max_edges: lets oversize() count without a device-to-host sync)
     no_tiles: bool = False                        # the plan of a batch's oversize graphs: the tile kernels are not asked again
     graph_ids: Optional[Tensor] = None            # int32 [B]: this plan's graphs are a CUT of a larger batch and these are their numbers
                                                   # there -- the samplers' in-kernel noise is keyed by them (ops._gid_ptr)
-    holes: Optional["OversizeGraphs"] = None      # set by run_split: the tile kernels pass over these graphs and NOTHING fills their rows
-    _memo: Optional[dict] = None                  # answers that depend on the plan and the switches only (tile_mode, a layer's route):
-                                                  # asked ~17 times per step by the layers, computed once (shared by run_split's copy)
+    holes: Optional["OversizeGraphs"] = None      # with_holes: the tile kernels pass over these graphs and NOTHING fills their rows
+    _memo: dict = field(default_factory=dict)     # answers that depend on the plan and the switches only (tile_mode, a layer's route):
+                                                  # asked ~17 times per step by the layers, computed once
+    _cache: _PlanCache = field(default_factory=_PlanCache)
+    _bounds_dev: Optional[Tensor] = None          # these three: set on a plan built from hints inside a hipGraph capture (build) --
+    _bounds_host: Optional[Tensor] = None         # where every replay leaves the true bounds, on the device and in pinned memory,
+    _hints: Optional[Tuple[int, Optional[int]]] = None        # and the hinted (max_nodes, max_edges or None) they are held against
 
     def memo(self) -> dict:
-        if self._memo is None:
-            self._memo = {}
         return self._memo
+
+    def with_holes(self, sub: "OversizeGraphs") -> "GraphPlan":
+        """A view of this plan for run_split's tile pass: the same tensors and the same cache, `holes` = sub, and a memo of its
+        own (a layer's route depends on `holes`).  This plan is not written to."""
+        return dataclasses.replace(self, holes=sub, _memo={})
 
     def edge_planes(self, edge_attr: Tensor) -> Tuple[Tensor, Tensor]:
         """(planes int16 [E, 2, 128], inv_scale fp32 [E]) of the batch's edge features in CSR slot order (isg_edge_planes): the
         operand of isg_gatv2_tile_conv.  Every layer and head reads the same edge features (mgat.py:144-148), so the split is
         made once per batch and kept on the plan (keyed by the tensor's identity, storage and version)."""
         self.require_csr()
-        hit = _if_from_tensor(self._edge_planes, edge_attr)
+        hit = _if_from_tensor(self._cache.edge_planes, edge_attr)
         if hit is None:
             lib = _lib.load()
             E, K = edge_attr.shape
             hit = _empty_node_planes(E, edge_attr.device)
             _lib.check(lib.isg_edge_planes(_chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), self.eid.data_ptr(), E, K,
                                            hit.planes.data_ptr(), hit.inv.data_ptr(), _stream()), "isg_edge_planes")
-            self._edge_planes = _from_tensor(edge_attr, hit)
+            self._cache.edge_planes = _from_tensor(edge_attr, hit)
         return hit.planes, hit.inv
 
     def tiles_and_edge_planes(self, edge_attr: Tensor, node_cap: int, edge_cap: int):
         """(tiles(node_cap, edge_cap), edge_planes(edge_attr)); when neither exists yet they are made by ONE launch
         (isg_tile_plan_edge_planes: the one-workgroup tile plan runs beside the row split instead of alone on the chip)."""
         key = (int(node_cap), int(edge_cap))
-        have_t = self._tiles is not None and key in self._tiles
-        have_e = _if_from_tensor(self._edge_planes, edge_attr) is not None
-        if CFG.plan_fused and not have_t and not have_e and edge_cap > 0 and edge_attr.dim() == 2 and edge_attr.size(1) <= 128 \
-                and edge_attr.size(1) % 4 == 0 and edge_attr.dtype == torch.float32:
+        if CFG.plan_fused and key not in self._cache.tiles and _if_from_tensor(self._cache.edge_planes, edge_attr) is None \
+                and edge_cap > 0 and edge_attr.dim() == 2 and edge_attr.size(1) <= 128 and edge_attr.size(1) % 4 == 0 \
+                and edge_attr.dtype == torch.float32:
             lib = _lib.load()
             self.require_csr()
             E, K = edge_attr.shape
-            cap = int(lib.isg_tile_plan_capacity(self.N, self.E, self.B, key[0], key[1]))
-            buf = torch.empty(9 * cap + 8, dtype=torch.int32, device=self.ptr.device)     # info first: 16-byte aligned
-            info, heavy, tp, nt = buf[:4 * cap], buf[4 * cap:8 * cap], buf[8 * cap + 4:9 * cap + 5], buf[9 * cap + 5:9 * cap + 6]
+            t = self._empty_tile_plan(lib, key)
             ep = _empty_node_planes(E, edge_attr.device)
-            rc = lib.isg_tile_plan_edge_planes(self.ptr.data_ptr(), self.eptr.data_ptr(), self.B, key[0], key[1], tp.data_ptr(),
-                                               nt.data_ptr(), info.data_ptr(), cap, heavy.data_ptr(), _chk_rows(edge_attr, "edge_attr"),
-                                               edge_attr.stride(0), self.eid.data_ptr(), E, K, ep.planes.data_ptr(),
-                                               ep.inv.data_ptr(), _stream())
+            rc = lib.isg_tile_plan_edge_planes(self.ptr.data_ptr(), self.eptr.data_ptr(), self.B, key[0], key[1], t.tile_ptr.data_ptr(),
+                                               t.ntiles.data_ptr(), t.info.data_ptr(), t.cap, t.heavy.data_ptr(),
+                                               _chk_rows(edge_attr, "edge_attr"), edge_attr.stride(0), self.eid.data_ptr(), E, K,
+                                               ep.planes.data_ptr(), ep.inv.data_ptr(), _stream())
             if rc != ISG_EUNSUPPORTED:
                 _lib.check(rc, "isg_tile_plan_edge_planes")
-                if self._tiles is None:
-                    self._tiles = {}
-                self._tiles[key] = (tp, nt, cap, info.view(cap, 4), heavy.view(cap, 4))
-                self._edge_planes = _from_tensor(edge_attr, ep)
+                self._cache.tiles[key] = t
+                self._cache.edge_planes = _from_tensor(edge_attr, ep)
         return self.tiles(node_cap, edge_cap), self.edge_planes(edge_attr)
+
+    def _empty_tile_plan(self, lib, key: Tuple[int, int]) -> TilePlan:
+        """The unfilled TilePlan of caps `key`: one allocation, info first (16-byte aligned)."""
+        cap = int(lib.isg_tile_plan_capacity(self.N, self.E, self.B, key[0], key[1]))
+        buf = torch.empty(9 * cap + 8, dtype=torch.int32, device=self.ptr.device)
+        return TilePlan(buf[8 * cap + 4:9 * cap + 5], buf[9 * cap + 5:9 * cap + 6], cap, buf[:4 * cap].view(cap, 4),
+                        buf[4 * cap:8 * cap].view(cap, 4))
 
     def tiles_heavy_first(self, node_cap: int = 64, edge_cap: int = 0) -> Tensor:
         """tile_info of tiles(node_cap, edge_cap) ordered by descending CSR-slot count (32-slot classes, ties in tile order): the list
         the PERSISTENT tile kernels (isg_gatv2_layer_conv / _tile_conv: workgroup w takes entries w, w + G, ...) are handed, so that
         every workgroup gets one tile of each weight class per round -- the slowest workgroup's share of the work is 1.03x the mean
         instead of 1.06x at BASELINE configs[1] (tools/sim_tile_balance.py).  Any order gives the same results."""
-        self.tiles(node_cap, edge_cap)
-        hit = self._tiles[(int(node_cap), int(edge_cap))]
-        return hit[4] if CFG.tile_heavy_first else hit[3]
+        t = self._tile_plan(node_cap, edge_cap)
+        return t.heavy if CFG.tile_heavy_first else t.info
 
     def tiles(self, node_cap: int = 64, edge_cap: int = 0) -> Tuple[Tensor, Tensor, int, Tensor]:
         """(tile_ptr int32[cap + 1], ntiles int32[1] on the device, cap, tile_info int32[cap, 4]): consecutive graphs packed greedily into tiles of
@@ -422,23 +462,21 @@ class GraphPlan:
         (csrc/isg_layer_tile.hip).  Tile t owns graphs tile_ptr[t] .. tile_ptr[t + 1] and tile_info[t] = (first node, nodes,
         first CSR slot, CSR slots); the count stays on the device (no sync): kernels are launched with `cap` workgroups, the ones
         beyond *ntiles return at once, or walk the tiles persistently.  Built on first use."""
+        return self._tile_plan(node_cap, edge_cap)[:4]
+
+    def _tile_plan(self, node_cap: int, edge_cap: int) -> TilePlan:
         key = (int(node_cap), int(edge_cap))
-        if self._tiles is None:
-            self._tiles = {}
-        hit = self._tiles.get(key)
-        if hit is None:
+        t = self._cache.tiles.get(key)
+        if t is None:
             lib = _lib.load()
             if edge_cap > 0:
                 self.require_csr()
-            cap = int(lib.isg_tile_plan_capacity(self.N, self.E, self.B, key[0], key[1]))
-            buf = torch.empty(9 * cap + 8, dtype=torch.int32, device=self.ptr.device)     # info first: 16-byte aligned
-            info, heavy, tp, nt = buf[:4 * cap], buf[4 * cap:8 * cap], buf[8 * cap + 4:9 * cap + 5], buf[9 * cap + 5:9 * cap + 6]
+            t = self._empty_tile_plan(lib, key)
             _lib.check(lib.isg_tile_plan(self.ptr.data_ptr(), self.eptr.data_ptr() if edge_cap > 0 else 0, self.B, key[0],
-                                         key[1], tp.data_ptr(), nt.data_ptr(), info.data_ptr(), cap, heavy.data_ptr(), _stream()),
-                       "isg_tile_plan")
-            hit = (tp, nt, cap, info.view(cap, 4), heavy.view(cap, 4))
-            self._tiles[key] = hit
-        return hit[:4]
+                                         key[1], t.tile_ptr.data_ptr(), t.ntiles.data_ptr(), t.info.data_ptr(), t.cap,
+                                         t.heavy.data_ptr(), _stream()), "isg_tile_plan")
+            self._cache.tiles[key] = t
+        return t
 
     def tile_mode(self, node_cap: int = 64, edge_cap: int = 256) -> str:
         """How the graph-tile kernels (isg_gatv2_layer_conv / _tile_conv, isg_mgat_dense_tail, isg_readout_tile) can take this
@@ -456,7 +494,7 @@ class GraphPlan:
         if self.N < CFG.mixed_min_nodes:
             return "none"                   # decided before the device-to-host sync below: a small batch never pays for it
         key = ("tile_mode", node_cap, ecap, CFG.mixed_max_fraction)
-        hit = self.memo().get(key)
+        hit = self._memo.get(key)
         if hit is None:
             st = self._oversize_stats(node_cap, edge_cap)
             if st is None or st["stats"][0] == 0:
@@ -470,11 +508,9 @@ class GraphPlan:
         """How many graphs of the batch lie beyond a tile, with their node / edge totals and maxima: ONE device-to-host sync, paid
         only by batches whose bounds say there is such a graph; cached per (plan, caps)."""
         ecap = int(edge_cap) if self.rowptr is not None else 0
-        key = ("stats", int(node_cap), ecap)
-        if self._oversize is None:
-            self._oversize = {}
-        if key in self._oversize:
-            return self._oversize[key]
+        key = (int(node_cap), ecap)
+        if key in self._cache.oversize_stats:
+            return self._cache.oversize_stats[key]
         res = None
         if self.nmax > int(node_cap) or (ecap > 0 and self.emax > ecap):
             ptr = self.ptr.long()
@@ -511,7 +547,7 @@ class GraphPlan:
                     stats += [eb.sum(), eb.max()]
                 st = [int(v) for v in torch.stack(stats).tolist()]
             res = {"stats": st, "ptr": ptr, "n": n, "big": big, "eptr": eptr, "e": e}
-        self._oversize[key] = res
+        self._cache.oversize_stats[key] = res
         return res
 
     def oversize(self, node_cap: int = 64, edge_cap: int = 256) -> Optional["OversizeGraphs"]:
@@ -521,14 +557,11 @@ class GraphPlan:
         batches that have such graphs.  The reference puts no cap on the objects of a scene graph (datasets/scene_graph.py:199-389)."""
         ecap = int(edge_cap) if self.rowptr is not None else 0
         key = (int(node_cap), ecap)
-        if self._oversize is None:
-            self._oversize = {}
-        if key in self._oversize:
-            return self._oversize[key]
+        if key in self._cache.oversize:
+            return self._cache.oversize[key]
         res = None
         st = self._oversize_stats(node_cap, edge_cap)        # ONE device-to-host sync: how many such graphs, their nodes / edges
         if st is not None:
-            dev = self.ptr.device
             stats, ptr, n, big, eptr, e = st["stats"], st["ptr"], st["n"], st["big"], st["eptr"], st["e"]
             G = stats[0]
             if G > 0:
@@ -550,26 +583,19 @@ class GraphPlan:
                 own = self.graph_ids                        # a cut of a cut keeps the ORIGINAL batch's numbers
                 sub_plan.graph_ids = (gids if own is None else own.long()[gids]).to(torch.int32).contiguous()
                 res = OversizeGraphs(gids, nodes, edges, seg, sub_ei, sub_plan)
-        self._oversize[key] = res
+        self._cache.oversize[key] = res
         return res
 
     def source_csr(self) -> Tuple[Tensor, Tensor, Tensor]:
         """(rowptr_s[N+1], eid_s[E], dst_s[E]): out-edges of every node in edge-id order.  Only the backward of the
         message passing needs it (d x_l is a scatter by source), so it is built on first use."""
         self.require_csr()
-        if self._by_src is None:
-            lib = _lib.load()
-            dev = self.rowptr.device
-            flipped = self.edge_index.flip(0).contiguous()
-            rowptr_s = torch.empty(self.N + 1, dtype=torch.int32, device=dev)
-            eid_s = torch.empty(max(self.E, 1), dtype=torch.int32, device=dev)
-            dst_s = torch.empty(max(self.E, 1), dtype=torch.int32, device=dev)
-            ws_bytes = lib.isg_csr_workspace_bytes(self.N, self.E)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.isg_csr_build(flipped.data_ptr(), self.N, self.E, rowptr_s.data_ptr(), eid_s.data_ptr(),
-                                         dst_s.data_ptr(), 0, ws.data_ptr(), ws_bytes, _stream()), "isg_csr_build")
-            self._by_src = (rowptr_s, eid_s, dst_s)
-        return self._by_src
+        if self._cache.by_src is None:
+            sizes = (self.N + 1, max(self.E, 1), max(self.E, 1))
+            by_src = tuple(torch.empty(n, dtype=torch.int32, device=self.rowptr.device) for n in sizes)
+            _csr_build(_lib.load(), self.edge_index.flip(0).contiguous(), self.N, self.E, *by_src, None)
+            self._cache.by_src = by_src
+        return self._cache.by_src
 
     @staticmethod
     def build(batch: Tensor, edge_index: Optional[Tensor] = None, num_graphs: Optional[int] = None,
@@ -595,18 +621,21 @@ class GraphPlan:
             _chk(edge_index, "edge_index", torch.int64)
             if edge_index.dim() != 2 or edge_index.size(0) != 2:
                 raise ValueError(f"edge_index must be [2,E], got {tuple(edge_index.shape)}")
+        if edge_index is None or not CFG.plan_fused:        # (the fused plan kernel below makes ptr and the bounds itself)
+            bounds.zero_()
+            _lib.check(lib.isg_graph_ptr(batch.data_ptr(), N, B, ptr.data_ptr(), nmax_dev.data_ptr(), _stream()), "isg_graph_ptr")
+        if edge_index is not None:
             E = edge_index.size(1)
-            plan.E = E
-            plan.edge_index = edge_index
-            # one allocation for the five index arrays (rows 16-byte aligned), one for the workspace
+            plan.E, plan.edge_index = E, edge_index
+            # one allocation for the five index arrays (rows 16-byte aligned)
             n1, e1 = (N + 1 + 3) // 4 * 4, (max(E, 1) + 3) // 4 * 4
             idx = torch.empty(n1 + 3 * e1 + B + 1, dtype=torch.int32, device=dev)
             plan.rowptr, plan.eid = idx[:N + 1], idx[n1:n1 + max(E, 1)]
             plan.src, plan.dst = idx[n1 + e1:n1 + e1 + max(E, 1)], idx[n1 + 2 * e1:n1 + 2 * e1 + max(E, 1)]
             plan.eptr = idx[n1 + 3 * e1:n1 + 3 * e1 + B + 1]
-            ws_bytes = lib.isg_csr_workspace_bytes(N, E)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             if CFG.plan_fused:
+                ws_bytes = lib.isg_csr_workspace_bytes(N, E)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
                 # hinted and eager: the plan's last kernel stores the bounds into pinned host memory itself (no copy in the stream)
                 if max_nodes is not None and max_edges is not None and CFG.bounds_to_host:
                     if not torch.cuda.is_current_stream_capturing():
@@ -620,18 +649,9 @@ class GraphPlan:
                                                     plan.src.data_ptr(), plan.dst.data_ptr(), plan.eptr.data_ptr(), ws.data_ptr(),
                                                     ws_bytes, _stream()), "isg_graph_plan_build")
             else:
-                bounds.zero_()
-                _lib.check(lib.isg_graph_ptr(batch.data_ptr(), N, B, ptr.data_ptr(), nmax_dev.data_ptr(), _stream()),
-                           "isg_graph_ptr")
-                _lib.check(lib.isg_csr_build(edge_index.data_ptr(), N, E, plan.rowptr.data_ptr(), plan.eid.data_ptr(),
-                                             plan.src.data_ptr(), plan.dst.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
-                           "isg_csr_build")
+                _csr_build(lib, edge_index, N, E, plan.rowptr, plan.eid, plan.src, plan.dst)
                 _lib.check(lib.isg_graph_edge_ptr(ptr.data_ptr(), plan.rowptr.data_ptr(), B, plan.eptr.data_ptr(),
                                                   bounds[1:].data_ptr(), _stream()), "isg_graph_edge_ptr")
-        else:
-            bounds.zero_()
-            _lib.check(lib.isg_graph_ptr(batch.data_ptr(), N, B, ptr.data_ptr(), nmax_dev.data_ptr(), _stream()),
-                       "isg_graph_ptr")
         if max_nodes is None or (edge_index is not None and max_edges is None):
             got = bounds.tolist()                   # one D2H sync per batch (to_dense_batch syncs per layer)
             max_nodes = got[0] if max_nodes is None else max(int(max_nodes), got[0])
@@ -665,14 +685,9 @@ class GraphPlan:
     def verify_hints(self) -> None:
         """For a plan built inside a hipGraph capture: compare the hints with the bounds the LAST replay computed (one
         device->host sync).  Raises IsgError like check_plans(); a no-op for plans built eagerly (those are verified there)."""
-        b = getattr(self, "_bounds_dev", None)
-        if b is None:
-            return
-        n_true, e_true = (int(v) for v in b.tolist())
-        hn, he = self._hints
-        if n_true > hn or (he is not None and e_true > he):
-            raise _lib.IsgError(f"GraphPlan hints understate the batch: max_nodes={hn} / max_edges={he} given, but a graph "
-                                f"has {n_true} nodes / {e_true} edges; results of that replay are invalid")
+        err = None if self._bounds_dev is None else _hint_error(self._bounds_dev.tolist(), self._hints, "that replay")
+        if err is not None:
+            raise err
 
     @staticmethod
     def edges_only(edge_index: Tensor, num_nodes: int) -> "GraphPlan":
@@ -685,18 +700,15 @@ class GraphPlan:
         plan.rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
         plan.eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
         plan.src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        ws_bytes = lib.isg_csr_workspace_bytes(N, E)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.isg_csr_build(edge_index.data_ptr(), N, E, plan.rowptr.data_ptr(), plan.eid.data_ptr(),
-                                     plan.src.data_ptr(), 0, ws.data_ptr(), ws_bytes, _stream()), "isg_csr_build")
+        _csr_build(lib, edge_index, N, E, plan.rowptr, plan.eid, plan.src, None)
         return plan
 
     def dense_slots(self) -> Tensor:
         """Position of every node in the padded [B * nmax] layout of to_dense_batch (int64 [N])."""
-        if self._slots is None:
+        if self._cache.slots is None:
             b = self.batch
-            self._slots = b * self.nmax + (torch.arange(self.N, device=b.device) - self.ptr.long()[b])
-        return self._slots
+            self._cache.slots = b * self.nmax + (torch.arange(self.N, device=b.device) - self.ptr.long()[b])
+        return self._cache.slots
 
     def require_csr(self) -> None:
         if self.rowptr is None:
@@ -1132,14 +1144,12 @@ class StepCapture:
         plan, host = ent["plan"], ent["host"]
         if plan is None or host is None or not ent["event"].query():
             return                                      # the last replay has not finished: its bounds stay in the running maximum
-        n_true, e_true = int(host[0]), int(host[1])     # the largest of every replay since the capture (or the last raise)
-        hn, he = plan._hints
-        if n_true > hn or (he is not None and e_true > he):
+        # `host` holds the largest of every replay since the capture (or the last raise)
+        err = _hint_error(host.tolist(), plan._hints, f"a recent replay (the capture of {ent['what']!r})")
+        if err is not None:
             ent["max"].zero_()                          # reported once: the running maximum starts over (in stream order; no
             host.zero_()                                # replay is in flight: the event has completed)
-            raise _lib.IsgError(f"GraphPlan hints understate the batch: max_nodes={hn} / max_edges={he} given, but a graph of a "
-                                f"recent replay has {n_true} nodes / {e_true} edges; results of that replay are invalid "
-                                f"(the capture of {ent['what']!r})")
+            raise err
 
     def _retire(self, key) -> None:
         """Drop an entry (its hipGraph and private allocator pool); its replays' bounds are compared first, none is lost: this
@@ -1176,7 +1186,7 @@ class StepCapture:
                     outs, plan = fn(*static)
             finally:
                 _CAPTURE_BOUNDS.pop()
-            if plan is not None and getattr(plan, "_bounds_host", None) is None:
+            if plan is not None and plan._bounds_host is None:
                 host = None                            # (a plan without an edge list / without both hints keeps its bounds on the device)
             ent = {"graph": graph, "static": static, "outs": outs, "plan": plan, "host": host, "max": running, "event": torch.cuda.Event(),
                    "stamp": stamp, "what": key_extra}
@@ -1335,20 +1345,9 @@ def run_split(plan: "GraphPlan", sub: "OversizeGraphs", core, x: Tensor, edge_in
         return core(xs, sub.edge_index, es, sub.batch, instr_s, glf_s, sub.plan, nz_s, seed, gate_s)
 
     def run_main():
-        # the SAME tensors and caches, its own `holes`: the caller's plan is not written to, and a second run_split on it (another
-        # thread, a re-entrant core) sees none.  The lazily created cache containers are made on `plan` BEFORE the copy, so that
-        # what the main pass builds (tiles, edge planes, memo) lands where the caller's plan finds it again
-        if plan._tiles is None:
-            plan._tiles = {}
-        if plan._oversize is None:
-            plan._oversize = {}
-        plan.memo()
-        holed = copy.copy(plan)
-        holed.holes = sub
-        holed._memo = {}               # (a layer's route depends on `holes`: the holed plan answers for itself)
-        res = core(x, edge_index, edge_attr, batch, instr, glf, holed, noises, seed, None)
-        plan._edge_planes = holed._edge_planes          # (a tuple, not a container: handed back)
-        return res
+        # a view with its own `holes`: the caller's plan is not written to, and a second run_split on it (another thread, a
+        # re-entrant core) sees none; what the pass builds lazily lands in the cache both share, where the caller's plan finds it
+        return core(x, edge_index, edge_attr, batch, instr, glf, plan.with_holes(sub), noises, seed, None)
 
     if CFG.split_stream and x.is_cuda and not torch.cuda.is_current_stream_capturing():
         # The sub-batch is a chain of ~60 launches of one or a few workgroups each (0.65 ms of GPU time for ONE 100-node graph):
@@ -1394,10 +1393,11 @@ def _oversize_conv(sub: "OversizeGraphs", x_l: Tensor, x_r: Tensor, edge_attr: T
     """Message passing of the graphs the tile kernels passed over (mgat_v2_conv.py:215-279 on the sub-batch): lin_edge +
     the per-graph kernel (256-node / 1024-edge tables, or node chunks beyond), written into the rows / edges of `out` /
     `alpha` / `rowmax` that belong to those graphs."""
-    rows = _if_from_tensor(getattr(sub.plan, "_parent_edge_rows", None), edge_attr)      # every layer reads the same edge features
+    cache = sub.plan._cache
+    rows = _if_from_tensor(cache.parent_edge_rows, edge_attr)      # every layer reads the same edge features
     if rows is None:
         rows = edge_attr.index_select(0, sub.edges)
-        sub.plan._parent_edge_rows = _from_tensor(edge_attr, rows)
+        cache.parent_edge_rows = _from_tensor(edge_attr, rows)
     e_proj = linear(rows, w_edge)
     nm = None if node_mask is None else node_mask.reshape(-1).index_select(0, sub.nodes)
     em = None if edge_mask is None else edge_mask.reshape(-1).index_select(0, sub.edges)

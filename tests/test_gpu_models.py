@@ -1137,6 +1137,47 @@ def test_split_forward_variants_agree(dev):
     assert torch.equal(m, m0) and (l - l0).abs().max() < 2e-5 and torch.allclose(g, g0, atol=1e-6)
 
 
+def test_split_forward_leaves_what_it_built_on_the_callers_plan(dev):
+    """ops.run_split's tile pass runs on a view of the caller's plan (GraphPlan.with_holes): the plan itself is never written
+    to, and what the pass builds lazily -- the (64, 256) tile plan, the edge planes -- lands in the cache both share, so a second
+    forward with the same plan builds nothing again and gives the bits of the first, and of a forward that builds its own plan.
+    Graphs exactly at the 64-node cap, one past it, far past it, and of a single node."""
+    from isubgvqa_amd import ops, synthetic
+    sizes = (20, 64, 65, 1, 20, 130, 20, 20)
+    cfg = synthetic.WorkloadConfig(num_graphs=len(sizes), sizes=sizes, sampler="imle")
+    wl = synthetic.make_workload(cfg).to(dev)
+    model = synthetic.build_answer_model(cfg).eval().to(dev)
+    P = ops.GraphPlan.build(wl.batch, wl.edge_index, num_graphs=wl.num_graphs, max_nodes=wl.max_nodes, max_edges=wl.max_edges,
+                            graph_sizes=wl.graph_sizes)
+    key = (ops.TILE_CONV_NODES, ops.TILE_CONV_EDGES)
+    assert key == (64, 256) and key not in P._cache.tiles and P._cache.edge_planes is None
+    seen = {}
+
+    def three():
+        ops.reset_counters()
+        first = model(wl, plan=P)
+        seen["counters"] = ops.counters()
+        seen["tiles"], seen["had_planes"] = P._cache.tiles.get(key), P._cache.edge_planes is not None
+        seen["tile_ptr"], seen["planes"] = P.tiles(*key)[0], P.edge_planes(wl.edge_attr)[0].data_ptr()
+        return first, model(wl, plan=P), model(wl, plan=None)
+
+    with torch.no_grad():
+        outs = _forced_mixed(three)
+    torch.cuda.synchronize()
+    c = seen["counters"]
+    assert c["tile_nodes"] > 0 and c["oversize_nodes"] > 0, c
+    assert P.holes is None
+    assert isinstance(seen["tiles"], ops.TilePlan), "the tile plan the holed pass built is not on the caller's plan"
+    assert seen["had_planes"], "the edge planes the holed pass built are not on the caller's plan"
+    assert P.tiles(*key)[0] is seen["tile_ptr"] is seen["tiles"].tile_ptr
+    assert P.edge_planes(wl.edge_attr)[0].data_ptr() == seen["planes"]
+    (l0, m0, g0) = outs[0]
+    assert torch.isfinite(l0).all()
+    for name, (l, m, g) in zip(("the same plan again", "a plan of its own"), outs[1:]):
+        assert torch.equal(l, l0) and torch.equal(m, m0) and torch.equal(g, g0), name
+    ops.check_plans()
+
+
 def test_split_forward_on_a_cold_weight_cache_matches_the_inline_pass(dev):
     """run_split's two passes share the weight caches (planes of w_edge / x_proj / node_nn, the concatenated lin_l |
     lin_r, the derived layouts).  On the FIRST mixed batch after a model load every entry is built by whichever pass asks first, on

@@ -636,6 +636,67 @@ def test_conv_route_memo_is_per_plan_and_follows_the_switches():
         assert conv.route(_StubPlan(mode="none"), 128, ea).conv == "pair" and conv.route(plan, 128, ea) is again
 
 
+def _hand_plan():
+    """A GraphPlan of two graphs (3 and 4 nodes) from CPU tensors: nothing here touches the library."""
+    from isubgvqa_amd import ops
+    batch = torch.tensor([0, 0, 0, 1, 1, 1, 1])
+    ei = torch.tensor([[0, 1, 3, 4, 5], [1, 2, 4, 5, 6]])
+    return ops.GraphPlan(N=7, E=5, B=2, ptr=torch.tensor([0, 3, 7], dtype=torch.int32), nmax_dev=torch.zeros(1, dtype=torch.int32),
+                         nmax=4, emax=3, batch=batch, edge_index=ei)
+
+
+def test_graph_plan_takes_no_attribute_it_does_not_declare():
+    """A lazily built member goes into the plan's cache object, a new fact into a declared field: a misspelt or forgotten name
+    raises instead of riding along unseen.  The cache object is closed in the same way."""
+    p = _hand_plan()
+    for name in ("_bound_dev", "_tiles", "_parent_edge_rows", "anything"):
+        with pytest.raises(AttributeError):
+            setattr(p, name, None)
+    with pytest.raises(AttributeError):
+        p._cache.tile = {}
+    assert p._bounds_dev is None and p._bounds_host is None and p._hints is None       # declared, unset outside a capture
+    p._hints = (4, 3)
+    p.verify_hints()                                                                   # no bounds on the device: nothing to compare
+
+
+def test_graph_plan_with_holes_is_a_view_that_shares_the_cache():
+    """GraphPlan.with_holes(sub) -- the plan run_split hands its tile pass: a new plan, equal field for field, with `holes` = sub,
+    an empty memo of its own and the SAME cache object, so that what the pass builds lazily the caller's plan finds again; the
+    caller's plan is not written to."""
+    import dataclasses
+    from isubgvqa_amd import ops
+    p = _hand_plan()
+    p.memo()["asked"] = 1
+    sub = ops.OversizeGraphs(torch.tensor([1]), torch.arange(3, 7), None, torch.zeros(4, dtype=torch.long), None, _hand_plan())
+    v = p.with_holes(sub)
+    assert v is not p and type(v) is ops.GraphPlan
+    assert v.holes is sub and p.holes is None
+    assert v._cache is p._cache and isinstance(p._cache, ops._PlanCache)
+    assert v.memo() == {} and v.memo() is not p.memo() and p.memo() == {"asked": 1}
+    names = [f.name for f in dataclasses.fields(ops.GraphPlan)]
+    assert "holes" in names and "_memo" in names and "_cache" in names
+    for name in names:
+        if name not in ("holes", "_memo"):
+            assert getattr(v, name) is getattr(p, name), name
+    # a tile plan in the cache answers both, without the library (these CPU tensors could not be handed to it)
+    t = ops.TilePlan(torch.tensor([0, 1, 2], dtype=torch.int32), torch.tensor([2], dtype=torch.int32), 2,
+                     torch.zeros(2, 4, dtype=torch.int32), torch.ones(2, 4, dtype=torch.int32))
+    p._cache.tiles[(64, 256)] = t
+    for plan in (p, v):
+        got = plan.tiles(64, 256)
+        assert type(got) is tuple and len(got) == 4 and all(a is b for a, b in zip(got, t[:4]))
+        assert plan.tiles_heavy_first(64, 256) is t.heavy
+        with ops.configured(tile_heavy_first=False):
+            assert plan.tiles_heavy_first(64, 256) is t.info
+    # what the view adds, the caller's plan sees -- and a view of the view too
+    t2 = t._replace(cap=3)
+    v._cache.tiles[(64, 0)] = t2
+    slots = v.dense_slots()
+    assert p.tiles(64, 0)[2] == 3 and p.dense_slots() is slots and slots.tolist() == [0, 1, 2, 4, 5, 6, 7]
+    assert v.with_holes(sub)._cache is p._cache and p.holes is None and p.memo() == {"asked": 1}
+    assert _hand_plan()._cache is not p._cache and _hand_plan().memo() is not p.memo()      # per plan, not per class
+
+
 def test_linear_relu_and_gelu_are_exclusive_at_every_size():
     from isubgvqa_amd import ops
     for M in (0, 12, 1024, 5000):

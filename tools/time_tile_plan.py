@@ -17,7 +17,8 @@ for heavy in (True, False, True, False):
     ops.TILE_HEAVY_FIRST = heavy
     ts = []
     for r in range(30):
-        plan._tiles, plan._edge_planes = None, None
+        plan._cache.tiles.clear()
+        plan._cache.edge_planes = None
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         plan.tiles_and_edge_planes(wl.edge_attr, ops.TILE_CONV_NODES, ops.TILE_CONV_EDGES)
@@ -44,12 +45,12 @@ def timed(fn, n=30):
 
 
 def plan_alone():
-    plan._tiles = None
+    plan._cache.tiles.clear()
     plan.tiles(ops.TILE_CONV_NODES, ops.TILE_CONV_EDGES)
 
 
 def planes_alone():
-    plan._edge_planes = None
+    plan._cache.edge_planes = None
     plan.edge_planes(wl.edge_attr)
 
 
