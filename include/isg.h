@@ -716,6 +716,45 @@ int isg_subgraph_cut(const float *node_mask, float threshold, int32_t complement
                      int64_t *edge_id, int64_t *edge_index_out, int64_t *batch_out, int32_t *ptr_out, int32_t *sel,
                      int32_t table_k, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring the explanations: token co-occurrence
+ * ------------------------------------------------------------------------------------------- */
+#define ISG_COO_TOKENS_MAX 128                       /* question words / text tokens per question            */
+#define ISG_COO_TOTALS (16 + 4 * (ISG_COO_TOKENS_MAX + 1)) /* int64 entries of the running totals                  */
+
+/* Token co-occurrence of a whole batch on the device: what the reference's interpretability experiment scores one question per
+ * forward on the host, over Python lists of strings (run_token_coo.py:145-173, utils/token_coo_fns.py).  Strings are vocabulary
+ * ids here (the host tables are built once per evaluation); all integer and exact.  For question g over its nodes
+ * [ptr[g], ptr[g+1]):
+ *   kept(n)     = node_mask[n] > threshold                 (a NaN is not kept, as in isg_subgraph_cut)
+ *   in_graph(v) = v >= 0 && some node has name v;   in_kept(v) = v >= 0 && some kept node has name v
+ *   p = ans_sg[pred[g]] if 0 <= pred[g] < A, else -1;   l = the same for label[g]
+ * table int32 [B, 8], row g:
+ *   0  pred[g] == label[g]          1  in_graph(p)          2  in_graph(l)          3  in_kept(p)
+ *   4  number of t < T with in_graph(qtok[g, t]) (a repeated word counts each time)    5  the same with in_kept
+ *   6  number of t < T2 with tkeep[g, t] == 1.0f && in_graph(ttok[g, t])               7  the same with in_kept
+ * totals int64 [ISG_COO_TOTALS], or NULL: the call ADDS this batch (zero it once per evaluation).  With correct = col 0,
+ * color = qflags[g] & 1, ans_valid = correct & col 2 & !color, qst_valid = correct & col 4 > 0, text_valid = correct & col 6 > 0:
+ *   [0] questions  [1] correct  [2] col 1  [3] correct & col 1  [4] ans_valid  [5] ans_valid & col 3
+ *   [6] qst_valid  [7] sum of col 4 over qst_valid  [8] sum of col 5 over qst_valid
+ *   [9] text_valid  [10] sum of col 6 over text_valid  [11] sum of col 7 over text_valid  [12..15] reserved, never written
+ *   then four histograms of ISG_COO_TOKENS_MAX + 1 entries indexed by the match count m: questions with col 4 == m among
+ *   qst_valid, the sum of col 5 over those, and the same pair for col 6 / col 7 among text_valid -- the mean of the per-question
+ *   ratios is sum_m H[m] / m on the host, with no floating-point sum on the device.
+ * names int64: node n's name id is names[n * name_stride] (x[N, 4] as it is, with stride 4); node_mask fp32 [N]; ptr int32 [B+1]
+ * (isg_graph_ptr); pred, label int64 [B]; ans_sg int32 [A]: answer class -> vocabulary id, -1 when the answer string is no
+ * vocabulary token; qtok int32 [B, T]: question words as vocabulary ids, -1 for none / pad (NULL when T == 0); qflags int32 [B],
+ * bit 0 = the raw question contains "color" (optional: NULL = all 0); ttok int32 [B, T2] and tkeep fp32 [B, T2]: the text
+ * explanation's tokens as vocabulary ids and its mask (both NULL when T2 == 0).
+ * Two launches (one when totals is NULL): one wave per question, the graph's names staged in LDS COO_NODE_CHUNK = 256 at a time;
+ * then one workgroup adds the table to totals.  No atomics on global memory: the outputs are a function of the inputs.
+ * ISG_EINVAL for a null required pointer, a negative size or name_stride < 1, before any HIP call; ISG_EUNSUPPORTED when T or
+ * T2 exceeds ISG_COO_TOKENS_MAX or N, B, A or name_stride does not fit int32 (the int64 sums cannot overflow below that). */
+int isg_token_coo(const int64_t *names, int64_t name_stride, const float *node_mask, float threshold, const int32_t *ptr,
+                  const int64_t *pred, const int64_t *label, const int32_t *ans_sg, const int32_t *qtok, const int32_t *qflags,
+                  const int32_t *ttok, const float *tkeep, int64_t N, int64_t B, int64_t A, int32_t T, int32_t T2,
+                  int32_t *table, int64_t *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,11 +5,18 @@ induced subgraph of the whole batch on the device; this module carries a batch a
 questions an intrinsic explanation has to answer (the reference evaluates them one question per forward, on the host:
 run_token_coo.py:65-173): does the subgraph ALONE still give the answer (fid_minus: sufficiency), and does the answer go away
 when the subgraph is REMOVED (fid_plus: necessity).
+
+The reference's third question is lexical (run_token_coo.py:145-185, utils/token_coo_fns.py): is the answer's name among the picked
+nodes, and how many of the question's words that name an object of the graph were picked.  `TokenTables` turns the strings into
+vocabulary ids once, `ops.token_coo` scores whole batches on the device into running totals, `CooReport` reads them -- the one
+device-to-host copy of an evaluation (`evaluate`).
 """
 from __future__ import annotations
 
 import argparse
-from typing import Dict, NamedTuple, Optional
+import math
+from dataclasses import dataclass
+from typing import Dict, Iterable, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -116,3 +123,121 @@ def faithfulness(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, s
         scores = fidelity_scores(logits, outs[0], outs[1], emptied)
         scores = scores._replace(fid_minus=torch.where(kept_none, torch.full_like(scores.p, float("nan")), scores.fid_minus))
     return Faithfulness(scores, logits, outs[0], outs[1], mask, kept_none, cuts[0], cuts[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Token co-occurrence
+# ---------------------------------------------------------------------------------------------------------------------
+class TokenTables:
+    """The strings of the reference's scoring as scene-graph vocabulary ids.  `stoi`: loader.SceneGraphVocab.get_stoi();
+    `answers`: the answer strings by class (label2ans); `clip_itos`: the question tokenizer's tokens by id, for the text
+    explanation (their `</w>` is stripped as at run_token_coo.py:83-85).  A string that is no vocabulary token maps to -1."""
+
+    def __init__(self, stoi: Mapping[str, int], answers: Sequence[str], clip_itos: Optional[Sequence[str]] = None):
+        self.stoi = dict(stoi)
+        ids = lambda strings: torch.tensor([self.stoi.get(s, -1) for s in strings], dtype=torch.int32)
+        self.ans_sg = ids(answers)
+        self.clip_sg = None if clip_itos is None else ids([clip_itos[i].replace("</w>", "") for i in range(len(clip_itos))])
+        self._on: Dict[Tuple[str, torch.device], Tensor] = {}
+
+    def on(self, name: str, device) -> Tensor:
+        """ans_sg / clip_sg on `device` (copied there once)."""
+        key = (name, torch.device(device))
+        if key not in self._on:
+            self._on[key] = getattr(self, name).to(device)
+        return self._on[key]
+
+    def question_words(self, questions: Sequence[str], device=None) -> Tuple[Tensor, Tensor]:
+        """(qtok int32 [B, T], qflags int32 [B]) of raw question strings: the words of `q.split("?")[0].lower().split(" ")`
+        (token_coo_fns.py:15 -- an empty word between two spaces is a word) as vocabulary ids, padded with -1 to the longest
+        question; bit 0 of qflags is `"color" in q` (token_coo_fns.py:8, on the raw string)."""
+        words = [[self.stoi.get(w, -1) for w in q.split("?")[0].lower().split(" ")] for q in questions]
+        T = max((len(w) for w in words), default=0)
+        qtok = torch.tensor([w + [-1] * (T - len(w)) for w in words], dtype=torch.int32).view(len(words), T)
+        qflags = torch.tensor([int("color" in q) for q in questions], dtype=torch.int32)
+        return (qtok, qflags) if device is None else (qtok.to(device), qflags.to(device))
+
+    def text_tokens(self, input_ids: Tensor) -> Tensor:
+        """clip_sg[input_ids]: the question's tokens as vocabulary ids (int32, on input_ids' device)."""
+        if self.clip_sg is None:
+            raise ValueError("TokenTables was built without clip_itos")
+        return self.on("clip_sg", input_ids.device)[input_ids.long()].contiguous()
+
+
+def _mean(num: float, den: float) -> float:
+    return num / den if den else float("nan")
+
+
+@dataclass(frozen=True)
+class CooReport:
+    """The figures of run_token_coo.py:181-185 from isg_token_coo's running totals.  The fields are plain means over the
+    questions that have the quantity (NaN when none has); as_printed_by_reference() gives what the script prints."""
+    totals: Tuple[int, ...]
+    accuracy: float            # correct / questions
+    accuracy_at: float         # ... among the questions whose predicted answer names a node of the graph
+    ans_tok_coo: float         # the answer's name is among the picked nodes; over correct, non-"color" questions whose answer names a node
+    qst_tok_coo: float         # mean over correct questions of (question words naming a picked node / naming a node)
+    text_tok_coo: float        # the same over the kept tokens of the text explanation
+
+    @staticmethod
+    def _ratio_sum(totals: Sequence[int], which: int) -> float:
+        """Sum of the per-question ratios hits / m from the histogram pair `which` (0 question words, 1 text tokens)."""
+        H = ops.COO_TOKENS_MAX + 1
+        hits = totals[16 + (2 * which + 1) * H:16 + (2 * which + 2) * H]
+        return math.fsum(h / m for m, h in enumerate(hits) if m > 0 and h)
+
+    @classmethod
+    def from_totals(cls, totals: Tensor) -> "CooReport":
+        t = tuple(int(v) for v in totals.tolist())          # an evaluation's one device-to-host copy
+        if len(t) != ops.COO_TOTALS:
+            raise ValueError(f"totals: expected {ops.COO_TOTALS} entries, got {len(t)}")
+        return cls(t, _mean(t[1], t[0]), _mean(t[3], t[2]), _mean(t[5], t[4]), _mean(cls._ratio_sum(t, 0), t[6]),
+                   _mean(cls._ratio_sum(t, 1), t[9]))
+
+    def as_printed_by_reference(self) -> Dict[str, float]:
+        """The five printed figures.  The script's np.nanmean runs over lists of (value, count) TUPLES for the answer and the
+        question words, so both columns enter the mean: a hit contributes 1 + 1 over two entries, a miss 0 + 0 over two, a NaN
+        question its count 0 over one; the text figure is a list of scalars and stays the plain mean."""
+        t = self.totals
+        return {"Accuracy": self.accuracy, "Accuracy AT": self.accuracy_at, "Ans. Tok. Coo": _mean(2 * t[5], t[4] + t[1]),
+                "Qst. Tok. Coo": _mean(self._ratio_sum(t, 0) + t[7], t[6] + t[1]), "Qst. Text Tok. Coo": self.text_tok_coo}
+
+
+class EvalBatch(NamedTuple):
+    inputs: object                     # synthetic.FullWorkload (or any object with its fields and scene_graphs()), or a Workload
+    label: Tensor                      # int64 [B], on the device
+    qtok: Optional[Tensor] = None      # TokenTables.question_words(...) on the device
+    qflags: Optional[Tensor] = None
+    names: Optional[Tensor] = None     # int64 [N] name ids; default inputs.x[:, 0]
+
+
+def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0) -> CooReport:
+    """run_token_coo.py's experiment over whole batches: forward, argmax, ops.token_coo into ONE running totals tensor; nothing is
+    copied to the host before the last batch has been queued.  With --text_sampling the forward's token mask is scored against
+    tables.clip_sg."""
+    full = not isinstance(model, synthetic.AnswerModel)
+    totals = None
+    with torch.no_grad():
+        for b in batches:
+            inp = b.inputs
+            B = int(inp.questions.size(0) if full else inp.glf.size(0))
+            plan = ops.GraphPlan.build(inp.batch, inp.edge_index, num_graphs=B, max_nodes=inp.max_nodes or None,
+                                       max_edges=inp.max_edges or None, graph_sizes=inp.graph_sizes)
+            if full:
+                out = model(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.questions, inp.att_mask, return_masks=True,
+                            scene_graphs=inp.scene_graphs(), plan=plan)
+            else:
+                out = model(inp, plan=plan)
+            logits, mask = out[0], out[1]
+            mask_text = out[4] if full and len(out) > 4 else None
+            if totals is None:
+                totals = torch.zeros(ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
+            ttok = tkeep = None
+            if mask_text is not None:
+                ttok = tables.text_tokens(inp.questions)
+                tkeep = mask_text.reshape(B, -1).float().contiguous()
+            ops.token_coo(inp.x[:, 0] if b.names is None else b.names, mask, plan, logits.argmax(dim=1), b.label,
+                          tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
+    if totals is None:
+        totals = torch.zeros(ops.COO_TOTALS, dtype=torch.int64)
+    return CooReport.from_totals(totals)

@@ -839,6 +839,57 @@ def subgraph_cut(node_mask: Tensor, edge_index: Tensor, plan: "GraphPlan", thres
 
 
 # ------------------------------------------------------------------------------------------------
+# Scoring the explanations: token co-occurrence
+# ------------------------------------------------------------------------------------------------
+COO_TOKENS_MAX = 128       # question words / text tokens per question (ISG_COO_TOKENS_MAX in include/isg.h)
+COO_TOTALS = 16 + 4 * (COO_TOKENS_MAX + 1)      # int64 entries of the running totals (ISG_COO_TOTALS)
+COO_NODE_CHUNK = 256       # nodes of a graph isg_token_coo stages in LDS per pass (COO_NODE_CHUNK in csrc/isg_token_coo.hip)
+
+
+class TokenCoo(NamedTuple):
+    table: Tensor                # int32 [B, 8]: the row of every question (include/isg.h, isg_token_coo)
+    totals: Optional[Tensor]     # int64 [COO_TOTALS]: the caller's running totals with this batch added, or None
+
+
+def token_coo(names: Tensor, node_mask: Tensor, plan: "GraphPlan", pred: Tensor, label: Tensor, ans_sg: Tensor,
+              qtok: Optional[Tensor] = None, qflags: Optional[Tensor] = None, ttok: Optional[Tensor] = None,
+              tkeep: Optional[Tensor] = None, threshold: float = 0.0, totals: Optional[Tensor] = None) -> TokenCoo:
+    """Token co-occurrence of a batch on the device (isg_token_coo: two launches, one without totals; no sync, no copy).
+    names int64 [N], possibly a strided column such as x[:, 0]; node_mask fp32 [N] or [N, 1] (a forward's imle_mask); pred, label
+    int64 [B]; ans_sg int32 [A]; qtok int32 [B, T], qflags int32 [B], ttok int32 [B, T2] with tkeep fp32 [B, T2] (both or neither).
+    `totals` (int64 [COO_TOTALS], zeroed by the caller once per evaluation) has this batch ADDED to it."""
+    lib = _lib.load()
+    if (ttok is None) != (tkeep is None):
+        raise ValueError("ttok and tkeep come together")
+    if node_mask.dim() == 2 and node_mask.size(1) == 1:
+        node_mask = node_mask.squeeze(1)
+    N, B = plan.N, plan.B
+    p_mask = _chk(node_mask, "node_mask", torch.float32, (N,))
+    if names.dim() != 1 or names.numel() != N or names.dtype != torch.int64:
+        raise ValueError(f"names: expected int64 [{N}] (a strided column is fine), got {names.dtype} {tuple(names.shape)}")
+    if not names.is_cuda:
+        raise _lib.IsgError(f"names must live on the GPU (got {names.device}); this path has no CPU fallback")
+    stride = names.stride(0) if N > 1 else 1
+    if stride < 1:
+        raise ValueError(f"names: stride {stride}")
+    T = 0 if qtok is None else (qtok.size(1) if qtok.dim() == 2 else -1)
+    T2 = 0 if ttok is None else (ttok.size(1) if ttok.dim() == 2 else -1)
+    if T < 0 or T2 < 0:
+        raise ValueError("qtok / ttok must be [B, T]")
+    p_qtok = _chk(qtok, "qtok", torch.int32, (B, T), optional=True)
+    p_ttok = _chk(ttok, "ttok", torch.int32, (B, T2), optional=True)
+    p_tkeep = _chk(tkeep, "tkeep", torch.float32, (B, T2), optional=True)
+    table = torch.empty(B, 8, dtype=torch.int32, device=node_mask.device)
+    _lib.check(lib.isg_token_coo(names.data_ptr(), stride, p_mask, float(threshold), _chk(plan.ptr, "plan.ptr", torch.int32, (B + 1,)),
+                                 _chk(pred, "pred", torch.int64, (B,)), _chk(label, "label", torch.int64, (B,)),
+                                 _chk(ans_sg, "ans_sg", torch.int32, (ans_sg.numel(),)), p_qtok,
+                                 _chk(qflags, "qflags", torch.int32, (B,), optional=True), p_ttok, p_tkeep, N, B, ans_sg.numel(),
+                                 T, T2, table.data_ptr(), _chk(totals, "totals", torch.int64, (COO_TOTALS,), optional=True),
+                                 _stream()), "isg_token_coo")
+    return TokenCoo(table, totals)
+
+
+# ------------------------------------------------------------------------------------------------
 # Message passing
 # ------------------------------------------------------------------------------------------------
 def instr_gate(x: Tensor, instr: Tensor, batch: Tensor, plan: Optional["GraphPlan"] = None) -> Tensor:
