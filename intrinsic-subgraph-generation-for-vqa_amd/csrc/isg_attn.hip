@@ -176,8 +176,8 @@ __global__ __launch_bounds__(64 * NW) void mha_small_kernel(MhaArgs a) {
 // ((v - mean) * rstd * gamma + beta, biased variance, fp32): the post-norm steps of nn.TransformerEncoderLayer /
 // DecoderLayer (question_encoder.py:20-38, question_decoder.py:25-71) with the residual add folded in, and the row's
 // largest |out| written beside it -- the row scale of the fp16 three-product Linear that reads `out` next, so that
-// Linear needs no pass of its own over its input.  Wave per row, the row in registers (NV float4 per lane), mean and
-// centred variance as two wave sums.
+// Linear needs no pass of its own over its input.  Wave per row, the row in registers (NV float4 per lane), mean, the
+// residue of the centred values and their variance as three wave sums.
 template <int NV>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ r,
                                                             const float *__restrict__ gamma,
@@ -204,12 +204,24 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restr
     }
   }
   const float mean = wave_sum(sum) / (float)D;
+  // A row whose mean is large beside its spread (1000 + N(0, 1)): the fp32 sum and the rounding of `mean` itself leave up to an
+  // ulp of the MEAN in every centred value (4e-5 of the largest output at D = 300).  The centred values are small and nearly
+  // exact, so their own mean is that residue: it is taken out once more, and the row holds v - mean from here on.
+  float res = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (lane + 64 * i < nv) {
+      v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
+      res += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+  }
+  res = wave_sum(res) / (float)D;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     if (lane + 64 * i < nv) {
-      const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-      sq += (a * a + b * b) + (c * c + d * d);
+      v[i].x -= res; v[i].y -= res; v[i].z -= res; v[i].w -= res;
+      sq += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)D + eps);
@@ -221,10 +233,10 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restr
       const float4 g = reinterpret_cast<const float4 *>(gamma)[c];
       const float4 bb = beta ? reinterpret_cast<const float4 *>(beta)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
       float4 o;
-      o.x = (v[i].x - mean) * rstd * g.x + bb.x;
-      o.y = (v[i].y - mean) * rstd * g.y + bb.y;
-      o.z = (v[i].z - mean) * rstd * g.z + bb.z;
-      o.w = (v[i].w - mean) * rstd * g.w + bb.w;
+      o.x = v[i].x * rstd * g.x + bb.x;
+      o.y = v[i].y * rstd * g.y + bb.y;
+      o.z = v[i].z * rstd * g.z + bb.z;
+      o.w = v[i].w * rstd * g.w + bb.w;
       reinterpret_cast<float4 *>(out + (int64_t)row * ldo)[c] = o;
       mx = fmaxf(mx, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
       v[i] = o;
