@@ -233,13 +233,14 @@ WGRAD_MIN_ROWS = 2048
 
 
 class _Linear(torch.autograd.Function):
-    """y = act(x W^T + b): forward on isg_linear_bf16x6 (pre-activation kept when act = GELU), backward as fp32 GEMMs."""
+    """y = act(x W^T + b): forward on isg_linear_bf16x6 (pre-activation kept when act = GELU; ReLU fused into the kernel's epilogue
+    and its RESULT kept: y > 0 is all the backward needs of it), backward as fp32 GEMMs."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gelu):
-        z = ops.linear(x, weight, bias, gelu=False, cache_planes=False)
-        ctx.gelu = gelu
-        ctx.save_for_backward(x, weight, z if gelu else None)
+    def forward(ctx, x, weight, bias, gelu, relu=False):
+        z = ops.linear(x, weight, bias, gelu=False, cache_planes=False, relu=relu)
+        ctx.gelu, ctx.relu = gelu, relu
+        ctx.save_for_backward(x, weight, z if gelu or relu else None)
         ctx.has_bias = bias is not None
         return F.gelu(z) if gelu else z
 
@@ -249,6 +250,8 @@ class _Linear(torch.autograd.Function):
         g = g.contiguous()
         if ctx.gelu:
             g = torch.ops.aten.gelu_backward(g, z)
+        elif ctx.relu:
+            g = g * (z > 0)
         dx = None
         if ctx.needs_input_grad[0]:     # dX = g W: the same matrix-core kernel on the transposed weight
             dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
@@ -257,11 +260,148 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[1]:   # long-and-thin reductions on the split-M kernel; short ones are hipBLASLt's home turf
             dw = ops.linear_wgrad(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def linear(x, weight, bias, gelu):
-    return _Linear.apply(x, weight, bias, gelu)
+def linear(x, weight, bias, gelu, relu=False):
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
+    return _Linear.apply(x, weight, bias, gelu, relu)
+
+
+# ------------------------------------------------------------------------------------------------
+# Question side: short-sequence attention, add + LayerNorm, dropout (include/isg_train.h)
+# ------------------------------------------------------------------------------------------------
+# No dropout mask is stored: a Function keeps its inputs and the seed, and its backward kernel draws the mask again from
+# (seed, position) -- the keep rule of include/isg_train.h.
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        ctx.cfg = (p, seed)
+        return ops.dropout(x, p, seed)
+
+    @staticmethod
+    def backward(ctx, g):
+        p, seed = ctx.cfg
+        return ops.dropout(g.contiguous(), p, seed), None, None
+
+
+def dropout(x, p, seed):
+    """x * keep / (1 - p), the mask a function of (seed, position); the identity at p == 0."""
+    return x if p == 0 else _Dropout.apply(x, p, seed)
+
+
+def _packed(parts):
+    """The tensor that `parts` are the consecutive equal column slices of (q | k | v of a fused in_proj, k | v of the memory's),
+    or None.  The Function then takes THAT tensor and returns ONE gradient for it: no zero-filled slice gradients to add up."""
+    base = parts[0]._base
+    if base is None or base.dim() != 2 or not base.is_contiguous() or any(t._base is not base for t in parts):
+        return None
+    D = parts[0].size(1)
+    if base.size(1) != D * len(parts):
+        return None
+    for i, t in enumerate(parts):
+        if tuple(t.shape) != (base.size(0), D) or t.stride() != base.stride() or t.storage_offset() != base.storage_offset() + i * D:
+            return None
+    return base
+
+
+class _MhaSmall(torch.autograd.Function):
+    """layout "qkv": one [T*B, 3D] tensor; "q_kv": q and one [S*B, 2D] tensor; "sep": q, k, v."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, layout, B, H, key_bias, p, seed):
+        D = a.size(1) // 3 if layout == "qkv" else a.size(1)
+        if layout == "qkv":
+            q, k, v = a[:, :D], a[:, D:2 * D], a[:, 2 * D:]
+        elif layout == "q_kv":
+            q, k, v = a, b[:, :D], b[:, D:]
+        else:
+            q, k, v = a, b, c
+        ctx.save_for_backward(a, b, c, key_bias)
+        ctx.cfg = (layout, B, H, D, p, seed)
+        return ops.mha_small(q, k, v, B, H, key_bias) if p == 0 else ops.mha_small_train(q, k, v, B, H, key_bias, p, seed)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, c, key_bias = ctx.saved_tensors
+        layout, B, H, D, p, seed = ctx.cfg
+        g = g.contiguous()
+        if layout == "qkv":
+            da, db, dc = torch.empty_like(a), None, None
+            q, k, v, dq, dk, dv = a[:, :D], a[:, D:2 * D], a[:, 2 * D:], da[:, :D], da[:, D:2 * D], da[:, 2 * D:]
+        elif layout == "q_kv":
+            da, db, dc = torch.empty_like(a), torch.empty_like(b), None
+            q, k, v, dq, dk, dv = a, b[:, :D], b[:, D:], da, db[:, :D], db[:, D:]
+        else:
+            da, db, dc = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (a, b, c))
+            q, k, v, dq, dk, dv = a, b, c, da, db, dc
+        if not ops.mha_small_backward(q, k, v, B, H, key_bias, g, dq, dk, dv, p, seed):
+            raise ops._lib.IsgError("isg_mha_small_bwd refused a shape autograd.mha_small had asked ops.mha_small_train_supported about")
+        return da, db, dc, None, None, None, None, None, None
+
+
+def _mha_torch(q, k, v, B, H, key_bias, p):
+    """Beyond the kernels' limits: the same formula on torch's ops (its own dropout stream), counted."""
+    ops.COUNTERS["torch_attention_train"] += 1
+    D = q.size(1)
+    hd = D // H
+    Tq, Tk = q.size(0) // B, k.size(0) // B
+    heads = lambda t, T: t.reshape(T, B, H, hd).permute(1, 2, 0, 3)          # [B, H, T, hd]
+    s = heads(q, Tq) @ heads(k, Tk).transpose(-1, -2) / math.sqrt(hd)
+    if key_bias is not None:
+        s = s + key_bias[:, None, None, :]
+    pr = F.dropout(torch.softmax(s, dim=-1), p, training=p > 0)
+    return (pr @ heads(v, Tk)).permute(2, 0, 1, 3).reshape(Tq * B, D)
+
+
+def mha_small(q, k, v, B, H, key_bias=None, p=0.0, seed=0):
+    """softmax(Q K^T / sqrt(hd) + key_bias) V with dropout p on the probabilities, differentiable in q, k, v (ops.mha_small's
+    operands; key_bias gets no gradient and must not require one).  Saves q, k, v and the seed."""
+    if key_bias is not None and key_bias.requires_grad:
+        raise NotImplementedError("autograd.mha_small: key_bias has no gradient here; detach it")
+    D = q.size(1)
+    if not ops.mha_small_train_supported(q.size(0) // B, k.size(0) // B, D // H) or D % H:
+        return _mha_torch(q, k, v, B, H, key_bias, p)
+    base = _packed((q, k, v))
+    if base is not None:
+        return _MhaSmall.apply(base, None, None, "qkv", B, H, key_bias, p, seed)
+    base = _packed((k, v))
+    if base is not None:
+        return _MhaSmall.apply(q, base, None, "q_kv", B, H, key_bias, p, seed)
+    return _MhaSmall.apply(q, k, v, "sep", B, H, key_bias, p, seed)
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, norm, p, seed):
+        ctx.save_for_backward(x, residual)
+        ctx.cfg = (norm, p, seed)
+        if p == 0:
+            return ops.add_layernorm(x, residual, norm, want_rowmax=False)
+        return ops.dropout_add_layernorm(x, residual, norm, p, seed)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, residual = ctx.saved_tensors
+        norm, p, seed = ctx.cfg
+        d_x, d_r, d_g, d_b = ops.add_layernorm_backward(x, residual, norm, g.contiguous(), p, seed,
+                                                        want_residual=residual is not None and ctx.needs_input_grad[1])
+        return d_x, d_r, d_g, d_b, None, None, None
+
+
+def add_layernorm_supported(D: int) -> bool:
+    return D % 4 == 0 and D <= 2048
+
+
+def add_layernorm(x, residual, norm, p=0.0, seed=0):
+    """LayerNorm(residual + dropout(x)), differentiable in x, residual and the norm's weight / bias (which the Function receives
+    as inputs so that autograd hands them their gradients; the kernels read them from `norm`)."""
+    if not add_layernorm_supported(x.size(1)):
+        ops.COUNTERS["torch_layer_norm"] += 1
+        y = F.dropout(x, p, training=p > 0)
+        return F.layer_norm(y if residual is None else y + residual, norm.normalized_shape, norm.weight, norm.bias, norm.eps)
+    return _AddLayerNorm.apply(x.contiguous(), None if residual is None else residual.contiguous(), norm.weight, norm.bias, norm, p, seed)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ from .. import ops
 from .att_pooling import GlobalAttention
 from .mgat import MGAT
 from .scene_graph_encoder import SceneGraphEncoder
-from .text_encoder import CLIPTextEmbeddings, QuestionDecoder, QuestionEncoder
+from .text_encoder import DECODER_SEED_OFFSET, CLIPTextEmbeddings, QuestionDecoder, QuestionEncoder
 
 NUM_ANSWERS = 1842   # isubgvqa.py:207
 
@@ -76,7 +76,8 @@ class ISubGVQA(torch.nn.Module):
     # -- pieces of forward that the benchmark also drives on their own -------------------------------
     def language_features(self, questions: Tensor, qsts_att_mask: Tensor, text_uniform: Optional[Tensor] = None,
                           seed: Optional[int] = None):
-        enc = self.question_encoder(questions, mask=qsts_att_mask)                       # :228
+        # `seed` also names the dropout masks of a training step on the kernels (text_encoder.py: base + site number per dropout)
+        enc = self.question_encoder(questions, mask=qsts_att_mask, seed=seed)            # :228
         self.last_mask_text = None
         if self.text_sampling:                                                           # :229-241: SIMPLE over the tokens
             T, B, D = enc.shape
@@ -86,7 +87,7 @@ class ISubGVQA(torch.nn.Module):
             mask_text, _ = self.text_sampler(logits.unsqueeze(-1), train=self.training, uniform=text_uniform, seed=seed)
             enc = (enc.permute(1, 0, 2) * mask_text.squeeze(0)).permute(1, 0, 2)
             self.last_mask_text = mask_text
-        qst_feats = self.program_decoder(memory=enc)                                     # :243
+        qst_feats = self.program_decoder(memory=enc, seed=None if seed is None else seed + DECODER_SEED_OFFSET)      # :243
         # :244-246 -- a .view, not a permute: rows 4b..4b+3 of the flattened [n_ins*B, 512] (quirk Q4)
         flat = qst_feats.contiguous().view(qst_feats.size(1), int(qst_feats.size(0)), qst_feats.size(2)).flatten(1)
         # Linear + GELU on this library's kernels (ops.mlp; autograd-aware), not the torch modules' hipBLASLt + GELU launches

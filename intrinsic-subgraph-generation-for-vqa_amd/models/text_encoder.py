@@ -16,7 +16,19 @@ forward pass below walks their layers itself: every projection and FFN layer is 
 matrix-core kernel with bias (+ReLU) fused (ops.linear: in_proj 512->1536 as ONE GEMM, out_proj, linear1+ReLU, linear2),
 attention is isg_mha_small (csrc/isg_attn.hip: a question's K / V live in LDS, the float key-padding mask is the additive
 bias it is in the reference), residual + LayerNorm are one launch of isg_add_layernorm.  Every producer leaves the row
-maxima of what it wrote (ops.attach_row_maxima) so the fp16 three-product Linears downstream need no pass for their scales.  Training (autograd recording) runs the torch modules.
+maxima of what it wrote (ops.attach_row_maxima) so the fp16 three-product Linears downstream need no pass for their scales.
+Device work (training: autograd records through the module, or train() mode with a dropout): the same walk on the autograd-aware
+operators of autograd.py -- linear (forward, dX, dW on this library's GEMMs; ReLU fused), mha_small (isg_mha_small_train /
+isg_mha_small_bwd), add_layernorm (isg_dropout_add_layernorm / isg_add_layernorm_bwd), dropout (isg_dropout) -- with the dropouts
+where nn.TransformerEncoderLayer / DecoderLayer have them.  No mask is stored: each dropout SITE of a forward has a seed,
+base + site number, and its backward kernel draws the mask again (keep rule: include/isg_train.h).  Site numbers, in call order:
+    encoder layer l:  4 l + 0  attention probabilities      4 l + 1  dropout1 (before norm1's residual add)
+                      4 l + 2  the FFN's dropout (after ReLU) 4 l + 3  dropout2 (before norm2's residual add)
+    decoder layer l:  6 l + 0  self-attention probabilities  6 l + 1  dropout1      6 l + 2  cross-attention probabilities
+                      6 l + 3  dropout2                      6 l + 4  the FFN's dropout      6 l + 5  dropout3
+A site keeps its number when its p is 0 (nothing is drawn there).  The base is the forward's `seed` argument, or, without one, a
+draw from torch's CPU generator (no device sync; torch.manual_seed reproduces a run).  Every p is read from the torch modules at
+call time and is 0 in eval() mode.  Switch off (FUSED_TEXT_TRAIN), CPU tensors or shapes beyond the kernels: the torch modules.
 """
 from __future__ import annotations
 
@@ -28,10 +40,13 @@ from torch import Tensor
 from .. import ops
 
 FUSED_TEXT = True     # inference path on this library's kernels (A/B switch: False = torch's nn.Transformer* forward)
+FUSED_TEXT_TRAIN = True     # the same under autograd / in train() mode (False = torch's modules: hipBLASLt, torch's attention)
+DECODER_SEED_OFFSET = 4096  # ISubGVQA.language_features: the decoder's base seed = the encoder's + this (sites never collide)
 
 
 def _recording(module: torch.nn.Module, *inputs) -> bool:
-    """True when the torch modules must run instead of the raw kernels (which have no autograd and no dropout): autograd is
+    """True when the raw inference kernels (no autograd, no dropout) cannot serve and the training walk runs (or, where that does
+    not fit or FUSED_TEXT_TRAIN is off, the torch modules): autograd is
     recording through a parameter OR an input (a frozen decoder over a trainable encoder's memory), or the module is in
     train() mode with a non-zero dropout somewhere in it."""
     if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or
@@ -84,6 +99,52 @@ def _ffn(layer, x: Tensor) -> Tensor:
     return ops.linear(h, w2, layer.linear2.bias)
 
 
+# ---- training walk ---------------------------------------------------------------------------------------------------------
+def _base_seed(seed) -> int:
+    if seed is not None:
+        return int(seed)
+    return int(torch.randint(0, 2 ** 62, (1,)).item())           # torch's CPU generator: no device sync
+
+
+def _train_fits(t_q: int, t_kv: int, d_model: int, heads: int) -> bool:
+    from .. import autograd
+    return (d_model % heads == 0 and ops.mha_small_train_supported(t_q, t_kv, d_model // heads)
+            and autograd.add_layernorm_supported(d_model))
+
+
+def _p(module: torch.nn.Module, p: float) -> float:
+    return float(p) if module.training else 0.0
+
+
+def _train_attention(mha: torch.nn.MultiheadAttention, x_q: Tensor, x_kv: Tensor, B: int, key_bias, self_attn: bool, p: float,
+                     seed: int) -> Tensor:
+    """_attention under autograd: the fused in_proj's gradient arrives as ONE [T*B, 3D] tensor from isg_mha_small_bwd; the
+    cross-attention's projections read plain views of in_proj_weight, which autograd differentiates."""
+    from .. import autograd
+    D = x_q.size(1)
+    w, b = mha.in_proj_weight, mha.in_proj_bias
+    if self_attn:
+        qkv = autograd.linear(x_q, w, b, False)
+        q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+    else:
+        q = autograd.linear(x_q, w[:D], None if b is None else b[:D], False)
+        kv = autograd.linear(x_kv, w[D:], None if b is None else b[D:], False)
+        k, v = kv[:, :D], kv[:, D:]
+    att = autograd.mha_small(q, k, v, B, mha.num_heads, key_bias, p, seed)
+    return autograd.linear(att, mha.out_proj.weight, mha.out_proj.bias, False)
+
+
+def _train_ffn(layer, x: Tensor, p: float, seed: int) -> Tensor:
+    from .. import autograd
+    h = autograd.linear(x, layer.linear1.weight, layer.linear1.bias, False, relu=True)
+    return autograd.linear(autograd.dropout(h, p, seed), layer.linear2.weight, layer.linear2.bias, False)
+
+
+def _relu_ffn(layers) -> bool:
+    return all(getattr(l, "activation", None) is torch.nn.functional.relu or getattr(l, "activation_relu_or_gelu", 0) == 1
+               for l in layers)
+
+
 class CLIPTextEmbeddings(torch.nn.Module):
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 512, max_position_embeddings: int = 77):
         super().__init__()
@@ -125,9 +186,27 @@ class QuestionEncoder(torch.nn.Module):
                                                                enable_nested_tensor=False)
         self.ninp = ninp
 
-    def forward(self, src: Tensor, mask: Tensor) -> Tensor:
+    def _forward_train(self, src: Tensor, mask: Tensor, seed) -> Tensor:
+        from .. import autograd
+        ops.COUNTERS["text_train_kernels"] += 1
+        enc, base = self.transformer_encoder, _base_seed(seed)
+        B, T, D = src.shape
+        x = src.permute(1, 0, 2).reshape(T * B, D).contiguous()
+        key_bias = mask.float().contiguous()
+        for i, layer in enumerate(enc.layers):
+            s0 = base + 4 * i
+            att = _train_attention(layer.self_attn, x, x, B, key_bias, True, _p(self, layer.self_attn.dropout), s0)
+            x = autograd.add_layernorm(att, x, layer.norm1, _p(self, layer.dropout1.p), s0 + 1)
+            x = autograd.add_layernorm(_train_ffn(layer, x, _p(self, layer.dropout.p), s0 + 2), x, layer.norm2,
+                                       _p(self, layer.dropout2.p), s0 + 3)
+        return autograd.add_layernorm(x, None, enc.norm).view(T, B, D)
+
+    def forward(self, src: Tensor, mask: Tensor, seed=None) -> Tensor:
         src = self.text_vocab_embedding(src)                                             # :32
         enc = self.transformer_encoder
+        if (FUSED_TEXT_TRAIN and src.is_cuda and src.dtype == torch.float32 and _recording(self, src) and _relu_ffn(enc.layers)
+                and _train_fits(src.size(1), src.size(1), src.size(2), enc.layers[0].self_attn.num_heads)):
+            return self._forward_train(src, mask, seed)
         if (not FUSED_TEXT or not src.is_cuda or _recording(self, src)
                 or not _kernels_fit(src.size(1), src.size(2) // enc.layers[0].self_attn.num_heads)):
             if src.is_cuda and not torch.is_grad_enabled():
@@ -152,10 +231,32 @@ class QuestionDecoder(torch.nn.Module):
         layer = torch.nn.TransformerDecoderLayer(ninp, nhead, nhid, dropout)
         self.coarse_decoder = torch.nn.TransformerDecoder(layer, nlayers, norm=torch.nn.LayerNorm(ninp))
 
-    def forward(self, memory: Tensor) -> Tensor:
+    def _forward_train(self, queries: Tensor, memory: Tensor, seed) -> Tensor:
+        from .. import autograd
+        ops.COUNTERS["text_train_kernels"] += 1
+        dec, base = self.coarse_decoder, _base_seed(seed)
+        (S, B, D), n = memory.shape, queries.size(0)
+        x = queries.reshape(n * B, D).contiguous()
+        mem = memory.reshape(S * B, D).contiguous()
+        for i, layer in enumerate(dec.layers):
+            s0 = base + 6 * i
+            att = _train_attention(layer.self_attn, x, x, B, None, True, _p(self, layer.self_attn.dropout), s0)
+            x = autograd.add_layernorm(att, x, layer.norm1, _p(self, layer.dropout1.p), s0 + 1)
+            att = _train_attention(layer.multihead_attn, x, mem, B, None, False, _p(self, layer.multihead_attn.dropout), s0 + 2)
+            x = autograd.add_layernorm(att, x, layer.norm2, _p(self, layer.dropout2.p), s0 + 3)
+            x = autograd.add_layernorm(_train_ffn(layer, x, _p(self, layer.dropout.p), s0 + 4), x, layer.norm3,
+                                       _p(self, layer.dropout3.p), s0 + 5)
+        return autograd.add_layernorm(x, None, dec.norm).view(n, B, D)
+
+    def forward(self, memory: Tensor, seed=None) -> Tensor:
         B = memory.size(1)
         queries = self.query_embed.weight.unsqueeze(1).repeat(1, B, 1)                   # :61-63
         dec = self.coarse_decoder
+        if (FUSED_TEXT_TRAIN and memory.is_cuda and memory.dtype == torch.float32 and _recording(self, memory)
+                and _relu_ffn(dec.layers) and
+                _train_fits(max(memory.size(0), queries.size(0)), max(memory.size(0), queries.size(0)), memory.size(2),
+                            dec.layers[0].self_attn.num_heads)):
+            return self._forward_train(queries, memory, seed)
         if (not FUSED_TEXT or not memory.is_cuda or _recording(self, memory)
                 or not _kernels_fit(max(memory.size(0), queries.size(0)), memory.size(2) // dec.layers[0].self_attn.num_heads)):
             if memory.is_cuda and not torch.is_grad_enabled():

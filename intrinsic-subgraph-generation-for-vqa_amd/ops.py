@@ -127,7 +127,9 @@ sys.modules[__name__].__class__ = _OpsModule
 # Launches that leave this library's own dense kernels, and extra passes a missing hand-off costs; bench.py prints them
 # per step ("no GEMM of the inference path runs on hipBLASLt" is then a number, not a sentence).
 COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row_absmax": 0, "linear_h3p": 0, "h3p_segmented": 0, "linear_skinny": 0,
-            "tile_nodes": 0, "oversize_nodes": 0}      # nodes the tile kernels took / nodes of graphs beyond a tile (mixed dispatch)
+            "tile_nodes": 0, "oversize_nodes": 0,      # nodes the tile kernels took / nodes of graphs beyond a tile (mixed dispatch)
+            "text_train_kernels": 0,                   # question encoder / decoder forwards under autograd on this library's kernels
+            "torch_attention_train": 0}                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
 
 
 def reset_counters() -> None:
@@ -3011,6 +3013,127 @@ def linear_wgrad(grad_out: Tensor, x: Tensor) -> Tensor:
     _lib.check(lib.isg_linear_wgrad(_chk(grad_out, "grad_out", torch.float32, (M, N)), _chk(x, "x", torch.float32, (M, K)),
                                     part.data_ptr(), M, N, K, N, K, splits, _stream()), "isg_linear_wgrad")
     return part.sum(0) if splits > 1 else part[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# Training of the question side (include/isg_train.h, csrc/isg_text_bwd.hip); autograd.py wires these
+# ------------------------------------------------------------------------------------------------
+MHA_BWD_LDS_MAX = 160 * 1024     # isg_mha_small_bwd: Q, K, V, dO and the two [Tq][Tk] strips in the LDS of one CU
+
+
+def mha_small_bwd_lds_bytes(head_dim: int, t_q: int, t_kv: int) -> int:
+    """isg_mha_small_bwd's LDS (restated from csrc/isg_text_bwd.hip): K and V rows padded by a float4, Q, dO, P~ and dS strips."""
+    return 4 * (2 * t_kv * (head_dim + 4) + 2 * t_q * head_dim + 2 * t_q * t_kv)
+
+
+def mha_small_train_supported(t_q: int, t_kv: int, head_dim: int) -> bool:
+    """Do isg_mha_small / isg_mha_small_train (the forward's 64 KB) and isg_mha_small_bwd (160 KB) both take the shape?"""
+    return (head_dim <= 64 and head_dim % 4 == 0 and 1 <= t_kv <= 128 and
+            (t_kv * (2 * head_dim + 4) + t_q * head_dim + 4 * 128) * 4 <= 64 * 1024 and
+            mha_small_bwd_lds_bytes(head_dim, t_q, t_kv) <= MHA_BWD_LDS_MAX)
+
+
+def _drop_args(p: float, seed: int):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability {p}: 0 <= p < 1")
+    return p, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def dropout(x: Tensor, p: float, seed: int) -> Tensor:
+    """x * keep / (1 - p) under the keep rule of include/isg_train.h (element (i, j): Philox block (i, j >> 2), word j & 3).  Its
+    backward is the same call on the gradient."""
+    from . import _lib_train
+    p, seed = _drop_args(p, seed)
+    M, D = x.shape
+    out = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    _lib.check(_lib_train.load().isg_dropout(_chk_rows(x, "x"), x.stride(0), out.data_ptr(), D, M, D, p, seed, _stream()), "isg_dropout")
+    return out
+
+
+def mha_small_train(q: Tensor, k: Tensor, v: Tensor, batch_size: int, heads: int, key_bias: Optional[Tensor], p: float,
+                    seed: int) -> Tensor:
+    """ops.mha_small's heads form with dropout on the attention probabilities (isg_mha_small_train)."""
+    from . import _lib_train
+    p, seed = _drop_args(p, seed)
+    B, H, D = int(batch_size), int(heads), q.size(1)
+    hd = D // H
+    Tq, Tk = q.size(0) // B, k.size(0) // B
+    if H * hd != D or Tq * B != q.size(0) or Tk * B != k.size(0) or tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f"mha_small_train: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} vs B={B}, H={H}")
+    out = torch.empty(Tq * B, D, dtype=torch.float32, device=q.device)
+    _lib.check(_lib_train.load().isg_mha_small_train(
+        _chk_rows(q, "q"), q.stride(0), _chk_rows(k, "k"), k.stride(0), _chk_rows(v, "v"), v.stride(0),
+        _chk(key_bias, "key_bias", torch.float32, (B, Tk), optional=True), out.data_ptr(), D, B, H, hd, Tq, Tk, p, seed, _stream()),
+        "isg_mha_small_train")
+    return out
+
+
+def mha_small_backward(q: Tensor, k: Tensor, v: Tensor, batch_size: int, heads: int, key_bias: Optional[Tensor], grad_out: Tensor,
+                       d_q: Tensor, d_k: Tensor, d_v: Tensor, p: float, seed: int) -> bool:
+    """isg_mha_small_bwd into the caller's d_q / d_k / d_v (column slices of one gradient are fine).  False: the kernel does not
+    take the shape (ISG_EUNSUPPORTED), nothing was written."""
+    from . import _lib_train
+    p, seed = _drop_args(p, seed)
+    B, H, D = int(batch_size), int(heads), q.size(1)
+    hd = D // H
+    Tq, Tk = q.size(0) // B, k.size(0) // B
+    if tuple(grad_out.shape) != tuple(q.shape) or tuple(d_q.shape) != tuple(q.shape) or tuple(d_k.shape) != tuple(k.shape) or \
+            tuple(d_v.shape) != tuple(v.shape):
+        raise ValueError("mha_small_backward: a gradient's shape differs from its operand's")
+    rc = _lib_train.load().isg_mha_small_bwd(
+        _chk_rows(q, "q"), q.stride(0), _chk_rows(k, "k"), k.stride(0), _chk_rows(v, "v"), v.stride(0),
+        _chk(key_bias, "key_bias", torch.float32, (B, Tk), optional=True), _chk_rows(grad_out, "grad_out"), grad_out.stride(0),
+        _chk_rows(d_q, "d_q"), d_q.stride(0), _chk_rows(d_k, "d_k"), d_k.stride(0), _chk_rows(d_v, "d_v"), d_v.stride(0),
+        B, H, hd, Tq, Tk, p, seed, _stream())
+    if rc == ISG_EUNSUPPORTED:
+        return False
+    _lib.check(rc, "isg_mha_small_bwd")
+    return True
+
+
+def _ln_operands(x: Tensor, residual: Optional[Tensor], norm: torch.nn.LayerNorm):
+    M, D = x.shape
+    if residual is not None and tuple(residual.shape) != (M, D):
+        raise ValueError(f"add_layernorm: x {tuple(x.shape)} vs residual {tuple(residual.shape)}")
+    if tuple(norm.normalized_shape) != (D,) or norm.weight is None:
+        raise ValueError("add_layernorm: an affine LayerNorm over the last dimension")
+    return (M, D, _chk_rows(x, "x"), x.stride(0), 0 if residual is None else _chk_rows(residual, "residual"),
+            0 if residual is None else residual.stride(0), _chk(norm.weight.detach(), "weight", torch.float32, (D,)))
+
+
+def dropout_add_layernorm(x: Tensor, residual: Optional[Tensor], norm: torch.nn.LayerNorm, p: float, seed: int) -> Optional[Tensor]:
+    """LayerNorm(residual + dropout(x)) in one launch (isg_dropout_add_layernorm).  None: a shape the kernel does not take."""
+    from . import _lib_train
+    p, seed = _drop_args(p, seed)
+    M, D, xp, ldx, rp, ldr, gp = _ln_operands(x, residual, norm)
+    out = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    rc = _lib_train.load().isg_dropout_add_layernorm(
+        xp, ldx, rp, ldr, gp, _chk(None if norm.bias is None else norm.bias.detach(), "bias", torch.float32, (D,), optional=True),
+        float(norm.eps), out.data_ptr(), D, M, D, p, seed, _stream())
+    if rc == ISG_EUNSUPPORTED:
+        return None
+    _lib.check(rc, "isg_dropout_add_layernorm")
+    return out
+
+
+def add_layernorm_backward(x: Tensor, residual: Optional[Tensor], norm: torch.nn.LayerNorm, grad_out: Tensor, p: float, seed: int,
+                           want_residual: bool = True):
+    """isg_add_layernorm_bwd: (d_x, d_residual or None, d_gamma, d_beta or None); the partial rows of d_gamma / d_beta (one per
+    workgroup) are summed here, in one fixed order."""
+    from . import _lib_train
+    lib = _lib_train.load()
+    p, seed = _drop_args(p, seed)
+    M, D, xp, ldx, rp, ldr, gp = _ln_operands(x, residual, norm)
+    parts = max(int(lib.isg_add_layernorm_bwd_parts(M)), 1)
+    d_x = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    d_r = torch.empty(M, D, dtype=torch.float32, device=x.device) if residual is not None and want_residual else None
+    dg = torch.zeros(parts, D, dtype=torch.float32, device=x.device)
+    db = torch.zeros(parts, D, dtype=torch.float32, device=x.device) if norm.bias is not None else None
+    _lib.check(lib.isg_add_layernorm_bwd(xp, ldx, rp, ldr, gp, float(norm.eps), _chk_rows(grad_out, "grad_out"), grad_out.stride(0),
+                                         d_x.data_ptr(), D, 0 if d_r is None else d_r.data_ptr(), D, dg.data_ptr(),
+                                         0 if db is None else db.data_ptr(), M, D, p, seed, _stream()), "isg_add_layernorm_bwd")
+    return d_x, d_r, dg.sum(0), None if db is None else db.sum(0)
 
 
 def cat_mul(a: Tensor, b: Tensor) -> Tensor:
