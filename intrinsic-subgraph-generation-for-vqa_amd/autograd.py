@@ -270,6 +270,31 @@ def linear(x, weight, bias, gelu, relu=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# The loss (include/isg_optim.h)
+# ------------------------------------------------------------------------------------------------
+class _CrossEntropy(torch.autograd.Function):
+    """ops.cross_entropy with isg_xent_bwd behind it.  Saved: the logits, the labels, the rows' log-sum-exp and the counts; the
+    probabilities are recomputed.  The upstream gradient reaches the kernel as the device scalar it is."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, totals):
+        r = ops.cross_entropy(logits, labels, ignore_index, totals)
+        ctx.ignore_index = ignore_index
+        ctx.save_for_backward(logits, labels, r.lse, r.stats)
+        ctx.mark_non_differentiable(r.pred, r.row_loss, r.stats, r.lse)
+        return tuple(r)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        logits, labels, lse, stats = ctx.saved_tensors
+        return ops.cross_entropy_backward(logits, labels, lse, stats, g.float().contiguous(), ctx.ignore_index), None, None, None
+
+
+def cross_entropy(logits, labels, ignore_index=-100, totals=None):
+    return ops.CrossEntropy(*_CrossEntropy.apply(logits, labels, ignore_index, totals))
+
+
+# ------------------------------------------------------------------------------------------------
 # Question side: short-sequence attention, add + LayerNorm, dropout (include/isg_train.h)
 # ------------------------------------------------------------------------------------------------
 # No dropout mask is stored: a Function keeps its inputs and the seed, and its backward kernel draws the mask again from

@@ -3136,6 +3136,70 @@ def add_layernorm_backward(x: Tensor, residual: Optional[Tensor], norm: torch.nn
     return d_x, d_r, dg.sum(0), None if db is None else db.sum(0)
 
 
+# ------------------------------------------------------------------------------------------------
+# The step's tail: loss, accuracy (include/isg_optim.h; the optimizer half is optim.py)
+# ------------------------------------------------------------------------------------------------
+class CrossEntropy(NamedTuple):
+    """What ops.cross_entropy returns.  Everything stays on the device: `stats` is the kernel's double [4] = (mean_loss, n_counted,
+    n_correct, n_rows), `loss` its first entry rounded to fp32 (the scalar to call .backward() on)."""
+    loss: Tensor        # 0-dim fp32
+    pred: Tensor        # [B] int32, the lowest index among a row's maxima
+    row_loss: Tensor    # [B] fp32; 0 on ignored rows, NaN where a label is outside [0, A)
+    stats: Tensor       # [4] float64
+    lse: Tensor         # [B] float64, what the backward recomputes the probabilities from
+
+
+def _xent_operands(logits: Tensor, labels: Tensor):
+    if not logits.is_cuda or not labels.is_cuda:
+        raise _lib.IsgError(f"cross_entropy: logits and labels must live on the GPU (got {logits.device}, {labels.device}); "
+                            "this path has no CPU fallback")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.size(1) < 1 or (logits.size(0) > 1 and logits.stride(0) < logits.size(1)) \
+            or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError("cross_entropy: logits are fp32 [B, A] with contiguous columns (a column slice of a wider matrix is fine)")
+    B, A = logits.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise ValueError(f"cross_entropy: labels are a contiguous int64 [{B}], got {labels.dtype} {tuple(labels.shape)}")
+    return B, A, max(logits.stride(0), A) if B > 1 else A
+
+
+def cross_entropy(logits: Tensor, labels: Tensor, ignore_index: int = -100, totals: Optional[Tensor] = None) -> CrossEntropy:
+    """Mean softmax cross-entropy over the rows whose label is not `ignore_index`, with top-1 (isg_xent_fwd): F.cross_entropy's
+    value, the reference's accuracy() count and, when `totals` (train.Meters.totals: a device float64 [8]) is given, the running
+    meters advanced in the same launch.  Nothing returns to the host.  Under autograd the call goes through
+    autograd.cross_entropy, whose backward is isg_xent_bwd."""
+    if _rec(logits):
+        from . import autograd
+        return autograd.cross_entropy(logits, labels, ignore_index, totals)
+    from . import _lib_optim
+    B, A, ld = _xent_operands(logits, labels)
+    dev = logits.device
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    lse = torch.empty(B, dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    pred = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib_optim.load().isg_xent_fwd(logits.data_ptr(), ld, labels.data_ptr(), int(ignore_index), row_loss.data_ptr(),
+                                              lse.data_ptr(), pred.data_ptr(), stats.data_ptr(), loss.data_ptr(),
+                                              _chk(totals, "totals", torch.float64, (8,), optional=True), B, A, _stream()),
+               "isg_xent_fwd")
+    return CrossEntropy(loss, pred, row_loss, stats, lse)
+
+
+def cross_entropy_backward(logits: Tensor, labels: Tensor, lse: Tensor, stats: Tensor, grad: Optional[Tensor],
+                           ignore_index: int = -100) -> Tensor:
+    """d loss / d logits times the upstream gradient `grad` (a device fp32 scalar, or None for 1): isg_xent_bwd, one pass."""
+    from . import _lib_optim
+    B, A, ld = _xent_operands(logits, labels)
+    if grad is not None and (not grad.is_cuda or grad.dtype != torch.float32 or grad.numel() != 1):
+        raise ValueError("cross_entropy_backward: the upstream gradient is one fp32 value on the GPU")
+    d = torch.empty(B, A, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib_optim.load().isg_xent_bwd(logits.data_ptr(), ld, labels.data_ptr(), int(ignore_index),
+                                              _chk(lse, "lse", torch.float64, (B,)), _chk(stats, "stats", torch.float64, (4,)),
+                                              0 if grad is None else grad.data_ptr(), d.data_ptr(), A, B, A, _stream()),
+               "isg_xent_bwd")
+    return d
+
+
 def cat_mul(a: Tensor, b: Tensor) -> Tensor:
     """cat((a, b, a * b), dim=1) (isubgvqa.py:288-291).  Inference on fp32 rows: one launch that also leaves the result's row
     maxima on it for the Linear that follows (isg_cat_mul_rowmax); otherwise the torch ops."""
