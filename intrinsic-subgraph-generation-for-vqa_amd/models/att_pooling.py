@@ -33,11 +33,13 @@ class GlobalAttention(torch.nn.Module):
                     m.reset_parameters()
 
     def forward(self, x, u, batch, size=None, return_mask=False, node_mask=None,
-                plan: Optional[ops.GraphPlan] = None):
+                plan: Optional[ops.GraphPlan] = None, q: Optional[torch.Tensor] = None):
+        # q: ques_nn(u), from a caller that ran it ahead of the layers (ops.small_mlps)
         x = x.unsqueeze(-1) if x.dim() == 1 else x
         if plan is None:
             plan = ops.GraphPlan.build(batch, None, num_graphs=u.size(0) if size is None else size)
-        q = ops.mlp(self.ques_nn, u)                                                     # :66
+        if q is None:
+            q = ops.mlp(self.ques_nn, u)                                                 # :66
         res = None
         if x.dtype == torch.float32 and x.dim() == 2 and ops.readout_tile_supported(plan, self.node_nn, x.size(1)):
             # node_nn, mask, per-graph softmax and pooled sum as one launch on graph-aligned tiles (csrc/isg_layer_conv.hip)

@@ -100,13 +100,14 @@ class ISubGVQA(torch.nn.Module):
                       return_masks=True, noises=None, seed=None, explainer=False, explainer_stage=False,
                       expl_bypass_x=False):
         """MGAT -> pooling -> classifier (isubgvqa.py:267-292)."""
+        gate_q, pool_q = self.gat_seq.question_side(glf, None, self.graph_global_attention_pooling)
         x_mgat, imle_mask, node_logits_layers, _ = self.gat_seq(
             x=x_encoded, edge_index=edge_index, edge_attr=edge_attr_encoded, instr_vectors=instr_vectors[:4],
             global_language_feats=glf, batch=batch, return_masks=return_masks, explainer=explainer,
-            explainer_stage=explainer_stage, expl_bypass_x=expl_bypass_x, plan=plan, noises=noises, seed=seed)
+            explainer_stage=explainer_stage, expl_bypass_x=expl_bypass_x, plan=plan, noises=noises, seed=seed, gate_q=gate_q)
         embed, gate = self.graph_global_attention_pooling(x=x_mgat, u=glf, batch=batch, size=None,
-                                                          return_mask=True, node_mask=imle_mask, plan=plan)
-        feats = ops.mlp(self.embedding, ops.cat_mul(embed, glf), want_rowmax=True)       # :288-291 (row maxima: for logit_fc)
+                                                          return_mask=True, node_mask=imle_mask, plan=plan, q=pool_q)
+        feats = ops.cat_mul_mlp(self.embedding, embed, glf, want_rowmax=True)           # :288-291 (row maxima: for logit_fc)
         return ops.linear(feats, self.logit_fc.weight, self.logit_fc.bias), imle_mask, gate, node_logits_layers   # :292
 
     def _captured(self, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, explainer, explainer_stage,

@@ -77,12 +77,35 @@ class MGAT(torch.nn.Module):
         beyond a tile through ops.run_split instead of having every layer fill their rows.)"""
         return self.convs[0].route(plan, in_channels, edge_attr).conv in ("layer_conv", "tile_conv")
 
+    def question_side(self, glf: Tensor, gate_feats: Optional[Tensor] = None, pooling=None):
+        """The question-side MLPs of a step as one launch ahead of the layers (ops.small_mlps): every masked layer's
+        mask.ques_nn on the rows its node gate reads, and the read-out's ques_nn on glf.  They read only the question rows and
+        weights, so their place is before the graph plan's first consumer.  -> ({layer: q} for forward(gate_q=), the read-out's q),
+        or (None, None) when the launch does not take them: every module then runs its own."""
+        # a host-bound forward (a few questions, width 300) learns here, before anything is gathered, that nothing changes for it:
+        # the pure rule on a square Linear of the rows' own width.  At a width the rule admits a Linear's route at a given M does not
+        # depend on N <= 128, so this refuses nothing ops.small_mlps takes.
+        if glf.dim() != 2 or not ops.small_mlps_supported(glf.size(0), (((glf.size(1), glf.size(1)),),), glf.dtype,
+                                                          torch.is_grad_enabled()):
+            return None, None
+        gate_u = (glf if gate_feats is None else gate_feats).contiguous()
+        masked = [i for i, conv in enumerate(self.convs) if conv.mask.masking_threshold != 1.0]
+        chains = [(self.convs[i].mask.ques_nn, gate_u) for i in masked]
+        if pooling is not None:
+            chains.append((pooling.ques_nn, glf.contiguous()))
+        qs = ops.small_mlps(chains, strict=False) if chains else None
+        if qs is None:
+            return None, None
+        return dict(zip(masked, qs)), (qs[-1] if pooling is not None else None)
+
     def forward(self, x, edge_index, instr_vectors, global_language_feats, edge_attr, batch, return_masks=False,
                 explainer=False, explainer_stage=False, expl_bypass_x=False, plan: Optional[ops.GraphPlan] = None,
                 noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
-                return_attention: bool = False, gate_feats: Optional[Tensor] = None):
+                return_attention: bool = False, gate_feats: Optional[Tensor] = None,
+                gate_q: Optional[Dict[int, Tensor]] = None):
         # gate_feats [B, C]: the rows the masked layers' node gates read, given per graph (ops.run_split's sub-batch); default:
         # global_language_feats under the reference's double index (masking.py:151-155, quirk Q3)
+        # gate_q {layer: mask.ques_nn(those rows)}: from a caller that ran the question-side MLPs ahead (question_side)
         if plan is None:
             plan = ops.GraphPlan.build(batch, edge_index, num_graphs=global_language_feats.size(0))
         h = x.float().contiguous()
@@ -118,6 +141,7 @@ class MGAT(torch.nn.Module):
                 plan=plan, noise=None if noises is None else noises.get(i),
                 seed=None if seed is None else seed + i,
                 e_proj=None if e_projs is None else e_projs[i], x_gated=x_gated, x_planes=x_planes,
+                gate_q=None if gate_q is None else gate_q.get(i),
                 out_planes=self._x_proj_reads_planes(i, h.size(0), explainer))                           # :144-154
             x_gated = x_planes = None
             if return_attention:

@@ -122,8 +122,9 @@ class MaskingGATv2Conv(torch.nn.Module):
                 plan: Optional[ops.GraphPlan] = None, noise: Optional[Tensor] = None, seed: Optional[int] = None,
                 e_proj: Optional[Tensor] = None, x_gated: Optional[Tensor] = None,
                 x_planes: Optional["ops.NodePlanes"] = None, out_planes: bool = False, gate_rows_given: bool = False,
-                route: Optional["ops.ConvRoute"] = None):
+                route: Optional["ops.ConvRoute"] = None, gate_q: Optional[Tensor] = None):
         # route: self.route(...) of this call, from a caller that has asked already (MGAT)
+        # gate_q: mask.ques_nn(imle_att), from a caller that ran it ahead of the layers (ops.small_mlps)
         # gate_rows_given: imle_att[g] already IS the row the node gate of graph g reads (ops.run_split's sub-batch: the reference's
         # double index batch[batch[n]], quirk Q3, refers to positions in the batch the graphs were taken from)
         # out_planes (inference): the caller feeds the result to a Linear + GELU on the planes32 engine (MGAT's x_proj.0) and
@@ -159,7 +160,7 @@ class MaskingGATv2Conv(torch.nn.Module):
         mask = None
         if masked:                                                                       # :161
             mask = self.mask(x, imle_att, batch, edge_index, use_all_instrs=False, plan=plan, noise=noise,
-                             seed=seed, u_is_per_graph=not gate_rows_given, x_planes=planes)             # :166-168
+                             seed=seed, u_is_per_graph=not gate_rows_given, x_planes=planes, q=gate_q)   # :166-168
 
         def done(out, alpha):
             if isinstance(return_attention_weights, bool):

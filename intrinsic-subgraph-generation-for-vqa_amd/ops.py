@@ -58,6 +58,8 @@ class Switches:
     fuse_dense_tail: bool = True           # x_proj + layer tail + next instruction gate as one kernel on graph-aligned tiles
     dense_tail_rows: int = 64              # nodes per tile of isg_mgat_dense_tail
     fuse_readout: bool = True              # node_nn + mask + per-graph softmax pooling as one launch on graph-aligned tiles
+    fuse_question_mlps: bool = True        # the masked layers' ques_nn and the read-out's ques_nn as one launch ahead of the layers (isg_small_mlps)
+    fuse_cat_mul_linear: bool = True       # the answer head's Linear over cat(a, b, a * b) reads a and b (isg_linear_f16x3_catmul): no isg_cat_mul_rowmax
     embedding_sum: bool = True             # sum of a node's token embeddings through isg_gather_add instead of gather + reduce
     # dense projections: which kernel runs a Linear (linear_route)
     gemm_backend: str = "bf16x6"           # "bf16x6": this library's kernels; "torch": hipBLASLt fp32 through torch
@@ -3218,6 +3220,56 @@ def cat_mul(a: Tensor, b: Tensor) -> Tensor:
     return attach_row_maxima(out, rm)
 
 
+CAT_MUL_MAX_C = 128       # ISG_CATMUL_MAX_C of include/isg_fused.h
+
+
+def cat_mul_linear_supported(M: int, N: int, C: int, x_dtype=torch.float32, grad: bool = False, cfg: Optional[Switches] = None) -> bool:
+    """May isg_linear_f16x3_catmul run act(cat(a, b, a * b) @ W^T + bias) for a, b [M, C], W [N, 3C]?  A pure function of plain
+    values.  Yes when: the switch is on; inference on fp32 rows; 32 | C <= 128 and 32 | N; and the two launches it stands for
+    would be isg_cat_mul_rowmax + isg_linear_f16x3_tile in ONE K-chunk -- ops.linear_route's answer for rows that carry their
+    row maxima -- whose bits it reproduces.  Everywhere else those two launches run."""
+    cfg = CFG if cfg is None else cfg
+    if not cfg.fuse_cat_mul_linear or grad or x_dtype != torch.float32 or M <= 0:
+        return False
+    if C <= 0 or C % 32 or C > CAT_MUL_MAX_C or N <= 0 or N % 32 or (M + 31) // 32 > 65535:
+        return False
+    return _k_chunks(3 * C)[0] == 1 and linear_route(M, N, 3 * C, rowmax_slices=True, cfg=cfg) == "f16x3_tile"
+
+
+def cat_mul_linear(a: Tensor, b: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gelu: bool = False,
+                   want_rowmax: bool = False) -> Tensor:
+    """ops.linear(ops.cat_mul(a, b), weight, bias, gelu=gelu, want_rowmax=want_rowmax), bit for bit (the result and the row
+    maxima left on it), as ONE launch that reads a and b (isg_linear_f16x3_catmul) where cat_mul_linear_supported says so;
+    those two launches everywhere else, also where the library declines (ISG_F16X3_MFMA=32)."""
+    ok = (a.dim() == 2 and a.shape == b.shape and a.is_cuda and a.dtype == b.dtype and weight.dim() == 2 and
+          weight.size(1) == 3 * a.size(1) and weight.dtype == torch.float32 and
+          cat_mul_linear_supported(a.size(0), weight.size(0), a.size(1), a.dtype, torch.is_grad_enabled()))
+    if ok:
+        from . import _lib_fused
+        lib = _lib_fused.load()
+        (M, C), N = a.shape, weight.size(0)
+        a, b = a.contiguous(), b.contiguous()
+        planes, inv = _weight_planes(weight, True, "f16x3_rows")
+        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+        rm = torch.empty(M, N // 32, dtype=torch.float32, device=a.device) if want_rowmax else None
+        rc = lib.isg_linear_f16x3_catmul(_chk(a, "a", torch.float32), _chk(b, "b", torch.float32), planes.data_ptr(), inv.data_ptr(),
+                                         _bias_ptr(bias, N), out.data_ptr(), 0 if rm is None else rm.data_ptr(), M, N, C, N,
+                                         1 if gelu else 0, _stream())
+        if rc != ISG_EUNSUPPORTED:
+            _lib.check(rc, "isg_linear_f16x3_catmul")
+            return out if rm is None else attach_row_maxima(out, rm)
+    return linear(cat_mul(a, b), weight, bias, gelu=gelu, want_rowmax=want_rowmax)
+
+
+def cat_mul_mlp(seq: torch.nn.Sequential, a: Tensor, b: Tensor, want_rowmax: bool = False) -> Tensor:
+    """ops.mlp(seq, ops.cat_mul(a, b), want_rowmax) for the answer heads: a Sequential that is ONE Linear (+ exact GELU, eval
+    Dropout) goes through cat_mul_linear, anything else through the two calls."""
+    steps = _mlp_steps(seq)
+    if steps is not None and len(steps) == 1:
+        return cat_mul_linear(a, b, steps[0][0].weight, steps[0][0].bias, gelu=steps[0][1], want_rowmax=want_rowmax)
+    return mlp(seq, cat_mul(a, b), want_rowmax=want_rowmax)
+
+
 def mlp(seq: torch.nn.Sequential, x: Tensor, want_rowmax: bool = False) -> Tensor:   # x may be fp16 feature rows; the output is fp32
     """Run an nn.Sequential of Linear / GELU / Dropout(eval) modules with every Linear(+GELU) pair as one launch.
     ``want_rowmax``: the caller feeds the result to another Linear (the last launch's epilogue leaves its row maxima on it)."""
@@ -3249,6 +3301,98 @@ def mlp(seq: torch.nn.Sequential, x: Tensor, want_rowmax: bool = False) -> Tenso
             x = m(x)
             i += 1
     return x
+
+
+SMALL_MLPS_MAX_CHAINS, SMALL_MLPS_MAX_WIDTH = 4, 128       # ISG_SMALL_MLPS_MAX_CHAINS / _MAX_WIDTH of include/isg_fused.h
+
+
+def small_mlps_supported(M: int, chains, x_dtype=torch.float32, grad: bool = False, cfg: Optional[Switches] = None) -> bool:
+    """May isg_small_mlps run these chains over M rows each?  A pure function of plain values.  chains: per chain the (N, K)
+    of its one or two Linears, in order.  Yes when: the switch is on; inference on fp32 rows; one to four chains; every width a
+    multiple of 32 of at most 128; a second Linear reads what the first wrote; and every Linear is one ops.linear_route sends to
+    "bf16x6" at this M -- the kernel whose bits the launch reproduces.  So at M <= 1024 (isg_linear_skinny's regime) and at
+    C = 300 nothing changes, and no row's bits depend on this switch."""
+    cfg = CFG if cfg is None else cfg
+    if not cfg.fuse_question_mlps or grad or x_dtype != torch.float32 or M <= 0:
+        return False
+    if not 1 <= len(chains) <= SMALL_MLPS_MAX_CHAINS:
+        return False
+    for chain in chains:
+        if not 1 <= len(chain) <= 2 or (len(chain) == 2 and chain[1][1] != chain[0][0]):
+            return False
+        for N, K in chain:
+            if N % 32 or K % 32 or not (32 <= N <= SMALL_MLPS_MAX_WIDTH and 32 <= K <= SMALL_MLPS_MAX_WIDTH):
+                return False
+            if linear_route(M, N, K, cfg=cfg) != "bf16x6":
+                return False
+    return True
+
+
+def _mlp_steps(seq) -> Optional[list]:
+    """An nn.Sequential as [(Linear, followed by an exact GELU)], or None when it holds anything but Linear / exact GELU (after a
+    Linear) / Dropout in eval mode."""
+    steps = []
+    for m in seq:
+        if isinstance(m, torch.nn.Linear):
+            steps.append([m, False])
+        elif isinstance(m, torch.nn.GELU) and m.approximate == "none" and steps and not steps[-1][1]:
+            steps[-1][1] = True
+        elif not (isinstance(m, torch.nn.Dropout) and not m.training):
+            return None
+    return steps
+
+
+def _small_mlps_plan(chains):
+    """[(nn.Sequential, x)] -> (M, the chains' [(Linear, gelu)] steps) when isg_small_mlps takes them, else None: the tensors'
+    facts, then the pure rule."""
+    if not chains or not isinstance(chains[0][1], Tensor) or chains[0][1].dim() != 2:
+        return None
+    x0, grad = chains[0][1], torch.is_grad_enabled()
+    M, plan, shapes = x0.size(0), [], []
+    for seq, x in chains:
+        steps = _mlp_steps(seq)
+        if (not steps or not isinstance(x, Tensor) or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or x.size(0) != M
+                or x.size(1) != steps[0][0].weight.size(1)
+                or any(m.weight.dtype != torch.float32 or m.weight.device != x.device for m, _ in steps)):
+            return None
+        plan.append(steps)
+        shapes.append([tuple(m.weight.shape) for m, _ in steps])
+    return (M, plan) if small_mlps_supported(M, shapes, torch.float32, grad) else None
+
+
+def small_mlps(chains, strict: bool = True) -> Optional[list]:
+    """[ops.mlp(seq, x) for seq, x in chains], bit for bit, as ONE launch (isg_small_mlps): up to four narrow MLPs over the same
+    number of rows.  Chains that ops.small_mlps_supported refuses raise; with ``strict=False`` the answer is None instead (the
+    caller lets every module run its own MLP, as it always did) -- also when the library declines the launch because
+    ISG_GEMM_KROT / ISG_GEMM_DUAL_K give isg_linear_bf16x6 another accumulation order."""
+    import ctypes
+    plan = _small_mlps_plan(chains)
+    if plan is None:
+        if strict:
+            raise ValueError("small_mlps: chains that ops.small_mlps_supported refuses (run them through ops.mlp)")
+        return None
+    from . import _lib_fused
+    lib = _lib_fused.load()
+    M, plan = plan
+    fields, outs, keep = [], [], []
+    for (seq, x), steps in zip(chains, plan):
+        x = x.contiguous()
+        out = torch.empty(M, steps[-1][0].weight.size(0), dtype=torch.float32, device=x.device)
+        row = [_chk(x, "x", torch.float32), x.stride(0), out.data_ptr(), out.stride(0), len(steps)]
+        for m, gelu in (steps + steps[:1])[:2]:        # one Linear: the second slot repeats the first (the kernel ignores it)
+            N, K = m.weight.shape
+            planes = _weight_planes(m.weight, True, "tile")
+            row += [planes.data_ptr(), _bias_ptr(m.bias, N), N, K, 1 if gelu else 0]
+            keep.append(planes)
+        fields += row
+        keep.append(x)
+        outs.append(out)
+    arr = (ctypes.c_int64 * len(fields))(*fields)
+    rc = lib.isg_small_mlps(ctypes.addressof(arr), len(chains), M, _stream())
+    if rc == ISG_EUNSUPPORTED and not strict:
+        return None
+    _lib.check(rc, "isg_small_mlps")
+    return outs
 
 
 def linear_fused(x: Tensor, layers, out_dtype=torch.float32) -> Tuple[Tensor, ...]:

@@ -209,12 +209,13 @@ class AnswerModel(torch.nn.Module):
 
     def _answer(self, x, edge_index, edge_attr, batch, instr, glf, plan, noises, seed, gate_feats):
         from . import ops as _ops
+        gate_q, pool_q = self.gat_seq.question_side(glf, gate_feats, self.graph_global_attention_pooling)
         h, mask, _, _ = self.gat_seq(x=x, edge_index=edge_index, edge_attr=edge_attr, instr_vectors=instr[:4],
                                      global_language_feats=glf, batch=batch, return_masks=True, plan=plan, noises=noises, seed=seed,
-                                     gate_feats=gate_feats)
+                                     gate_feats=gate_feats, gate_q=gate_q)
         embed, gate = self.graph_global_attention_pooling(x=h, u=glf, batch=batch, size=None, return_mask=True,
-                                                          node_mask=mask, plan=plan)
-        feats = _ops.mlp(self.embedding, _ops.cat_mul(embed, glf), want_rowmax=True)
+                                                          node_mask=mask, plan=plan, q=pool_q)
+        feats = _ops.cat_mul_mlp(self.embedding, embed, glf, want_rowmax=True)
         return _ops.linear(feats, self.logit_fc.weight, self.logit_fc.bias), mask, gate
 
 
