@@ -13,9 +13,10 @@ off, so the same `ops.*` call runs the plain forward kernel.  Three kinds of bac
     fp32 matrix-core instruction (csrc/isg_wgrad.hip);
   * the per-graph operators around the message passing -- layer tail (instruction attention + GraphNorm + residual),
     pooling, instruction gate, node gate: per-graph HIP backward kernels (csrc/isg_tail_bwd.hip);
-  * what only the scene-graph encoder / stand-alone utilities use (GraphNorm alone, scatter attention alone,
-    scatter_mean, the SIMPLE marginals): forward = fused kernel, backward re-evaluates a torch-op restatement ON THE
-    DEVICE under autograd (`_Recomputed`).  These are plain autograd in the reference too.
+  * the scene-graph encoder's operators -- gather-add, the node tokens' embedding sum, scatter_mean, GraphNorm alone (both modes):
+    HIP backward kernels of their own (csrc/isg_sgenc_bwd.hip); every scatter among them is one segment sum without atomics;
+  * what only stand-alone utilities use (scatter attention alone, the SIMPLE marginals, gates without a plan): forward = fused
+    kernel, backward re-evaluates a torch-op restatement ON THE DEVICE under autograd (`_Recomputed`).
 
 Nothing here runs on the CPU and nothing imports `oracle/`.
 """
@@ -194,11 +195,26 @@ def global_attn_pool(xn, q, plan, node_mask):
     return _Pool.apply(xn, q, node_mask, plan)
 
 
+class _GraphNorm(torch.autograd.Function):
+    """ops.graph_norm with isg_graph_norm_bwd behind it, in the forward's mode (fp64: every intermediate a double).  Saved: the
+    inputs; the statistics are recomputed per graph.  `_graph_norm_t` above stays as the restatement the tests compare against."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mean_scale, plan, eps, fp64):
+        ctx.save_for_backward(x, weight, mean_scale)
+        ctx.cfg = (plan, eps, fp64)
+        return ops.graph_norm(x, plan, weight, bias, mean_scale, eps, fp64)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, mean_scale = ctx.saved_tensors
+        plan, eps, fp64 = ctx.cfg
+        d_x, d_w, d_b, d_ms = ops.graph_norm_bwd(x, plan, weight, mean_scale, eps, fp64, g.contiguous())
+        return d_x, d_w, d_b, d_ms, None, None, None
+
+
 def graph_norm(x, plan, weight, bias, mean_scale, eps, fp64):
-    batch, B = plan.batch, plan.B
-    return _Recomputed.apply(lambda v, w, b, m, p, e, f: ops.graph_norm(v, p, w, b, m, e, f),
-                             lambda v, w, b, m, p, e, f: _graph_norm_t(v, w, b, m, batch, B, e, f),
-                             (plan, eps, fp64), x, weight, bias, mean_scale)
+    return _GraphNorm.apply(x.contiguous(), weight, bias, mean_scale, plan, eps, fp64)
 
 
 def scatter_attention(query, key, plan, value):
@@ -210,14 +226,149 @@ def scatter_attention(query, key, plan, value):
     return _Recomputed.apply(lambda qr, k, v, p: ops.scatter_attention(qr, k, p, v), restate, (plan,), query, key, value)
 
 
-def scatter_mean(msg, plan):
-    dst = plan.edge_index[1]
-    N = plan.N
+class _ScatterMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, msg, plan):
+        ctx.plan = plan
+        return ops.scatter_mean(msg, plan)
 
-    def restate(m, _p):
-        cnt = torch.bincount(dst, minlength=N).clamp(min=1).to(m.dtype).unsqueeze(1)
-        return _seg_sum(m, dst, N) / cnt
-    return _Recomputed.apply(ops.scatter_mean, restate, (plan,), msg)
+    @staticmethod
+    def backward(ctx, g):
+        return ops.scatter_mean_bwd(g.contiguous(), ctx.plan), None
+
+
+def scatter_mean(msg, plan):
+    return _ScatterMean.apply(msg, plan)
+
+
+# ------------------------------------------------------------------------------------------------
+# Scene-graph encoder without its concatenations (include/isg_sgenc_train.h)
+# ------------------------------------------------------------------------------------------------
+def _column_slice(t):
+    """(base, first column) when `t` is a column slice t = base[:, c0:c0 + C] of a contiguous 2-D tensor, else None."""
+    base = None if t is None else t._base
+    if base is None or base.dim() != 2 or t.dim() != 2 or not base.is_contiguous() or t.stride() != base.stride() \
+            or t.size(0) != base.size(0):
+        return None
+    c0 = t.storage_offset() - base.storage_offset()
+    return (base, c0) if 0 <= c0 and c0 + t.size(1) <= base.size(1) else None
+
+
+class _GatherAdd(torch.autograd.Function):
+    """ops.gather_add with isg_gather_add_bwd and isg_segment_rows_sum behind it.  Saved: the inputs only; the pre-activation is
+    evaluated again.  cols = (column of A, column of B or None): `a` is then the tensor A and B are column slices of, and ONE
+    gradient goes back to it (its other columns zero) -- no zero-filled slice gradients for autograd to add up, as _MhaSmall has it
+    for q, k, v.  T2 / sign2 (optional): a second tensor with T's VALUES that is only differentiated, its gradient the segment sum
+    of dz weighted by sign2 instead of sign (the encoder's duplicate-sym rule, scene_graph_encoder.py)."""
+
+    @staticmethod
+    def forward(ctx, a, b, T, D, bias, T2, ia, ib, it, sign, sign2, gelu, cols, csrs):
+        if cols is not None:
+            A = a[:, cols[0]:cols[0] + cols[2]]
+            B = None if cols[1] is None else a[:, cols[1]:cols[1] + cols[2]]
+        else:
+            A, B = a, b
+        ctx.save_for_backward(a, b, T, D, bias, ia, ib, it, sign, sign2)
+        ctx.cfg = (gelu, cols, csrs)
+        return ops.gather_add(A, ia, B, ib, T, it, sign, D, bias, gelu=gelu)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, T, D, bias, ia, ib, it, sign, sign2 = ctx.saved_tensors
+        gelu, cols, (csr_a, csr_b, csr_t) = ctx.cfg
+        need = ctx.needs_input_grad
+        if cols is not None:
+            A = a[:, cols[0]:cols[0] + cols[2]]
+            B = None if cols[1] is None else a[:, cols[1]:cols[1] + cols[2]]
+        else:
+            A, B = a, b
+        E = ia.numel()
+        dz, d_bias = ops.gather_add_bwd(A, ia, B, ib, T, it, sign, D, bias, gelu, g.contiguous(),
+                                        want_bias=bias is not None and need[4])
+        csr = lambda given, index, rows: given if given is not None else ops.token_csr(index, rows)
+        d_a = d_b = d_T = d_T2 = None
+        if cols is not None:
+            if need[0]:
+                covered = cols[2] * (1 if cols[1] is None else 2) == a.size(1)
+                d_a = torch.empty_like(a) if covered else torch.zeros_like(a)
+                ops.segment_rows_sum(*csr(csr_a, ia, a.size(0)), dz, out=d_a[:, cols[0]:cols[0] + cols[2]], M=E)
+                if cols[1] is not None:
+                    ops.segment_rows_sum(*csr(csr_b, ib, a.size(0)), dz, out=d_a[:, cols[1]:cols[1] + cols[2]], M=E)
+        else:
+            if need[0]:
+                d_a = ops.segment_rows_sum(*csr(csr_a, ia, a.size(0)), dz, M=E)
+            if b is not None and need[1]:
+                d_b = ops.segment_rows_sum(*csr(csr_b, ib, b.size(0)), dz, M=E)
+        if T is not None and (need[2] or need[5]):
+            csr_t = csr(csr_t, it, T.size(0))
+            if need[2]:
+                d_T = ops.segment_rows_sum(*csr_t, dz, w=sign, M=E)
+            if need[5]:
+                d_T2 = ops.segment_rows_sum(*csr_t, dz, w=sign2, M=E)
+        return (d_a, d_b, d_T, (dz if D is not None and need[3] else None), d_bias, d_T2, None, None, None, None, None, None,
+                None, None)
+
+
+def gather_add(A, ia, B=None, ib=None, T=None, it=None, sign=None, D=None, bias=None, gelu=False, csr_a=None, csr_b=None,
+               csr_t=None, T2=None, sign2=None):
+    """act(A[ia] + B[ib] + sign * T[it] + D + bias), differentiable in A, B, T, D and bias (sign and the indices get no gradient).
+    csr_*: (rowptr int32, eid int32) of the index tensors where the caller has them; ops.token_csr builds the others.
+    T2, sign2: see _GatherAdd."""
+    if (T2 is None) != (sign2 is None) or (T2 is not None and (T is None or T2.shape != T.shape)):
+        raise ValueError("gather_add: T2 and sign2 come together, beside a T of T2's shape")
+    sa, sb = _column_slice(A), _column_slice(B)
+    cols = None
+    if sa is not None and (B is None or (sb is not None and sb[0] is sa[0])):
+        cols = (sa[1], None if B is None else sb[1], A.size(1))
+        if cols[1] is not None and abs(cols[1] - cols[0]) < cols[2]:
+            cols = None                                   # overlapping slices: two gradients for autograd to add
+    if cols is not None:
+        return _GatherAdd.apply(sa[0], None, T, D, bias, T2, ia, ib, it, sign, sign2, gelu, cols, (csr_a, csr_b, csr_t))
+    return _GatherAdd.apply(A, B, T, D, bias, T2, ia, ib, it, sign, sign2, gelu, None, (csr_a, csr_b, csr_t))
+
+
+class _EmbeddingSum(torch.autograd.Function):
+    """sum_t weight[idx[:, t]]: forward on the inference kernels (ops.embedding_sum), backward one segment sum over the tokens'
+    CSR -- entry n * T + t reads row n of the gradient (gdiv = T), and row padding_idx is written as zeros."""
+
+    @staticmethod
+    def forward(ctx, weight, idx, padding_idx):
+        ctx.save_for_backward(idx)
+        ctx.cfg = (weight.size(0), padding_idx)
+        return ops.embedding_sum(weight, idx, padding_idx)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, = ctx.saved_tensors
+        V, padding_idx = ctx.cfg
+        rowptr, eid = ops.token_csr(idx, V)
+        return ops.segment_rows_sum(rowptr, eid, g.contiguous(), gdiv=idx.size(1), skip=padding_idx), None, None
+
+
+def embedding_sum(weight, idx, padding_idx=None):
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx += weight.size(0)
+    return _EmbeddingSum.apply(weight, idx, padding_idx)
+
+
+class _ZeroRowGrad(torch.autograd.Function):
+    """The identity whose backward zeroes one row: an embedding matrix read as a whole (projected into a table) keeps its
+    padding_idx row without gradient, as nn.Embedding's own lookup does."""
+
+    @staticmethod
+    def forward(ctx, weight, row):
+        ctx.row = row
+        return weight.view_as(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.clone()
+        g[ctx.row].zero_()
+        return g, None
+
+
+def zero_row_grad(weight, row):
+    return weight if row is None else _ZeroRowGrad.apply(weight, row)
 
 
 # ------------------------------------------------------------------------------------------------

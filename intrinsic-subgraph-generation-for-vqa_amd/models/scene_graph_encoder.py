@@ -19,10 +19,13 @@ from typing import Optional
 
 import torch
 
-from .. import ops
+from .. import autograd, ops
 from .layers import GraphNorm
 
 SPLIT_LINEARS = True    # inference path without the [E, 900] / [E, 600] concatenations (A/B switch for tests and tools)
+SPLIT_TRAIN = True      # the same walk under autograd (forward_split_train, csrc/isg_sgenc_bwd.hip); off: training takes the reference's
+                        # form, with the concatenations.  On by measurement: the full step at 4096 questions 127.8 against 131.8 ms,
+                        # round spreads 0.3 ms (tools/time_train_full.py --sgenc, profiles/r09_a_sgenc_train_ab.json)
 SG_VOCAB_SIZE = 2578   # reconstruction of the reference's torchtext vocab over meta_info/* 
 
 
@@ -93,6 +96,42 @@ class _MetaLayer(torch.nn.Module):
         agg = ops.scatter_mean(m, plan)                                    # :141
         return ops.mlp(self.node_model.node_mlp_2, torch.cat([x, agg], dim=1)), e_new   # :142-143
 
+    def forward_split_train(self, x, edge_index, edge_tokens, edge_sign, embedding, plan, edge_sign_grad=None):
+        """forward_split under autograd (SPLIT_TRAIN).  The slices and the concatenation of the parameters are torch ops, so that
+        their gradients flow back into edge_mlp.0 / node_mlp_1.0 (ops.derived_weight builds under no_grad); the token table is made
+        every step from the embedding matrix, behind an identity that keeps its padding_idx row without gradient (zeroing that row
+        of d table instead would also drop the pad row's share of d w_tok); every Linear is autograd.linear; both gather-adds
+        write fp32 rows and differentiate through isg_gather_add_bwd + isg_segment_rows_sum over the plan's two CSRs and the edge
+        tokens' CSR.  Nothing of size [E, 900] or [E, 600] is made or kept.
+        edge_sign_grad: `e[sym] = e[sym] * -1` (:80) flips an edge named m times in added_sym_edge ONCE, but autograd differentiates
+        the indexed read by an index_add: the embedding receives -m times that edge's gradient, while the gradient of edge_mlp.0's
+        weight is formed with the row's forward value, flipped once.  The reference trains with that and so does this walk: with
+        a sign of the backward's own, the table is made twice with equal values -- one differentiated into the weight slice under
+        edge_sign, one into the embedding under edge_sign_grad (a [V, C] Linear and one more segment sum over dz)."""
+        em, nm = self.edge_model.edge_mlp, self.node_model.node_mlp_1
+        nf, C = x.size(1), em[0].weight.size(0)
+        w_nodes = torch.cat([em[0].weight[:, :nf], em[0].weight[:, nf:2 * nf], nm[0].weight[:, :nf]], dim=0)
+        w_tok = em[0].weight[:, 2 * nf:].contiguous()
+        w_e = nm[0].weight[:, nf:].contiguous()
+        row, col = edge_index[0].contiguous(), edge_index[1].contiguous()
+        by_src, by_dst = plan.source_csr()[:2], (plan.rowptr, plan.eid)
+        by_tok = ops.token_csr(edge_tokens, embedding.weight.size(0))
+        P = autograd.linear(x, w_nodes, None, False)                       # [N, 3C]: W_a x | W_b x | W_x x
+        emb = autograd.zero_row_grad(embedding.weight, embedding.padding_idx)
+        if edge_sign_grad is None:
+            table, table_e = autograd.linear(emb, w_tok, None, False), None                # [V, C]: W_c emb
+        else:
+            table = autograd.linear(embedding.weight.detach(), w_tok, None, False)
+            table_e = autograd.linear(emb, w_tok.detach(), None, False)
+        h = ops.gather_add(P[:, :C], row, P[:, C:2 * C], col, table, edge_tokens, edge_sign, bias=em[0].bias, gelu=True,
+                           csr_a=by_src, csr_b=by_dst, csr_t=by_tok, T2=table_e, sign2=edge_sign_grad)
+        e_new = autograd.linear(h, em[2].weight, em[2].bias, False)        # :119-120 second layer
+        g = autograd.linear(e_new, w_e, None, False)                       # W_e e'
+        h = ops.gather_add(P[:, 2 * C:], row, D=g, bias=nm[0].bias, gelu=True, csr_a=by_src)
+        m = autograd.linear(h, nm[2].weight, nm[2].bias, False)            # :139-140
+        agg = ops.scatter_mean(m, plan)                                    # :141
+        return ops.mlp(self.node_model.node_mlp_2, torch.cat([x, agg], dim=1)), e_new   # :142-143
+
 
 class SceneGraphEncoder(torch.nn.Module):
     def __init__(self, hidden_dim, dist=False, vocab_size: int = SG_VOCAB_SIZE, pad_idx: Optional[int] = 1):
@@ -111,25 +150,34 @@ class SceneGraphEncoder(torch.nn.Module):
 
     def forward(self, x, edge_index, edge_attr, batch, explainer=False, explainer_stage=False, gt_scene_graphs=None,
                 plan: Optional[ops.GraphPlan] = None):
-        # train(): the BatchNorm layers use batch statistics like the reference's (torch modules); the two HIP operators
-        # of this encoder (scatter_mean, fp64 GraphNorm) differentiate through autograd.py
+        # train(): the BatchNorm layers use batch statistics like the reference's (torch modules); the HIP operators of this
+        # encoder (embedding sum, gather-add, scatter_mean, fp64 GraphNorm) differentiate through autograd.py
         first = explainer and (explainer_stage == 0)
-        x_embed_sum = x if first else ops.embedding_sum(self.sg_vocab_embedding.weight, x)   # :63-70 (sum of the token rows)
+        x_embed_sum = x if first else ops.embedding_sum(self.sg_vocab_embedding.weight, x,     # :63-70 (sum of the token rows)
+                                                        self.sg_vocab_embedding.padding_idx)
         x_bbox = ops.mlp(self.bbox_encoding, gt_scene_graphs.x_bbox.to(dtype=x_embed_sum.dtype))   # :72
         x_embed_sum = ops.mlp(self.feat_reduc, torch.cat((x_embed_sum, x_bbox), dim=1))  # :73-74
         sym = gt_scene_graphs.added_sym_edge
         if plan is None:
             plan = ops.GraphPlan.build(batch, edge_index)
-        split = (SPLIT_LINEARS and self.hidden_dim % 4 == 0 and self.sg_emb_dim % 4 == 0       # isg_gather_add: float4 rows
-                 and not (torch.is_grad_enabled() and (x_embed_sum.requires_grad or
-                                                       any(p.requires_grad for p in self.parameters()))))
-        if split:   # inference: no [E, 900] concatenation (forward_split); the sign of :80 rides along as a vector
+        rec = torch.is_grad_enabled() and (x_embed_sum.requires_grad or any(p.requires_grad for p in self.parameters()))
+        shapes = self.hidden_dim % 4 == 0 and self.sg_emb_dim % 4 == 0                       # isg_gather_add: float4 rows
+        split = shapes and (SPLIT_TRAIN if rec else SPLIT_LINEARS)
+        if split:   # no [E, 900] concatenation (forward_split / forward_split_train); the sign of :80 rides along as a vector
             sign = torch.ones(edge_attr.numel(), dtype=torch.float32, device=edge_attr.device)
             if sym is not None and sym.numel() > 0:
                 sign.index_fill_(0, sym, -1.0)        # :80 (duplicates: flipped once); index_fill_, not sign[sym] = ...: the indexed
                                                       # assignment synchronises on this stack and cannot sit in a captured step
-            x_enc, e_enc = self.scene_graph_encoding_layer.forward_split(
-                x_embed_sum.contiguous(), edge_index, edge_attr.contiguous(), sign, self.sg_vocab_embedding, plan)
+            operands = (x_embed_sum.contiguous(), edge_index, edge_attr.contiguous(), sign, self.sg_vocab_embedding, plan)
+            if rec:
+                ops.COUNTERS["sgenc_train_kernels"] += 1
+                sign_grad = None
+                if sym is not None and sym.numel() > 0:       # an edge named m times: -m in the backward (forward_split_train)
+                    named = torch.zeros_like(sign).index_add_(0, sym, torch.ones(sym.numel(), dtype=sign.dtype, device=sign.device))
+                    sign_grad = torch.where(named > 0, -named, sign)
+                x_enc, e_enc = self.scene_graph_encoding_layer.forward_split_train(*operands, edge_sign_grad=sign_grad)
+            else:
+                x_enc, e_enc = self.scene_graph_encoding_layer.forward_split(*operands)
         else:
             edge_embed = self.sg_vocab_embedding(edge_attr)                              # :76
             if sym is not None and sym.numel() > 0:

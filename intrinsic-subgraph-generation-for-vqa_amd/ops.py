@@ -131,6 +131,7 @@ sys.modules[__name__].__class__ = _OpsModule
 COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row_absmax": 0, "linear_h3p": 0, "h3p_segmented": 0, "linear_skinny": 0,
             "tile_nodes": 0, "oversize_nodes": 0,      # nodes the tile kernels took / nodes of graphs beyond a tile (mixed dispatch)
             "text_train_kernels": 0,                   # question encoder / decoder forwards under autograd on this library's kernels
+            "sgenc_train_kernels": 0,                  # scene-graph encoder forwards under autograd without the concatenations (SPLIT_TRAIN)
             "torch_attention_train": 0}                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
 
 
@@ -2128,11 +2129,25 @@ def derived_weight(tag, sources, build):
 
 def gather_add(A: Tensor, ia: Tensor, B: Optional[Tensor] = None, ib: Optional[Tensor] = None, T: Optional[Tensor] = None,
                it: Optional[Tensor] = None, sign: Optional[Tensor] = None, D: Optional[Tensor] = None,
-               bias: Optional[Tensor] = None, gelu: bool = False, planes_out: bool = False):
+               bias: Optional[Tensor] = None, gelu: bool = False, planes_out: bool = False, csr_a=None, csr_b=None, csr_t=None,
+               T2: Optional[Tensor] = None, sign2: Optional[Tensor] = None):
     """act(A[ia] + B[ib] + sign * T[it] + D + bias) -> [E, C]: the per-edge remainder of a Linear over
     cat([x[row], x[col], emb]) once its node parts are projected per node (scene_graph_encoder.py:119-120,139-140;
     csrc/isg_sgenc.hip).  A / B / T / D may be column slices of wider tensors (row stride a multiple of 4).
-    planes_out: the rows as Planes32 only (the operand of the Linear that follows, no split pass, no fp32 rows)."""
+    planes_out: the rows as Planes32 only (the operand of the Linear that follows, no split pass, no fp32 rows).
+    Under autograd through A, B, T, D or bias the call goes to autograd.gather_add (fp32 rows only: planes have no backward);
+    csr_a / csr_b / csr_t: (rowptr, eid) of ia / ib / it where the caller has them (a plan's CSRs), else token_csr builds them.
+    T2 / sign2 (autograd only): a second tensor with T's values that is only differentiated, under the factor sign2."""
+    if T2 is not None and not _rec(T2):
+        raise ValueError("gather_add: T2 is a tensor to differentiate; it takes no part in the value")
+    if _rec(A, B, T, D, bias, T2):
+        if planes_out:
+            raise NotImplementedError("gather_add(planes_out=True) has no backward: an operand requires grad; ask for fp32 rows "
+                                      "(planes_out=False), wrap the call in torch.no_grad() or detach the operands")
+        if any(t is not None and t.requires_grad for t in (sign, sign2)):
+            raise NotImplementedError("gather_add: sign has no gradient here; detach it")
+        from . import autograd
+        return autograd.gather_add(A, ia, B, ib, T, it, sign, D, bias, gelu, csr_a, csr_b, csr_t, T2, sign2)
     lib = _lib.load()
     E, C = ia.numel(), A.size(1)
     out = None if planes_out else torch.empty(E, C, dtype=torch.float32, device=A.device)
@@ -2168,14 +2183,19 @@ def gather_add(A: Tensor, ia: Tensor, B: Optional[Tensor] = None, ib: Optional[T
     return Planes32(pl, pinv, E, C) if planes_out else out
 
 
-def embedding_sum(weight: Tensor, idx: Tensor) -> Tensor:
+def embedding_sum(weight: Tensor, idx: Tensor, padding_idx: Optional[int] = None) -> Tensor:
     """sum_t weight[idx[:, t]] -> [N, C]: torch.sum(embedding(idx), dim=-2) (scene_graph_encoder.py:63-70) without the [N, T, C]
     intermediate -- isg_gather_add adds up to three gathered rows (and a dense term) per launch, so four tokens are two launches
-    over a table that sits in L2 (1.5 MB) instead of a 79 us gather x 2 and a 116 us reduction at 82 k nodes.  Inference, fp32,
-    4 | C; anything else: the torch ops.  (The sum runs ((t0 + t1) + t2) then + t3: equal to torch's to rounding.)"""
-    if (not CFG.embedding_sum or _rec(weight) or weight.dtype != torch.float32 or idx.dim() != 2 or idx.size(1) < 2 or
+    over a table that sits in L2 (1.5 MB) instead of a 79 us gather x 2 and a 116 us reduction at 82 k nodes.  fp32, 4 | C;
+    anything else: the torch ops.  (The sum runs ((t0 + t1) + t2) then + t3: equal to torch's to rounding.)
+    padding_idx: the row that gets no gradient, as nn.Embedding(padding_idx=...) has it -- under autograd the call goes to
+    autograd.embedding_sum (a segment sum over the tokens' CSR that skips that row), and the torch ops are told of it too."""
+    if (not CFG.embedding_sum or weight.dtype != torch.float32 or idx.dim() != 2 or idx.size(1) < 2 or
             weight.size(1) % 4 != 0 or not weight.is_cuda or idx.dtype != torch.int64):
-        return torch.sum(torch.nn.functional.embedding(idx, weight), dim=-2)
+        return torch.sum(torch.nn.functional.embedding(idx, weight, padding_idx=padding_idx), dim=-2)
+    if _rec(weight):
+        from . import autograd
+        return autograd.embedding_sum(weight, idx, padding_idx)
     w = weight.detach()
     cols = [idx[:, t].contiguous() for t in range(idx.size(1))]
     out, t = None, 0
@@ -2187,6 +2207,134 @@ def embedding_sum(weight: Tensor, idx: Tensor) -> Tensor:
         out = gather_add(*args, None, out)
         t += len(take)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Training of the scene-graph encoder (include/isg_sgenc_train.h, csrc/isg_sgenc_bwd.hip)
+# ------------------------------------------------------------------------------------------------
+def token_csr(idx: Tensor, V: int) -> Tuple[Tensor, Tensor]:
+    """(rowptr int32[V+1], eid int32[M]): for every token v in [0, V) the positions of `idx` (flattened) that hold it, in
+    ascending position.  A stable sort and a bisection of the sorted values, no host read -- and NOT isg_csr_build, whose rank
+    kernel compares every slot with its whole segment: fine for in-degrees bounded by a graph's size, 10^10 comparisons for a token
+    that owns 10^5 entries.  Values outside [0, V) are the caller's error (their entries land in no segment's range)."""
+    flat = idx.reshape(-1)
+    if flat.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"token_csr: integer indices, got {flat.dtype}")
+    if flat.numel() >= (1 << 31) - 1024 or V >= (1 << 31) - 1024:
+        raise ValueError("token_csr: int32 positions")
+    vals, order = torch.sort(flat, stable=True)
+    rowptr = torch.searchsorted(vals, torch.arange(V + 1, dtype=vals.dtype, device=vals.device)).to(torch.int32)
+    return rowptr, order.to(torch.int32)
+
+
+def segment_rows_chunk() -> int:
+    """Slots per piece of isg_segment_rows_sum."""
+    from . import _lib_sgenc_train
+    return int(_lib_sgenc_train.load().isg_segment_rows_chunk())
+
+
+def segment_rows_sum(rowptr: Tensor, eid: Tensor, G: Tensor, w: Optional[Tensor] = None, gdiv: int = 1, skip: Optional[int] = None,
+                     out: Optional[Tensor] = None, M: Optional[int] = None) -> Tensor:
+    """out[s] = sum over t in [rowptr[s], rowptr[s+1]) of w[eid[t]] * G[eid[t] // gdiv]  -> [S, C]  (isg_segment_rows_sum: no
+    atomics, the order of every sum a function of the CSR alone).  M: the number of entries where eid is longer than that (a
+    plan's eid has one element for an edgeless batch).  out: fp32 [S, C] rows to write, e.g. a column slice of a wider tensor.
+    skip: a segment written as zeros (padding_idx).  The entry ids are trusted like every index the forward kernels take."""
+    from . import _lib_sgenc_train
+    lib = _lib_sgenc_train.load()
+    S = rowptr.numel() - 1
+    M = eid.numel() if M is None else int(M)
+    if S < 0 or M > eid.numel() or gdiv < 1:
+        raise ValueError(f"segment_rows_sum: rowptr of {rowptr.numel()} entries, eid of {eid.numel()}, M = {M}, gdiv = {gdiv}")
+    if G.dim() != 2:
+        raise ValueError(f"segment_rows_sum: G is [rows, C], got {tuple(G.shape)}")
+    C = G.size(1)
+    if w is not None and w.numel() < M:
+        raise ValueError(f"segment_rows_sum: w has {w.numel()} factors for {M} entries")
+    if out is None:
+        out = torch.empty(S, C, dtype=torch.float32, device=G.device)
+    elif tuple(out.shape) != (S, C):
+        raise ValueError(f"segment_rows_sum: out {tuple(out.shape)}, expected {(S, C)}")
+    if S == 0:
+        return out
+    sk = -1 if skip is None else int(skip)
+    if sk < -1:
+        raise ValueError(f"segment_rows_sum: skip = {skip}")
+    ws_bytes = int(lib.isg_segment_rows_ws_bytes(M, C))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=G.device)
+    _lib.check(lib.isg_segment_rows_sum(_chk(rowptr, "rowptr", torch.int32), _chk(eid, "eid", torch.int32),
+                                        _chk(None if w is None else w.reshape(-1), "w", torch.float32, optional=True),
+                                        _chk_rows(G, "G"), G.stride(0), int(gdiv), _chk_rows(out, "out"), out.stride(0), S, M, C, sk,
+                                        ws.data_ptr(), ws_bytes, _stream()), "isg_segment_rows_sum")
+    return out
+
+
+def gather_add_bwd(A: Tensor, ia: Tensor, B: Optional[Tensor], ib: Optional[Tensor], T: Optional[Tensor], it: Optional[Tensor],
+                   sign: Optional[Tensor], D: Optional[Tensor], bias: Optional[Tensor], gelu: bool, grad_out: Tensor,
+                   want_bias: bool = True):
+    """(dz [E, C], d_bias [C] or None) of gather_add: the pre-activation is evaluated again from the operands (isg_gather_add_bwd);
+    dz is the gradient of D, and segment_rows_sum of it over the CSRs of ia / ib / it gives those of A / B / T."""
+    from . import _lib_sgenc_train
+    lib = _lib_sgenc_train.load()
+    E, C = ia.numel(), A.size(1)
+
+    def rows(t, name, n=None):
+        if t is None:
+            return 0, 0
+        if tuple(t.shape[1:]) != (C,) or (n is not None and t.size(0) != n):
+            raise ValueError(f"{name}: expected [{'*' if n is None else n}, {C}], got {tuple(t.shape)}")
+        return _chk_rows(t, name), t.stride(0)
+
+    def idx(t, name):
+        if t is None:
+            return 0
+        if t.numel() != E:
+            raise ValueError(f"{name}: expected {E} indices, got {t.numel()}")
+        return _chk(t.reshape(-1), name, torch.int64)
+
+    pa, la = rows(A, "A")
+    pb, lb = rows(B, "B")
+    pt, lt = rows(T, "T")
+    pd, ld = rows(D, "D", E)
+    pg, lg = rows(grad_out, "grad_out", E)
+    dz = torch.empty(E, C, dtype=torch.float32, device=A.device)
+    parts = max(int(lib.isg_gather_add_bwd_parts(E)), 1)
+    part = torch.zeros(parts, C, dtype=torch.float32, device=A.device) if want_bias else None
+    _lib.check(lib.isg_gather_add_bwd(pa, idx(ia, "ia"), la, pb, idx(ib, "ib"), lb, pt, idx(it, "it"),
+                                      _chk(None if sign is None else sign.reshape(-1), "sign", torch.float32, (E,), optional=True),
+                                      lt, pd, ld, _chk(bias, "bias", torch.float32, (C,), optional=True), pg, lg, dz.data_ptr(), C,
+                                      0 if part is None else part.data_ptr(), E, C, 1 if gelu else 0, _stream()),
+               "isg_gather_add_bwd")
+    return dz, (part.sum(0) if want_bias else None)
+
+
+def scatter_mean_bwd(grad_out: Tensor, plan: GraphPlan) -> Tensor:
+    """d_msg[e] = grad_out[dst[e]] / max(deg(dst[e]), 1) -> [E, C]: the backward of scatter_mean over the same plan."""
+    from . import _lib_sgenc_train
+    plan.require_csr()
+    N, C = grad_out.shape
+    if N != plan.N:
+        raise ValueError(f"grad_out has {N} rows, plan has {plan.N} nodes")
+    d_msg = torch.empty(plan.E, C, dtype=torch.float32, device=grad_out.device)
+    _lib.check(_lib_sgenc_train.load().isg_scatter_mean_bwd(
+        _chk_rows(grad_out, "grad_out"), grad_out.stride(0), _chk(plan.edge_index[1], "dst", torch.int64, (plan.E,)),
+        plan.rowptr.data_ptr(), d_msg.data_ptr(), C, plan.N, plan.E, C, _stream()), "isg_scatter_mean_bwd")
+    return d_msg
+
+
+def graph_norm_bwd(x: Tensor, plan: GraphPlan, weight: Tensor, mean_scale: Tensor, eps: float, fp64: bool, grad_out: Tensor):
+    """(d_x, d_weight, d_bias, d_mean_scale) of graph_norm in the same mode (isg_graph_norm_bwd): the per-graph partial rows of the
+    three parameter gradients -- doubles with fp64 -- are summed here in graph order and rounded once."""
+    from . import _lib_sgenc_train
+    N, C = x.shape
+    d_x = torch.empty(N, C, dtype=torch.float32, device=x.device)
+    part = torch.zeros(max(plan.B, 1), 3, C, dtype=torch.float64 if fp64 else torch.float32, device=x.device)
+    _lib.check(_lib_sgenc_train.load().isg_graph_norm_bwd(
+        _chk(x, "x", torch.float32, (plan.N, C)), plan.ptr.data_ptr(), _chk(weight, "weight", torch.float32, (C,)),
+        _chk(mean_scale, "mean_scale", torch.float32, (C,)), float(eps), 1 if fp64 else 0,
+        _chk(grad_out, "grad_out", torch.float32, (N, C)), d_x.data_ptr(), part.data_ptr(), plan.B, C, _stream()),
+        "isg_graph_norm_bwd")
+    sums = part.sum(0).float()
+    return d_x, sums[0], sums[1], sums[2]
 
 
 _WEIGHTS_GENERATION = 0      # invalidate_weight_cache() counts up: part of every weights_stamp()
