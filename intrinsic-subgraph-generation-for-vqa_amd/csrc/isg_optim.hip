@@ -6,6 +6,7 @@
 // strides over the rest, with 16-byte accesses wherever the addresses allow them.  No atomic in global memory: a sum is lanes
 // (fp32) -> xor butterfly -> the four waves in order -> ONE finishing workgroup over rows / chunks ascending, all three in double.
 #include "isg_common.hpp"
+#include "isg_mt.hpp"                 // MT_CHUNK, MT_THREADS, MT_GRID_MAX, chunk_tensor, head_elems, mt_grid: shared with isg_dist.hip
 #include "../../include/isg_optim.h"
 
 #include <limits.h>
@@ -13,10 +14,7 @@
 
 namespace isg {
 
-constexpr int MT_CHUNK = 4096;        // elements of one chunk: 4 float4 per lane of a 256-thread workgroup, 112 KB of Adam traffic
-constexpr int MT_THREADS = 256;
-constexpr int MT_GRID_MAX = 2048;     // 8 workgroups per CU resident at once; the rest of the chunks are strided over
-constexpr int FIN_THREADS = 256;      // the finishing workgroups: thread i sums a contiguous run, thread 0 the 256 runs in order
+constexpr int FIN_THREADS = 256;     // the finishing workgroups: thread i sums a contiguous run, thread 0 the 256 runs in order
 constexpr int XENT_ROWS = 4;          // rows (waves) per workgroup of the cross-entropy kernels
 
 // ---- cross-entropy ------------------------------------------------------------------------------------------------------------
@@ -150,19 +148,7 @@ __global__ __launch_bounds__(64 * XENT_ROWS) void xent_bwd_kernel(XentBwdArgs a)
   }
 }
 
-// ---- the tensor table ---------------------------------------------------------------------------------------------------------
-// The tensor of absolute chunk c (prefix[0] <= c < prefix[T]): the largest t with prefix[t] <= c.  Tensors of numel 0 own no
-// chunk (prefix[t] == prefix[t + 1]) and are stepped over.  Uniform across the workgroup: the compiler keeps it on the scalar unit.
-__device__ __forceinline__ int chunk_tensor(const int64_t *prefix, int T, int64_t c) {
-  int lo = 0, hi = T - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= c) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
+// ---- the tensor table (its geometry: isg_mt.hpp) --------------------------------------------------------------------------------
 // Sum of the lanes' fp32 totals over the workgroup, in double and in a fixed order: the xor butterfly inside a wave, then the
 // four waves ascending.  Every thread returns the total.  (Added in fp32, the 256 lane totals of a 4096-element chunk cost the
 // norm a whole fp32 ulp; in double the lanes' own roundings are all that is left, and they average out.)  `s` is 4 doubles of
@@ -175,9 +161,6 @@ __device__ __forceinline__ double block_sum(float lane_total, double *s) {
   __syncthreads();
   return t;
 }
-
-// elements in front of the first 16-byte boundary of a 4-byte aligned address
-__device__ __forceinline__ int head_elems(const void *p) { return (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2); }
 
 struct SqnormArgs {
   const int64_t *table;      // [T][4]: column 1, the gradient's address, is read
@@ -341,8 +324,6 @@ __global__ __launch_bounds__(MT_THREADS) void mt_adam_kernel(AdamArgs a) {
     }
   }
 }
-
-static inline unsigned mt_grid(int64_t chunks) { return (unsigned)(chunks < MT_GRID_MAX ? chunks : MT_GRID_MAX); }
 
 }  // namespace isg
 

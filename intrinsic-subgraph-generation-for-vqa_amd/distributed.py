@@ -6,15 +6,19 @@ collective of this path is one all-gather of answer logits [B_local, 1842] per s
 the process group backend is "nccl"; gloo in the CPU tests).  Because of reference quirks Q1/Q3/Q4 a
 shard's result is defined as the CPU path run on that shard ALONE: shards are re-indexed
 locally and nothing else crosses ranks.
+
+Training exchanges gradients: GradSync packs every gradient, scaled by 1 / world, into ONE persistent flat fp32
+bucket (isg_mt_pack, include/isg_dist.h), all-reduces the bucket once per step, and optim.Adam(grad_sync=...) takes the norm and
+the update from the reduced bucket in place.  What replaces DistributedDataParallel(...) is in INTEGRATION.md.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from .synthetic import Workload
+from .synthetic import FullWorkload, Workload
 
 
 def graph_ranges(nodes_per_graph: Tensor, edges_per_graph: Optional[Tensor], world: int, balance: bool = False
@@ -39,8 +43,11 @@ def graph_ranges(nodes_per_graph: Tensor, edges_per_graph: Optional[Tensor], wor
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
 
 
-def shard_workload(wl: Workload, rank: int, world: int, balance: bool = False) -> Workload:
-    """Rank `rank`'s contiguous graph range of `wl`, re-indexed locally (works on any device)."""
+def shard_workload(wl, rank: int, world: int, balance: bool = False):
+    """Rank `rank`'s contiguous graph range of `wl` (a Workload, or the full model's FullWorkload with its questions), re-indexed
+    locally (works on any device)."""
+    if isinstance(wl, FullWorkload):
+        return _shard_full_workload(wl, rank, world, balance)
     B = wl.glf.size(0)
     npg = torch.bincount(wl.batch, minlength=B)
     eg = wl.batch[wl.edge_index[1]]
@@ -55,6 +62,26 @@ def shard_workload(wl: Workload, rank: int, world: int, balance: bool = False) -
                     instr=wl.instr[:, lo:hi].contiguous(), glf=wl.glf[lo:hi].contiguous(), num_graphs=hi - lo,
                     max_nodes=int(npg[lo:hi].max()) if hi > lo else 0,
                     max_edges=int(epg[lo:hi].max()) if hi > lo else 0)
+
+
+def _shard_full_workload(wl: FullWorkload, rank: int, world: int, balance: bool) -> FullWorkload:
+    B = wl.questions.size(0)
+    if wl.added_sym_edge.numel() != B:
+        raise ValueError("shard_workload: a FullWorkload is cut by graph only where it holds one added_sym_edge entry per graph")
+    npg = torch.bincount(wl.batch, minlength=B)
+    eg = wl.batch[wl.edge_index[1]]
+    epg = torch.bincount(eg, minlength=B)
+    lo, hi = graph_ranges(npg.cpu(), epg.cpu(), world, balance)[rank]
+    ptr = torch.zeros(B + 1, dtype=torch.long, device=wl.batch.device)
+    ptr[1:] = npg.cumsum(0)
+    n_lo, n_hi = int(ptr[lo]), int(ptr[hi])
+    emask = (eg >= lo) & (eg < hi)
+    return FullWorkload(x=wl.x[n_lo:n_hi].contiguous(), edge_index=(wl.edge_index[:, emask] - n_lo).contiguous(),
+                        edge_attr=wl.edge_attr[emask].contiguous(), batch=(wl.batch[n_lo:n_hi] - lo).contiguous(),
+                        x_bbox=wl.x_bbox[n_lo:n_hi].contiguous(), added_sym_edge=wl.added_sym_edge[lo:hi].contiguous(),
+                        questions=wl.questions[lo:hi].contiguous(), att_mask=wl.att_mask[lo:hi].contiguous(),
+                        max_nodes=int(npg[lo:hi].max()) if hi > lo else 0, max_edges=int(epg[lo:hi].max()) if hi > lo else 0,
+                        graph_sizes=torch.stack([npg[lo:hi], epg[lo:hi]]).cpu())
 
 
 def all_gather_logits(logits: Tensor, out: Optional[Tensor] = None, group=None, async_op: bool = False):
@@ -174,3 +201,243 @@ class GatherPipeline:
             d.update(ragged=True, rows_per_rank=list(self.sizes), padded_rows=self.b_max,
                      payload_bytes_per_rank=[n * row for n in self.sizes])
         return d
+
+
+# ---- data-parallel training: one flat gradient bucket ----------------------------------------------------------------------------
+# launches and sends since import: tests and tools/time_train_ddp.py count them
+LAUNCHES = {"pack": 0, "reduce": 0, "src_copies": 0}
+
+
+def bucket_layout(numels: Sequence[int], align: int = 64) -> Tuple[List[int], int]:
+    """(offsets, total) of the slots of tensors of `numels` elements in one flat buffer, in elements: every slot starts on a
+    multiple of `align` (64 fp32 = 256 B: a slot and a gradient that torch allocated share their offset from a 16-byte boundary,
+    so the pack, the norm and Adam take their float4 bodies), slots follow one another in order and never overlap; `total` is the
+    end of the last slot rounded up to `align`.  An empty tensor owns an empty slot at the next slot's offset."""
+    if align < 1:
+        raise ValueError(f"bucket_layout: align = {align}")
+    offsets, off = [], 0
+    for n in numels:
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"bucket_layout: numel {n}")
+        offsets.append(off)
+        off += (n + align - 1) // align * align
+    return offsets, off
+
+
+def union_mask(mask: Sequence[bool], group=None, device=None) -> List[bool]:
+    """The element-wise OR of every rank's `mask` over `group`: ONE all-gather of the T flags (uint8, on `device`: the GPU for an
+    nccl group, the host for gloo) and one copy to the host.  Without an initialised process group the mask comes back as it is."""
+    import torch.distributed as dist
+    mask = [bool(m) for m in mask]
+    if not (dist.is_available() and dist.is_initialized()):
+        return mask
+    world = dist.get_world_size(group)
+    mine = torch.tensor(mask, dtype=torch.uint8, device=device)
+    if mine.numel() == 0:
+        return mask
+    out = torch.empty(world * mine.numel(), dtype=torch.uint8, device=mine.device)
+    dist.all_gather_into_tensor(out, mine, group=group)
+    return [bool(v) for v in out.view(world, -1).amax(dim=0).cpu().tolist()]
+
+
+def _named(params) -> List[Tuple[str, Tensor]]:
+    out = []
+    for i, item in enumerate(params):
+        if isinstance(item, tuple):
+            name, p = item
+            out.append((f"parameter '{name}'", p))
+        else:
+            out.append((f"parameter {i} (shape {tuple(item.shape)})", item))
+    return out
+
+
+class GradSync:
+    """The gradients of `params` (an iterable of parameters, or of (name, parameter) as named_parameters() gives them), averaged
+    over the ranks of `group` in one flat fp32 bucket.
+
+      sync = GradSync(model.named_parameters())
+      opt = optim.Adam(model.parameters(), ..., grad_sync=sync)
+      loss.backward(); sync.pack(); sync.reduce(); opt.step()            # train.train_step(..., sync=sync) does this
+
+    pack() launches isg_mt_pack once: slot = grad / world (times `scale`; `accumulate=True` adds into the slot with one fmaf, for
+    micro-batches).  reduce() is ONE all-reduce (SUM) of the whole bucket, ordered behind the pack on the current stream:
+    torch.distributed.all_reduce(bucket, group=group), or `all_reduce(bucket)` -- the hook for another transport, a callable that
+    sums a tensor in place over the ranks.  The optimizer then reads the reduced gradients where they lie (grad_ptr); nothing is
+    unpacked, p.grad keeps the local gradient.  Neither call reads a device value on the host.
+
+    The parameter set is fixed at the first pack(): the union over the ranks of the parameters that have a gradient there (one
+    all-gather of a T-bit mask; with an `all_reduce` hook the mask goes through the hook once, as a [T] fp32 tensor on the
+    parameters' device, and is read back once).  From then on a member whose local grad is None packs zeros and is still stepped
+    with the other ranks' average -- DistributedDataParallel(find_unused_parameters=True) -- and a parameter outside the set that
+    receives a gradient raises an error that names it.  Slots start on multiples of 64 elements; the padding between them is
+    zeroed once, stays zero under a sum and adds nothing to a norm taken over the slots.
+
+    `world` defaults to the group's size (1 without a process group), `rank` to the group's rank (0).  With world 1 and
+    force=False the sync is inactive: pack() and reduce() return at once and the optimizer reads p.grad as it does without one.
+    The all-reduce is not overlapped with the backward and nothing here is captured into a hipGraph."""
+
+    def __init__(self, params, group=None, world: Optional[int] = None, all_reduce: Optional[Callable[[Tensor], None]] = None,
+                 force: bool = False, rank: Optional[int] = None):
+        import torch.distributed as dist
+        from . import optim
+        self.named = _named(params)
+        if not self.named:
+            raise ValueError("GradSync: no parameters")
+        self.params = [p for _, p in self.named]
+        self.group, self.all_reduce = group, all_reduce
+        up = dist.is_available() and dist.is_initialized()
+        self.world = int(world) if world is not None else (dist.get_world_size(group) if up else 1)
+        self.rank = int(rank) if rank is not None else (dist.get_rank(group) if up else 0)
+        if self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError(f"GradSync: rank {self.rank} of world {self.world}")
+        self.active = self.world > 1 or bool(force)
+        self.device = self.params[0].device
+        for name, p in self.named:
+            optim._check_param(p, f"GradSync: {name}")
+            if p.device != self.device:
+                raise ValueError(f"GradSync: {name} lives on {p.device}, the first parameter on {self.device}; one bucket, one device")
+        self._index = {id(p): i for i, p in enumerate(self.params)}
+        if len(self._index) != len(self.params):
+            raise ValueError("GradSync: a parameter is listed twice")
+        self.bucket: Optional[Tensor] = None
+        self.members: Optional[List[int]] = None          # indices into params of the set, fixed at the first pack()
+        self._slot = {}                                   # id(param) -> (offset, numel)
+        self._table: Optional[Tensor] = None              # device int64 [4 T + 1]: src | dst | numel | chunk_prefix
+        self._src_key = None
+        self._chunks = 0
+
+    # ---- the set and the bucket -----------------------------------------------------------------------------------------------
+    def _agree(self, mask: List[bool]) -> List[bool]:
+        if self.all_reduce is not None:
+            t = torch.tensor([1.0 if m else 0.0 for m in mask], dtype=torch.float32).to(self.device)
+            self.all_reduce(t)
+            return [v > 0.0 for v in t.cpu().tolist()]
+        return union_mask(mask, self.group, self.device) if self.world > 1 else mask
+
+    def _fix_set(self) -> None:
+        from . import _lib_optim, optim
+        mask = self._agree([p.grad is not None for p in self.params])
+        self.members = [i for i, m in enumerate(mask) if m]
+        numels = [self.params[i].numel() for i in self.members]
+        offsets, total = bucket_layout(numels)
+        self.bucket = torch.zeros(total, dtype=torch.float32, device=self.device)       # the padding is zeroed here, once
+        assert self.bucket.data_ptr() % 16 == 0
+        self._slot = {id(self.params[i]): (o, n) for i, o, n in zip(self.members, offsets, numels)}
+        prefix = optim.chunk_prefix(numels, int(_lib_optim.load().isg_mt_chunk_elems()))
+        self._chunks = prefix[-1]
+        T, base = len(numels), self.bucket.data_ptr()
+        self._table = torch.zeros(4 * T + 1, dtype=torch.int64, device=self.device)
+        fixed = [base + 4 * o for o in offsets] + numels + prefix
+        self._send(self._table[T:], fixed)
+
+    def _send(self, dst: Tensor, values: List[int]) -> None:
+        host = torch.tensor(values, dtype=torch.int64)
+        if self.device.type == "cuda":
+            host = host.pin_memory()                      # fresh per send: never rewritten under a pending copy
+        dst.copy_(host, non_blocking=True)
+
+    def _sources(self) -> List[int]:
+        src = []
+        for i, (name, p) in enumerate(self.named):
+            g = p.grad
+            if id(p) not in self._slot:
+                if g is not None:
+                    raise RuntimeError(f"GradSync: {name} received a gradient but had none on any rank at the first pack(); the "
+                                       "set of synchronised parameters is fixed there")
+                continue
+            if g is None:
+                src.append(0)                             # unused on this rank in this step: zeros
+                continue
+            if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device:
+                raise ValueError(f"GradSync: the gradient of {name} is not a dense contiguous fp32 tensor on the parameter's device")
+            src.append(g.data_ptr())
+        return src
+
+    # ---- the step -------------------------------------------------------------------------------------------------------------
+    def pack(self, accumulate: bool = False, scale: float = 1.0) -> None:
+        """bucket slot = (scale / world) * grad, or += with accumulate=True (train_step's micro-batches pass scale = 1 /
+        accumulate).  One launch; the source addresses are sent only when one changed since the last pack."""
+        if not self.active:
+            return
+        from . import _lib, _lib_dist, ops
+        if self.members is None:
+            self._fix_set()
+        src = self._sources()
+        T = len(src)
+        if T == 0:
+            return
+        key = tuple(src)
+        if key != self._src_key:
+            self._send(self._table[:T], src)
+            self._src_key = key
+            LAUNCHES["src_copies"] += 1
+        base = self._table.data_ptr()
+        _lib.check(_lib_dist.load().isg_mt_pack(base, base + 8 * T, base + 16 * T, base + 24 * T, T, self._chunks,
+                                                float(scale) / self.world, int(bool(accumulate)), ops._stream()), "isg_mt_pack")
+        LAUNCHES["pack"] += 1
+
+    def reduce(self) -> None:
+        """One all-reduce (SUM) of the whole bucket, behind the pack in the current stream's order."""
+        if not self.active:
+            return
+        if self.bucket is None:
+            raise RuntimeError("GradSync.reduce: nothing was packed yet")
+        if self.bucket.numel() == 0:
+            return
+        if self.all_reduce is not None:
+            self.all_reduce(self.bucket)
+        else:
+            import torch.distributed as dist
+            dist.all_reduce(self.bucket, group=self.group)
+        LAUNCHES["reduce"] += 1
+
+    def has(self, p: Tensor) -> bool:
+        """Whether p belongs to the synchronised set (known after the first pack())."""
+        if self.members is None:
+            raise RuntimeError("GradSync: the parameter set is fixed by the first pack()")
+        return id(p) in self._slot
+
+    def knows(self, p: Tensor) -> bool:
+        return id(p) in self._index
+
+    def grad(self, p: Tensor) -> Tensor:
+        """The averaged gradient of p after reduce(): a view of its slot, in p's shape."""
+        if not self.has(p):
+            raise KeyError("GradSync.grad: the parameter is not in the synchronised set")
+        o, n = self._slot[id(p)]
+        return self.bucket[o:o + n].view(p.shape)
+
+    def grad_ptr(self, p: Tensor) -> int:
+        if not self.has(p):
+            raise KeyError("GradSync.grad_ptr: the parameter is not in the synchronised set")
+        return self.bucket.data_ptr() + 4 * self._slot[id(p)][0]
+
+    # ---- the replicas ---------------------------------------------------------------------------------------------------------
+    def broadcast_params(self, src: int = 0) -> None:
+        """Every parameter takes rank `src`'s values (a global rank, as torch.distributed.broadcast counts): the start of training,
+        as DistributedDataParallel's constructor does."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            if self.world == 1:
+                return
+            raise RuntimeError("GradSync.broadcast_params needs an initialised process group")
+        with torch.no_grad():
+            for p in self.params:
+                dist.broadcast(p.data, src=src, group=self.group)
+
+    def params_in_sync(self) -> Tensor:
+        """A device flag (uint8 0-dim, 1 = in sync) and no host read: every rank sums its parameters and their squares in float64,
+        the two checksums are all-reduced with MAX and with MIN, and the flag is set where both differences are exactly 0."""
+        import torch.distributed as dist
+        with torch.no_grad():
+            sums = torch.stack([torch.stack([p.sum(dtype=torch.float64), (p.double() * p).sum()]) if p.numel() else
+                                torch.zeros(2, dtype=torch.float64, device=self.device) for p in self.params]).sum(dim=0)
+            if not (dist.is_available() and dist.is_initialized()):
+                if self.world == 1:
+                    return torch.ones((), dtype=torch.uint8, device=self.device)
+                raise RuntimeError("GradSync.params_in_sync needs an initialised process group")
+            hi, lo = sums.clone(), sums.clone()
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
+            dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.group)
+            return ((hi - lo) == 0).all().to(torch.uint8)

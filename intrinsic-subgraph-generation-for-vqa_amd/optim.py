@@ -21,6 +21,11 @@ a sync whenever an address changed since the last step (zero_grad(set_to_none=Tr
 usually hands the same blocks back, and then nothing is sent).  A staging buffer is never rewritten: torch's pinned allocator
 keeps a block that a pending copy reads out of circulation until the copy has run.
 
+With `grad_sync` (a distributed.GradSync that is active) the gradient column of the table holds the addresses of the sync's bucket
+slots, for every parameter of the sync's set -- also one whose local p.grad is None, which steps with the other ranks' average.
+The norm is then the norm of the AVERAGED gradients (DistributedDataParallel followed by clip_grad_norm_), identical on every
+rank, and so is the decision to skip; the slots never move, so the table is sent once per run.
+
 When the norm is taken (either option set), a nonfinite norm always skips the step: with skip_nonfinite=False and a
 max_grad_norm, torch would multiply every gradient by NaN instead; that is not reproduced.
 """
@@ -58,13 +63,15 @@ def _check_param(p: Tensor, name: str) -> None:
 
 class Adam(torch.optim.Adam):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 decoupled: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = True, amsgrad: bool = False):
+                 decoupled: bool = False, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = True, amsgrad: bool = False,
+                 grad_sync=None):
         if amsgrad:
             raise NotImplementedError("optim.Adam: amsgrad=True is not built (no max_exp_avg_sq in the kernel)")
         if isinstance(lr, Tensor):
             raise TypeError("optim.Adam: a tensor lr would be read on the host every step; pass a float")
         self.decoupled, self.skip_nonfinite = bool(decoupled), bool(skip_nonfinite)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_sync = grad_sync
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
         first = self.param_groups[0]["params"][0]
         dev = self._device = first.device
@@ -133,11 +140,19 @@ class Adam(torch.optim.Adam):
         """[(param, grad, exp_avg, exp_avg_sq addresses, numel)] of the parameters that have a gradient, group after group, and
         each group's (first row, end row)."""
         rows, spans = [], []
+        sync = self.grad_sync if self.grad_sync is not None and self.grad_sync.active else None
         for gi, group in enumerate(self.param_groups):
             r0 = len(rows)
             if isinstance(group["lr"], Tensor):
                 raise TypeError("optim.Adam: a tensor lr would be read on the host every step; write a float into param_groups")
             for i, p in enumerate(group["params"]):
+                if sync is not None:
+                    if not sync.knows(p):
+                        raise ValueError(f"optim.Adam: parameter {i} of group {gi} (shape {tuple(p.shape)}) is not among grad_sync's parameters")
+                    if sync.has(p):               # the reduced gradient in its bucket slot, whether or not this rank had one
+                        st = self._init_state(p)
+                        rows.append((p.data_ptr(), sync.grad_ptr(p), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()))
+                    continue
                 g = p.grad
                 if g is None:
                     continue                      # as torch: a parameter without a gradient sits this step out
