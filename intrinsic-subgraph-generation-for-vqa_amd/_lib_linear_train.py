@@ -1,0 +1,35 @@
+"""ctypes binding of the entry points of a Linear's backward in libisg_hip.so (include/isg_linear_train.h), derived from the header like _lib's.
+
+The header has an ABI version of its own (ISG_LINEAR_TRAIN_ABI_VERSION): no other header moves when the backward's kernels do.  The
+symbols live in the same shared library (csrc/isg_linear_bwd.hip).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+from . import _lib
+
+HEADER_PATH = os.path.join(os.path.dirname(_lib._HERE), "include", "isg_linear_train.h")
+# name -> (restype, argtypes) of every symbol include/isg_linear_train.h declares; ISG_LINEAR_TRAIN_ABI_VERSION
+SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
+
+_bound = None
+
+
+def load():
+    """The product library with the Linear-backward symbols bound; raises (never falls back) when one is missing."""
+    global _bound
+    if _bound is not None:
+        return _bound
+    _lib.load()                                   # existence, the inference ABI
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    try:
+        _lib.bind(lib, SIGNATURES)
+    except AttributeError as e:
+        raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/isg_linear_train.h ({e}): rebuild it (build())") from None
+    v = lib.isg_linear_train_abi_version()
+    if v != ABI_VERSION:
+        raise _lib.IsgError(f"libisg_hip.so Linear-backward ABI version {v}, binding expects {ABI_VERSION}")
+    _bound = lib
+    return lib

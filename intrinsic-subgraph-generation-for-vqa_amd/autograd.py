@@ -381,11 +381,18 @@ def zero_row_grad(weight, row):
 # (`tools/time_wgrad.py --mid` times that range; at 4096 x 1842 x 512 it is 26 us slower, profiles/r01_o_wgrad_vs_hipblaslt.txt): the
 # switch sits here for the error, not for the time.
 WGRAD_MIN_ROWS = 2048
+# The backward on csrc/isg_linear_bwd.hip (include/isg_linear_train.h): dz and db in one pass (ops.linear_bwd_prep) instead of
+# aten.gelu_backward / g * (z > 0), g.sum(0) and g.contiguous(); dW on the bf16 matrix cores (ops.linear_wgrad_bf16x6) at
+# M >= WGRAD_MIN_ROWS.  Off: every line runs as before.  On by DESIGN.md section 24's rule: the full training step at 4096
+# questions takes 98.4 ms with it and 125.4 ms without (7 rounds each, spreads 0.3 ms, every round of one below every round of the
+# other; profiles/r14_b_linear_bwd_ab.json).
+LINEAR_BWD_KERNELS = True
 
 
 class _Linear(torch.autograd.Function):
     """y = act(x W^T + b): forward on isg_linear_bf16x6 (pre-activation kept when act = GELU; ReLU fused into the kernel's epilogue
-    and its RESULT kept: y > 0 is all the backward needs of it), backward as fp32 GEMMs."""
+    and its RESULT kept: y > 0 is all the backward needs of it); backward on csrc/isg_linear_bwd.hip (LINEAR_BWD_KERNELS), or as
+    fp32 GEMMs and torch passes with the switch off."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gelu, relu=False):
@@ -398,6 +405,8 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, z = ctx.saved_tensors
+        if LINEAR_BWD_KERNELS:
+            return _Linear._backward_kernels(ctx, g, x, weight, z)
         g = g.contiguous()
         if ctx.gelu:
             g = torch.ops.aten.gelu_backward(g, z)
@@ -411,6 +420,28 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[1]:   # long-and-thin reductions on the split-M kernel; short ones are hipBLASLt's home turf
             dw = ops.linear_wgrad(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None
+
+    @staticmethod
+    def _backward_kernels(ctx, g, x, weight, z):
+        ops.COUNTERS["linear_bwd_kernels"] += 1
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        mode = 1 if ctx.gelu else 2 if ctx.relu else 0
+        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
+            g = g.contiguous()
+        if mode == 0:                   # identity: the bias gradient alone, g is not copied
+            db = ops.linear_bwd_prep(g, None, 0, want_dz=False, want_db=True)[1] if want_db else None
+            if not g.is_contiguous():
+                g = g.contiguous()
+        else:
+            g, db = ops.linear_bwd_prep(g, z, mode, want_dz=True, want_db=want_db)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
+                  if (g.size(1) & 3) == 0 else g @ weight)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
         return dx, dw, db, None, None
 
 

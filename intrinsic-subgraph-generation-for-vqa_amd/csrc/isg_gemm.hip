@@ -19,6 +19,7 @@
 //   epilogue acc (col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)) -> + bias -> optional exact GELU -> transposed
 //           through a per-wave LDS patch -> 16-byte-per-lane row stores
 #include "isg_common.hpp"
+#include "isg_bf16x3.hpp"   // bf16_to_f32, split3
 
 #include <stdlib.h>
 
@@ -31,23 +32,10 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int GM_BM = 128, GM_BN = 128, GM_BK = 32;
 constexpr int GM_LD = GM_BK + 8;   // bf16 elements per LDS row (80 bytes)
 
-__device__ __forceinline__ float bf16_to_f32(__bf16 v) {
-  return __uint_as_float(((unsigned)__builtin_bit_cast(unsigned short, v)) << 16);
-}
-
 // keep a value alive without using it (ablation builds only)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void keep(const float4 &v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
 __device__ __forceinline__ void keep(const bf16x8 &v) { asm volatile("" ::"v"(__builtin_bit_cast(i32x4, v))); }
-
-// x -> (x1, x2, x3), xk = bf16(remainder)
-__device__ __forceinline__ void split3(float x, __bf16 &p1, __bf16 &p2, __bf16 &p3) {
-  p1 = (__bf16)x;
-  const float r1 = x - bf16_to_f32(p1);
-  p2 = (__bf16)r1;
-  const float r2 = r1 - bf16_to_f32(p2);
-  p3 = (__bf16)r2;
-}
 
 // planes[q][row][kp] (kp = K rounded up to GM_BK, zero filled) from fp32 w[row][K]
 __global__ void split_bf16x3_kernel(const float *__restrict__ w, int rows, int K, int Kp, __bf16 *__restrict__ planes) {

@@ -7,7 +7,9 @@
 // operands, one fp32 per lane taken along a ROW of g / x -- exactly how the row-major activations sit in memory and in
 // LDS -- whereas the bf16 instruction wants 8 consecutive values along the contraction axis, i.e. a transpose of both
 // operands.  Products are exact fp32 x fp32 with fp32 accumulation.  (The fp32 MFMA peak is 157 TF; the fp32 hipBLASLt
-// kernels torch picks for these shapes reach ~50.)
+// kernels torch picks for these shapes reach ~50.)  isg_linear_wgrad_bf16x6 (isg_linear_bwd.hip) is this kernel with that
+// transpose done by gfx950's transposed LDS read and the forward's six bf16 products; autograd._Linear uses it when
+// autograd.LINEAR_BWD_KERNELS is on, and this one otherwise.
 #include "isg_common.hpp"
 
 #include <stdlib.h>

@@ -132,7 +132,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "tile_nodes": 0, "oversize_nodes": 0,      # nodes the tile kernels took / nodes of graphs beyond a tile (mixed dispatch)
             "text_train_kernels": 0,                   # question encoder / decoder forwards under autograd on this library's kernels
             "sgenc_train_kernels": 0,                  # scene-graph encoder forwards under autograd without the concatenations (SPLIT_TRAIN)
-            "torch_attention_train": 0}                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
+            "torch_attention_train": 0,                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
+            "linear_bwd_kernels": 0}                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
 
 
 def reset_counters() -> None:
@@ -3162,6 +3163,74 @@ def linear_wgrad(grad_out: Tensor, x: Tensor) -> Tensor:
     part = torch.empty(splits, N, K, dtype=torch.float32, device=x.device)
     _lib.check(lib.isg_linear_wgrad(_chk(grad_out, "grad_out", torch.float32, (M, N)), _chk(x, "x", torch.float32, (M, K)),
                                     part.data_ptr(), M, N, K, N, K, splits, _stream()), "isg_linear_wgrad")
+    return part.sum(0) if splits > 1 else part[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# A Linear's backward (include/isg_linear_train.h, csrc/isg_linear_bwd.hip); autograd._Linear wires these
+# ------------------------------------------------------------------------------------------------
+def _chk_rows4(t: Tensor, name: str) -> int:
+    """_chk for a 2-D fp32 tensor whose rows may be strided and are aligned to 4 bytes only (a column slice of a wider tensor)."""
+    if not t.is_cuda:
+        raise _lib.IsgError(f"{name} must live on the GPU (got {t.device}); this path has no CPU fallback")
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)):
+        raise ValueError(f"{name}: expected fp32 [rows, cols] with contiguous columns and a row pitch of at least cols")
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise NotImplementedError(f"{name} requires grad but this operator has no backward (see autograd.py)")
+    return t.data_ptr()
+
+
+def _pitch(t: Tensor) -> int:
+    return max(int(t.stride(0)), int(t.size(1))) if t.size(0) > 1 else int(t.size(1))
+
+
+LINEAR_BWD_MODES = {"identity": 0, "gelu": 1, "relu": 2}
+
+
+def linear_bwd_prep(g: Tensor, saved: Optional[Tensor], mode: int, want_dz: bool = True, want_db: bool = True):
+    """(dz | None, db | None) of a Linear's upstream gradient g [M, N] in one pass (isg_linear_bwd_prep): mode 0 dz = g (asked for
+    db alone, g is not copied), 1 dz = g * GELU'(saved = the pre-activation), 2 dz = g * (saved = the ReLU's result > 0); db = the
+    column sums of dz, from the kernel's partial rows."""
+    from . import _lib_linear_train
+    lib = _lib_linear_train.load()
+    if not (want_dz or want_db):
+        raise ValueError("linear_bwd_prep: nothing asked for")
+    if mode not in (0, 1, 2):
+        raise ValueError(f"linear_bwd_prep: mode {mode} (0 identity, 1 GELU, 2 ReLU)")
+    if mode != 0 and (saved is None or saved.shape != g.shape):
+        raise ValueError("linear_bwd_prep: modes 1 and 2 need the saved tensor, of the gradient's shape")
+    gp = _chk_rows4(g, "g")
+    sp = 0 if mode == 0 else _chk_rows4(saved, "saved")
+    M, N = g.shape
+    dz = torch.empty(M, N, dtype=torch.float32, device=g.device) if want_dz else None
+    if M == 0 or N == 0:
+        return dz, (torch.zeros(N, dtype=torch.float32, device=g.device) if want_db else None)
+    P = int(lib.isg_linear_bwd_prep_parts(M, N))
+    part = torch.empty(P, N, dtype=torch.float32, device=g.device) if want_db else None
+    _lib.check(lib.isg_linear_bwd_prep(gp, _pitch(g), sp, 0 if mode == 0 else _pitch(saved), mode,
+                                       0 if dz is None else dz.data_ptr(), N, 0 if part is None else part.data_ptr(), M, N,
+                                       _stream()), "isg_linear_bwd_prep")
+    db = None if part is None else (part.sum(0) if P > 1 else part[0])
+    return dz, db
+
+
+def linear_wgrad_bf16x6(grad_out: Tensor, x: Tensor, splits: Optional[int] = None) -> Tensor:
+    """dW[N,K] = grad_out^T x for y = x W^T: split-M GEMM on the bf16 matrix cores, six products per pair of fp32 values
+    (csrc/isg_linear_bwd.hip).  Rows of both operands may be strided (column slices)."""
+    from . import _lib_linear_train
+    lib = _lib_linear_train.load()
+    M, N = grad_out.shape
+    K = x.size(1)
+    if x.size(0) != M:
+        raise ValueError(f"linear_wgrad_bf16x6: grad_out has {M} rows, x {x.size(0)}")
+    if M == 0 or N == 0 or K == 0:
+        return torch.zeros(N, K, dtype=torch.float32, device=x.device)
+    gp, xp = _chk_rows4(grad_out, "grad_out"), _chk_rows4(x, "x")
+    if splits is None:
+        splits = int(lib.isg_linear_wgrad_bf16x6_splits(M, N, K))
+    part = torch.empty(splits, N, K, dtype=torch.float32, device=x.device)
+    _lib.check(lib.isg_linear_wgrad_bf16x6(gp, xp, part.data_ptr(), M, N, K, _pitch(grad_out), _pitch(x), splits, _stream()),
+               "isg_linear_wgrad_bf16x6")
     return part.sum(0) if splits > 1 else part[0]
 
 

@@ -4,6 +4,7 @@ process, the two alternating round by round.
 
   python tools/time_train_full.py [--graphs 4096] [--rounds 7] [--steps 5] [--out profiles/<name>.json] [--kernels]
   python tools/time_train_full.py --sgenc [--out profiles/<name>.json]
+  python tools/time_train_full.py --linear-bwd [--out profiles/<name>.json]
 
 --sgenc is the same A/B for the scene-graph encoder's switch (models/scene_graph_encoder.SPLIT_TRAIN: on = the walk without the
 [E, 900] / [E, 600] concatenations on csrc/isg_sgenc_bwd.hip, off = the reference's form): the full step, the encoder alone
@@ -11,6 +12,11 @@ process, the two alternating round by round.
 over the workload's CSRs (by source, by destination, by edge token; the node tokens with gdiv = 4) beside a torch copy_ of the
 rows it reads, the token CSRs once as the workload has them (evenly loaded) and once skewed the way GQA is (one relation on 40 % of
 the edges, the pad id in half of the attribute slots).
+
+--linear-bwd is the A/B of autograd.LINEAR_BWD_KERNELS (on = every Linear's backward through csrc/isg_linear_bwd.hip: dz and db in
+one pass, dW on the bf16 matrix cores; off = the torch passes and the fp32 split-M kernel) on the full step and on the question
+side, with section 22's rule for the default: on iff the median gain exceeds the larger round spread and every round of one
+variant lies below every round of the other.
 
 Shape: bench.py --full's `full_model` leg (synthetic.make_full_workload: 4096 questions of 12 tokens, C = 300, I-MLE k = 5), the
 model in train() mode with the constructors' dropouts (0.1 on the question side).  Each figure is the median over the rounds of
@@ -161,6 +167,43 @@ def sgenc_main(a, model, wl, sg, target, dev):
     return res
 
 
+def linear_bwd_main(a, model, wl, sg, target):
+    from isubgvqa_amd import autograd
+    switch, names = (autograd, "LINEAR_BWD_KERNELS"), ("linear_bwd_kernels", "torch_passes")
+    w_lang = None
+
+    def full_step(i):
+        model.zero_grad(set_to_none=True)
+        logits = model(wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.questions, wl.att_mask, return_masks=True, scene_graphs=sg,
+                       seed=1000 + i)[0]
+        torch.nn.functional.cross_entropy(logits, target).backward()
+
+    def language_step(i):
+        nonlocal w_lang
+        model.zero_grad(set_to_none=True)
+        glf, instr = model.language_features(wl.questions, wl.att_mask, None, 1000 + i)
+        if w_lang is None:
+            w_lang = (torch.randn_like(glf), torch.randn_like(instr))
+        ((glf * w_lang[0]).sum() + (instr * w_lang[1]).sum()).backward()
+
+    res = {"workload": f"full ISubGVQA model, {a.graphs} questions, N = {wl.x.size(0)} nodes, E = {wl.edge_attr.numel()} edges, train() mode",
+           "method": f"{a.rounds} rounds x {a.steps} steps per variant, variants alternating inside a round; host clock around synchronised steps",
+           "device": torch.cuda.get_device_name(0), "shipped_default_LINEAR_BWD_KERNELS": autograd.LINEAR_BWD_KERNELS}
+    ops.reset_counters()
+    res["question_side_fwd_bwd"] = summary(ab(language_step, a.rounds, a.steps, switch=switch, names=names))
+    res["full_model_fwd_bwd"] = summary(ab(full_step, a.rounds, a.steps, switch=switch, names=names))
+    res["counters"] = {k: v for k, v in ops.counters().items() if k in ("linear_bwd_kernels", "text_train_kernels", "torch_linear")}
+    on, off = (res["full_model_fwd_bwd"][n] for n in names)
+    gain = off["median_ms"] - on["median_ms"]
+    noise = max(on["max_ms"] - on["min_ms"], off["max_ms"] - off["min_ms"])
+    separated = on["max_ms"] < off["min_ms"]
+    res["decision"] = {"full_step_gain_ms": round(gain, 3), "larger_round_spread_ms": round(noise, 3),
+                       "every_round_on_below_every_round_off": bool(separated), "ships_on": bool(gain > noise and separated),
+                       "rule": "on iff median(off) - median(on) > the larger of the two variants' (max - min) over the rounds and every "
+                               "round of `on` is below every round of `off`"}
+    return res
+
+
 def operator_times(model, wl, dev):
     """HIP-event time of the question side's forward and of its backward, per variant, and of the autograd operators one by one
     (each timed alone on the shapes of encoder layer 0: forward, then backward)."""
@@ -228,6 +271,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--sgenc", action="store_true", help="A/B of the scene-graph encoder's SPLIT_TRAIN instead of the question side's switch")
+    ap.add_argument("--linear-bwd", action="store_true", help="A/B of autograd.LINEAR_BWD_KERNELS instead of the question side's switch")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
     dev = torch.device("cuda:0")
@@ -237,8 +281,8 @@ def main():
     sg = wl.scene_graphs()
     target = torch.randint(0, 1842, (a.graphs,), device=dev)
     w_lang = None
-    if a.sgenc:
-        res = sgenc_main(a, model, wl, sg, target, dev)
+    if a.sgenc or a.linear_bwd:
+        res = sgenc_main(a, model, wl, sg, target, dev) if a.sgenc else linear_bwd_main(a, model, wl, sg, target)
         print(json.dumps(res), flush=True)
         if a.out:
             with open(a.out, "w") as fh:
