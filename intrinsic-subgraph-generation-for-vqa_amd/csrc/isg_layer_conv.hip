@@ -24,6 +24,8 @@
 #include "isg_f16x3.hpp"
 
 #include "isg_diag.hpp"
+#include "isg_live_tables.hpp"
+#include "../../include/isg_masked.h"
 
 ISG_DIAG_BUFFER(g_lc_stamps)            // -DISG_DIAG builds only (tools/stamp_layer_conv.py): [workgroups * 8 waves][16] int64
 #define LC_STAMP(i) ISG_DIAG_ADD(i)
@@ -64,6 +66,8 @@ struct LcArgs {
   unsigned char *row_dead;          // optional, masked launches: [N, H], 1 = every accumulator bit of the (row, head) was zero
                                     // (last: the fields before it keep the offsets the unmasked instantiations were compiled with)
   int G;                            // tiles per group of gatv2_layer_conv_groups_kernel (the per-tile kernel does not read it)
+  const unsigned char *live_tables; // optional, the groups kernel: every tile's table set as isg_layer_conv_live_tables wrote it,
+                                    // image t at t * LG_TILE_BYTES (NULL: the kernel scans the tiles itself); no other kernel reads it
 };
 
 // The live slots of a masked tile: bit s of w[s >> 6] is set when slot s carries a mask whose bits are not +-0.  A slot with a
@@ -792,18 +796,20 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
 // sits in, so out / alpha / rowmax / row_dead are the per-tile kernel's bits for finite inputs.  A group whose list would pass 64
 // rows runs its tiles one by one through the same code.  The panel of node planes and the edge panel image share their LDS here
 // (nothing of the next group is in flight under a product), which pays for the G table sets.
-constexpr int LG_MAXG = 6, LC_GROUP_DEFAULT = 4;
-constexpr int LG_T_LG = LC_ECAP * 8, LG_T_SP = LG_T_LG + LC_ECAP * 4, LG_T_DR = LG_T_SP + LC_ECAP, LG_T_LV = LG_T_DR + LC_ECAP,
-              LG_T_RP = LG_T_LV + LC_ECAP, LG_T_POS = LG_T_RP + 68 * 4, LG_TILE_BYTES = LG_T_POS + 64;
+constexpr int LG_MAXG = 6, LC_GROUP_DEFAULT = 6;      // 6 since the tables come from memory (4 before)
+// LG_T_* / LG_TILE_BYTES, a table set's fields: csrc/isg_live_tables.hpp, shared with the pre-pass that writes them to memory
+static_assert(LT_ROWS == LC_ROWS && LT_ECAP == LC_ECAP, "the table sets are cut for this kernel's tiles");
 constexpr int LG_OFF_T = LC_OFF_A + 2 * 64 * LC_LDA * 2;
 constexpr int LG_OFF_MISC = LG_OFF_T + LG_MAXG * LG_TILE_BYTES;
 constexpr int LG_MISC_FLOATS = 4 * 64 + 3 * LC_C + 4 * LC_C + 64;       // s_part, att / we_inv / bias, bn / wn_inv, s_nodes
 constexpr int LG_SMEM_BYTES = LG_OFF_MISC + LG_MISC_FLOATS * 4 + LG_MAXG * 16 + LG_MAXG * 8 + LG_MAXG * 4 * 8;
-static_assert(LG_TILE_BYTES % 16 == 0 && LG_OFF_MISC % 16 == 0, "16-byte pieces");
+static_assert(LG_TILE_BYTES % 16 == 0 && LG_OFF_T % 16 == 0 && LG_OFF_MISC % 16 == 0 && LG_T_RP + 64 * 4 == 4 * 1024 &&
+                  LG_TILE_BYTES == 4 * 1024 + 5 * 16 && LG_H_DESC == 4096 + 16 && LG_H_TOUCH == 4096 + 32 && LG_H_LIVE == 4096 + 48,
+              "16-byte pieces; the fetch of a table set from memory: four 1 KiB pieces, then five 16-byte ones");
 static_assert(64 * 512 <= 2 * 64 * LC_LDA * 2, "the node planes fit the panel image they share LDS with");
 static_assert(LG_SMEM_BYTES <= 160 * 1024, "one workgroup per CU");
 
-template <int KSE_T, bool SL01>
+template <int KSE_T, bool SL01, bool TABLES>
 __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(LcArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
   typedef float (*BufX)[LC_LDX];
@@ -884,65 +890,99 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
 
 #pragma unroll 1
   for (int tg = t; tg < T; tg += G * ngrp) {
-    // ---- scan: descriptors, then every tile's raw tables (LC_REQUEST_TILE / LC_REQUEST_MASKS, one slot per thread of waves 0-3) ----
     int tl = tid, ll = lane;      // laundered: what the scan derives from them is not hoisted out of the group loop and spilled
     asm volatile("" : "+v"(tl), "+v"(ll));
-    int4 dsc[LG_MAXG];
     int ng = 0;
+    if constexpr (TABLES) {
+      // ---- fetch: the group's table sets as the pre-pass wrote them (isg_layer_conv_live_tables), addresses from the tile numbers
+      // alone: four 1 KiB pieces per tile by LDS-DMA, the last 80 bytes -- four row pointers and the header -- through registers,
+      // the header straight to s_desc / s_touch / s_livew (in LDS its bytes are the POS field, which compaction fills)
 #pragma unroll
-    for (int j = 0; j < LG_MAXG; ++j) {
-      const int tj = tg + j * ngrp;
-      const bool on = j < G && tj < T;
-      const int4 d = a.tile_info[min(tj, T - 1)];
-      dsc[j] = make_int4(on ? __builtin_amdgcn_readfirstlane(d.x) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.y), LC_ROWS) : 0,
-                         on ? __builtin_amdgcn_readfirstlane(d.z) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.w), LC_ECAP) : 0);
-      ng += on ? 1 : 0;
-    }
-    int srcv[LG_MAXG], eidv[LG_MAXG], dstv[LG_MAXG], rpv[LG_MAXG];
-    float einvv[LG_MAXG], mskv[LG_MAXG];
-#pragma unroll
-    for (int j = 0; j < LG_MAXG; ++j) {
-      srcv[j] = eidv[j] = dstv[j] = rpv[j] = 0;
-      einvv[j] = 1.f;
-      if (j < ng) {
-        if (tl <= dsc[j].y) rpv[j] = a.rowptr[dsc[j].x + tl];
-        if (tl < dsc[j].w) {
-          srcv[j] = a.src[dsc[j].z + tl];
-          eidv[j] = a.eid[dsc[j].z + tl];
-          dstv[j] = a.dst[dsc[j].z + tl];
-          einvv[j] = a.ep_inv[dsc[j].z + tl];
+      for (int j = 0; j < LG_MAXG; ++j) ng += j < G && tg + j * ngrp < T ? 1 : 0;
+      __syncthreads();       // every wave is done with the previous group's tables and slices
+#pragma unroll 1
+      for (int u = wave; u < 4 * ng; u += LC_THREADS / 64) {
+        const int j = u >> 2, pc = u & 3;
+        const unsigned char *img = a.live_tables + (size_t)(tg + j * ngrp) * LG_TILE_BYTES;
+        __builtin_amdgcn_global_load_lds((lc_glb_t *)(img + pc * 1024 + ll * 16), (lc_lds_t *)(s_tiles + j * LG_TILE_BYTES + pc * 1024),
+                                         16, 0, 0);
+      }
+      if (tl < 5 * ng) {
+        const int j = tl / 5, pc = tl - 5 * j;
+        const uint4 v = *reinterpret_cast<const uint4 *>(a.live_tables + (size_t)(tg + j * ngrp) * LG_TILE_BYTES + 4096 + pc * 16);
+        const unsigned long long lo = (unsigned long long)v.x | ((unsigned long long)v.y << 32),
+                                 hi = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+        if (pc == 0) {
+          *reinterpret_cast<uint4 *>(s_tiles + j * LG_TILE_BYTES + 4096) = v;
+        } else if (pc == 1) {
+          s_desc[j] = make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w);
+        } else if (pc == 2) {
+          s_touch[j] = lo;
+        } else {
+          s_livew[j * 4 + 2 * (pc - 3)] = lo;
+          s_livew[j * 4 + 2 * (pc - 3) + 1] = hi;
         }
       }
-    }
-    if (tl < LG_MAXG) s_touch[tl] = 0ull;      // (read last before the previous group's compaction barrier)
-    __syncthreads();         // every wave is done with the previous group's tables and slices; the row sets are empty
+      ISG_WAIT(0x0F70);      // vmcnt(0): this wave's pieces have landed
+      __syncthreads();
+    } else {
+      // ---- scan: descriptors, then every tile's raw tables (LC_REQUEST_TILE / LC_REQUEST_MASKS, one slot per thread of waves 0-3) ----
+      int4 dsc[LG_MAXG];
 #pragma unroll
-    for (int j = 0; j < LG_MAXG; ++j) {
-      mskv[j] = 1.f;
-      if (j < ng && tl < dsc[j].w)
-        mskv[j] = a.edge_mask ? a.edge_mask[eidv[j]] : a.node_mask[srcv[j]] * a.node_mask[dstv[j]];
-    }
+      for (int j = 0; j < LG_MAXG; ++j) {
+        const int tj = tg + j * ngrp;
+        const bool on = j < G && tj < T;
+        const int4 d = a.tile_info[min(tj, T - 1)];
+        dsc[j] = make_int4(on ? __builtin_amdgcn_readfirstlane(d.x) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.y), LC_ROWS) : 0,
+                           on ? __builtin_amdgcn_readfirstlane(d.z) : 0, on ? min(__builtin_amdgcn_readfirstlane(d.w), LC_ECAP) : 0);
+        ng += on ? 1 : 0;
+      }
+      int srcv[LG_MAXG], eidv[LG_MAXG], dstv[LG_MAXG], rpv[LG_MAXG];
+      float einvv[LG_MAXG], mskv[LG_MAXG];
 #pragma unroll
-    for (int j = 0; j < LG_MAXG; ++j) {
-      if (j < ng) {
-        const int r0n = dsc[j].x, nrn = dsc[j].y, e0n = dsc[j].z, nen = dsc[j].w;
-        if (tl <= nrn) LG_RP(j)[tl] = rpv[j] - e0n;
-        if (tl == 0) s_desc[j] = dsc[j];
-        if (tl < LC_ECAP) {                          /* a source outside its tile is clamped into it */
-          const int sx = min(max(srcv[j] - r0n, 0), max(nrn - 1, 0));
-          const int dz = min(max(dstv[j] - r0n, 0), max(nrn - 1, 0));
-          const bool lv = tl < nen && (__float_as_int(mskv[j]) & 0x7fffffff) != 0;        // LC_BALLOT's test
-          const unsigned long long bw = __ballot(lv);
-          if (ll == 0) s_livew[j * 4 + wave] = bw;
-          if (lv) atomicOr(&s_touch[j], (1ull << sx) | (1ull << dz));
-          LG_EM(j)[tl] = make_int2(eidv[j], __float_as_int(mskv[j]));
-          LG_LG(j)[tl] = lv ? einvv[j] : 0.f;        // a dead slot's logit is +0
-          LG_SP(j)[tl] = (unsigned char)sx;
-          LG_DR(j)[tl] = (unsigned char)dz;
+      for (int j = 0; j < LG_MAXG; ++j) {
+        srcv[j] = eidv[j] = dstv[j] = rpv[j] = 0;
+        einvv[j] = 1.f;
+        if (j < ng) {
+          if (tl <= dsc[j].y) rpv[j] = a.rowptr[dsc[j].x + tl];
+          if (tl < dsc[j].w) {
+            srcv[j] = a.src[dsc[j].z + tl];
+            eidv[j] = a.eid[dsc[j].z + tl];
+            dstv[j] = a.dst[dsc[j].z + tl];
+            einvv[j] = a.ep_inv[dsc[j].z + tl];
+          }
         }
       }
+      if (tl < LG_MAXG) s_touch[tl] = 0ull;      // (read last before the previous group's compaction barrier)
+      __syncthreads();         // every wave is done with the previous group's tables and slices; the row sets are empty
+#pragma unroll
+      for (int j = 0; j < LG_MAXG; ++j) {
+        mskv[j] = 1.f;
+        if (j < ng && tl < dsc[j].w)
+          mskv[j] = a.edge_mask ? a.edge_mask[eidv[j]] : a.node_mask[srcv[j]] * a.node_mask[dstv[j]];
+      }
+#pragma unroll
+      for (int j = 0; j < LG_MAXG; ++j) {
+        if (j < ng) {
+          const int r0n = dsc[j].x, nrn = dsc[j].y, e0n = dsc[j].z, nen = dsc[j].w;
+          if (tl <= nrn) LG_RP(j)[tl] = rpv[j] - e0n;
+          if (tl == 0) s_desc[j] = dsc[j];
+          if (tl < LC_ECAP) {                          /* a source outside its tile is clamped into it */
+            const int sx = min(max(srcv[j] - r0n, 0), max(nrn - 1, 0));
+            const int dz = min(max(dstv[j] - r0n, 0), max(nrn - 1, 0));
+            const bool lv = tl < nen && (__float_as_int(mskv[j]) & 0x7fffffff) != 0;        // LC_BALLOT's test
+            const unsigned long long bw = __ballot(lv);
+            if (ll == 0) s_livew[j * 4 + wave] = bw;
+            if (lv) atomicOr(&s_touch[j], (1ull << sx) | (1ull << dz));
+            LG_EM(j)[tl] = make_int2(eidv[j], __float_as_int(mskv[j]));
+            LG_LG(j)[tl] = lv ? einvv[j] : 0.f;        // a dead slot's logit is +0
+            LG_SP(j)[tl] = (unsigned char)sx;
+            LG_DR(j)[tl] = (unsigned char)dz;
+          }
+        }
+      }
+      __syncthreads();
     }
-    __syncthreads();
     LC_STAMP(0)              // scan: requests, tables, ballots
 
     int ntot = 0;
@@ -972,10 +1012,12 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
             const unsigned long long w = s_livew[j * 4 + i];
             c[i] = __builtin_amdgcn_readfirstlane(__popc((unsigned)w) + __popc((unsigned)(w >> 32)));
           }
-          if (tl < LC_ECAP) {
-            const unsigned long long w = s_livew[j * 4 + wave];
-            const int pre = (wave > 0 ? c[0] : 0) + (wave > 1 ? c[1] : 0) + (wave > 2 ? c[2] : 0);
-            if ((w >> ll) & 1ull) LG_LV(j)[pre + __popcll(w & ((1ull << ll) - 1ull))] = (unsigned char)tl;
+          if constexpr (!TABLES) {       // the live lists: a table set from memory carries its own
+            if (tl < LC_ECAP) {
+              const unsigned long long w = s_livew[j * 4 + wave];
+              const int pre = (wave > 0 ? c[0] : 0) + (wave > 1 ? c[1] : 0) + (wave > 2 ? c[2] : 0);
+              if ((w >> ll) & 1ull) LG_LV(j)[pre + __popcll(w & ((1ull << ll) - 1ull))] = (unsigned char)tl;
+            }
           }
           nl += __builtin_amdgcn_readfirstlane(__popcll(m));
           nlive += (c[0] + c[1]) + (c[2] + c[3]);
@@ -1207,22 +1249,40 @@ extern "C" int isg_node_gate_planes(const uint16_t *x_planes, const float *x_inv
   return check_launch();
 }
 
+// Tiles per group of the masked, live form and the persistent grid's groups per XCD.  ISG_LC_GROUP=n forces the
+// group size (1 = the per-tile kernel, as before); otherwise LC_GROUP_DEFAULT where a workgroup's tile sequence is that long, by
+// the estimate ops.dense_tail_group uses.
+static int lc_group_rule(int64_t N, int64_t E, int32_t H, int64_t max_tiles, int *gpx_out) {
+  static const int force_group = [] { const char *e = getenv("ISG_LC_GROUP"); return e ? atoi(e) : 0; }();
+  const int cus = device_cus();
+  int gpx = (cus / 8) / H;                                // groups per XCD: one workgroup per CU
+  if (gpx < 1) gpx = 1;
+  const long long need = (max_tiles + 7) / 8;
+  if (gpx > need) gpx = (int)need;
+  if (gpx < 1) gpx = 1;
+  if (gpx_out) *gpx_out = gpx;
+  const long long tiles = std::max((N + LC_ROWS - 1) / LC_ROWS, (E + LC_ECAP - 1) / LC_ECAP);
+  const long long per_wg = (std::min<long long>(tiles, max_tiles) + 8 * gpx - 1) / (8 * gpx);
+  return force_group > 0 ? std::min(force_group, LG_MAXG) : (int)std::max<long long>(1, std::min<long long>(LC_GROUP_DEFAULT, per_wg));
+}
+
 // lin_l | lin_r + MaskingGATv2Conv.message + aggregate (lin_edge inside) as one persistent launch: see the file header.
 // x_planes [N][2][128] fp16 + x_inv_scale [N] = the gated layer input gelu(h * instruction[batch]) as scaled (hi, mid) planes
 // (isg_instr_gate_planes, isg_mgat_dense_tail's xp_out, or isg_edge_planes with eid = NULL on fp32 rows); wn_frag / wn_inv_scale =
 // isg_split_f16x2_frag of cat(lin_l.weight, lin_r.weight) [2*H*C, 128], bn fp32 [2*H*C] their biases; the rest as isg_gatv2_tile_conv.
-extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
-                                    const float *bn, const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,
-                                    const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr,
-                                    const int32_t *eid, const int32_t *src, const int32_t *dst, const int32_t *tile_info,
-                                    const int32_t *ntiles, int64_t max_tiles, const float *node_mask, const float *edge_mask,
-                                    float *out, int32_t ldo, float *alpha, float *rowmax, uint8_t *row_dead, int64_t N, int64_t E,
-                                    int32_t H,
-                                    int32_t C, int32_t K_in, int32_t K_edge, float negative_slope, void *stream) {
+// One body for isg_gatv2_layer_conv and isg_gatv2_layer_conv_tables (live_tables NULL: the former).
+static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
+                     const float *bn, const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,
+                     const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr, const int32_t *eid,
+                     const int32_t *src, const int32_t *dst, const int32_t *tile_info, const int32_t *ntiles, int64_t max_tiles,
+                     const float *node_mask, const float *edge_mask, float *out, int32_t ldo, float *alpha, float *rowmax,
+                     uint8_t *row_dead, const uint8_t *live_tables, int64_t N, int64_t E, int32_t H, int32_t C, int32_t K_in,
+                     int32_t K_edge, float negative_slope, void *stream) {
   if (N < 0 || E < 0 || H <= 0 || C <= 0 || K_in <= 0 || K_edge <= 0 || max_tiles < 0 || ldo < H * C) return ISG_EINVAL;
   auto mis = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (C != LC_C || K_in != LC_K || K_edge > LC_K || (K_edge & 3) != 0 || (ldo & 3) != 0 || H > 16 || mis(x_planes) ||
-      mis(edge_planes) || mis(out) || (bias && mis(bias)) || mis(tile_info) || N >= (1ll << 31) || E >= (1ll << 31))
+      mis(edge_planes) || mis(out) || (bias && mis(bias)) || mis(tile_info) || mis(live_tables) || N >= (1ll << 31) ||
+      E >= (1ll << 31))
     return ISG_EUNSUPPORTED;
   if (N == 0 || max_tiles == 0) return ISG_OK;
   if (!x_planes || !x_inv_scale || !wn_frag || !wn_inv_scale || !bn ||
@@ -1231,6 +1291,8 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
     return ISG_EINVAL;
   // ISG_LC_DENSE_MASK=1: a masked layer walks every slot, as before the live-slot walk (A/B; the same bits either way)
   static const bool dense_mask = [] { const char *e = getenv("ISG_LC_DENSE_MASK"); return e && atoi(e) != 0; }();
+  // ISG_LC_TABLES=0: the groups kernel scans its tiles itself whatever the caller hands in (A/B; the same bits either way)
+  if (!isg_layer_conv_live_tables_enabled()) live_tables = nullptr;
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   LcArgs a = {
       .xp = reinterpret_cast<const _Float16 *>(x_planes), .xinv = x_inv_scale, .Wn = reinterpret_cast<const _Float16 *>(wn_frag),
@@ -1238,29 +1300,23 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
       .We = reinterpret_cast<const _Float16 *>(we_frag), .we_inv = we_inv_scale, .att = att, .bias = bias, .rowptr = rowptr,
       .eid = eid, .src = src, .dst = dst, .ntiles = ntiles, .tile_info = reinterpret_cast<const int4 *>(tile_info),
       .edge_mask = edge_mask, .node_mask = node_mask, .out = out, .alpha = alpha, .rowmax = rowmax, .N = (int)N, .E = (int)E,
-      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead, .G = 1};
+      .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead, .G = 1,
+      .live_tables = live_tables};
   if (!a.xp || !a.xinv || !a.Wn || !a.wn_inv || !a.bn || (a.E > 0 && (!a.ep || !a.ep_inv || !a.eid || !a.src || !a.dst || !a.alpha)) ||
       !a.We || !a.we_inv || !a.att || !a.rowptr || !a.tile_info || !a.ntiles || !a.out)
     return ISG_EINVAL;                         // the struct the kernel dereferences, not the parameters it was filled from
-  const int cus = device_cus();
-  int gpx = (cus / 8) / H;                                // groups per XCD: one workgroup per CU
-  if (gpx < 1) gpx = 1;
-  const long long need = (max_tiles + 7) / 8;
-  if (gpx > need) gpx = (int)need;
+  int gpx = 1;
+  a.G = lc_group_rule(N, E, H, max_tiles, &gpx);
   const unsigned grid = 8u * (unsigned)H * (unsigned)gpx;
   hipStream_t st = as_stream(stream);
-  // Tiles per group of the masked, live form.  ISG_LC_GROUP=n forces it (1 = the per-tile kernel, as before);
-  // otherwise LC_GROUP_DEFAULT where a workgroup's tile sequence is that long, by the estimate ops.dense_tail_group uses.
-  static const int force_group = [] { const char *e = getenv("ISG_LC_GROUP"); return e ? atoi(e) : 0; }();
-  {
-    const long long tiles = std::max((N + LC_ROWS - 1) / LC_ROWS, (E + LC_ECAP - 1) / LC_ECAP);
-    const long long per_wg = (std::min<long long>(tiles, max_tiles) + 8 * gpx - 1) / (8 * gpx);
-    a.G = force_group > 0 ? std::min(force_group, LG_MAXG) : (int)std::max<long long>(1, std::min<long long>(LC_GROUP_DEFAULT, per_wg));
+#define LC_LAUNCH_GT(KT, SL, TB)                                                                                     \
+  {                                                                                                                  \
+    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL, TB>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;            \
+    gatv2_layer_conv_groups_kernel<KT, SL, TB><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                          \
   }
 #define LC_LAUNCH_G(KT, SL)                                                                                          \
   {                                                                                                                  \
-    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;                \
-    gatv2_layer_conv_groups_kernel<KT, SL><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                              \
+    if (a.live_tables) LC_LAUNCH_GT(KT, SL, true) else LC_LAUNCH_GT(KT, SL, false)                                   \
   }
 #define LC_LAUNCH(M, KT, SL, LV)                                                                                     \
   {                                                                                                                  \
@@ -1282,8 +1338,47 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
   }
 #undef LC_LAUNCH_M
 #undef LC_LAUNCH_G
+#undef LC_LAUNCH_GT
 #undef LC_LAUNCH
   return check_launch();
+}
+
+extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
+                                    const float *bn, const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,
+                                    const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr,
+                                    const int32_t *eid, const int32_t *src, const int32_t *dst, const int32_t *tile_info,
+                                    const int32_t *ntiles, int64_t max_tiles, const float *node_mask, const float *edge_mask,
+                                    float *out, int32_t ldo, float *alpha, float *rowmax, uint8_t *row_dead, int64_t N, int64_t E,
+                                    int32_t H,
+                                    int32_t C, int32_t K_in, int32_t K_edge, float negative_slope, void *stream) {
+  return lc_launch(x_planes, x_inv_scale, wn_frag, wn_inv_scale, bn, edge_planes, edge_inv_scale, we_frag, we_inv_scale, att, bias,
+                   rowptr, eid, src, dst, tile_info, ntiles, max_tiles, node_mask, edge_mask, out, ldo, alpha, rowmax, row_dead,
+                   nullptr, N, E, H, C, K_in, K_edge, negative_slope, stream);
+}
+
+// The same launch with the masked tiles' table sets read from memory (include/isg_masked.h, csrc/isg_live_tables.hip).
+extern "C" int isg_gatv2_layer_conv_tables(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag,
+                                           const float *wn_inv_scale, const float *bn, const uint16_t *edge_planes,
+                                           const float *edge_inv_scale, const uint16_t *we_frag, const float *we_inv_scale,
+                                           const float *att, const float *bias, const int32_t *rowptr, const int32_t *eid,
+                                           const int32_t *src, const int32_t *dst, const int32_t *tile_info, const int32_t *ntiles,
+                                           int64_t max_tiles, const float *node_mask, const float *edge_mask, float *out, int32_t ldo,
+                                           float *alpha, float *rowmax, uint8_t *row_dead, const uint8_t *live_tables, int64_t N,
+                                           int64_t E, int32_t H, int32_t C, int32_t K_in, int32_t K_edge, float negative_slope,
+                                           void *stream) {
+  return lc_launch(x_planes, x_inv_scale, wn_frag, wn_inv_scale, bn, edge_planes, edge_inv_scale, we_frag, we_inv_scale, att, bias,
+                   rowptr, eid, src, dst, tile_info, ntiles, max_tiles, node_mask, edge_mask, out, ldo, alpha, rowmax, row_dead,
+                   live_tables, N, E, H, C, K_in, K_edge, negative_slope, stream);
+}
+
+extern "C" int32_t isg_gatv2_layer_conv_group(int64_t N, int64_t E, int32_t H, int64_t max_tiles) {
+  if (N <= 0 || E < 0 || H <= 0 || H > 16 || max_tiles <= 0) return 1;
+  return lc_group_rule(N, E, H, max_tiles, nullptr);
+}
+
+extern "C" int32_t isg_layer_conv_live_tables_enabled(void) {
+  static const bool on = [] { const char *e = getenv("ISG_LC_TABLES"); return !e || atoi(e) != 0; }();
+  return on ? 1 : 0;
 }
 
 // =====================================================================================================================

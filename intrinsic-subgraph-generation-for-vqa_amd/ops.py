@@ -1525,15 +1525,28 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
     if rowmax is not None and (node_mask is not None or edge_mask is not None):
         whole = plan.tile_mode(TILE_CONV_NODES, TILE_CONV_EDGES) == "tiles"
         row_dead = (torch.empty if whole else torch.zeros)(N, H, dtype=torch.uint8, device=dev)
+    # a masked launch on groups of tiles reads every tile's live tables from memory: one pre-pass builds them for all heads
+    # (include/isg_masked.h).  Rebuilt on every call -- the mask is the step's -- in a buffer of this call, on the launch stream.
+    mlib, tables = None, None
+    if (node_mask is not None or edge_mask is not None) and cap > 0:
+        from . import _lib_masked
+        mlib = _lib_masked.load()
+        if mlib.isg_layer_conv_live_tables_enabled() and mlib.isg_gatv2_layer_conv_group(N, E, H, cap) > 1:
+            tables = torch.empty(mlib.isg_layer_conv_live_tables_bytes(cap), dtype=torch.uint8, device=dev)
     timer, ev1 = MP_TIMER, None
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "K": K, "masked": node_mask is not None or edge_mask is not None,
                                   "feat_bytes": 4, "tile_conv": True, "layer_conv": True, "K_in": K_in})
         ev0.record()
-    rc = lib.isg_gatv2_layer_conv(
-        x.planes.data_ptr(), x.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(), ep_inv.data_ptr(),
-        we.data_ptr(), we_inv.data_ptr(), *shared, 0 if row_dead is None else row_dead.data_ptr(), N, E, H, C, K_in, K,
-        float(negative_slope), _stream())
+    front = (x.planes.data_ptr(), x.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(), ep_inv.data_ptr(),
+             we.data_ptr(), we_inv.data_ptr(), *shared, 0 if row_dead is None else row_dead.data_ptr())
+    if tables is None:
+        rc = lib.isg_gatv2_layer_conv(*front, N, E, H, C, K_in, K, float(negative_slope), _stream())
+    else:
+        _, _, rowptr_p, eid_p, src_p, dst_p, tile_info_p, ntiles_p, _, nm_p, em_p = shared[:11]
+        _lib.check(mlib.isg_layer_conv_live_tables(rowptr_p, eid_p, src_p, dst_p, ep_inv.data_ptr(), tile_info_p, ntiles_p, cap,
+                                                   nm_p, em_p, tables.data_ptr(), N, E, _stream()), "isg_layer_conv_live_tables")
+        rc = mlib.isg_gatv2_layer_conv_tables(*front, tables.data_ptr(), N, E, H, C, K_in, K, float(negative_slope), _stream())
     if not _launched(rc, "isg_gatv2_layer_conv", timer, ev1):
         return None
     sub = _mixed_sub(plan)

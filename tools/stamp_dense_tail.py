@@ -19,6 +19,7 @@ if "--build" in sys.argv:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-DISG_DIAG",
                            *[a for a in sys.argv[1:] if a.startswith("-D")],
                            os.path.join(CSRC, "isg_layer_tile.hip"), os.path.join(CSRC, "isg_layer_conv.hip"), os.path.join(CSRC, "isg_graph.hip"),
+                           os.path.join(CSRC, "isg_live_tables.hip"),
                            "-o", OUT])
     print("built", OUT)
     sys.exit(0)

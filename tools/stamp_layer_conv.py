@@ -4,7 +4,9 @@
 
 --masked: the masked launch, with the node mask the model's masked layer (BASELINE configs[1]'s third, Gumbel top-k) gives on this
 batch -- taken from one forward of the model -- and, first, how many of each tile's CSR slots that mask leaves live (nonzero).
-The masked launch is the grouped form unless ISG_LC_GROUP=1 is set: its phases carry their own labels."""
+The masked launch is the grouped form unless ISG_LC_GROUP=1 is set: its phases carry their own labels.
+--tables (with --masked): the tiles' live tables come from isg_layer_conv_live_tables, whose launch the stamps
+do not cover: the first phase is then the fetch of the images, and compaction builds no live lists."""
 import ctypes
 import os
 import sys
@@ -15,11 +17,13 @@ OUT = os.path.join(ROOT, "tools", "_build", "libisg_dt_stamp.so")
 
 import torch
 
-from isubgvqa_amd import _lib, ops, synthetic
+from isubgvqa_amd import _lib, _lib_masked, ops, synthetic
 
 stamp = ctypes.CDLL(OUT)
 stamp.isg_gatv2_layer_conv.restype, stamp.isg_gatv2_layer_conv.argtypes = _lib.SIGNATURES["isg_gatv2_layer_conv"]
 stamp.isg_lc_set_stamp_buffer.argtypes = [ctypes.c_void_p]
+for sym in ("isg_gatv2_layer_conv_tables", "isg_layer_conv_live_tables", "isg_layer_conv_live_tables_bytes"):
+    getattr(stamp, sym).restype, getattr(stamp, sym).argtypes = _lib_masked.SIGNATURES[sym]
 dev = torch.device("cuda:0")
 cfg = synthetic.CFG2
 wl = synthetic.make_workload(cfg).to(dev)
@@ -69,13 +73,22 @@ if "--masked" in sys.argv:
 buf = torch.zeros(4096 * 8, 16, dtype=torch.int64, device=dev)
 assert stamp.isg_lc_set_stamp_buffer(buf.data_ptr()) == 0
 att = conv.att.detach().reshape(-1).contiguous()
+use_tables = bool(nm_arg) and "--tables" in sys.argv
+tables = torch.empty(stamp.isg_layer_conv_live_tables_bytes(cap) if use_tables else 0, dtype=torch.uint8, device=dev)
+st = torch.cuda.current_stream().cuda_stream
 for rep in range(2):
     buf.zero_()
-    rc = stamp.isg_gatv2_layer_conv(xp.planes.data_ptr(), xp.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(),
-                                    ep_inv.data_ptr(), we.data_ptr(), we_inv.data_ptr(), att.data_ptr(), conv.bias.data_ptr(),
-                                    plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
-                                    tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, alpha.data_ptr(),
-                                    rowmax.data_ptr(), 0, N, E, H, C, 128, 128, 0.2, torch.cuda.current_stream().cuda_stream)
+    front = (xp.planes.data_ptr(), xp.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(),
+             ep_inv.data_ptr(), we.data_ptr(), we_inv.data_ptr(), att.data_ptr(), conv.bias.data_ptr(),
+             plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
+             tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, alpha.data_ptr(), rowmax.data_ptr(), 0)
+    if use_tables:
+        assert stamp.isg_layer_conv_live_tables(plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
+                                                ep_inv.data_ptr(), tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0,
+                                                tables.data_ptr(), N, E, st) == 0
+        rc = stamp.isg_gatv2_layer_conv_tables(*front, tables.data_ptr(), N, E, H, C, 128, 128, 0.2, st)
+    else:
+        rc = stamp.isg_gatv2_layer_conv(*front, N, E, H, C, 128, 128, 0.2, st)
     assert rc == 0
     torch.cuda.synchronize()
 s = buf.double().cpu()
@@ -85,7 +98,8 @@ names = ["first tile's inputs (once)", "node GEMM: barrier", "chunks: staging ba
          "hand-over barrier", "node GEMM: k loop", "node GEMM: epilogue (LDS writes)", "chunks: wait for the planes, LDS writes", "last logit sums + barrier", "(total)", "(probe) other", "(probe) exposed latency of a chunk request"]
 if nm_arg and os.environ.get("ISG_LC_GROUP") != "1" and os.environ.get("ISG_LC_DENSE_MASK", "0") == "0":
     # gatv2_layer_conv_groups_kernel's stamps (per group of tiles; 3, 4, 10 per chunk; 6 covers the group's tiles)
-    names = ["scan: requests, tables, ballots (per group)", "compaction: node list, maps, live lists", "gather: node planes, first edge planes (wait)",
+    names = ["fetch: the group's table images (per group)" if use_tables else "scan: requests, tables, ballots (per group)",
+             "compaction: node list, maps" if use_tables else "compaction: node list, maps, live lists", "gather: node planes, first edge planes (wait)",
              "group chunks: k loops", "group chunks: epilogue + barrier", "-", "per tile: softmax + aggregation, stores (all tiles of the group)",
              "-", "group node product: k loop", "group node product: barrier + epilogue (LDS writes)", "panel staging + barrier",
              "last logit sums + barrier", "(total)"]
