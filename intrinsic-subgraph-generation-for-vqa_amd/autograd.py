@@ -9,14 +9,17 @@ off, so the same `ops.*` call runs the plain forward kernel.  Three kinds of bac
       GumbelTopK         isg_topk_gumbel_bwd         (straight-through, gumbel_scheme.py:83-90)
       ImleTopK/AimleTopK isg_topk_threshold again    (second MAP solve, wrapper.py:124-172; aimle.py:141-243;
                                                       adaptive beta, target_aimle.py:88-162 -- state kept ON THE DEVICE)
+      SimpleTopK         isg_simple_topk_bwd         (the exact marginals' reverse pass over the circuit's two trees, one launch;
+                                                      autograd through simple.py:203-236 in the reference)
   * Linear: forward and dX on the bf16x6 matrix-core kernel, dW (a reduction over the rows) as a split-M GEMM on the
     fp32 matrix-core instruction (csrc/isg_wgrad.hip);
   * the per-graph operators around the message passing -- layer tail (instruction attention + GraphNorm + residual),
     pooling, instruction gate, node gate: per-graph HIP backward kernels (csrc/isg_tail_bwd.hip);
   * the scene-graph encoder's operators -- gather-add, the node tokens' embedding sum, scatter_mean, GraphNorm alone (both modes):
     HIP backward kernels of their own (csrc/isg_sgenc_bwd.hip); every scatter among them is one segment sum without atomics;
-  * what only stand-alone utilities use (scatter attention alone, the SIMPLE marginals, gates without a plan): forward = fused
-    kernel, backward re-evaluates a torch-op restatement ON THE DEVICE under autograd (`_Recomputed`).
+  * what only stand-alone utilities use (scatter attention alone, gates without a plan), and a SIMPLE sampler row too long for the
+    backward kernel's LDS rule: forward = fused kernel, backward re-evaluates a torch-op restatement ON THE DEVICE under autograd
+    (`_Recomputed`).
 
 Nothing here runs on the CPU and nothing imports `oracle/`.
 """
@@ -683,9 +686,14 @@ def topk_gumbel(scores, k, tau, plan, noise, seed):
     return _GumbelTopK.apply(scores, k, tau, plan, noise, seed)
 
 
-def simple_topk(scores, k, plan, uniform, seed, return_marginals):
-    """forward = isg_simple_topk; backward = autograd over the torch restatement of the circuit's marginals (the only
-    differentiable part: out = (sample - marginals).detach() + marginals)."""
+# The SIMPLE marginals' backward on csrc/isg_simple_bwd.hip (one launch).  False: autograd through the torch restatement of the
+# circuit (`_Recomputed`, a few thousand launches per call), which also takes the rows the kernel's LDS rule refuses.  A/B:
+# tools/time_simple_bwd.py, DESIGN.md 25.
+SIMPLE_BWD_KERNEL = True
+
+
+def _simple_restatement(scores, k, plan, return_marginals):
+    """The differentiable part of simple_topk written with torch ops: (out [, marginals]) = the marginals in both layouts."""
     from .sampling.methods.simple import LARGE_NUMBER, log_marginals
     if plan is not None:
         B, nmax, slots = plan.B, plan.nmax, plan.dense_slots()
@@ -693,9 +701,6 @@ def simple_topk(scores, k, plan, uniform, seed, return_marginals):
         B, nmax, slots = scores.shape[0], scores.shape[1], None
     n = 1 << max(nmax - 1, 0).bit_length()
     kk = min(int(k), nmax)
-
-    def fused(sc, *_c):
-        return ops.simple_topk(sc, k, plan, uniform, seed, return_marginals)
 
     def restate(sc, *_c):
         if slots is not None:
@@ -707,7 +712,49 @@ def simple_topk(scores, k, plan, uniform, seed, return_marginals):
         out = marg.reshape(-1)[slots].view(sc.shape) if slots is not None else marg.view(sc.shape)
         return (out, marg) if return_marginals else out
 
-    return _Recomputed.apply(fused, restate, (), scores)
+    return restate
+
+
+class _SimpleTopK(torch.autograd.Function):
+    """out = (sample - marginals).detach() + marginals: only the marginals are differentiable and the sample carries no gradient,
+    so the backward needs the scores alone."""
+
+    @staticmethod
+    def forward(ctx, scores, k, plan, uniform, seed, return_marginals):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(scores)
+        ctx.cfg = (k, plan, return_marginals)
+        return ops.simple_topk(scores, k, plan, uniform, seed, return_marginals)
+
+    @staticmethod
+    def backward(ctx, g_out, g_marg=None):
+        scores, = ctx.saved_tensors
+        k, plan, return_marginals = ctx.cfg
+        if g_out is None and g_marg is None:
+            return (None,) * 6
+        d = ops.simple_topk_backward(scores, k, plan, None if g_out is None else g_out.contiguous(),
+                                     None if g_marg is None else g_marg.contiguous())
+        if d is None:                                   # a row beyond the kernel's LDS rule: the restatement, as with the switch off
+            with torch.enable_grad():
+                sc = scores.detach().requires_grad_(True)
+                outs = _simple_restatement(sc, k, plan, return_marginals)(sc)
+                outs = outs if isinstance(outs, tuple) else (outs,)
+                pairs = [(o, g) for o, g in zip(outs, (g_out, g_marg)) if g is not None]
+                d, = torch.autograd.grad([o for o, _ in pairs], [sc], [g for _, g in pairs])
+        return (d,) + (None,) * 5
+
+
+def simple_topk(scores, k, plan, uniform, seed, return_marginals):
+    """forward = isg_simple_topk; backward = isg_simple_topk_bwd, the reverse pass over the circuit's trees as one launch, or --
+    SIMPLE_BWD_KERNEL off, or a row the kernel refuses -- autograd over the torch restatement of the circuit's marginals (the only
+    differentiable part: out = (sample - marginals).detach() + marginals)."""
+    if SIMPLE_BWD_KERNEL:
+        return _SimpleTopK.apply(scores, k, plan, uniform, seed, return_marginals)
+
+    def fused(sc, *_c):
+        return ops.simple_topk(sc, k, plan, uniform, seed, return_marginals)
+
+    return _Recomputed.apply(fused, _simple_restatement(scores, k, plan, return_marginals), (), scores)
 
 
 class _ImleTopK(torch.autograd.Function):

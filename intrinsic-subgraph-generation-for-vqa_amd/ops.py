@@ -133,7 +133,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "text_train_kernels": 0,                   # question encoder / decoder forwards under autograd on this library's kernels
             "sgenc_train_kernels": 0,                  # scene-graph encoder forwards under autograd without the concatenations (SPLIT_TRAIN)
             "torch_attention_train": 0,                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
-            "linear_bwd_kernels": 0}                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
+            "linear_bwd_kernels": 0,                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
+            "simple_bwd_kernel": 0}                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
 
 
 def reset_counters() -> None:
@@ -1893,6 +1894,29 @@ def simple_topk(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, unifor
                                    0 if marg is None else marg.data_ptr(), _stream()), "isg_simple_topk")
     out = out.view(scores.shape)
     return (out, marg) if return_marginals else out
+
+
+def simple_topk_backward(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, g_out: Optional[Tensor] = None,
+                         g_marg: Optional[Tensor] = None) -> Optional[Tensor]:
+    """d scores of simple_topk for d out = g_out (the layout of scores) and d marginals = g_marg ([B, Nmax]); either may be None
+    (= 0).  One launch of isg_simple_topk_bwd, which rebuilds the circuit's trees from the scores alone: the sample carries no
+    gradient, so neither ``uniform`` nor ``seed`` is an argument.  None when the library refuses the shape (a row whose four trees
+    exceed the LDS rule of isg_simple_topk_bwd_row_bytes): the caller differentiates the torch restatement instead."""
+    from . import _lib_sampler_train
+    lib = _lib_sampler_train.load()
+    scores = scores.detach()
+    flat, ptr, B, nmax, _ = _rows(scores, plan)
+    go = None if g_out is None else g_out.detach().reshape(flat.shape)          # held until the launch is queued
+    gm = None if g_marg is None else g_marg.detach().reshape(B, nmax)
+    d = torch.empty_like(flat)
+    status = lib.isg_simple_topk_bwd(_chk(flat, "scores", torch.float32), ptr, B, nmax, int(k),
+                                     _chk(go, "g_out", torch.float32, optional=True), _chk(gm, "g_marg", torch.float32, optional=True),
+                                     d.data_ptr(), _stream())
+    if status == ISG_EUNSUPPORTED:
+        return None
+    _lib.check(status, "isg_simple_topk_bwd")
+    COUNTERS["simple_bwd_kernel"] += 1
+    return d.view(scores.shape)
 
 
 def topk_gumbel_backward(scores: Tensor, grad_out: Tensor, k: int, tau: float = 0.1, plan: Optional[GraphPlan] = None,

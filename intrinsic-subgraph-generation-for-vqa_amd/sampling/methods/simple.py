@@ -3,8 +3,10 @@
 Reference behaviour: Layer, ISubGVQA/sampling/methods/simple.py:120-252, over the circuit of
 create_simple_constraint.py:34-73 (pickled to ./simple_configs/{n}C{k}.pkl there; nothing is pickled here).
 Forward = isg_simple_topk (csrc/isg_simple.hip): marginals and the Gumbel top-k sample in one launch per batch.
+Backward = isg_simple_topk_bwd (csrc/isg_simple_bwd.hip), the reverse pass over the same trees in one launch.
 `log_marginals` below is the same function written with differentiable torch ops ON THE DEVICE; it is only evaluated in
-the backward pass (autograd._Recomputed), where the reference also relies on autograd through its levelwise tensors.
+the backward pass, when autograd.SIMPLE_BWD_KERNEL is off or a row is beyond the kernel's LDS rule (autograd._Recomputed),
+and it is the restatement the tests hold the kernel against; the reference also relies on autograd through its levelwise tensors.
 The circuit is a balanced binary tree; every block of a level is alike, so its structure is three small (level, count)
 tables -- see the kernel's header for the two dummy-padding accidents that are part of the function.
 """

@@ -3,8 +3,8 @@
 Reference behaviour: EdgeSIMPLEBatched, ISubGVQA/sampling/methods/simple_scheme.py:23-191, policy 'edge_candid' (the
 only one ISubGVQA constructs, masking.py:110-119).  forward(scores [B, Nmax, 1], train) -> (mask [1, B, Nmax, 1],
 marginals [B, Nmax, 1]) with mask = (sample - marginals).detach() + marginals.  One launch of isg_simple_topk; the
-gradient of the marginals comes from autograd over sampling/methods/simple.py::log_marginals, evaluated on the device in
-the backward pass only.
+gradient of the marginals is one launch of isg_simple_topk_bwd (autograd._SimpleTopK), or, for a row beyond its LDS rule,
+autograd over sampling/methods/simple.py::log_marginals, evaluated on the device in the backward pass only.
 
 Extension over the reference signature: ``uniform`` (the explicit [B, n] torch.rand draw behind the Gumbel keys, for
 parity runs) and ``seed`` (in-kernel Philox stream).
