@@ -670,20 +670,21 @@ def node_to_edge_mask(mask, edge_index, plan):
 # ------------------------------------------------------------------------------------------------
 class _GumbelTopK(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores, k, tau, plan, noise, seed):
+    def forward(ctx, scores, k, tau, plan, noise, seed, k_cap):
         ctx.save_for_backward(scores, noise)
-        ctx.cfg = (k, tau, plan, seed)
-        return ops.topk_gumbel(scores, k, tau, plan=plan, noise=noise, seed=seed)
+        ctx.cfg = (k, tau, plan, seed, k_cap)          # k: an int, or the int32 [B] budget (no gradient, not written after)
+        return ops.topk_gumbel(scores, k, tau, plan=plan, noise=noise, seed=seed, k_cap=k_cap)
 
     @staticmethod
     def backward(ctx, g):
         scores, noise = ctx.saved_tensors
-        k, tau, plan, seed = ctx.cfg
-        return ops.topk_gumbel_backward(scores, g, k, tau, plan=plan, noise=noise, seed=seed), None, None, None, None, None
+        k, tau, plan, seed, k_cap = ctx.cfg
+        return (ops.topk_gumbel_backward(scores, g, k, tau, plan=plan, noise=noise, seed=seed, k_cap=k_cap),) + (None,) * 6
 
 
-def topk_gumbel(scores, k, tau, plan, noise, seed):
-    return _GumbelTopK.apply(scores, k, tau, plan, noise, seed)
+def topk_gumbel(scores, k, tau, plan, noise, seed, k_cap=None):
+    """``k``: an int, or a k per row (int32 [B] device tensor) with ``k_cap`` the bound of its entries."""
+    return _GumbelTopK.apply(scores, k, tau, plan, noise, seed, k_cap)
 
 
 # The SIMPLE marginals' backward on csrc/isg_simple_bwd.hip (one launch).  False: autograd through the torch restatement of the
@@ -761,19 +762,19 @@ class _ImleTopK(torch.autograd.Function):
     """z = MAP(theta + tau_in * eps);  d theta = z - MAP(alpha * theta - beta * dy + tau_t * eps)."""
 
     @staticmethod
-    def forward(ctx, scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target):
-        z = ops.topk_threshold(scores, k, plan=plan, noise=noise, noise_scale=tau_in, seed=seed)
+    def forward(ctx, scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target, k_cap):
+        z = ops.topk_threshold(scores, k, plan=plan, noise=noise, noise_scale=tau_in, seed=seed, k_cap=k_cap)
         ctx.save_for_backward(scores, noise, z)
-        ctx.cfg = (k, plan, seed, alpha, beta, tau_target)
+        ctx.cfg = (k, plan, seed, alpha, beta, tau_target, k_cap)
         return z
 
     @staticmethod
     def backward(ctx, dy):
         scores, noise, z = ctx.saved_tensors
-        k, plan, seed, alpha, beta, tau_target = ctx.cfg
+        k, plan, seed, alpha, beta, tau_target, k_cap = ctx.cfg
         target = alpha * scores - beta * dy                                              # target.py:43
-        z_t = ops.topk_threshold(target.contiguous(), k, plan=plan, noise=noise, noise_scale=tau_target, seed=seed)
-        return (z - z_t,) + (None,) * 8                                                  # wrapper.py:170-172 (S = 1)
+        z_t = ops.topk_threshold(target.contiguous(), k, plan=plan, noise=noise, noise_scale=tau_target, seed=seed, k_cap=k_cap)
+        return (z - z_t,) + (None,) * 9                                                  # wrapper.py:170-172 (S = 1)
 
 
 class AdaptiveTarget:
@@ -827,31 +828,33 @@ class _AimleTopK(torch.autograd.Function):
     selection over the padded rows: the adaptive rule counts the flipped slots INCLUDING the pads."""
 
     @staticmethod
-    def forward(ctx, scores, k, plan, noise, seed, state, tau_theta, tau_target):
-        z = ops.topk_threshold(scores, k, plan=plan, noise=noise, noise_scale=tau_theta, seed=seed)
+    def forward(ctx, scores, k, plan, noise, seed, state, tau_theta, tau_target, k_cap):
+        z = ops.topk_threshold(scores, k, plan=plan, noise=noise, noise_scale=tau_theta, seed=seed, k_cap=k_cap)
         ctx.save_for_backward(scores, noise)
-        ctx.cfg = (k, plan, seed, state, tau_target)
+        ctx.cfg = (k, plan, seed, state, tau_target, k_cap)
         return z
 
     @staticmethod
     def backward(ctx, dy):
         scores, noise = ctx.saved_tensors
-        k, plan, seed, state, tau_target = ctx.cfg
+        k, plan, seed, state, tau_target, k_cap = ctx.cfg
         pm = state.magnitude(scores, dy)
         t_r = (state.alpha * scores - pm * dy).contiguous()                              # aimle.py:173-176
         t_l = (state.alpha * scores + pm * dy).contiguous()                              # :178-182 (params(theta, -dy))
         z_r, dense_r = ops.topk_threshold(t_r, k, plan=plan, noise=noise, noise_scale=tau_target, seed=seed,
-                                          return_dense=True)
+                                          return_dense=True, k_cap=k_cap)
         z_l, dense_l = ops.topk_threshold(t_l, k, plan=plan, noise=noise, noise_scale=tau_target, seed=seed,
-                                          return_dense=True)
+                                          return_dense=True, k_cap=k_cap)
         state.update((dense_l - dense_r) / 2.0, dense_l.size(0))                         # target_aimle.py:131-159
         g = (z_l - z_r) / 2.0 / torch.where(pm > 0, pm, torch.ones_like(pm))             # aimle.py:231-237, :161
-        return (g,) + (None,) * 7
+        return (g,) + (None,) * 8
 
 
-def imle_topk(scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target):
-    return _ImleTopK.apply(scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target)
+def imle_topk(scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target, k_cap=None):
+    """``k``: an int, or a k per row (int32 [B] device tensor) with ``k_cap``; the backward's target solve uses the same k."""
+    return _ImleTopK.apply(scores, k, plan, noise, seed, alpha, beta, tau_in, tau_target, k_cap)
 
 
-def aimle_topk(scores, k, plan, noise, seed, state, tau_theta, tau_target):
-    return _AimleTopK.apply(scores, k, plan, noise, seed, state, tau_theta, tau_target)
+def aimle_topk(scores, k, plan, noise, seed, state, tau_theta, tau_target, k_cap=None):
+    """``k``: an int, or a k per row (int32 [B] device tensor) with ``k_cap``; both target solves of the backward use the same k."""
+    return _AimleTopK.apply(scores, k, plan, noise, seed, state, tau_theta, tau_target, k_cap)

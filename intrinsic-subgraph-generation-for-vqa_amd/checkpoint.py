@@ -20,7 +20,9 @@ _ARG_DEFAULTS = dict(text_sampling=False, general_hidden_dim=300, distributed=Fa
                      use_global_mask=False, node_classification=False, sampler_type=None, sample_k=None, nb_samples=1,
                      alpha=1.0, beta=10.0, tau=1.0, use_masking=1, use_instruction=1, use_mgat=1,
                      mgat_masks=[1.0, 1.0, 1.0, 0.15], use_topk=True, interpretable_mode=False, concat_instr=0,
-                     embed_cat=0, device="cuda")
+                     embed_cat=0, device="cuda",
+                     # this project's own flags (a node budget per graph); a reference checkpoint has neither
+                     sample_ratio=None, sample_k_min=1)
 
 
 def strip_ddp_prefix(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -61,7 +61,9 @@ def fidelity_scores(logits: Tensor, logits_keep: Tensor, logits_removed: Tensor,
 
 def cut_workload(wl: "synthetic.Workload", cut: "ops.SubgraphCut") -> "synthetic.Workload":
     """The batch of an AnswerModel across a cut: node and edge rows gathered, the questions' tensors and the per-graph bounds
-    (which hold for any subgraph) carried over; graph_sizes no longer describes the batch and is dropped."""
+    (which hold for any subgraph) carried over; graph_sizes no longer describes the batch and is dropped.  A cut is driven by the
+    mask, not by k: with a node budget per graph (sample_ratio) a caller who wants SubgraphCut.sel passes the cap
+    (sample_k) as ops.subgraph_cut's table_k, and the rows of graphs with a smaller budget end in -1 earlier."""
     return synthetic.Workload(cut.gather_nodes(wl.x), cut.edge_index, cut.gather_edges(wl.edge_attr), cut.batch, wl.instr, wl.glf,
                               wl.num_graphs, wl.max_nodes, wl.max_edges, None)
 

@@ -62,7 +62,9 @@ class ISubGVQA(torch.nn.Module):
                             node_classification=getattr(args, "node_classification", False),
                             sampler_type=args.sampler_type, sample_k=args.sample_k,
                             nb_samples=getattr(args, "nb_samples", 1), alpha=getattr(args, "alpha", 1.0),
-                            beta=getattr(args, "beta", 10.0), tau=getattr(args, "tau", 1.0))
+                            beta=getattr(args, "beta", 10.0), tau=getattr(args, "tau", 1.0),
+                            # a node budget per graph; a reference checkpoint's Namespace has neither field
+                            sample_ratio=getattr(args, "sample_ratio", None), sample_k_min=getattr(args, "sample_k_min", 1))
         self.graph_global_attention_pooling = GlobalAttention(num_node_features=self.question_hidden_dim,
                                                               num_out_features=self.question_hidden_dim)
         self.qsts_reduction = torch.nn.Sequential(

@@ -27,10 +27,22 @@ _IMLE_NOISE_SCALE = 0.3    # masking.py:215,249
 
 class MaskingModel(torch.nn.Module):
     def __init__(self, dim_nodes, dim_questions, masking_threshold=0.3, use_topk=False, sample_k=None,
-                 sampler_type=None, nb_samples=1, alpha=1.0, beta=10.0, tau=1.0):
+                 sampler_type=None, nb_samples=1, alpha=1.0, beta=10.0, tau=1.0, sample_ratio: Optional[float] = None,
+                 sample_k_min: int = 1):
         super().__init__()
         self.use_topk = use_topk
         self.sample_k = sample_k
+        # a node budget per graph: k_g = min(sample_k, max(sample_k_min, ceil(sample_ratio * n_g))), the rule the
+        # reference left as a comment (masking.py:113).  None: sample_k for every graph, the reference's behaviour.
+        self.sample_ratio = None if sample_ratio is None else float(sample_ratio)
+        self.sample_k_min = int(sample_k_min)
+        if self.sample_ratio is not None:
+            if sampler_type == "simple":
+                raise NotImplementedError("sample_ratio with sampler_type='simple': the SIMPLE sampler's circuit and tables are "
+                                          "built per (n, k) for the launch, so a per-graph budget is out of its scope")
+            if not self.sample_ratio > 0.0 or sample_k is None or not 1 <= self.sample_k_min <= int(sample_k):
+                raise ValueError(f"sample_ratio needs 0 < sample_ratio and 1 <= sample_k_min <= sample_k (the cap), got "
+                                 f"sample_ratio={sample_ratio}, sample_k_min={sample_k_min}, sample_k={sample_k}")
         self.sampler_type = sampler_type
         self.masking_threshold = int(masking_threshold) if masking_threshold > 1 else masking_threshold
         self.dim_nodes, self.dim_questions = dim_nodes, dim_questions
@@ -97,12 +109,16 @@ class MaskingModel(torch.nn.Module):
             return (torch.sigmoid(gate) > 0.5).to(dtype=gate.dtype)
         gate = F.dropout(gate, p=self.gate_dropout, training=self.training)  # :159
         B, nmax = plan.B, plan.nmax
+        if self.sample_ratio is None:
+            k, k_cap = (None if self.sample_k is None else int(self.sample_k)), None
+        else:                                          # int32 [B] on the device, one launch per batch (kept on the plan)
+            k, k_cap = ops.topk_budget(plan, self.sample_ratio, self.sample_k_min, int(self.sample_k)), int(self.sample_k)
         if self.sampler_type == "gumbel":
             if noise is None and seed is None:                               # torch generator, like the reference
                 from ..sampling.methods.noise import gumbel_from_uniform
                 noise = gumbel_from_uniform(torch.rand(B, nmax, device=gate.device))
-            return ops.topk_gumbel(gate, int(self.sample_k), float(self.sampler.tau), plan=plan, noise=noise,
-                                   seed=0 if seed is None else seed)
+            return ops.topk_gumbel(gate, k, float(self.sampler.tau), plan=plan, noise=noise,
+                                   seed=0 if seed is None else seed, k_cap=k_cap)
         if self.sampler_type == "simple":          # masking.py:175-176 (same call as the Gumbel sampler)
             n = 1 << max(nmax - 1, 0).bit_length()
             if noise is None and seed is None:
@@ -115,13 +131,13 @@ class MaskingModel(torch.nn.Module):
                 if noise is None and seed is None:
                     noise = sampler.noise_distribution.sample(torch.Size([B, 1, nmax, 1])).to(gate.device)
                 nz = None if noise is None else noise.reshape(B, nmax).contiguous().float()
-                return sampler.differentiable(gate, plan, nz, 0 if seed is None else seed)
+                return sampler.differentiable(gate, plan, nz, 0 if seed is None else seed, k=k, k_cap=k_cap)
             if temp == 0.0:
-                return ops.topk_threshold(gate, int(self.sample_k), plan=plan)
+                return ops.topk_threshold(gate, k, plan=plan, k_cap=k_cap)
             if noise is None and seed is None:
                 noise = sampler.noise_distribution.sample(torch.Size([B, 1, nmax, 1])).to(gate.device)
-            return ops.topk_threshold(gate, int(self.sample_k), plan=plan, noise=noise, noise_scale=temp,
-                                      seed=0 if seed is None else seed)
+            return ops.topk_threshold(gate, k, plan=plan, noise=noise, noise_scale=temp,
+                                      seed=0 if seed is None else seed, k_cap=k_cap)
         raise NotImplementedError(f"sampler_type={self.sampler_type!r}")
 
 

@@ -21,7 +21,8 @@ class MGAT(torch.nn.Module):
     def __init__(self, channels, num_ins, dropout=0.0, heads=4, use_instr=False, masking_thresholds=None,
                  use_topk: bool = False, interpretable_mode: bool = True, concat_instr: bool = False,
                  use_all_instrs: bool = False, use_global_mask: bool = False, node_classification: bool = False,
-                 sampler_type: str = None, sample_k: int = None, nb_samples: int = 1, alpha=1.0, beta=10.0, tau=1.0):
+                 sampler_type: str = None, sample_k: int = None, nb_samples: int = 1, alpha=1.0, beta=10.0, tau=1.0,
+                 sample_ratio: Optional[float] = None, sample_k_min: int = 1):
         super().__init__()
         if not use_instr:
             raise NotImplementedError("use_instr=False leaves the reference without its layer lists (mgat.py:46-64)")
@@ -37,7 +38,7 @@ class MGAT(torch.nn.Module):
         wide, mid = heads * channels, channels * int(heads / 2)        # H*C -> C*H/2 -> C   (mgat.py:66-91)
 
         sampler_opts = dict(sampler_type=sampler_type, sample_k=sample_k, nb_samples=nb_samples, alpha=alpha, beta=beta,
-                            tau=tau)
+                            tau=tau, sample_ratio=sample_ratio, sample_k_min=sample_k_min)
 
         def conv_layer(threshold):
             return MaskingGATv2Conv(width_in, channels, heads=heads, edge_dim=channels, add_self_loops=False,

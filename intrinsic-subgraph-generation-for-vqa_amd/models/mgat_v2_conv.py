@@ -35,7 +35,7 @@ class MaskingGATv2Conv(torch.nn.Module):
                  edge_dim: Optional[int] = None, fill_value="mean", bias: bool = True, share_weights: bool = False,
                  masking_threshold=None, use_instr: bool = False, use_topk: bool = False, concat_instr: bool = False,
                  use_all_instrs: bool = False, sampler_type: str = None, sample_k: int = None, nb_samples: int = 1,
-                 alpha=1.0, beta=10.0, tau=1.0, **kwargs):
+                 alpha=1.0, beta=10.0, tau=1.0, sample_ratio: Optional[float] = None, sample_k_min: int = 1, **kwargs):
         super().__init__()
         if not isinstance(in_channels, int):
             raise NotImplementedError("bipartite in_channels=(src, dst) is never used by ISubGVQA (mgat.py:58)")
@@ -63,7 +63,7 @@ class MaskingGATv2Conv(torch.nn.Module):
             self.register_parameter("bias", None)
         self.mask = MaskingModel(in_channels, out_channels, masking_threshold, use_topk=use_topk,
                                  sampler_type=sampler_type, sample_k=sample_k, nb_samples=nb_samples, alpha=alpha,
-                                 beta=beta, tau=tau)
+                                 beta=beta, tau=tau, sample_ratio=sample_ratio, sample_k_min=sample_k_min)
         self.masking = NodeMaskToEdgeMask.apply
         # storage type of the projected rows x_l / x_r / e_proj and of the aggregated output (fp32 arithmetic either way):
         # torch.float16 is BASELINE configs[4] ("fp16 features / fp32 accumulate"), inference only

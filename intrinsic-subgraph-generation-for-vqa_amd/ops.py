@@ -134,7 +134,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "sgenc_train_kernels": 0,                  # scene-graph encoder forwards under autograd without the concatenations (SPLIT_TRAIN)
             "torch_attention_train": 0,                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
             "linear_bwd_kernels": 0,                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
-            "simple_bwd_kernel": 0}                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
+            "simple_bwd_kernel": 0,                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
+            "topk_rows": 0}                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
 
 
 def reset_counters() -> None:
@@ -1831,44 +1832,99 @@ def _noise_ptr(noise: Optional[Tensor], B: int, nmax: int) -> int:
     return _chk(noise.reshape(B, nmax), "noise", torch.float32)
 
 
-def topk_gumbel(scores: Tensor, k: int, tau: float = 0.1, plan: Optional[GraphPlan] = None,
-                noise: Optional[Tensor] = None, seed: int = 0, return_khot: bool = False):
+def topk_budget(plan: GraphPlan, ratio: float, k_min: int, k_cap: int) -> Tensor:
+    """The per-graph node budget k_rows int32 [B]: k_rows[b] = min(k_cap, max(k_min, ceil(ratio * n_b))), n_b the graph's node
+    count -- torch.ceil(torch.tensor(ratio, dtype=torch.float32) * n.float()), clamped (isg_topk_budget).  One launch,
+    nothing is read back (usable inside a capture), kept in plan.memo() under its arguments: a batch's layers share one tensor."""
+    ratio, k_min, k_cap = float(ratio), int(k_min), int(k_cap)
+    if not ratio > 0.0 or k_min < 1 or k_cap < k_min:
+        raise ValueError(f"topk_budget needs 0 < ratio and 1 <= k_min <= k_cap, got ratio={ratio}, k_min={k_min}, k_cap={k_cap}")
+    key = ("topk_budget", ratio, k_min, k_cap)
+    hit = plan.memo().get(key)
+    if hit is None:
+        from . import _lib_topk_rows
+        lib = _lib_topk_rows.load()
+        hit = torch.empty(plan.B, dtype=torch.int32, device=plan.ptr.device)
+        _lib.check(lib.isg_topk_budget(plan.ptr.data_ptr(), plan.B, ratio, k_min, k_cap, hit.data_ptr(), _stream()),
+                   "isg_topk_budget")
+        plan.memo()[key] = hit
+    return hit
+
+
+def _k_rows(k, k_cap: Optional[int], B: int, device) -> Optional[Tuple[int, int]]:
+    """None for an int k (the scalar entry points).  For a tensor k -- a k per row, int32 [B] on the rows' device, entries in
+    [1, k_cap] -- (its address, k_cap); the caller holds the tensor until the launch is queued."""
+    if not isinstance(k, Tensor):
+        if k_cap is not None:
+            raise ValueError("k_cap goes with a tensor k (a k per row); an int k is its own bound")
+        return None
+    if k_cap is None:
+        raise ValueError("a tensor k (a k per row) needs k_cap, the bound of its entries")
+    if k.dtype != torch.int32 or k.device != device or k.dim() != 1 or k.numel() != B or not k.is_contiguous():
+        raise ValueError(f"a k per row must be a contiguous int32 [{B}] tensor on {device}, got {k.dtype} {tuple(k.shape)} on {k.device}")
+    if int(k_cap) < 1:
+        raise ValueError(f"k_cap must be at least 1, got {k_cap}")
+    return k.data_ptr(), int(k_cap)
+
+
+def topk_gumbel(scores: Tensor, k, tau: float = 0.1, plan: Optional[GraphPlan] = None,
+                noise: Optional[Tensor] = None, seed: int = 0, return_khot: bool = False, k_cap: Optional[int] = None):
     """Relaxed Gumbel top-k + straight-through hard mask (gumbel_scheme.py:55-104).
 
     Ragged (plan given): scores [N] / [N,1] -> mask of the same shape (the dense-pad and the `[mask]`
     un-pad of masking.py:162,176 are fused).  Dense: scores [B,Nmax] -> [B,Nmax].
+    ``k``: an int, or a k per row as an int32 [B] device tensor with ``k_cap`` the bound of its entries (isg_topk_gumbel_rows).
     """
     if _rec(scores):
         from . import autograd
         if return_khot:
             raise ValueError("return_khot is an inspection output and is not differentiable")
-        return autograd.topk_gumbel(scores, k, tau, plan, noise, seed)
-    lib = _lib.load()
+        return autograd.topk_gumbel(scores, k, tau, plan, noise, seed, k_cap)
     flat, ptr, B, nmax, nmax_dev = _rows(scores, plan)
+    rows = _k_rows(k, k_cap, B, scores.device)
     out = torch.empty_like(flat)
     khot = torch.empty(B, nmax, dtype=torch.float32, device=scores.device) if return_khot else None
-    _lib.check(lib.isg_topk_gumbel(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
-                                   _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1), _gid_ptr(plan), int(k), float(tau),
-                                   out.data_ptr(), 0 if khot is None else khot.data_ptr(), _stream()),
-               "isg_topk_gumbel")
+    if rows is None:
+        lib = _lib.load()
+        _lib.check(lib.isg_topk_gumbel(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
+                                       _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1), _gid_ptr(plan), int(k), float(tau),
+                                       out.data_ptr(), 0 if khot is None else khot.data_ptr(), _stream()),
+                   "isg_topk_gumbel")
+    else:
+        from . import _lib_topk_rows
+        _lib.check(_lib_topk_rows.load().isg_topk_gumbel_rows(
+            _chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev, _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1),
+            _gid_ptr(plan), rows[0], rows[1], float(tau), out.data_ptr(), 0 if khot is None else khot.data_ptr(), _stream()),
+            "isg_topk_gumbel_rows")
+        COUNTERS["topk_rows"] += 1
     out = out.view(scores.shape)
     return (out, khot) if return_khot else out
 
 
-def topk_threshold(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, noise: Optional[Tensor] = None,
-                   noise_scale: float = 0.0, seed: int = 0, return_dense: bool = False):
+def topk_threshold(scores: Tensor, k, plan: Optional[GraphPlan] = None, noise: Optional[Tensor] = None,
+                   noise_scale: float = 0.0, seed: int = 0, return_dense: bool = False, k_cap: Optional[int] = None):
     """(scores + noise*noise_scale) >= k-th largest, per row (deterministic_scheme.py:36-43).  Not differentiable by
     itself: the I-MLE / AIMLE estimators around it are autograd.imle_topk / aimle_topk.  ``return_dense`` also returns
-    the selection over the padded [B, Nmax] rows (pads included)."""
-    lib = _lib.load()
+    the selection over the padded [B, Nmax] rows (pads included).  ``k``: an int, or a k per row as an int32 [B] device tensor
+    with ``k_cap`` the bound of its entries (isg_topk_threshold_rows)."""
     scores = scores.detach()
     flat, ptr, B, nmax, nmax_dev = _rows(scores, plan)
+    rows = _k_rows(k, k_cap, B, scores.device)
     out = torch.empty_like(flat)
     dense = torch.empty(B, nmax, dtype=torch.float32, device=scores.device) if return_dense else None
-    _lib.check(lib.isg_topk_threshold(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
-                                      _noise_ptr(noise, B, nmax), float(noise_scale), int(seed) & (2 ** 64 - 1), _gid_ptr(plan),
-                                      int(k), out.data_ptr(), 0 if dense is None else dense.data_ptr(), _stream()),
-               "isg_topk_threshold")
+    if rows is None:
+        lib = _lib.load()
+        _lib.check(lib.isg_topk_threshold(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
+                                          _noise_ptr(noise, B, nmax), float(noise_scale), int(seed) & (2 ** 64 - 1), _gid_ptr(plan),
+                                          int(k), out.data_ptr(), 0 if dense is None else dense.data_ptr(), _stream()),
+                   "isg_topk_threshold")
+    else:
+        from . import _lib_topk_rows
+        _lib.check(_lib_topk_rows.load().isg_topk_threshold_rows(
+            _chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev, _noise_ptr(noise, B, nmax), float(noise_scale),
+            int(seed) & (2 ** 64 - 1), _gid_ptr(plan), rows[0], rows[1], out.data_ptr(),
+            0 if dense is None else dense.data_ptr(), _stream()), "isg_topk_threshold_rows")
+        COUNTERS["topk_rows"] += 1
     out = out.view(scores.shape)
     return (out, dense) if return_dense else out
 
@@ -1877,7 +1933,11 @@ def simple_topk(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, unifor
                 seed: int = 0, return_marginals: bool = False):
     """SIMPLE sampler (simple_scheme.py:44-162): mask = (Gumbel top-k sample - marginals) + marginals, marginals exact
     through the exactly-k circuit.  Ragged (plan given; plan.nmax must be the batch's true longest row): scores [N] /
-    [N,1]; dense: scores [B,Nmax].  ``uniform``: the [B, n] torch.rand draw (n = Nmax rounded up to a power of two)."""
+    [N,1]; dense: scores [B,Nmax].  ``uniform``: the [B, n] torch.rand draw (n = Nmax rounded up to a power of two).
+    ``k`` is an int: the circuit and its tables are built per (n, k) for the launch, a k per row is not implemented."""
+    if isinstance(k, Tensor):
+        raise NotImplementedError("simple_topk takes one k for the batch: the SIMPLE sampler's circuit and tables are built per "
+                                  "(n, k) for the launch, so a per-graph budget (a k per row) is out of its scope")
     if _rec(scores):
         from . import autograd
         return autograd.simple_topk(scores, k, plan, uniform, seed, return_marginals)
@@ -1919,18 +1979,27 @@ def simple_topk_backward(scores: Tensor, k: int, plan: Optional[GraphPlan] = Non
     return d.view(scores.shape)
 
 
-def topk_gumbel_backward(scores: Tensor, grad_out: Tensor, k: int, tau: float = 0.1, plan: Optional[GraphPlan] = None,
-                         noise: Optional[Tensor] = None, seed: int = 0) -> Tensor:
+def topk_gumbel_backward(scores: Tensor, grad_out: Tensor, k, tau: float = 0.1, plan: Optional[GraphPlan] = None,
+                         noise: Optional[Tensor] = None, seed: int = 0, k_cap: Optional[int] = None) -> Tensor:
     """d scores of topk_gumbel for d out = grad_out (straight-through, gumbel_scheme.py:83-90); same arguments as the
-    forward (the relaxation is replayed from scores + noise/seed)."""
-    lib = _lib.load()
+    forward (the relaxation is replayed from scores + noise/seed).  With a k per row, ``k_cap`` sizes the kernel's LDS history."""
     flat, ptr, B, nmax, nmax_dev = _rows(scores, plan)
+    rows = _k_rows(k, k_cap, B, scores.device)
     g = grad_out.reshape(flat.shape).contiguous()
     out = torch.empty_like(flat)
-    _lib.check(lib.isg_topk_gumbel_bwd(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
-                                       _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1), _gid_ptr(plan), int(k), float(tau),
-                                       _chk(g, "grad_out", torch.float32), out.data_ptr(), _stream()),
-               "isg_topk_gumbel_bwd")
+    if rows is None:
+        lib = _lib.load()
+        _lib.check(lib.isg_topk_gumbel_bwd(_chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev,
+                                           _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1), _gid_ptr(plan), int(k), float(tau),
+                                           _chk(g, "grad_out", torch.float32), out.data_ptr(), _stream()),
+                   "isg_topk_gumbel_bwd")
+    else:
+        from . import _lib_topk_rows
+        _lib.check(_lib_topk_rows.load().isg_topk_gumbel_rows_bwd(
+            _chk(flat, "scores", torch.float32), ptr, B, nmax, nmax_dev, _noise_ptr(noise, B, nmax), int(seed) & (2 ** 64 - 1),
+            _gid_ptr(plan), rows[0], rows[1], float(tau), _chk(g, "grad_out", torch.float32), out.data_ptr(), _stream()),
+            "isg_topk_gumbel_rows_bwd")
+        COUNTERS["topk_rows"] += 1
     return out.view(scores.shape)
 
 

@@ -49,22 +49,24 @@ class PerturbAndMAP:
         """k of the wrapped IMLEScheme when the solver is the stock threshold top-k, else None."""
         return getattr(self.function, "_isg_threshold_k", None)
 
-    def differentiable(self, scores: Tensor, plan, noise: Optional[Tensor], seed: int = 0) -> Tensor:
+    def differentiable(self, scores: Tensor, plan, noise: Optional[Tensor], seed: int = 0, k=None,
+                       k_cap: Optional[int] = None) -> Tensor:
         """The estimator on one row layout (ragged with ``plan``, dense [B, Nmax] without); scores requires grad.
-        ``noise`` [B, Nmax] Gumbel(0, 0.3) draw or None for the in-kernel Philox stream of ``seed``."""
+        ``noise`` [B, Nmax] Gumbel(0, 0.3) draw or None for the in-kernel Philox stream of ``seed``.  ``k``: None for the
+        scheme's k, or a k per row (int32 [B] device tensor, with ``k_cap``) that the forward and the target solves share."""
         from ... import autograd
-        k = self._scheme_k()
-        if self.nb_samples != 1 or k is None:
+        if self.nb_samples != 1 or self._scheme_k() is None:
             raise NotImplementedError("backward needs nb_samples == 1 and the stock threshold top-k solver")
+        k = int(self._scheme_k()) if k is None else k
         if self.kind == "imle":
             t = self.target_distribution
-            return autograd.imle_topk(scores, int(k), plan, noise, seed, float(t.alpha), float(t.beta),
-                                      self.noise_temperature, self.target_noise_temperature)
+            return autograd.imle_topk(scores, k, plan, noise, seed, float(t.alpha), float(t.beta),
+                                      self.noise_temperature, self.target_noise_temperature, k_cap)
         from .target_aimle import AdaptiveTargetDistribution
         if not isinstance(self.target_distribution, AdaptiveTargetDistribution):
             raise NotImplementedError("AIMLE backward is implemented for the adaptive target (masking.py:258-260)")
-        return autograd.aimle_topk(scores, int(k), plan, noise, seed, self.target_distribution,
-                                   self.noise_temperature, self.target_noise_temperature)
+        return autograd.aimle_topk(scores, k, plan, noise, seed, self.target_distribution,
+                                   self.noise_temperature, self.target_noise_temperature, k_cap)
 
     def __call__(self, theta: Tensor, *args, noise: Optional[Tensor] = None):
         if theta.dim() != 3:
