@@ -279,6 +279,13 @@ __global__ __launch_bounds__(256, 3) void node_gate_planes_kernel(const _Float16
     const int q8 = lane >> 3, j8 = lane & 7;                                                                                               \
     const int k = 8 * wave + q8;                                                                                                           \
     if (k < nrows) {                                                                                                                       \
+      LC_AGGREGATE_ROW(REC)                                                                                                                \
+    }                                                                                                                                      \
+  }
+// One destination row on the eight lanes j8 of a lane octet: row k of the tile whose tables are s_rp / s_lg / REC and whose first
+// node and slot count are r0 / ne.  LC_AGGREGATE hands in wave-uniform tables, the grouped kernel's list pass per-lane ones.
+#define LC_AGGREGATE_ROW(REC)                                                                                                              \
+    {                                                                                                                                      \
       const int rb = s_rp[k], re = min(s_rp[k + 1], ne);                                                                                   \
       float lg4[4], e4[4];                                                                                                                 \
       int4 rc4[4];                                                                                                                         \
@@ -396,8 +403,7 @@ __global__ __launch_bounds__(256, 3) void node_gate_planes_kernel(const _Float16
         zb |= (unsigned)dpp_mov_i<ISG_DPP_HMIRROR>((int)zb);                                                                               \
         if (j8 == 0) a.row_dead[(int64_t)(r0 + k) * a.H + hd] = zb == 0u ? 1 : 0;                                                          \
       }                                                                                                                                    \
-    }                                                                                                                                      \
-  }
+    }
 
 // KSE_T: 16-column steps of the edge product when known at compile time (8 = the 128 edge features of the model: no branch between
 // the MFMAs), 0 = read it from the arguments
@@ -790,26 +796,37 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
 //            the live slots in (tile, CSR slot) order -> per-tile lists of slot numbers
 //   node product ONCE for the listed rows (a gather: the LDS-DMA's source address is per lane), the second 32-row block only for
 //            a list longer than 32; edge product once per 64 live slots of the group, logits to their (tile, slot) places
-//   per tile softmax + aggregation over EVERY in-edge as above (LC_AGGREGATE): a dead slot's source maps to list position 0 (any
-//            finite row: its weight is +-0), its logit is the +0 the scan wrote
+//   softmax + aggregation (LC_AGGREGATE_ROW) ONCE per sub-group, over the rows that are the destination of a live slot (per tile
+//            the 64-bit set ldst, a subset of the named rows, so at most 64 per sub-group): entry i of their (tile, row) list goes
+//            to wave i & 7, lane octet i >> 3, with its own tile's tables per lane.  A listed row walks EVERY in-edge as above: a
+//            dead slot's source maps to list position 0 (any finite row: its weight is +-0), its logit is the +0 the scan wrote
+//   fill     every other row of the sub-group's tiles holds only dead in-slots: all logits +0, so the maximum is +0, every
+//            exp2f((0 - 0) * log2e) is 1, the denominator n ones added in order = n, alpha = 1 * rcp(n + 1e-16) for each of its n
+//            in-slots, every term fmaf(x, w * +-0, o) leaves o = +0 for finite x, the row is +0 + bias, flagged dead, and its
+//            maximum is that vector's -- computed once per workgroup (the head is fixed) with LC_AGGREGATE_ROW's expression and
+//            lane layout.  These rows are written as constants, 16 bytes per lane, without walking an edge.
+//            AGG_ALL (ISG_LC_AGG_ALL_ROWS=1): LC_AGGREGATE per tile over all 64 rows instead, as before (A/B; the same bits)
 // A product element depends on its own row's planes, the W fragments, the MFMA shape and the k order, not on the column its row
-// sits in, so out / alpha / rowmax / row_dead are the per-tile kernel's bits for finite inputs.  A group whose list would pass 64
-// rows runs its tiles one by one through the same code.  The panel of node planes and the edge panel image share their LDS here
-// (nothing of the next group is in flight under a product), which pays for the G table sets.
+// sits in, so out / alpha / rowmax / row_dead are the per-tile kernel's bits for FINITE inputs (both the dead slots' reads of list
+// position 0 and the fill rest on x * +-0 = +-0).  A group whose list would pass 64 rows runs its tiles one by one through the
+// same code.  The panel of node planes and the edge panel image share their LDS here (nothing of the next group is in flight
+// under a product), which pays for the G table sets.
 constexpr int LG_MAXG = 6, LC_GROUP_DEFAULT = 6;      // 6 since the tables come from memory (4 before)
 // LG_T_* / LG_TILE_BYTES, a table set's fields: csrc/isg_live_tables.hpp, shared with the pre-pass that writes them to memory
 static_assert(LT_ROWS == LC_ROWS && LT_ECAP == LC_ECAP, "the table sets are cut for this kernel's tiles");
 constexpr int LG_OFF_T = LC_OFF_A + 2 * 64 * LC_LDA * 2;
 constexpr int LG_OFF_MISC = LG_OFF_T + LG_MAXG * LG_TILE_BYTES;
 constexpr int LG_MISC_FLOATS = 4 * 64 + 3 * LC_C + 4 * LC_C + 64;       // s_part, att / we_inv / bias, bn / wn_inv, s_nodes
-constexpr int LG_SMEM_BYTES = LG_OFF_MISC + LG_MISC_FLOATS * 4 + LG_MAXG * 16 + LG_MAXG * 8 + LG_MAXG * 4 * 8;
+// ... s_desc, s_touch, s_livew, then the live-destination row sets of two groups in turn, the aggregation list (64 byte pairs)
+// and the fill's row maximum
+constexpr int LG_SMEM_BYTES = LG_OFF_MISC + LG_MISC_FLOATS * 4 + LG_MAXG * 16 + LG_MAXG * 8 + LG_MAXG * 4 * 8 + 2 * LG_MAXG * 8 + 64 * 2 + 16;
 static_assert(LG_TILE_BYTES % 16 == 0 && LG_OFF_T % 16 == 0 && LG_OFF_MISC % 16 == 0 && LG_T_RP + 64 * 4 == 4 * 1024 &&
                   LG_TILE_BYTES == 4 * 1024 + 5 * 16 && LG_H_DESC == 4096 + 16 && LG_H_TOUCH == 4096 + 32 && LG_H_LIVE == 4096 + 48,
               "16-byte pieces; the fetch of a table set from memory: four 1 KiB pieces, then five 16-byte ones");
 static_assert(64 * 512 <= 2 * 64 * LC_LDA * 2, "the node planes fit the panel image they share LDS with");
 static_assert(LG_SMEM_BYTES <= 160 * 1024, "one workgroup per CU");
 
-template <int KSE_T, bool SL01, bool TABLES>
+template <int KSE_T, bool SL01, bool TABLES, bool AGG_ALL>
 __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(LcArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
   typedef float (*BufX)[LC_LDX];
@@ -833,6 +850,10 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
   int4 *s_desc = reinterpret_cast<int4 *>(s_nodes + 64);                     // [LG_MAXG] the group's {r0, nrows, e0, ne}
   unsigned long long *s_touch = reinterpret_cast<unsigned long long *>(s_desc + LG_MAXG);      // [LG_MAXG] rows a live slot names
   unsigned long long *s_livew = s_touch + LG_MAXG;                           // [LG_MAXG][4] live-slot bit words
+  unsigned long long *s_ldst0 = s_livew + 4 * LG_MAXG;     // [2][LG_MAXG] rows a live slot has as destination; a group's set is read
+                                                           // until its last store, so the next group fills the other one
+  unsigned short *s_alist = reinterpret_cast<unsigned short *>(s_ldst0 + 2 * LG_MAXG);      // [64] aggregation list: tile << 8 | row
+  float *s_fillmax = reinterpret_cast<float *>(s_alist + 64);                // the row maximum of a row without a live in-slot
 
   const int bid = blockIdx.x;
   const int per_xcd = gridDim.x >> 3, jx = bid >> 3;
@@ -887,11 +908,34 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
   }
   const float slope = a.slope;
   const int prow = half * 32 + fr;
+  // the fill's row maximum, once per workgroup (the head is fixed): a row without a live in-slot is +0 + bias, and its maximum is
+  // LC_AGGREGATE_ROW's expression on that vector in its lane layout (lane j8 of an octet: four columns of each 32), so that a NaN
+  // or a -0 in the bias gives the macro's bits.  The zero is opaque like the macro's accumulators: +0 + -0 = +0 stays an addition.
+  // Kept in LDS, not in a register for the launch's length (the group loop's barriers order the write before its reads).
+  if constexpr (!AGG_ALL) {
+    float zero = 0.f, fill_max = 0.f;
+    asm volatile("" : "+v"(zero));
+    const int j8 = lane & 7;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      float4 o = make_float4(zero, zero, zero, zero);
+      if (a.bias) {
+        const float4 b4 = *reinterpret_cast<const float4 *>(a.bias + hoff + 32 * m + j8 * 4);
+        o.x += b4.x; o.y += b4.y; o.z += b4.z; o.w += b4.w;
+      }
+      fill_max = fmaxf(fill_max, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+    }
+    fill_max = group_max<8>(fill_max);
+    if (tid == 0) *s_fillmax = fill_max;
+  }
+  int par = 0;
 
 #pragma unroll 1
   for (int tg = t; tg < T; tg += G * ngrp) {
     int tl = tid, ll = lane;      // laundered: what the scan derives from them is not hoisted out of the group loop and spilled
     asm volatile("" : "+v"(tl), "+v"(ll));
+    unsigned long long *s_ldst = s_ldst0 + par * LG_MAXG;
+    par ^= 1;
     int ng = 0;
     if constexpr (TABLES) {
       // ---- fetch: the group's table sets as the pre-pass wrote them (isg_layer_conv_live_tables), addresses from the tile numbers
@@ -953,7 +997,16 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
           }
         }
       }
-      if (tl < LG_MAXG) s_touch[tl] = 0ull;      // (read last before the previous group's compaction barrier)
+      if constexpr (AGG_ALL) {
+        if (tl < LG_MAXG) s_touch[tl] = 0ull;    // (read last before the previous group's compaction barrier)
+      } else {
+        unsigned zz = 0u;      // made here: a zero pair hoisted out of the group loop costs two registers for the launch's length
+        asm volatile("" : "+v"(zz));
+        if (tl < LG_MAXG) {    // s_touch: as above; s_ldst: the previous group's fill may still read the OTHER set
+          s_touch[tl] = (unsigned long long)zz << 32 | zz;
+          s_ldst[tl] = (unsigned long long)zz << 32 | zz;
+        }
+      }
       __syncthreads();         // every wave is done with the previous group's tables and slices; the row sets are empty
 #pragma unroll
       for (int j = 0; j < LG_MAXG; ++j) {
@@ -974,6 +1027,9 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
             const unsigned long long bw = __ballot(lv);
             if (ll == 0) s_livew[j * 4 + wave] = bw;
             if (lv) atomicOr(&s_touch[j], (1ull << sx) | (1ull << dz));
+            if constexpr (!AGG_ALL) {
+              if (lv) atomicOr(&s_ldst[j], 1ull << dz);
+            }
             LG_EM(j)[tl] = make_int2(eidv[j], __float_as_int(mskv[j]));
             LG_LG(j)[tl] = lv ? einvv[j] : 0.f;        // a dead slot's logit is +0
             LG_SP(j)[tl] = (unsigned char)sx;
@@ -1019,6 +1075,26 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
               if ((w >> ll) & 1ull) LG_LV(j)[pre + __popcll(w & ((1ull << ll) - 1ull))] = (unsigned char)tl;
             }
           }
+          if constexpr (TABLES && !AGG_ALL) {
+            // the rows with a live in-slot, as the aggregation walks them: row k's slots are rp[k] .. min(rp[k + 1], ne), and the
+            // live words say whether one of them is live.  One row per lane of wave 0 and one ballot: the live list's destination
+            // bytes name the same rows, but OR-ing them into LDS behind two dependent reads cost 24 k cycles of a wave's 160 k.
+            // Tile j on wave j + 1 (wave 0 has the maps above): the tiles' chains of LDS reads run side by side
+            if (wave == j + 1) {
+              int rl = ll;               // laundered here: six row-pointer addresses held across the sub-group loop are spilled
+              asm volatile("" : "+v"(rl));
+              const int4 dj = s_desc[j];
+              const int rb = rl < dj.y ? LG_RP(j)[rl] : 0, re = rl < dj.y ? min(LG_RP(j)[rl + 1], dj.w) : 0;
+              bool any = false;
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const int lo = min(max(rb - 64 * i, 0), 64), hi = min(max(re - 64 * i, 0), 64);
+                if (hi > lo) any |= ((s_livew[j * 4 + i] >> lo) << (lo + 64 - hi)) != 0ull;      // bits lo .. hi - 1
+              }
+              const unsigned long long rows = __ballot(any);
+              if (ll == 0) s_ldst[j] = rows;
+            }
+          }
           nl += __builtin_amdgcn_readfirstlane(__popcll(m));
           nlive += (c[0] + c[1]) + (c[2] + c[3]);
         }
@@ -1042,6 +1118,21 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
 #pragma unroll
       for (int j = 0; j < LG_MAXG; ++j)
         if (j >= ja && j < jb && tid < LC_ECAP) LG_SP(j)[tid] = LG_POS(j)[LG_SP(j)[tid]];
+      // the aggregation list: (tile, row) of every live-destination row, in that order; at most 64, being named rows
+      int nagg = 0;
+      if constexpr (!AGG_ALL) {
+        unsigned long long lm[LG_MAXG];      // every tile's set first (independent reads), then tile j's entries on wave j
+#pragma unroll
+        for (int j = 0; j < LG_MAXG; ++j) lm[j] = s_ldst[j];
+#pragma unroll
+        for (int j = 0; j < LG_MAXG; ++j) {
+          const unsigned long long m = j >= ja && j < jb ? lm[j] : 0ull;
+          const int p = nagg + __popcll(m & ((1ull << ll) - 1ull));
+          if (wave == j && ((m >> ll) & 1ull) && p < LC_ROWS) s_alist[p] = (unsigned short)(j << 8 | ll);
+          nagg += __builtin_amdgcn_readfirstlane(__popcll(m));
+        }
+        nagg = min(nagg, LC_ROWS);       // (row pointers that disagree with the destinations could list more: never past the list)
+      }
       if (nlive == 0) {
         __syncthreads();     // no live slot: no product; the sources' positions (all 0) are complete
       } else {
@@ -1180,21 +1271,87 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
         LC_STAMP(11)         // last logit sums + barrier
       }
 #undef LG_FIND
-      // ---- per tile: softmax + aggregation over every in-edge, out / alpha / rowmax / row_dead for every row ---------------------
-#pragma unroll 1
-      for (int j = ja; j < jb; ++j) {
-        const int4 dj = s_desc[j];
-        const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
-                  ne = __builtin_amdgcn_readfirstlane(dj.w);
-        const float *s_lg = LG_LG(j);
-        const int *s_rp = LG_RP(j);
-        const int2 *s_em = LG_EM(j);
-        const unsigned char *s_sp = LG_SP(j);
 #define LG_REC(i) make_int4((int)s_sp[i], s_em[i].x, 0, s_em[i].y)
-        LC_AGGREGATE(LG_REC)
-#undef LG_REC
+      if constexpr (AGG_ALL) {
+        // ---- per tile: softmax + aggregation over every in-edge, out / alpha / rowmax / row_dead for every row -------------------
+#pragma unroll 1
+        for (int j = ja; j < jb; ++j) {
+          const int4 dj = s_desc[j];
+          const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
+                    ne = __builtin_amdgcn_readfirstlane(dj.w);
+          const float *s_lg = LG_LG(j);
+          const int *s_rp = LG_RP(j);
+          const int2 *s_em = LG_EM(j);
+          const unsigned char *s_sp = LG_SP(j);
+          LC_AGGREGATE(LG_REC)
+        }
+        LC_STAMP(6)          // per tile: softmax + aggregation, stores
+      } else {
+        // ---- fill: the rows without a live in-slot, as constants.  out: 16 rows x 32 lanes x 16 bytes per store instruction, a
+        // tile's four passes unrolled (nothing to wait for between them); alpha: one in-slot per thread of waves 0-3, its row from
+        // the destination byte, rcp(n) from the row pointers; row maxima and flags: one row per lane of wave 4 ---------------------
+        int ft = tl;                               // laundered here: the stores' addresses are formed per pass, not held in
+        asm volatile("" : "+v"(ft));               // registers under the products
+        const int fc4 = ft & 31, frow = ft >> 5;
+        hf32x4 fill4 = {0.f, 0.f, 0.f, 0.f};       // this lane's 16 bytes of +0 + bias (an addition, as for the row maximum above)
+        if (a.bias) {
+          float zero = 0.f;
+          asm volatile("" : "+v"(zero));
+          const float4 b4 = *reinterpret_cast<const float4 *>(&s_bias[fc4 * 4]);
+          fill4 = hf32x4{zero + b4.x, zero + b4.y, zero + b4.z, zero + b4.w};
+        }
+        const float fill_max = *s_fillmax;
+#pragma unroll 1
+        for (int j = ja; j < jb; ++j) {
+          const int4 dj = s_desc[j];
+          const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
+                    ne = __builtin_amdgcn_readfirstlane(dj.w);
+          const unsigned long long m = s_ldst[j];
+#pragma unroll
+          for (int u = 0; u < LC_ROWS * 32 / LC_THREADS; ++u) {
+            const int k = frow + u * (LC_THREADS / 32);
+            if (k < nrows && !((m >> k) & 1ull))
+              __builtin_nontemporal_store(fill4, reinterpret_cast<hf32x4 *>(a.out + (int64_t)(r0 + k) * a.ldo + hoff + fc4 * 4));
+          }
+          if (ft < LC_ECAP) {
+            if (ft < ne) {
+              const int dz = LG_DR(j)[ft];         // the slot's row: its in-degree is the row's segment, cut at the tile's slots
+              if (!((m >> dz) & 1ull)) {
+                const int n = min(LG_RP(j)[dz + 1], ne) - LG_RP(j)[dz];
+                a.alpha[(int64_t)LG_EM(j)[ft].x * a.H + hd] = __builtin_amdgcn_rcpf((float)n + 1e-16f);
+              }
+            }
+          } else if (ft < LC_ECAP + LC_ROWS) {
+            const int k = ft - LC_ECAP;
+            if (k < nrows && !((m >> k) & 1ull)) {
+              if (a.rowmax) a.rowmax[(int64_t)(r0 + k) * a.H + hd] = fill_max;
+              if (a.row_dead) a.row_dead[(int64_t)(r0 + k) * a.H + hd] = 1;
+            }
+          }
+        }
+        LC_STAMP(5)          // fill: constant rows, alpha = 1 / n
+        // ---- list pass: softmax + aggregation of the live-destination rows, each with its own tile's tables ---------------------
+        {
+          const int q8 = ll >> 3;
+          int j8 = ll & 7;                       // laundered here, as in the fill
+          asm volatile("" : "+v"(j8));
+          const int i = 8 * q8 + wave;           // entry i: wave i & 7, octet i >> 3 -- short lists keep all eight waves busy
+          if (i < nagg) {
+            const int ent = s_alist[i];
+            const int k = ent & 255;
+            const unsigned char *tb = s_tiles + (ent >> 8) * LG_TILE_BYTES;
+            const int4 dj = s_desc[ent >> 8];
+            const int r0 = dj.x, ne = dj.w;
+            const float *s_lg = reinterpret_cast<const float *>(tb + LG_T_LG);
+            const int *s_rp = reinterpret_cast<const int *>(tb + LG_T_RP);
+            const int2 *s_em = reinterpret_cast<const int2 *>(tb);
+            const unsigned char *s_sp = tb + LG_T_SP;
+            LC_AGGREGATE_ROW(LG_REC)
+          }
+        }
+        LC_STAMP(7)          // list pass: softmax + aggregation of live-destination rows, stores
       }
-      LC_STAMP(6)            // per tile: softmax + aggregation, stores
+#undef LG_REC
     }
   }
 #undef LG_EM
@@ -1293,6 +1450,9 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
   static const bool dense_mask = [] { const char *e = getenv("ISG_LC_DENSE_MASK"); return e && atoi(e) != 0; }();
   // ISG_LC_TABLES=0: the groups kernel scans its tiles itself whatever the caller hands in (A/B; the same bits either way)
   if (!isg_layer_conv_live_tables_enabled()) live_tables = nullptr;
+  // ISG_LC_AGG_ALL_ROWS=1: the groups kernel aggregates every row of every tile, as before the list pass and the constant fill
+  // (A/B; the same bits either way)
+  static const bool agg_all_rows = [] { const char *e = getenv("ISG_LC_AGG_ALL_ROWS"); return e && atoi(e) != 0; }();
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   LcArgs a = {
       .xp = reinterpret_cast<const _Float16 *>(x_planes), .xinv = x_inv_scale, .Wn = reinterpret_cast<const _Float16 *>(wn_frag),
@@ -1309,10 +1469,14 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
   a.G = lc_group_rule(N, E, H, max_tiles, &gpx);
   const unsigned grid = 8u * (unsigned)H * (unsigned)gpx;
   hipStream_t st = as_stream(stream);
+#define LC_LAUNCH_GTA(KT, SL, TB, AA)                                                                                \
+  {                                                                                                                  \
+    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL, TB, AA>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;        \
+    gatv2_layer_conv_groups_kernel<KT, SL, TB, AA><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                      \
+  }
 #define LC_LAUNCH_GT(KT, SL, TB)                                                                                     \
   {                                                                                                                  \
-    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL, TB>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;            \
-    gatv2_layer_conv_groups_kernel<KT, SL, TB><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                          \
+    if (agg_all_rows) LC_LAUNCH_GTA(KT, SL, TB, true) else LC_LAUNCH_GTA(KT, SL, TB, false)                          \
   }
 #define LC_LAUNCH_G(KT, SL)                                                                                          \
   {                                                                                                                  \
@@ -1339,6 +1503,7 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
 #undef LC_LAUNCH_M
 #undef LC_LAUNCH_G
 #undef LC_LAUNCH_GT
+#undef LC_LAUNCH_GTA
 #undef LC_LAUNCH
   return check_launch();
 }

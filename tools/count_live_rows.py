@@ -4,7 +4,9 @@ configs[1] -- live rows of the masked layer (a destination with an in-slot whose
 dead rows -- from synthetic.make_workload, the model's CPU path (its mask indices are bit-exact with the GPU's) and isg_tile_plan's
 packing rule (64 nodes / 256 slots, consecutive graphs, 1024-graph chunks).       python3 tools/count_live_rows.py [graphs]
 Then DESIGN.md 17.12's count: per group of G tiles of the masked layer kernel's grouped form, the nodes that a live slot names and
-the live slots, in the order the kernel walks (heavy-first list, a workgroup takes every 64th entry: 256 CUs, 4 heads)."""
+the live slots, in the order the kernel walks (heavy-first list, a workgroup takes every 64th entry: 256 CUs, 4 heads).
+Then DESIGN.md 17.15's count: the live-destination rows (the rows the grouped kernel's one aggregation pass lists; every other row
+of a tile is a constant fill) per tile and per group of G tiles in the same walk, and the fill rows' in-slots (one alpha store each)."""
 import os
 import sys
 
@@ -80,3 +82,32 @@ for G in (1, 2, 3, 4, 5, 6):
     pc = lambda m: f"{100 * m.double().mean().item():.1f} %"
     print(f"| {G} | {len(nn)} | {nn.double().mean().item():.1f} / {int(nn.max())} | {pc(nn > 32)} | {pc(nn > 64)} | "
           f"{ns.double().mean().item():.1f} / {int(ns.max())} | {pc(ns > 64)} |")
+
+# ---- 17.15: the rows the grouped kernel aggregates.  A row is listed when a live slot has it as destination (`live` above); the
+# list of a sub-group is one pass of at most 64 rows (a subset of the named nodes: a group beyond 64 named nodes runs tile by tile).
+cs_live = torch.cat([torch.zeros(1, dtype=torch.long), live.long().cumsum(0)])
+indeg = torch.bincount(dst, minlength=N)
+per_tile = torch.tensor([int(cs_live[a + n] - cs_live[a]) for a, n, _ in tiles])
+rows_tile = torch.tensor([n for _, n, _ in tiles])
+print(f"\n{int(live.sum())} of {N} rows are the destination of a live slot ({100 * live.double().mean().item():.1f} %): listed; the other "
+      f"{int((~live).sum())} are fills, holding {int(indeg[~live].sum())} of {src.numel()} in-slots (one alpha store each) and "
+      f"{int((indeg[~live] == 0).sum())} rows without an in-slot")
+print(f"per tile: rows {rows_tile.double().mean().item():.1f}, listed mean {per_tile.double().mean().item():.2f} / max {int(per_tile.max())}, "
+      f"tiles without a listed row {int((per_tile == 0).sum())} of {len(tiles)}")
+print("| tiles per group G | groups | listed rows mean / max | groups > 8 rows (a wave with two) | groups > 64 rows | 64-row passes before (one per tile) | after (one per sub-group) |")
+print("|---|---|---|---|---|---|---|")
+for G in (1, 2, 4, 6):
+    nl, passes = [], 0
+    for w in range(min(NGRP, len(heavy))):
+        seq = heavy[w::NGRP]
+        for i in range(0, len(seq), G):
+            grp = [tiles[t] for t in seq[i:i + G]]
+            named_rows = sum(int(cs_named[a + n] - cs_named[a]) for a, n, _ in grp)
+            listed = [int(cs_live[a + n] - cs_live[a]) for a, n, _ in grp]
+            if named_rows <= 64:
+                nl.append(sum(listed)); passes += 1
+            else:                          # the fall-back: the group's tiles one by one
+                nl += listed; passes += len(grp)
+    nl = torch.tensor(nl)
+    pc = lambda m: f"{100 * m.double().mean().item():.1f} %"
+    print(f"| {G} | {len(nl)} | {nl.double().mean().item():.1f} / {int(nl.max())} | {pc(nl > 8)} | {pc(nl > 64)} | {len(tiles)} | {passes} |")

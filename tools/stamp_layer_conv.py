@@ -6,7 +6,9 @@
 batch -- taken from one forward of the model -- and, first, how many of each tile's CSR slots that mask leaves live (nonzero).
 The masked launch is the grouped form unless ISG_LC_GROUP=1 is set: its phases carry their own labels.
 --tables (with --masked): the tiles' live tables come from isg_layer_conv_live_tables, whose launch the stamps
-do not cover: the first phase is then the fetch of the images, and compaction builds no live lists."""
+do not cover: the first phase is then the fetch of the images, and compaction builds no live lists.
+The grouped form ends in the constant fill and the list pass, each with a line of its own; with
+ISG_LC_AGG_ALL_ROWS=1 it ends in the per-tile aggregation over all rows instead, as before."""
 import ctypes
 import os
 import sys
@@ -98,11 +100,13 @@ names = ["first tile's inputs (once)", "node GEMM: barrier", "chunks: staging ba
          "hand-over barrier", "node GEMM: k loop", "node GEMM: epilogue (LDS writes)", "chunks: wait for the planes, LDS writes", "last logit sums + barrier", "(total)", "(probe) other", "(probe) exposed latency of a chunk request"]
 if nm_arg and os.environ.get("ISG_LC_GROUP") != "1" and os.environ.get("ISG_LC_DENSE_MASK", "0") == "0":
     # gatv2_layer_conv_groups_kernel's stamps (per group of tiles; 3, 4, 10 per chunk; 6 covers the group's tiles)
+    # 5 and 7: the constant fill and the list pass; 6 only with ISG_LC_AGG_ALL_ROWS=1, which runs neither
     names = ["fetch: the group's table images (per group)" if use_tables else "scan: requests, tables, ballots (per group)",
              "compaction: node list, maps" if use_tables else "compaction: node list, maps, live lists", "gather: node planes, first edge planes (wait)",
-             "group chunks: k loops", "group chunks: epilogue + barrier", "-", "per tile: softmax + aggregation, stores (all tiles of the group)",
-             "-", "group node product: k loop", "group node product: barrier + epilogue (LDS writes)", "panel staging + barrier",
-             "last logit sums + barrier", "(total)"]
+             "group chunks: k loops", "group chunks: epilogue + barrier", "fill: rows without a live in-slot, as constants (per sub-group)",
+             "per tile: softmax + aggregation, stores (all tiles of the group)",
+             "list pass: softmax + aggregation of live-destination rows (per sub-group)", "group node product: k loop",
+             "group node product: barrier + epilogue (LDS writes)", "panel staging + barrier", "last logit sums + barrier", "(total)"]
 tot = s[:, 12].mean().item()
 nwg = s.size(0) // 8
 print(f"{T} tiles x {H} heads on {nwg} persistent workgroups of 8 waves; a wave lives {tot:.0f} cycles = {tot * nwg / max(T * H, 1):.0f} per (tile, head)")
