@@ -619,11 +619,13 @@ def add_layernorm(x, residual, norm, p=0.0, seed=0):
 # ------------------------------------------------------------------------------------------------
 class _GatV2MP(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, slope, kernel):
+    def forward(ctx, x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, slope, kernel, drop_p=0.0, drop_seed=0):
         out, alpha = ops.gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias=bias, node_mask=node_mask,
-                                  edge_mask=edge_mask, negative_slope=slope, kernel=kernel)
+                                  edge_mask=edge_mask, negative_slope=slope, kernel=kernel, dropout_p=drop_p,
+                                  dropout_seed=drop_seed)
         ctx.save_for_backward(x_l, x_r, e_proj, att, alpha, node_mask, edge_mask)
         ctx.cfg = (plan, heads, slope, bias is not None)
+        ctx.drop = (drop_p, drop_seed)        # no mask is kept: the backward draws it again from (seed, edge id, head)
         ctx.mark_non_differentiable(alpha)
         return out, alpha
 
@@ -635,18 +637,19 @@ class _GatV2MP(torch.autograd.Function):
         want_mask = (node_mask is not None and need[5]) or (edge_mask is not None and need[6])
         d_xl, d_xr, d_e, d_att, d_bias, d_m = ops.gatv2_mp_backward(
             x_l, x_r, e_proj, att, alpha, g_out, plan, heads, node_mask=node_mask, edge_mask=edge_mask,
-            negative_slope=slope, want_mask_grad=want_mask)
+            negative_slope=slope, want_mask_grad=want_mask, dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1])
         d_node = d_edge = None
         if want_mask and node_mask is not None:       # the fused mask[src]*mask[dst] product keeps the reference's rule
             d_node = ops.node_to_edge_mask_backward(d_m, plan).view_as(node_mask)
         elif want_mask:
             d_edge = d_m.view_as(edge_mask)
         return (d_xl, d_xr, d_e, d_att.view_as(att), d_bias if has_bias else None, d_node, d_edge,
-                None, None, None, None)
+                None, None, None, None, None, None)
 
 
-def gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, negative_slope, kernel):
-    return _GatV2MP.apply(x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, negative_slope, kernel)
+def gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, negative_slope, kernel, dropout_p=0.0, dropout_seed=0):
+    return _GatV2MP.apply(x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, negative_slope, kernel, dropout_p,
+                          dropout_seed)
 
 
 class _NodeToEdgeMask(torch.autograd.Function):

@@ -22,7 +22,9 @@ _ARG_DEFAULTS = dict(text_sampling=False, general_hidden_dim=300, distributed=Fa
                      mgat_masks=[1.0, 1.0, 1.0, 0.15], use_topk=True, interpretable_mode=False, concat_instr=0,
                      embed_cat=0, device="cuda",
                      # this project's own flags (a node budget per graph); a reference checkpoint has neither
-                     sample_ratio=None, sample_k_min=1)
+                     sample_ratio=None, sample_k_min=1,
+                     # attention dropout of the GATv2 layers in training; an older checkpoint trains without
+                     attn_dropout=0.0)
 
 
 def strip_ddp_prefix(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -15,6 +15,7 @@
 //     the reference's CPU scatter, ONE fma per term (a single rounding where the CPU's multiply and
 //     add round twice; written as fmaf so that it does not depend on the compiler's contraction)
 #include "isg_mp.hpp"
+#include "../../include/isg_mp_train.h"
 
 #include <stdlib.h>
 
@@ -22,7 +23,9 @@
 
 namespace isg {
 
-template <int H, int P>
+// DROP: attention dropout on the aggregation's weights (include/isg_mp_train.h) -- alpha leaves as the softmax, the message is
+// weighted by (alpha * r) * m.  A compile-time switch: the instantiations without it hold no trace of it.
+template <int H, int P, bool DROP = false>
 __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_kernel(MpArgs a) {
   constexpr int G = 64 / H;
   __shared__ int s_rowptr[MP_NPB + 1];
@@ -148,8 +151,14 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_kernel(MpArgs a) {
       const float w = expf(lg - mx) / den;
       if (l == 0) a.alpha[(size_t)e * H + g] = w;
       float wm = w;
-      if (mode == 1) wm = mul_rn(w, a.node_mask[j] * mi);
-      else if (mode == 2) wm = mul_rn(w, a.edge_mask[e]);
+      if (DROP) {   // the slot's edge id is wave-uniform: one Philox block per edge and four heads
+        uint32_t c[4];
+        const int eu = __builtin_amdgcn_readfirstlane(e);
+        mp_drop_block(a.drop_seed, (uint32_t)eu, H > 4 ? (uint32_t)(g >> 2) : 0u, c);
+        wm = mul_rn(w, mp_drop_head(c, g, a.drop_p, a.drop_inv));
+      }
+      if (mode == 1) wm = mul_rn(wm, a.node_mask[j] * mi);
+      else if (mode == 2) wm = mul_rn(wm, a.edge_mask[e]);
       const float4 *xl = a.x_l + (size_t)j * a.ldl4;
 #pragma unroll
       for (int p = 0; p < P; ++p) {
@@ -187,6 +196,20 @@ static int launch_mp(const MpArgs &a, hipStream_t st) {
   b.nchunks = blocks;
   const int gridx = (b.flags & 2) ? ((blocks + 7) / 8) * 8 : blocks;
   dim3 grid(gridx), block(MP_WAVES * 64);
+  if (b.drop_p > 0.f) {
+    switch (P) {
+      case 1: gatv2_mp_kernel<H, 1, true><<<grid, block, 0, st>>>(b); break;
+      case 2: gatv2_mp_kernel<H, 2, true><<<grid, block, 0, st>>>(b); break;
+      case 3: gatv2_mp_kernel<H, 3, true><<<grid, block, 0, st>>>(b); break;
+      case 4: gatv2_mp_kernel<H, 4, true><<<grid, block, 0, st>>>(b); break;
+      case 5: gatv2_mp_kernel<H, 5, true><<<grid, block, 0, st>>>(b); break;
+      case 6: gatv2_mp_kernel<H, 6, true><<<grid, block, 0, st>>>(b); break;
+      case 7: gatv2_mp_kernel<H, 7, true><<<grid, block, 0, st>>>(b); break;
+      case 8: gatv2_mp_kernel<H, 8, true><<<grid, block, 0, st>>>(b); break;
+      default: return ISG_EUNSUPPORTED;
+    }
+    return check_launch();
+  }
   switch (P) {
     case 1: gatv2_mp_kernel<H, 1><<<grid, block, 0, st>>>(b); break;
     case 2: gatv2_mp_kernel<H, 2><<<grid, block, 0, st>>>(b); break;
@@ -277,7 +300,7 @@ static int mp_fwd(const void *x_l, const void *x_r, const void *e_proj, const fl
                   float negative_slope, const int32_t *graph_ptr, const int32_t *graph_eptr, const int32_t *dst,
                   int64_t B, int32_t nmax_host, int32_t emax_host, int32_t ld_l, int32_t ld_r, int32_t ld_e,
                   void *stream, int f16, float *rowmax = nullptr, const float *logits = nullptr, uint16_t *planes = nullptr,
-                  float *planes_inv = nullptr) {
+                  float *planes_inv = nullptr, float drop_p = 0.f, uint64_t drop_seed = 0) {
   if (N < 0 || E < 0 || H <= 0 || C <= 0) return ISG_EINVAL;
   if (N == 0) return ISG_OK;
   if (!x_l || !att || !rowptr || (!out && !planes) || (E > 0 && (!eid || !src || !alpha))) return ISG_EINVAL;
@@ -297,7 +320,8 @@ static int mp_fwd(const void *x_l, const void *x_r, const void *e_proj, const fl
       .slope = negative_slope, .graph_ptr = graph_ptr, .graph_eptr = graph_eptr, .dst = dst, .B = (int)B, .lrows = 0, .f16 = f16,
       .flags = mp_flags,           // experiment switch, read once; default = tuned setting
       .nchunks = 0, .logits = logits, .rowmax = rowmax, .planes = planes, .planes_inv = planes_inv,
-      .planes_kt = 2 * ((2 * (C >> 2) + 7) >> 3)};     // two half rows of 2 C columns, each padded to whole 32-column lines
+      .planes_kt = 2 * ((2 * (C >> 2) + 7) >> 3),      // two half rows of 2 C columns, each padded to whole 32-column lines
+      .drop_p = drop_p, .drop_inv = 1.0f / (1.0f - drop_p), .drop_seed = drop_seed};
   if (!a.x_l || !a.att || !a.rowptr || (!a.out && !a.planes) || (E > 0 && (!a.eid || !a.src || !a.alpha)) ||
       (!a.logits && (!a.x_r || (E > 0 && !a.e_proj))) || (a.planes && !a.planes_inv))
     return ISG_EINVAL;                         // the struct the kernels dereference, not the parameters it was filled from
@@ -325,6 +349,22 @@ extern "C" int isg_gatv2_mp_fwd(const float *x_l, const float *x_r, const float 
                                 int32_t emax_host, int32_t ld_l, int32_t ld_r, int32_t ld_e, void *stream) {
   return mp_fwd(x_l, x_r, e_proj, att, bias, rowptr, eid, src, node_mask, edge_mask, out, alpha, N, E, H, C,
                 negative_slope, graph_ptr, graph_eptr, dst, B, nmax_host, emax_host, ld_l, ld_r, ld_e, stream, 0);
+}
+
+extern "C" int isg_mp_train_abi_version(void) { return ISG_MP_TRAIN_ABI_VERSION; }
+
+// isg_gatv2_mp_fwd with dropout on the attention weights (include/isg_mp_train.h).  p == 0: isg_gatv2_mp_fwd's launch.
+extern "C" int isg_gatv2_mp_fwd_dropout(const float *x_l, const float *x_r, const float *e_proj, const float *att,
+                                        const float *bias, const int32_t *rowptr, const int32_t *eid, const int32_t *src,
+                                        const float *node_mask, const float *edge_mask, float *out, float *alpha, int64_t N,
+                                        int64_t E, int32_t H, int32_t C, float negative_slope, const int32_t *graph_ptr,
+                                        const int32_t *graph_eptr, const int32_t *dst, int64_t B, int32_t nmax_host,
+                                        int32_t emax_host, int32_t ld_l, int32_t ld_r, int32_t ld_e, float p, uint64_t seed,
+                                        void *stream) {
+  if (!(p >= 0.f && p < 1.f) || !alpha) return ISG_EINVAL;     // a NaN fails both comparisons
+  return mp_fwd(x_l, x_r, e_proj, att, bias, rowptr, eid, src, node_mask, edge_mask, out, alpha, N, E, H, C,
+                negative_slope, graph_ptr, graph_eptr, dst, B, nmax_host, emax_host, ld_l, ld_r, ld_e, stream, 0, nullptr,
+                nullptr, nullptr, nullptr, p, p > 0.f ? seed : 0);
 }
 
 extern "C" int isg_gatv2_mp_fwd_f16(const uint16_t *x_l, const uint16_t *x_r, const uint16_t *e_proj, const float *att,

@@ -38,7 +38,31 @@ struct MpArgs {
   float *planes_inv;      // planes32 operand of isg_linear_h3p -- columns [0, 2C) and [2C, 4C) each padded to whole 32-column
   int planes_kt;          // lines and each under its own row scale planes_inv[segment * N + node] (a workgroup owns two heads:
                           // it knows that half row's largest magnitude, not the whole row's); planes_kt = lines per row
+  float drop_p, drop_inv; // attention dropout (include/isg_mp_train.h): drop probability and 1.0f / (1.0f - p); 0 and 1 = none, and
+  uint64_t drop_seed;     // then only the instantiations without dropout are launched.  Kernel arguments: all three sit in SGPRs
 };
+
+// ---- attention dropout (include/isg_mp_train.h): r(e, h) = keep(e, h) / (1 - p) under the keep rule of include/isg_train.h with
+//      i = the ORIGINAL edge id, j = the head.  One Philox block serves heads 4 hq .. 4 hq + 3 of an edge; with e and hq
+//      wave-uniform (every kernel of the family walks one CSR slot per wave at a time) the ten rounds are scalar instructions.
+__device__ __forceinline__ void mp_drop_block(uint64_t seed, uint32_t e, uint32_t hq, uint32_t (&c)[4]) {
+  c[0] = e; c[1] = hq; c[2] = 0x1571u; c[3] = 0x9E37u;
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    Philox::round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+__device__ __forceinline__ float mp_drop_factor(uint32_t word, float p, float inv) {
+  return (float)(word >> 8) * (1.0f / 16777216.0f) >= p ? inv : 0.f;
+}
+// ... of head h (any lane-varying h inside the block's four heads)
+__device__ __forceinline__ float mp_drop_head(const uint32_t (&c)[4], int h, float p, float inv) {
+  const uint32_t lo = (h & 1) ? c[1] : c[0], hi = (h & 1) ? c[3] : c[2];
+  return mp_drop_factor((h & 2) ? hi : lo, p, inv);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_stream(const float4 *p, bool nt) {

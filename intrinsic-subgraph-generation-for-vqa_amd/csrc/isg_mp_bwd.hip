@@ -20,7 +20,12 @@
 //   K2  source-major over a CSR-by-source plan: d x_l[j] = sum over j's out-edges, in edge-id order, of
 //       (d ep[e] + alpha_e m_e g[dst_e]).
 // The gradient flowing into the returned attention weights `alpha` is not supported (the model never consumes them).
+//
+// With attention dropout (include/isg_mp_train.h; the DROP instantiations, p > 0), r_e = keep(e, h) / (1 - p) regenerated from
+// (seed, original edge id, head) and out_i = sum_e (alpha_e r_e) m_e x_l[j]:  dalpha_e = r_e m_e <g, x_l[j]>, the `raw` that feeds
+// d m_e is r_e <g, x_l[j]>, and K2's weight is (alpha_e r_e) m_e; S, da_e, ds_e, d att, d x_r, d ep follow from those unchanged.
 #include "isg_mp.hpp"
+#include "../../include/isg_mp_train.h"
 
 namespace isg {
 
@@ -34,9 +39,11 @@ struct MpBwdArgs {
   float *d_edge_mask;                      // optional [E]
   int N, C, H;
   float slope;
+  float drop_p, drop_inv;                  // attention dropout: p and 1.0f / (1.0f - p) (0 and 1: none, the plain instantiations)
+  uint64_t drop_seed;
 };
 
-template <int H, int P>
+template <int H, int P, bool DROP = false>
 __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdArgs a) {
   constexpr int G = 64 / H;
   __shared__ int s_rowptr[MP_NPB + 1];
@@ -100,7 +107,12 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
 #pragma unroll
       for (int p = 0; p < P; ++p)
         if (ok[p]) part += dot4(g4[p], xl[off[p]]);
-      const float raw = group_sum<G>(part);
+      float raw = group_sum<G>(part);
+      if (DROP) {   // the slot's edge id is wave-uniform: one Philox block per edge and four heads; pass 2 reads what is stored here
+        uint32_t c[4];
+        mp_drop_block(a.drop_seed, (uint32_t)__builtin_amdgcn_readfirstlane(e), H > 4 ? (uint32_t)(g >> 2) : 0u, c);
+        raw *= mp_drop_head(c, g, a.drop_p, a.drop_inv);
+      }
       const float dal = raw * me;
       const float al = a.alpha[(size_t)e * H + g];
       sum_ad += (double)al * (double)dal;
@@ -200,7 +212,7 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
 }
 
 // K2: one wave per source node; d x_l[j] = sum_{e in out(j)} (d ep[e] + alpha_e m_e g[dst_e]), ascending edge id
-template <int H, int P>
+template <int H, int P, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_mp_bwd_src_kernel(MpBwdArgs a) {
   constexpr int G = 64 / H;
   const int lane = threadIdx.x & 63;
@@ -226,7 +238,13 @@ __global__ __launch_bounds__(256) void gatv2_mp_bwd_src_kernel(MpBwdArgs a) {
     float me = 1.f;
     if (mode == 1) me = mj * a.node_mask[d];
     else if (mode == 2) me = a.edge_mask[e];
-    const float w = a.alpha[(size_t)e * H + g] * me;
+    float al = a.alpha[(size_t)e * H + g];
+    if (DROP) {   // the forward's weight, rounded as the forward rounds it: (alpha r) m
+      uint32_t c[4];
+      mp_drop_block(a.drop_seed, (uint32_t)__builtin_amdgcn_readfirstlane(e), H > 4 ? (uint32_t)(g >> 2) : 0u, c);
+      al = mul_rn(al, mp_drop_head(c, g, a.drop_p, a.drop_inv));
+    }
+    const float w = al * me;
     const float4 *dep = a.d_e_proj + (size_t)e * R;
     const float4 *go = a.grad_out + (size_t)d * R;
 #pragma unroll
@@ -262,13 +280,21 @@ static int launch_bwd(const MpBwdArgs &a, hipStream_t st) {
   const int Q = a.C >> 2;
   const int P = (Q + G - 1) / G;
   const int blocks = (a.N + MP_NPB - 1) / MP_NPB;
-#define ISG_BW(p)                                                                              \
+#define ISG_BW(p, D)                                                                           \
   case p:                                                                                      \
-    gatv2_mp_bwd_dst_kernel<H, p><<<blocks, MP_WAVES * 64, 0, st>>>(a);                        \
-    gatv2_mp_bwd_src_kernel<H, p><<<(a.N + 3) / 4, 256, 0, st>>>(a);                           \
+    gatv2_mp_bwd_dst_kernel<H, p, D><<<blocks, MP_WAVES * 64, 0, st>>>(a);                     \
+    gatv2_mp_bwd_src_kernel<H, p, D><<<(a.N + 3) / 4, 256, 0, st>>>(a);                        \
     break;
+  if (a.drop_p > 0.f) {
+    switch (P) {
+      ISG_BW(1, true) ISG_BW(2, true) ISG_BW(3, true) ISG_BW(4, true) ISG_BW(5, true) ISG_BW(6, true) ISG_BW(7, true) ISG_BW(8, true)
+      default: return ISG_EUNSUPPORTED;
+    }
+    return check_launch();
+  }
   switch (P) {
-    ISG_BW(1) ISG_BW(2) ISG_BW(3) ISG_BW(4) ISG_BW(5) ISG_BW(6) ISG_BW(7) ISG_BW(8)
+    ISG_BW(1, false) ISG_BW(2, false) ISG_BW(3, false) ISG_BW(4, false) ISG_BW(5, false) ISG_BW(6, false) ISG_BW(7, false)
+    ISG_BW(8, false)
     default: return ISG_EUNSUPPORTED;
   }
 #undef ISG_BW
@@ -279,12 +305,11 @@ static int launch_bwd(const MpBwdArgs &a, hipStream_t st) {
 
 using namespace isg;
 
-extern "C" int isg_gatv2_mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const float *att,
-                                const float *alpha, const float *grad_out, const int32_t *rowptr, const int32_t *eid,
-                                const int32_t *src, const int32_t *rowptr_s, const int32_t *eid_s, const int32_t *dst_s,
-                                const float *node_mask, const float *edge_mask, float *d_x_l, float *d_x_r,
-                                float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
-                                int32_t H, int32_t C, float negative_slope, void *stream) {
+static int mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const float *att, const float *alpha,
+                  const float *grad_out, const int32_t *rowptr, const int32_t *eid, const int32_t *src, const int32_t *rowptr_s,
+                  const int32_t *eid_s, const int32_t *dst_s, const float *node_mask, const float *edge_mask, float *d_x_l,
+                  float *d_x_r, float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E, int32_t H,
+                  int32_t C, float negative_slope, float drop_p, uint64_t drop_seed, void *stream) {
   if (N < 0 || E < 0 || H <= 0 || C <= 0) return ISG_EINVAL;
   if (N == 0) return ISG_OK;
   if (!x_l || !x_r || !att || !grad_out || !rowptr || !rowptr_s || !d_x_l || !d_x_r || !d_att_partial) return ISG_EINVAL;
@@ -296,7 +321,8 @@ extern "C" int isg_gatv2_mp_bwd(const float *x_l, const float *x_r, const float 
       .grad_out = (const float4 *)grad_out, .alpha = alpha, .rowptr = rowptr, .eid = eid, .src = src, .rowptr_s = rowptr_s,
       .eid_s = eid_s, .dst_s = dst_s, .node_mask = node_mask, .edge_mask = edge_mask, .d_e_proj = (float4 *)d_e_proj,
       .d_x_r = (float4 *)d_x_r, .d_x_l = (float4 *)d_x_l, .d_att_partial = (float4 *)d_att_partial, .d_edge_mask = d_edge_mask,
-      .N = (int)N, .C = C, .H = H, .slope = negative_slope};
+      .N = (int)N, .C = C, .H = H, .slope = negative_slope, .drop_p = drop_p, .drop_inv = 1.0f / (1.0f - drop_p),
+      .drop_seed = drop_seed};
   if (!a.x_l || !a.x_r || !a.att || !a.grad_out || !a.rowptr || !a.rowptr_s || !a.d_x_l || !a.d_x_r || !a.d_att_partial ||
       (E > 0 && (!a.e_proj || !a.alpha || !a.eid || !a.src || !a.eid_s || !a.dst_s || !a.d_e_proj)))
     return ISG_EINVAL;                         // the struct the kernels dereference, not the parameters it was filled from
@@ -308,6 +334,29 @@ extern "C" int isg_gatv2_mp_bwd(const float *x_l, const float *x_r, const float 
     case 8: return launch_bwd<8>(a, st);
     default: return ISG_EUNSUPPORTED;
   }
+}
+
+extern "C" int isg_gatv2_mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const float *att,
+                                const float *alpha, const float *grad_out, const int32_t *rowptr, const int32_t *eid,
+                                const int32_t *src, const int32_t *rowptr_s, const int32_t *eid_s, const int32_t *dst_s,
+                                const float *node_mask, const float *edge_mask, float *d_x_l, float *d_x_r,
+                                float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
+                                int32_t H, int32_t C, float negative_slope, void *stream) {
+  return mp_bwd(x_l, x_r, e_proj, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask, edge_mask, d_x_l,
+                d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, 0.f, 0, stream);
+}
+
+// isg_gatv2_mp_bwd behind isg_gatv2_mp_fwd_dropout: the mask is drawn again from (seed, edge id, head).  p == 0: isg_gatv2_mp_bwd's
+// launches.
+extern "C" int isg_gatv2_mp_bwd_dropout(const float *x_l, const float *x_r, const float *e_proj, const float *att,
+                                        const float *alpha, const float *grad_out, const int32_t *rowptr, const int32_t *eid,
+                                        const int32_t *src, const int32_t *rowptr_s, const int32_t *eid_s, const int32_t *dst_s,
+                                        const float *node_mask, const float *edge_mask, float *d_x_l, float *d_x_r,
+                                        float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
+                                        int32_t H, int32_t C, float negative_slope, float p, uint64_t seed, void *stream) {
+  if (!(p >= 0.f && p < 1.f)) return ISG_EINVAL;     // a NaN fails both comparisons
+  return mp_bwd(x_l, x_r, e_proj, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask, edge_mask, d_x_l,
+                d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, p, p > 0.f ? seed : 0, stream);
 }
 
 extern "C" int isg_node_to_edge_mask_bwd(const float *d_edge_mask, const int32_t *rowptr, const int32_t *eid,

@@ -54,7 +54,10 @@ __device__ __forceinline__ float unif(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
-template <int HS, int P, bool MASKED, bool EXACT, int GK_NCAP, int GK_ECAP, bool F16>
+// DROP (fp32 rows, training): attention dropout on phase C's weights (include/isg_mp_train.h); phases A and B are untouched, so
+// alpha has the bits of the instantiation without it.  The slot's edge id is already in an SGPR and, at HS <= 4, so is the
+// Philox block of this workgroup's heads: the ten rounds are scalar instructions beside the aggregation's LDS reads.
+template <int HS, int P, bool MASKED, bool EXACT, int GK_NCAP, int GK_ECAP, bool F16, bool DROP = false>
 __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_kernel(MpArgs a) {
   constexpr int G = 64 / HS;
   extern __shared__ __attribute__((aligned(16))) float4 s_xl[];   // [lrows][HS*Q]
@@ -222,7 +225,13 @@ __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_kernel(MpArgs a) {
           if (nt_al) __builtin_nontemporal_store(w, a.alpha + (size_t)uni(rec.y) * a.H + hd);
           else a.alpha[(size_t)uni(rec.y) * a.H + hd] = w;
         }
-        const float wm = MASKED ? mul_rn(w, unif(__int_as_float(rec.w))) : w;
+        float wd = w;
+        if (DROP) {
+          uint32_t c[4];
+          mp_drop_block(a.drop_seed, (uint32_t)uni(rec.y), HS <= 4 ? (uint32_t)uni(hd >> 2) : (uint32_t)(hd >> 2), c);
+          wd = mul_rn(w, mp_drop_head(c, hd, a.drop_p, a.drop_inv));
+        }
+        const float wm = MASKED ? mul_rn(wd, unif(__int_as_float(rec.w))) : wd;
         const int jl = uni(rec.x);
         const bool in_lds = jl < rows;
         const float4 *xl_s = s_xl + (in_lds ? jl : 0) * RQ;
@@ -269,8 +278,10 @@ __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_kernel(MpArgs a) {
 // (P passes; 150 of 192 slots at HS = 2, C = 300); a pass's element belongs to head (index / Q), so a lane may serve two
 // heads: per-head logits are HS full-wave sums of per-head partials, and the softmax weights of all HS heads are formed
 // in every lane.  Phases, LDS tables, arithmetic and summation orders are those of the grouped kernel.
-template <int HS, int P, bool MASKED, int GK_NCAP, int GK_ECAP>
+// DROP: as in the grouped kernel.  A workgroup's HS = 2 heads lie in one Philox block, whose index is an SGPR like the edge id.
+template <int HS, int P, bool MASKED, int GK_NCAP, int GK_ECAP, bool DROP = false>
 __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_flat_kernel(MpArgs a) {
+  static_assert(HS <= 4 && 4 % HS == 0, "the heads of a workgroup share one Philox block");
   constexpr int U = ISG_GKF_U;    // CSR slots a wave has in flight in phase B (P passes x 2 operands x U rows of loads)
   extern __shared__ __attribute__((aligned(16))) float4 s_xl[];   // [lrows][HS*Q]
   __shared__ __attribute__((aligned(16))) int4 s_tab[GK_ECAP];    // {src - nb, eid, dst - nb, bits(edge mask)}
@@ -428,10 +439,13 @@ __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_flat_kernel(MpArgs 
     for (int t = rb; t < re; ++t) {
       const int4 rec = s_tab[t];
       float w[HS];
+      uint32_t dc[4];
+      if (DROP) mp_drop_block(a.drop_seed, (uint32_t)uni(rec.y), (uint32_t)((hg * HS) >> 2), dc);
 #pragma unroll
       for (int hh = 0; hh < HS; ++hh) {
         w[hh] = __builtin_amdgcn_exp2f((s_lg[t * HS + hh] - mx[hh]) * 1.4426950408889634f) * rden[hh];
         if (lane == 0) a.alpha[(size_t)uni(rec.y) * a.H + hg * HS + hh] = w[hh];
+        if (DROP) w[hh] = mul_rn(w[hh], mp_drop_head(dc, hg * HS + hh, a.drop_p, a.drop_inv));
         if (MASKED) w[hh] = mul_rn(w[hh], unif(__int_as_float(rec.w)));
       }
       const int jl = uni(rec.x);
@@ -453,7 +467,7 @@ __global__ __launch_bounds__(GK_THREADS) void gatv2_mp_graph_flat_kernel(MpArgs 
       }
     }
     const size_t orow = (size_t)(nb + k) * R + hoff;
-    if (a.planes) {
+    if (!DROP && a.planes) {     // an inference form: no dropout
       // the half row (this workgroup's two heads) as planes32 lines under its own scale: x_proj.0 reads the result from
       // these, with no fp32 copy and no split pass in between (isg_linear_h3p's segmented A operand)
       float mx = 0.f;
@@ -519,6 +533,21 @@ static int launch_flat_sized(MpArgs a, int nmax_host, hipStream_t st) {
   const size_t dyn = (size_t)a.lrows * row_bytes;
   dim3 grid((unsigned)items), block(GK_THREADS);
   const bool masked = a.node_mask || a.edge_mask;
+  if (a.drop_p > 0.f) {
+    if (a.planes || a.logits) return ISG_EINVAL;      // inference forms: mp_fwd hands neither over with a dropout
+    if (masked) {
+      static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&gatv2_mp_graph_flat_kernel<HS, P, true, NC, EC, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+      if (!ok) return ISG_EUNSUPPORTED;
+      gatv2_mp_graph_flat_kernel<HS, P, true, NC, EC, true><<<grid, block, dyn, st>>>(a);
+    } else {
+      static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&gatv2_mp_graph_flat_kernel<HS, P, false, NC, EC, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+      if (!ok) return ISG_EUNSUPPORTED;
+      gatv2_mp_graph_flat_kernel<HS, P, false, NC, EC, true><<<grid, block, dyn, st>>>(a);
+    }
+    return check_launch();
+  }
   if (masked) {
     static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&gatv2_mp_graph_flat_kernel<HS, P, true, NC, EC>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
@@ -563,7 +592,13 @@ static int launch_sized(MpArgs a, int nmax_host, hipStream_t st) {
   const bool masked = a.node_mask || a.edge_mask;
   const bool exact = (a.C >> 2) == (64 / HS) * P;
 #define ISG_GK_LAUNCH(M_, X_, F_) gatv2_mp_graph_kernel<HS, P, M_, X_, NC, EC, F_><<<grid, block, dyn, st>>>(a)
-  if (a.f16) {
+  if (a.drop_p > 0.f) {     // training: fp32 rows, logits formed here, no row maxima (mp_fwd hands nothing else over)
+    if (a.f16 || a.logits || a.rowmax) return ISG_EINVAL;
+#define ISG_GK_LAUNCH_DROP(M_, X_) gatv2_mp_graph_kernel<HS, P, M_, X_, NC, EC, false, true><<<grid, block, dyn, st>>>(a)
+    if (masked) { if (exact) ISG_GK_LAUNCH_DROP(true, true); else ISG_GK_LAUNCH_DROP(true, false); }
+    else { if (exact) ISG_GK_LAUNCH_DROP(false, true); else ISG_GK_LAUNCH_DROP(false, false); }
+#undef ISG_GK_LAUNCH_DROP
+  } else if (a.f16) {
     if (masked) { if (exact) ISG_GK_LAUNCH(true, true, true); else ISG_GK_LAUNCH(true, false, true); }
     else { if (exact) ISG_GK_LAUNCH(false, true, true); else ISG_GK_LAUNCH(false, false, true); }
   } else {

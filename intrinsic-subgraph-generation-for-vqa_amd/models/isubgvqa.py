@@ -64,7 +64,9 @@ class ISubGVQA(torch.nn.Module):
                             nb_samples=getattr(args, "nb_samples", 1), alpha=getattr(args, "alpha", 1.0),
                             beta=getattr(args, "beta", 10.0), tau=getattr(args, "tau", 1.0),
                             # a node budget per graph; a reference checkpoint's Namespace has neither field
-                            sample_ratio=getattr(args, "sample_ratio", None), sample_k_min=getattr(args, "sample_k_min", 1))
+                            sample_ratio=getattr(args, "sample_ratio", None), sample_k_min=getattr(args, "sample_k_min", 1),
+                            # dropout on the layers' attention weights in train(); absent from a reference Namespace
+                            attn_dropout=getattr(args, "attn_dropout", 0.0))
         self.graph_global_attention_pooling = GlobalAttention(num_node_features=self.question_hidden_dim,
                                                               num_out_features=self.question_hidden_dim)
         self.qsts_reduction = torch.nn.Sequential(

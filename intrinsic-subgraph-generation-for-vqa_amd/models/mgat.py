@@ -22,7 +22,7 @@ class MGAT(torch.nn.Module):
                  use_topk: bool = False, interpretable_mode: bool = True, concat_instr: bool = False,
                  use_all_instrs: bool = False, use_global_mask: bool = False, node_classification: bool = False,
                  sampler_type: str = None, sample_k: int = None, nb_samples: int = 1, alpha=1.0, beta=10.0, tau=1.0,
-                 sample_ratio: Optional[float] = None, sample_k_min: int = 1):
+                 attn_dropout: float = 0.0, sample_ratio: Optional[float] = None, sample_k_min: int = 1):
         super().__init__()
         if not use_instr:
             raise NotImplementedError("use_instr=False leaves the reference without its layer lists (mgat.py:46-64)")
@@ -33,6 +33,9 @@ class MGAT(torch.nn.Module):
         self.masking_thresholds, self.use_global_mask = masking_thresholds, use_global_mask
         self.interpretable_mode, self.use_all_instrs = interpretable_mode, use_all_instrs
         self.node_classification = node_classification
+        # attn_dropout: the `dropout` of every MaskingGATv2Conv (attention weights, train() only; include/isg_mp_train.h).  The
+        # reference's own `dropout` argument is stored and unused there (mgat.py:32) and stays so here
+        self.attn_dropout = float(attn_dropout)
         width_in = 2 * channels if concat_instr else channels
         self.in_channels = width_in
         wide, mid = heads * channels, channels * int(heads / 2)        # H*C -> C*H/2 -> C   (mgat.py:66-91)
@@ -41,8 +44,8 @@ class MGAT(torch.nn.Module):
                             tau=tau, sample_ratio=sample_ratio, sample_k_min=sample_k_min)
 
         def conv_layer(threshold):
-            return MaskingGATv2Conv(width_in, channels, heads=heads, edge_dim=channels, add_self_loops=False,
-                                    masking_threshold=threshold, use_instr=True, use_topk=use_topk,
+            return MaskingGATv2Conv(width_in, channels, heads=heads, dropout=self.attn_dropout, edge_dim=channels,
+                                    add_self_loops=False, masking_threshold=threshold, use_instr=True, use_topk=use_topk,
                                     concat_instr=concat_instr, use_all_instrs=use_all_instrs, **sampler_opts)
 
         def head_projection():

@@ -9,6 +9,8 @@ Device work per call:
   three dense projections        lin_l, lin_r (C -> H*C, +bias), lin_edge (no bias)     (:177,181,259)
   isg_gatv2_mp_fwd               message + segment softmax + aggregate + bias, with the node->edge
                                  mask product of NodeMaskToEdgeMask fused in            (:169-171,215-232,243-279)
+  isg_gatv2_mp_fwd_dropout       the same in train() with dropout > 0: alpha = F.dropout(alpha, p, training) between the
+                                 softmax and the aggregation, keep or drop drawn from (seed, edge id, head)  (:274-279)
 Which of these launches a layer makes on a batch -- message passing as one persistent launch on graph tiles, with lin_l | lin_r
 inside or before it, as the edge-logits pair, or un-fused; what the gate writes -- is decided by ops.conv_route, nowhere else:
 route() asks it once per forward, forward() follows the answer.
@@ -27,6 +29,10 @@ from .. import ops
 from ..sampling.node_edge_masks import NodeMaskToEdgeMask
 from .layers import GlorotLinear, glorot_
 from .masking import MaskingModel
+
+# The attention dropout of a layer draws from the stream of (layer seed + this): the sampler of the same layer draws from the
+# layer seed itself (MaskingModel), so an edge's keep decision never shares a Philox stream with a node's noise.
+ATTN_DROPOUT_SEED_OFFSET = 8192
 
 
 class MaskingGATv2Conv(torch.nn.Module):
@@ -68,7 +74,13 @@ class MaskingGATv2Conv(torch.nn.Module):
         # storage type of the projected rows x_l / x_r / e_proj and of the aggregated output (fp32 arithmetic either way):
         # torch.float16 is BASELINE configs[4] ("fp16 features / fp32 accumulate"), inference only
         self.feature_dtype = torch.float32
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"dropout={dropout}: the attention dropout needs 0 <= dropout < 1")
         self.reset_parameters()
+
+    def attn_dropout_active(self) -> bool:
+        """Does this call drop attention weights?  train() with dropout > 0, whether or not autograd records."""
+        return bool(self.training and self.dropout > 0.0)
 
     def reset_parameters(self):
         self.lin_l.reset_parameters()
@@ -97,7 +109,8 @@ class MaskingGATv2Conv(torch.nn.Module):
                      edge_dim=edge_attr.size(1) if edge_attr is not None and edge_attr.dim() == 2 else None,
                      rows_dtype=self.rows_dtype(plan), share_weights=self.share_weights, use_instr=self.use_instr, masked=masked,
                      gate_on_planes=masked and self.mask.planes_ready(imle_att), grad=torch.is_grad_enabled(),
-                     e_proj_given=e_proj is not None, has_edge_lin=self.lin_edge is not None)
+                     e_proj_given=e_proj is not None, has_edge_lin=self.lin_edge is not None,
+                     attn_dropout=self.attn_dropout_active())
         if plan is None:
             return ops.conv_route(N=0, B=0, E=0, nmax=0, has_csr=False, tile_mode="none", **facts)
         memo, key = plan.memo(), ("route", id(self), *facts.values())
@@ -132,8 +145,6 @@ class MaskingGATv2Conv(torch.nn.Module):
         H, C = self.heads, self.out_channels
         if x.dim() != 2:
             raise ValueError("x must be [N, C]")
-        if self.dropout != 0.0 and self.training:
-            raise NotImplementedError("attention dropout in training mode (forward-only path)")
         if plan is None:
             plan = ops.GraphPlan.build(batch, edge_index,
                                        num_graphs=None if instruction is None else instruction.size(0))
@@ -169,6 +180,10 @@ class MaskingGATv2Conv(torch.nn.Module):
 
         fdt = self.rows_dtype(plan)
         kw = dict(bias=self.bias, node_mask=mask, negative_slope=self.negative_slope)
+        drop = self.attn_dropout_active()
+        if drop and (how != "unfused" or fdt != torch.float32):
+            raise RuntimeError(f"attention dropout runs on the un-fused route with fp32 rows only, not on {how!r} / {fdt}: a "
+                               "route handed in must come from self.route() of this call")
         if how == "layer_conv":
             # lin_l | lin_r, lin_edge, logits, softmax and aggregation as ONE persistent launch on graph-aligned tiles
             # (csrc/isg_layer_conv.hip): x_l / x_r live in LDS only                       # :177-181, :215-232, :243-279
@@ -203,6 +218,15 @@ class MaskingGATv2Conv(torch.nn.Module):
             if edge_attr.dim() == 1:
                 edge_attr = edge_attr.view(-1, 1)
             e_proj = ops.linear(edge_attr.float().contiguous(), self.lin_edge.weight, None, out_dtype=fdt)   # :259
+        if drop:                                                                         # :274-279
+            # seed: the layer's, as for its sampler; without one a draw from torch's CPU generator (no device sync, and
+            # torch.manual_seed reproduces a run), as models/text_encoder._base_seed
+            if seed is None and x_l.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("attention dropout inside a captured step needs an explicit seed per replay: a base drawn "
+                                   "here is a kernel argument and would repeat in every replay")
+            base = int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+            return done(*ops.gatv2_mp(x_l, x_r, e_proj, self.att, plan, H, dropout_p=float(self.dropout),
+                                      dropout_seed=base + ATTN_DROPOUT_SEED_OFFSET, **kw))
         return done(*ops.gatv2_mp(x_l, x_r, e_proj, self.att, plan, H, want_rowmax=not torch.is_grad_enabled(),
                                   want_planes=out_planes and not torch.is_grad_enabled(), **kw))          # :215-232
 

@@ -135,7 +135,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "torch_attention_train": 0,                # autograd.mha_small calls beyond the backward kernel's limits (torch's ops)
             "linear_bwd_kernels": 0,                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
             "simple_bwd_kernel": 0,                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
-            "topk_rows": 0}                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
+            "topk_rows": 0,                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
+            "mp_dropout": 0}                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
 
 
 def reset_counters() -> None:
@@ -966,16 +967,21 @@ def _segmented_planes32(N: int, H: int, C: int, device):
 def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphPlan, heads: int,
              bias: Optional[Tensor] = None, node_mask: Optional[Tensor] = None, edge_mask: Optional[Tensor] = None,
              negative_slope: float = 0.2, kernel: Optional[str] = None, want_rowmax: bool = False,
-             want_planes: bool = False) -> Tuple[Tensor, Tensor]:
+             want_planes: bool = False, dropout_p: float = 0.0, dropout_seed: int = 0) -> Tuple[Tensor, Tensor]:
     """MaskingGATv2Conv.message + aggregate (mgat_v2_conv.py:243-279).  Returns (out[N,H*C], alpha[E,H]).
+    dropout_p > 0 (training, fp32 rows): attention dropout on the aggregation's weights, keep or drop a pure function of
+    (dropout_seed, original edge id, head) (include/isg_mp_train.h); alpha is the softmax before it, as the reference's
+    ``self._alpha``.  The row-maxima and planes forms are inference forms and are not asked for then.
     want_rowmax (inference, fp32 rows): the kernel also writes max |out| per (node, head) and `out` carries it as
     ``out._isg_rowmax`` [N, H] -- the row scales of the fp16 three-product GEMM that reads `out` next (x_proj).
     want_planes (inference, fp32 rows, H = 4): where the flat per-graph kernel runs (the reference's C = 300), `out` comes back
     as a SEGMENTED Planes32 -- the operand of x_proj.0 on isg_linear_h3p with no fp32 copy and no split pass; anywhere else the
     fp32 rows as always."""
+    dropout_p, dropout_seed = _drop_args(dropout_p, dropout_seed)
     if _rec(x_l, x_r, e_proj, att, bias, node_mask, edge_mask):
         from . import autograd
-        return autograd.gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, negative_slope, kernel)
+        return autograd.gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, negative_slope, kernel,
+                                 dropout_p, dropout_seed)
     lib = _lib.load()
     plan.require_csr()
     N, HC = x_l.shape
@@ -1008,6 +1014,16 @@ def gatv2_mp(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, plan: GraphP
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "masked": node_mask is not None or edge_mask is not None,
                                   "feat_bytes": 2 if fdt == torch.float16 else 4})
         ev0.record()
+    if dropout_p > 0.0:
+        if fdt != torch.float32:
+            raise _lib.IsgError("attention dropout exists on fp32 feature rows only (fp16 rows are an inference form)")
+        from . import _lib_mp_train
+        COUNTERS["mp_dropout"] += 1
+        _lib.check(_lib_mp_train.load().isg_gatv2_mp_fwd_dropout(*ins, out.data_ptr(), alpha.data_ptr(), *dims[:-1], dropout_p,
+                                                                 dropout_seed, dims[-1]), "isg_gatv2_mp_fwd_dropout")
+        if timer is not None:
+            ev1.record()
+        return out, alpha
     # the richer result first; ISG_EUNSUPPORTED = this batch / width takes another kernel: the next form, inside the same bracket
     if want_planes and CFG.mp_planes and use_graph and fdt == torch.float32 and E > 0 and H == 4 and C % 4 == 0:
         planes, pl, pinv = _segmented_planes32(N, H, C, x_l.device)
@@ -1608,12 +1624,15 @@ def gatv2_tile_conv(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor,
 
 def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
                       plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
-                      edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False):
+                      edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
+                      dropout_p: float = 0.0, dropout_seed: int = 0):
     """Backward of gatv2_mp: (d_x_l, d_x_r, d_e_proj, d_att[H*C], d_bias[H*C], d_edge_mask[E] or None).
+    dropout_p / dropout_seed: those of the forward; the kernels draw its mask again (include/isg_mp_train.h).
 
     No reference counterpart file: the reference relies on autograd through PyG's propagate
     (mgat_v2_conv.py:215-279); the formulas are derived in csrc/isg_mp_bwd.hip.
     """
+    dropout_p, dropout_seed = _drop_args(dropout_p, dropout_seed)
     lib = _lib.load()
     plan.require_csr()
     N, HC = x_l.shape
@@ -1629,7 +1648,12 @@ def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alp
     blocks = (N + 15) // 16
     part = torch.empty(blocks, HC, dtype=torch.float32, device=dev)
     d_m = torch.empty(E, dtype=torch.float32, device=dev) if want_mask_grad else None
-    _lib.check(lib.isg_gatv2_mp_bwd(
+    if dropout_p > 0.0:
+        from . import _lib_mp_train
+        entry, name, drop = _lib_mp_train.load().isg_gatv2_mp_bwd_dropout, "isg_gatv2_mp_bwd_dropout", (dropout_p, dropout_seed)
+    else:
+        entry, name, drop = lib.isg_gatv2_mp_bwd, "isg_gatv2_mp_bwd", ()
+    _lib.check(entry(
         _chk(x_l, "x_l", torch.float32, (N, HC)), _chk(x_r, "x_r", torch.float32, (N, HC)),
         _chk(e_proj, "e_proj", torch.float32, (E, HC)) if E > 0 else 0,
         _chk(att.reshape(-1), "att", torch.float32, (HC,)), _chk(alpha, "alpha", torch.float32, (E, H)) if E > 0 else 0,
@@ -1639,7 +1663,7 @@ def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alp
         _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
         _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
         d_x_l.data_ptr(), d_x_r.data_ptr(), d_e.data_ptr(), part.data_ptr(), 0 if d_m is None else d_m.data_ptr(),
-        N, E, H, C, float(negative_slope), _stream()), "isg_gatv2_mp_bwd")
+        N, E, H, C, float(negative_slope), *drop, _stream()), name)
     return d_x_l, d_x_r, d_e, part.sum(0), grad_out.sum(0), d_m
 
 
@@ -2751,16 +2775,19 @@ class ConvRoute(NamedTuple):
 def conv_route(*, heads: int, channels: int, in_channels: int, edge_dim: Optional[int], N: int, B: int, E: int, nmax: int,
                has_csr: bool, tile_mode: str, rows_dtype=torch.float32, share_weights: bool = False,
                use_instr: bool = True, masked: bool = False, gate_on_planes: bool = False, grad: bool = False,
-               e_proj_given: bool = False, has_edge_lin: bool = True, cfg: Optional[Switches] = None) -> ConvRoute:
+               e_proj_given: bool = False, has_edge_lin: bool = True, cfg: Optional[Switches] = None,
+               attn_dropout: bool = False) -> ConvRoute:
     """How a MaskingGATv2Conv layer (in_channels -> heads x channels, edge features edge_dim wide) runs on a batch of B graphs, N
     nodes (at most nmax per graph) and E edges: a pure function of plain values, the ONE place that decides.
 
     edge_dim: None without 2-D edge features; has_csr: the plan holds the CSR by destination; tile_mode: GraphPlan.tile_mode of the
     64-node / 256-slot tiles; rows_dtype: MaskingGATv2Conv.rows_dtype(plan); masked: the layer has a node gate (masking_threshold
     != 1), gate_on_planes: which can run on the input's planes (MaskingModel.planes_ready); grad: autograd is recording;
-    e_proj_given: the caller hands e_proj in; has_edge_lin: the layer has a lin_edge.
+    e_proj_given: the caller hands e_proj in; has_edge_lin: the layer has a lin_edge; attn_dropout: the layer drops attention
+    weights on this call (self.training and self.dropout > 0, under no_grad too) -- only the un-fused message-passing kernels
+    have a dropout form (include/isg_mp_train.h), so it selects "unfused" as autograd does and a fused kernel never skips it.
     conv, the first match of (under the default switches):
-      e_proj given, no edge features or lin_edge, autograd                   "unfused"  lin_edge as a Linear + the message-passing kernel
+      e_proj given, no edge features or lin_edge, autograd, attn_dropout     "unfused"  lin_edge as a Linear + the message-passing kernel
       4 !| C, H ceil32(C) > 2048, K = 0, K > 304, 4 !| K, nothing to do (B, E, nmax = 0), no CSR,
         or a wide layer (32 !| C or K > 128) under 16 384 edges              "unfused"
       fp16 rows                                                              "pair" when K >= 128, else "unfused"
@@ -2778,7 +2805,7 @@ def conv_route(*, heads: int, channels: int, in_channels: int, edge_dim: Optiona
     gate_rows: everything but "layer_conv" reads rows, and so does a node gate that cannot run on the planes.  e_proj: conv is
     "unfused" (a stack of layers then projects every layer's edge rows in one launch)."""
     cfg = CFG if cfg is None else cfg
-    if e_proj_given or edge_dim is None or not has_edge_lin or grad:
+    if e_proj_given or edge_dim is None or not has_edge_lin or grad or attn_dropout:
         conv = "unfused"
     elif not _fused_logits_ok(heads, channels, edge_dim, B, E, nmax, has_csr, cfg):
         conv = "unfused"
