@@ -21,11 +21,16 @@
 // The arithmetic is isg_linear_f16x3's (row scale, planes, MFMA order, epilogue) followed by isg_gatv2_tile_conv's, operation
 // for operation: out / alpha / rowmax are bit-identical to the two-launch path.  What bounds the kernel (it is the sum of its
 // phases) and what was tried: DESIGN.md 9.1, profiles/r03_bg_layer_conv_ablation.md.
+// `alpha` is optional in every kernel of this file (NULL: the attention weights are not stored; the test is wave-uniform, the
+// pointer being a kernel argument).  `out` and `rowmax` hold every row < N of every listed tile, EXCEPT after a sparse launch
+// of the masked form on groups of tiles (isg_gatv2_layer_conv_sparse, include/isg_sparse_out.h): then a row that
+// no live slot has as destination is written for the first such row of its tile only -- see gatv2_layer_conv_groups_kernel.
 #include "isg_f16x3.hpp"
 
 #include "isg_diag.hpp"
 #include "isg_live_tables.hpp"
 #include "../../include/isg_masked.h"
+#include "../../include/isg_sparse_out.h"
 
 ISG_DIAG_BUFFER(g_lc_stamps)            // -DISG_DIAG builds only (tools/stamp_layer_conv.py): [workgroups * 8 waves][16] int64
 #define LC_STAMP(i) ISG_DIAG_ADD(i)
@@ -59,7 +64,8 @@ struct LcArgs {
   const int *rowptr, *eid, *src, *dst, *ntiles;
   const int4 *tile_info;
   const float *edge_mask, *node_mask;   // optional (NULL: the layer is not masked)
-  float *out, *alpha;
+  float *out;
+  float *alpha;                     // optional (NULL: the attention weights are not stored)
   float *rowmax;                    // optional
   int N, E, H, KSE, NTE, ldo;
   float slope;
@@ -331,7 +337,7 @@ __global__ __launch_bounds__(256, 3) void node_gate_planes_kernel(const _Float16
       int s = rb;                                                                                                                          \
     _Pragma("unroll 1")                                                                                                                    \
       while (true) {          /* four in-edges per round (two and two), edge-id order, one fma per term like every kernel of the family */ \
-        {     /* alpha: ONE store instruction per round, lane u of a node's eight writes in-edge u */                                      \
+        if (a.alpha) {     /* alpha (optional): ONE store instruction per round, lane u of a node's eight writes in-edge u */               \
           const float wsel = (j8 & 2) ? ((j8 & 1) ? e4[3] : e4[2]) : ((j8 & 1) ? e4[1] : e4[0]);                                           \
           const int esel = (j8 & 2) ? ((j8 & 1) ? rc4[3].y : rc4[2].y) : ((j8 & 1) ? rc4[1].y : rc4[0].y);                                 \
           if (j8 < 4 && s + j8 < re) a.alpha[(int64_t)esel * a.H + hd] = wsel * rden;                                                      \
@@ -806,6 +812,11 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_kernel(LcArgs 
 //            maximum is that vector's -- computed once per workgroup (the head is fixed) with LC_AGGREGATE_ROW's expression and
 //            lane layout.  These rows are written as constants, 16 bytes per lane, without walking an edge.
 //            AGG_ALL (ISG_LC_AGG_ALL_ROWS=1): LC_AGGREGATE per tile over all 64 rows instead, as before (A/B; the same bits)
+//            SPARSE (isg_gatv2_layer_conv_sparse): these rows are all one vector, and their one reader
+//            (isg_mgat_dense_tail's live-row form) takes them from a single representative -- so `out` and `rowmax` are stored
+//            for ONE fill row per tile, the lowest, and the others keep only row_dead = 1 and their alpha entries.  The
+//            representative a reader picks -- the first row of a tile whose H flags are all set -- is that row, or a listed row
+//            before it that the list pass wrote and found dead: written either way.  Tables or scan: the fill is the same code.
 // A product element depends on its own row's planes, the W fragments, the MFMA shape and the k order, not on the column its row
 // sits in, so out / alpha / rowmax / row_dead are the per-tile kernel's bits for FINITE inputs (both the dead slots' reads of list
 // position 0 and the fill rest on x * +-0 = +-0).  A group whose list would pass 64 rows runs its tiles one by one through the
@@ -826,8 +837,10 @@ static_assert(LG_TILE_BYTES % 16 == 0 && LG_OFF_T % 16 == 0 && LG_OFF_MISC % 16 
 static_assert(64 * 512 <= 2 * 64 * LC_LDA * 2, "the node planes fit the panel image they share LDS with");
 static_assert(LG_SMEM_BYTES <= 160 * 1024, "one workgroup per CU");
 
-template <int KSE_T, bool SL01, bool TABLES, bool AGG_ALL>
+// SPARSE (with AGG_ALL = false): see the fill above; a group that runs its tiles one by one (step = 1) writes every row.
+template <int KSE_T, bool SL01, bool TABLES, bool AGG_ALL, bool SPARSE>
 __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(LcArgs a) {
+  static_assert(!(AGG_ALL && SPARSE), "the per-tile aggregation writes every row");
   extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
   typedef float (*BufX)[LC_LDX];
   typedef _Float16 (*BufP)[64][LC_LDA];
@@ -1301,8 +1314,44 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
           fill4 = hf32x4{zero + b4.x, zero + b4.y, zero + b4.z, zero + b4.w};
         }
         const float fill_max = *s_fillmax;
+        // SPARSE, a group that runs as one sub-group: tile j on wave j (at most six tiles, eight waves), nothing of a tile waits for
+        // another tile's.  Lane k is row k: `out` (the 32 lanes below 32, 16 bytes each) and `rowmax` for ONE row, the lowest row
+        // k < nrows whose bit in ldst is clear; row_dead = 1 for every such row; alpha, when asked for, 64 slots per round.  A
+        // group that runs its tiles one by one (step = 1: its list would pass 64 rows) writes every row below.
+        bool every_row = true;
+        if constexpr (SPARSE) {
+          if (ntot <= LC_ROWS) {
+            every_row = false;
+            const int j = ja + wave;
+            if (j < jb) {
+              const int4 dj = s_desc[j];
+              const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
+                        ne = __builtin_amdgcn_readfirstlane(dj.w);
+              const unsigned long long m = s_ldst[j];
+              const unsigned long long free_rows = ~m & (nrows >= 64 ? ~0ull : (1ull << nrows) - 1ull);
+              const int fl = ft & 63;
+              if (free_rows) {
+                const int kf = (int)__builtin_ctzll(free_rows);          // < nrows
+                if (fl < 32)
+                  __builtin_nontemporal_store(fill4, reinterpret_cast<hf32x4 *>(a.out + (int64_t)(r0 + kf) * a.ldo + hoff + fc4 * 4));
+                if (fl == kf && a.rowmax) a.rowmax[(int64_t)(r0 + kf) * a.H + hd] = fill_max;
+                if (((free_rows >> fl) & 1ull) && a.row_dead) a.row_dead[(int64_t)(r0 + fl) * a.H + hd] = 1;
+              }
+              if (a.alpha) {
 #pragma unroll 1
-        for (int j = ja; j < jb; ++j) {
+                for (int sl = fl; sl < ne; sl += 64) {
+                  const int dz = LG_DR(j)[sl];
+                  if (!((m >> dz) & 1ull)) {
+                    const int n = min(LG_RP(j)[dz + 1], ne) - LG_RP(j)[dz];
+                    a.alpha[(int64_t)LG_EM(j)[sl].x * a.H + hd] = __builtin_amdgcn_rcpf((float)n + 1e-16f);
+                  }
+                }
+              }
+            }
+          }
+        }
+#pragma unroll 1
+        for (int j = ja; j < (every_row ? jb : ja); ++j) {
           const int4 dj = s_desc[j];
           const int r0 = __builtin_amdgcn_readfirstlane(dj.x), nrows = __builtin_amdgcn_readfirstlane(dj.y),
                     ne = __builtin_amdgcn_readfirstlane(dj.w);
@@ -1314,7 +1363,7 @@ __global__ __launch_bounds__(LC_THREADS, 2) void gatv2_layer_conv_groups_kernel(
               __builtin_nontemporal_store(fill4, reinterpret_cast<hf32x4 *>(a.out + (int64_t)(r0 + k) * a.ldo + hoff + fc4 * 4));
           }
           if (ft < LC_ECAP) {
-            if (ft < ne) {
+            if (ft < ne && a.alpha) {              // (alpha is optional; wave-uniform: the pointer is a kernel argument)
               const int dz = LG_DR(j)[ft];         // the slot's row: its in-degree is the row's segment, cut at the tile's slots
               if (!((m >> dz) & 1ull)) {
                 const int n = min(LG_RP(j)[dz + 1], ne) - LG_RP(j)[dz];
@@ -1427,14 +1476,15 @@ static int lc_group_rule(int64_t N, int64_t E, int32_t H, int64_t max_tiles, int
 // x_planes [N][2][128] fp16 + x_inv_scale [N] = the gated layer input gelu(h * instruction[batch]) as scaled (hi, mid) planes
 // (isg_instr_gate_planes, isg_mgat_dense_tail's xp_out, or isg_edge_planes with eid = NULL on fp32 rows); wn_frag / wn_inv_scale =
 // isg_split_f16x2_frag of cat(lin_l.weight, lin_r.weight) [2*H*C, 128], bn fp32 [2*H*C] their biases; the rest as isg_gatv2_tile_conv.
-// One body for isg_gatv2_layer_conv and isg_gatv2_layer_conv_tables (live_tables NULL: the former).
+// One body for isg_gatv2_layer_conv, isg_gatv2_layer_conv_tables (live_tables NULL: the former) and isg_gatv2_layer_conv_sparse
+// (sparse_out: what its ISG_LC_SPARSE_OUT flag asks for; false: the other two, bit for bit).  alpha may be NULL.
 static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag, const float *wn_inv_scale,
                      const float *bn, const uint16_t *edge_planes, const float *edge_inv_scale, const uint16_t *we_frag,
                      const float *we_inv_scale, const float *att, const float *bias, const int32_t *rowptr, const int32_t *eid,
                      const int32_t *src, const int32_t *dst, const int32_t *tile_info, const int32_t *ntiles, int64_t max_tiles,
                      const float *node_mask, const float *edge_mask, float *out, int32_t ldo, float *alpha, float *rowmax,
-                     uint8_t *row_dead, const uint8_t *live_tables, int64_t N, int64_t E, int32_t H, int32_t C, int32_t K_in,
-                     int32_t K_edge, float negative_slope, void *stream) {
+                     uint8_t *row_dead, const uint8_t *live_tables, bool sparse_out, int64_t N, int64_t E, int32_t H, int32_t C,
+                     int32_t K_in, int32_t K_edge, float negative_slope, void *stream) {
   if (N < 0 || E < 0 || H <= 0 || C <= 0 || K_in <= 0 || K_edge <= 0 || max_tiles < 0 || ldo < H * C) return ISG_EINVAL;
   auto mis = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (C != LC_C || K_in != LC_K || K_edge > LC_K || (K_edge & 3) != 0 || (ldo & 3) != 0 || H > 16 || mis(x_planes) ||
@@ -1443,7 +1493,7 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
     return ISG_EUNSUPPORTED;
   if (N == 0 || max_tiles == 0) return ISG_OK;
   if (!x_planes || !x_inv_scale || !wn_frag || !wn_inv_scale || !bn ||
-      (E > 0 && (!edge_planes || !edge_inv_scale || !eid || !src || !dst || !alpha)) || !we_frag || !we_inv_scale || !att || !rowptr ||
+      (E > 0 && (!edge_planes || !edge_inv_scale || !eid || !src || !dst)) || !we_frag || !we_inv_scale || !att || !rowptr ||
       !tile_info || !ntiles || !out)
     return ISG_EINVAL;
   // ISG_LC_DENSE_MASK=1: a masked layer walks every slot, as before the live-slot walk (A/B; the same bits either way)
@@ -1453,6 +1503,10 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
   // ISG_LC_AGG_ALL_ROWS=1: the groups kernel aggregates every row of every tile, as before the list pass and the constant fill
   // (A/B; the same bits either way)
   static const bool agg_all_rows = [] { const char *e = getenv("ISG_LC_AGG_ALL_ROWS"); return e && atoi(e) != 0; }();
+  // ISG_LC_DENSE_OUT=1: a launch asked for sparse output (isg_gatv2_layer_conv_sparse) writes every row all the same (DESIGN.md
+  // 17.16; A/B; the rows that are read hold the same bits either way)
+  static const bool dense_out = [] { const char *e = getenv("ISG_LC_DENSE_OUT"); return e && atoi(e) != 0; }();
+  if (dense_out || agg_all_rows) sparse_out = false;
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   LcArgs a = {
       .xp = reinterpret_cast<const _Float16 *>(x_planes), .xinv = x_inv_scale, .Wn = reinterpret_cast<const _Float16 *>(wn_frag),
@@ -1462,21 +1516,22 @@ static int lc_launch(const uint16_t *x_planes, const float *x_inv_scale, const u
       .edge_mask = edge_mask, .node_mask = node_mask, .out = out, .alpha = alpha, .rowmax = rowmax, .N = (int)N, .E = (int)E,
       .H = H, .KSE = (K_edge + 15) / 16, .NTE = H * C / 32, .ldo = ldo, .slope = negative_slope, .row_dead = row_dead, .G = 1,
       .live_tables = live_tables};
-  if (!a.xp || !a.xinv || !a.Wn || !a.wn_inv || !a.bn || (a.E > 0 && (!a.ep || !a.ep_inv || !a.eid || !a.src || !a.dst || !a.alpha)) ||
+  if (!a.xp || !a.xinv || !a.Wn || !a.wn_inv || !a.bn || (a.E > 0 && (!a.ep || !a.ep_inv || !a.eid || !a.src || !a.dst)) ||
       !a.We || !a.we_inv || !a.att || !a.rowptr || !a.tile_info || !a.ntiles || !a.out)
     return ISG_EINVAL;                         // the struct the kernel dereferences, not the parameters it was filled from
   int gpx = 1;
   a.G = lc_group_rule(N, E, H, max_tiles, &gpx);
   const unsigned grid = 8u * (unsigned)H * (unsigned)gpx;
   hipStream_t st = as_stream(stream);
-#define LC_LAUNCH_GTA(KT, SL, TB, AA)                                                                                \
+#define LC_LAUNCH_GTA(KT, SL, TB, AA, SP)                                                                            \
   {                                                                                                                  \
-    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL, TB, AA>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;        \
-    gatv2_layer_conv_groups_kernel<KT, SL, TB, AA><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                      \
+    if (!dyn_lds_ok<&gatv2_layer_conv_groups_kernel<KT, SL, TB, AA, SP>>(LG_SMEM_BYTES)) return ISG_EUNSUPPORTED;    \
+    gatv2_layer_conv_groups_kernel<KT, SL, TB, AA, SP><<<grid, LC_THREADS, LG_SMEM_BYTES, st>>>(a);                  \
   }
 #define LC_LAUNCH_GT(KT, SL, TB)                                                                                     \
   {                                                                                                                  \
-    if (agg_all_rows) LC_LAUNCH_GTA(KT, SL, TB, true) else LC_LAUNCH_GTA(KT, SL, TB, false)                          \
+    if (agg_all_rows) LC_LAUNCH_GTA(KT, SL, TB, true, false)                                                         \
+    else if (sparse_out) LC_LAUNCH_GTA(KT, SL, TB, false, true) else LC_LAUNCH_GTA(KT, SL, TB, false, false)         \
   }
 #define LC_LAUNCH_G(KT, SL)                                                                                          \
   {                                                                                                                  \
@@ -1518,7 +1573,7 @@ extern "C" int isg_gatv2_layer_conv(const uint16_t *x_planes, const float *x_inv
                                     int32_t C, int32_t K_in, int32_t K_edge, float negative_slope, void *stream) {
   return lc_launch(x_planes, x_inv_scale, wn_frag, wn_inv_scale, bn, edge_planes, edge_inv_scale, we_frag, we_inv_scale, att, bias,
                    rowptr, eid, src, dst, tile_info, ntiles, max_tiles, node_mask, edge_mask, out, ldo, alpha, rowmax, row_dead,
-                   nullptr, N, E, H, C, K_in, K_edge, negative_slope, stream);
+                   nullptr, false, N, E, H, C, K_in, K_edge, negative_slope, stream);
 }
 
 // The same launch with the masked tiles' table sets read from memory (include/isg_masked.h, csrc/isg_live_tables.hip).
@@ -1533,8 +1588,30 @@ extern "C" int isg_gatv2_layer_conv_tables(const uint16_t *x_planes, const float
                                            void *stream) {
   return lc_launch(x_planes, x_inv_scale, wn_frag, wn_inv_scale, bn, edge_planes, edge_inv_scale, we_frag, we_inv_scale, att, bias,
                    rowptr, eid, src, dst, tile_info, ntiles, max_tiles, node_mask, edge_mask, out, ldo, alpha, rowmax, row_dead,
-                   live_tables, N, E, H, C, K_in, K_edge, negative_slope, stream);
+                   live_tables, false, N, E, H, C, K_in, K_edge, negative_slope, stream);
 }
+
+// The same launch again with a flag word behind live_tables (include/isg_sparse_out.h).  ISG_LC_SPARSE_OUT: on groups
+// of tiles, `out` and `rowmax` are written only where isg_mgat_dense_tail's live-row form reads them.
+extern "C" int isg_gatv2_layer_conv_sparse(const uint16_t *x_planes, const float *x_inv_scale, const uint16_t *wn_frag,
+                                           const float *wn_inv_scale, const float *bn, const uint16_t *edge_planes,
+                                           const float *edge_inv_scale, const uint16_t *we_frag, const float *we_inv_scale,
+                                           const float *att, const float *bias, const int32_t *rowptr, const int32_t *eid,
+                                           const int32_t *src, const int32_t *dst, const int32_t *tile_info, const int32_t *ntiles,
+                                           int64_t max_tiles, const float *node_mask, const float *edge_mask, float *out, int32_t ldo,
+                                           float *alpha, float *rowmax, uint8_t *row_dead, const uint8_t *live_tables, int32_t flags,
+                                           int64_t N, int64_t E, int32_t H, int32_t C, int32_t K_in, int32_t K_edge,
+                                           float negative_slope, void *stream) {
+  if ((flags & ~ISG_LC_SPARSE_OUT) != 0) return ISG_EINVAL;
+  const bool sparse = (flags & ISG_LC_SPARSE_OUT) != 0;
+  // the rows left out are found again by their flags: a sparse launch without them (or without a mask) has no reader
+  if (sparse && (!row_dead || (!node_mask && !edge_mask))) return ISG_EINVAL;
+  return lc_launch(x_planes, x_inv_scale, wn_frag, wn_inv_scale, bn, edge_planes, edge_inv_scale, we_frag, we_inv_scale, att, bias,
+                   rowptr, eid, src, dst, tile_info, ntiles, max_tiles, node_mask, edge_mask, out, ldo, alpha, rowmax, row_dead,
+                   live_tables, sparse, N, E, H, C, K_in, K_edge, negative_slope, stream);
+}
+
+extern "C" int isg_sparse_out_abi_version(void) { return ISG_SPARSE_OUT_ABI_VERSION; }
 
 extern "C" int32_t isg_gatv2_layer_conv_group(int64_t N, int64_t E, int32_t H, int64_t max_tiles) {
   if (N <= 0 || E < 0 || H <= 0 || H > 16 || max_tiles <= 0) return 1;

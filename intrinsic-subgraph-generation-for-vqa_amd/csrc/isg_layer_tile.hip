@@ -760,9 +760,14 @@ __global__ __launch_bounds__(256, 2) void mgat_dense_tail_kernel(DtArgs a) {
       g0 = a.tile_ptr[t], g1 = a.tile_ptr[t + 1];
       ng = g1 - g0;
       if (!grouped) {                // today's walk: the tile's own rows, in place (x_proj opens with a barrier)
+        // A row whose four flags are set is read from the tile's FIRST such row: every such row holds the same bits by the flags'
+        // definition, and a sparse launch of the convolution wrote only that one.  The tile's rows sit on wave 0.
         L = nrows;
+        const int trow = min(r0 + min(tid, nrows - 1), a.N - 1);
+        const bool dead = tid < nrows && a.row_dead[trow] == 0x01010101u;
+        const unsigned long long db = __ballot(dead);
         if (tid < nrows) {
-          s_list[tid] = min(r0 + tid, a.N - 1);
+          s_list[tid] = dead ? min(r0 + (int)__builtin_ctzll(db), a.N - 1) : trow;
           s_cpos[tb + tid] = (unsigned char)tid;
         }
       }

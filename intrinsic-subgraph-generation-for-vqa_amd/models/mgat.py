@@ -138,9 +138,15 @@ class MGAT(torch.nn.Module):
             if explainer:
                 h = expl_bypass_x if (explainer_stage - 1) == i else h                   # :140-141
                 x_gated = x_planes = None
+            # does the fused tail's live-row form read this layer's convolution, and nothing else?  Then the convolution may leave
+            # the rows without a live in-slot unwritten (ops.sparse_conv_out_rule)
+            tail_ok = not explainer and ops.dense_tail_supported(plan, self.x_proj[i], wide, self.convs[0].out_channels)
+            sparse = ops.sparse_conv_out_rule(self.convs[i].mask.masking_threshold != 1.0, tail_ok, bool(explainer),
+                                              ops.dense_tail_dense_rows(), routes[i].conv)
             conv_res, mask, edge_att = self.convs[i](
                 x=h, edge_index=edge_index, edge_attr=edge_attr, instruction=ins, batch=batch,
                 return_masks=return_masks, return_attention_weights=True, imle_att=gate_u,
+                want_alpha=bool(return_attention) or not ops.CFG.skip_unread_alpha, sparse_out=sparse,
                 gate_rows_given=gate_feats is not None, all_instrs=instr_vectors, route=routes[i],
                 plan=plan, noise=None if noises is None else noises.get(i),
                 seed=None if seed is None else seed + i,
@@ -157,8 +163,7 @@ class MGAT(torch.nn.Module):
             elif self.interpretable_mode and mask is not None:                           # :176-177
                 tail_mask = mask
             bn = self.bns[i]
-            if (isinstance(conv_res, Tensor) and conv_res.dtype == torch.float32 and not explainer
-                    and ops.dense_tail_supported(plan, self.x_proj[i], wide, self.convs[0].out_channels)):
+            if isinstance(conv_res, Tensor) and conv_res.dtype == torch.float32 and tail_ok:
                 # x_proj + instruction attention + GraphNorm + residual (+ mask) + the NEXT layer's instruction gate: one
                 # launch on graph-aligned row tiles (csrc/isg_layer_tile.hip); :156-177 and mgat_v2_conv.py:156-157
                 nxt = instr_vectors[i + 1].contiguous() if i + 1 < L and self.convs[i + 1].use_instr else None
@@ -171,6 +176,8 @@ class MGAT(torch.nn.Module):
                 if res is not None:
                     h, x_gated, x_planes = res
                     continue
+            if isinstance(conv_res, Tensor):
+                conv_res = ops.dense_conv_out(conv_res)                                  # every row, whatever the launch left out
             conv_res = ops.mlp(self.x_proj[i], conv_res)                                 # :156 (Linear+GELU fused)
             h = ops.mgat_layer_tail(ins, conv_res.contiguous(), h, plan, bn.weight, bn.bias, bn.mean_scale, bn.eps,
                                     node_mask=tail_mask)                                 # :168-177

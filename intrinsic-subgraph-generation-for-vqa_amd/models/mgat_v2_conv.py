@@ -135,7 +135,11 @@ class MaskingGATv2Conv(torch.nn.Module):
                 plan: Optional[ops.GraphPlan] = None, noise: Optional[Tensor] = None, seed: Optional[int] = None,
                 e_proj: Optional[Tensor] = None, x_gated: Optional[Tensor] = None,
                 x_planes: Optional["ops.NodePlanes"] = None, out_planes: bool = False, gate_rows_given: bool = False,
-                route: Optional["ops.ConvRoute"] = None, gate_q: Optional[Tensor] = None):
+                route: Optional["ops.ConvRoute"] = None, gate_q: Optional[Tensor] = None, want_alpha: bool = True,
+                sparse_out: bool = False):
+        # want_alpha / sparse_out (the layer_conv route alone; ops.gatv2_layer_conv): False = the attention weights are not stored and
+        # None is returned for them; True = the result may lack the rows without a live in-slot (the caller reads it through
+        # ops.mgat_dense_tail or ops.dense_conv_out)
         # route: self.route(...) of this call, from a caller that has asked already (MGAT)
         # gate_q: mask.ques_nn(imle_att), from a caller that ran it ahead of the layers (ops.small_mlps)
         # gate_rows_given: imle_att[g] already IS the row the node gate of graph g reads (ops.run_split's sub-batch: the reference's
@@ -175,7 +179,7 @@ class MaskingGATv2Conv(torch.nn.Module):
 
         def done(out, alpha):
             if isinstance(return_attention_weights, bool):
-                return out, mask, (edge_index, alpha)                                    # :237
+                return out, mask, (None if alpha is None else (edge_index, alpha))       # :237 (None: want_alpha=False)
             return out, mask                                                             # :241
 
         fdt = self.rows_dtype(plan)
@@ -188,7 +192,8 @@ class MaskingGATv2Conv(torch.nn.Module):
             # lin_l | lin_r, lin_edge, logits, softmax and aggregation as ONE persistent launch on graph-aligned tiles
             # (csrc/isg_layer_conv.hip): x_l / x_r live in LDS only                       # :177-181, :215-232, :243-279
             res = ops.gatv2_layer_conv(planes if planes is not None else x, self.lin_l, self.lin_r, edge_attr.float().contiguous(),
-                                       self.lin_edge.weight, self.att, plan, H, want_rowmax=True, **kw)
+                                       self.lin_edge.weight, self.att, plan, H, want_rowmax=True, want_alpha=want_alpha,
+                                       sparse_out=sparse_out, **kw)
             if res is not None:
                 return done(*res)
             if x is None:

@@ -11,6 +11,7 @@ from __future__ import annotations
 import contextlib
 import dataclasses
 import operator
+import os
 import sys
 import types
 import weakref
@@ -56,6 +57,9 @@ class Switches:
     tile_heavy_first: bool = True          # persistent tile kernels walk the tile list heavy tiles first
     fuse_gate: bool = True                 # the masked layer's node gate from the layer input's planes, node_nn inside
     fuse_dense_tail: bool = True           # x_proj + layer tail + next instruction gate as one kernel on graph-aligned tiles
+    sparse_conv_out: bool = True           # a masked layer's convolution writes `out` only where that tail's live-row form reads it
+    skip_unread_alpha: bool = True         # MGAT asks isg_gatv2_layer_conv for attention weights only under return_attention
+    poison_sparse_out: bool = False        # debug: such a launch starts from NaN-filled `out` / `rowmax` (a read of an unwritten row shows)
     dense_tail_rows: int = 64              # nodes per tile of isg_mgat_dense_tail
     fuse_readout: bool = True              # node_nn + mask + per-graph softmax pooling as one launch on graph-aligned tiles
     fuse_question_mlps: bool = True        # the masked layers' ques_nn and the read-out's ques_nn as one launch ahead of the layers (isg_small_mlps)
@@ -1288,6 +1292,7 @@ class StepCapture:
 
 
 ISG_EUNSUPPORTED = -2      # include/isg.h
+ISG_LC_SPARSE_OUT = 1      # include/isg_sparse_out.h
 
 # message + softmax + aggregation with lin_edge inside as ONE launch on graph-aligned tiles (csrc/isg_layer_tile.hip): the
 # head's x_l slice of a tile is staged once in LDS and serves the logit epilogue's row gathers and the aggregation
@@ -1479,7 +1484,8 @@ def _oversize_conv(sub: "OversizeGraphs", x_l: Tensor, x_r: Tensor, edge_attr: T
     o, a = gatv2_mp(x_l, x_r, e_proj, att, sub.plan, heads, bias=bias, node_mask=nm, edge_mask=em,
                     negative_slope=negative_slope, want_rowmax=rowmax is not None)
     out.index_copy_(0, sub.nodes, o)
-    alpha.index_copy_(0, sub.edges, a)
+    if alpha is not None:
+        alpha.index_copy_(0, sub.edges, a)
     if rowmax is not None:
         rm = row_maxima(o)
         if rm is None:                                  # the node-chunk kernel leaves none: one pass over the few rows
@@ -1488,27 +1494,36 @@ def _oversize_conv(sub: "OversizeGraphs", x_l: Tensor, x_r: Tensor, edge_attr: T
 
 
 def _tile_conv_operands(plan: "GraphPlan", ntiles: Tensor, cap: int, att: Tensor, bias, node_mask, edge_mask, H: int, HC: int,
-                        want_rowmax: bool, device):
+                        want_rowmax: bool, device, want_alpha: bool = True, poison: bool = False):
     """What isg_gatv2_layer_conv and isg_gatv2_tile_conv take alike, in the order both take it -- att, bias, the CSR, the tile list,
-    the masks, out, its row stride, alpha, rowmax -- and the three result tensors (rowmax: None unless wanted)."""
+    the masks, out, its row stride, alpha, rowmax -- and the three result tensors (rowmax: None unless wanted; alpha: None and a
+    null pointer when not wanted, which isg_gatv2_layer_conv alone takes).  poison: out / rowmax start NaN-filled."""
     N, E = plan.N, plan.E
     tile_info = plan.tiles_heavy_first(TILE_CONV_NODES, TILE_CONV_EDGES)        # a persistent kernel: balanced rounds
-    out = torch.empty(N, HC, dtype=torch.float32, device=device)
-    alpha = torch.empty(E, H, dtype=torch.float32, device=device)
-    rowmax = torch.empty(N, H, dtype=torch.float32, device=device) if want_rowmax else None
+    new = (lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=device)) if poison else \
+        (lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device))
+    out = new(N, HC)
+    alpha = torch.empty(E, H, dtype=torch.float32, device=device) if want_alpha else None
+    rowmax = new(N, H) if want_rowmax else None
     attp, biasp, nm, em = _mp_operands(att, bias, node_mask, edge_mask, N, E, HC)
     shared = (attp, biasp, plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(), tile_info.data_ptr(),
-              ntiles.data_ptr(), cap, nm, em, out.data_ptr(), HC, alpha.data_ptr(), 0 if rowmax is None else rowmax.data_ptr())
+              ntiles.data_ptr(), cap, nm, em, out.data_ptr(), HC, 0 if alpha is None else alpha.data_ptr(),
+              0 if rowmax is None else rowmax.data_ptr())
     return shared, out, alpha, rowmax
 
 
 def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Tensor, plan: "GraphPlan", heads: int,
                      bias: Optional[Tensor] = None, node_mask: Optional[Tensor] = None, edge_mask: Optional[Tensor] = None,
-                     negative_slope: float = 0.2, want_rowmax: bool = False):
+                     negative_slope: float = 0.2, want_rowmax: bool = False, want_alpha: bool = True, sparse_out: bool = False):
     """lin_l(x), lin_r(x), lin_edge(edge_attr), message, softmax and aggregation of one MaskingGATv2Conv as ONE launch
     (mgat_v2_conv.py:177-181, :215-232, :243-279): isg_gatv2_layer_conv.  x = the gated layer input [N, 128], as NodePlanes (from
     instr_gate_planes / mgat_dense_tail) or as fp32 rows (split here, one more launch).  Bit-identical to linear_fused +
-    gatv2_tile_conv.  Returns (out, alpha), or None when the kernel has no launch for this shape."""
+    gatv2_tile_conv.  Returns (out, alpha), or None when the kernel has no launch for this shape.
+    want_alpha=False: the attention weights are not stored and alpha is None (out keeps its bits).
+    sparse_out=True (a masked launch with want_rowmax, on groups of tiles): a row that no live slot has as
+    destination -- flagged dead in every head, `+0 + bias` -- is written in `out` and its maxima for the first such row of every
+    tile only; `out` then carries a marker, mgat_dense_tail's live-row form reads it as it is, and EVERY other reader goes through
+    dense_conv_out(out)."""
     lib = _lib.load()
     plan.require_csr()
     if not isinstance(x, NodePlanes):
@@ -1536,7 +1551,17 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
     wn, wn_inv = _weight_planes(cat_w, True, "f16x3")
     we, we_inv = _weight_planes(w_edge, True, "f16x3")
     (_, ntiles, cap, _), (ep, ep_inv) = plan.tiles_and_edge_planes(edge_attr, TILE_CONV_NODES, TILE_CONV_EDGES)
-    shared, out, alpha, rowmax = _tile_conv_operands(plan, ntiles, cap, att, bias, node_mask, edge_mask, H, HC, want_rowmax, dev)
+    # a sparse launch: masked, with flags for its readers, on groups of tiles (the library's rule for this shape)
+    masked = node_mask is not None or edge_mask is not None
+    mlib, group = None, 1
+    if masked and cap > 0:
+        from . import _lib_masked
+        mlib = _lib_masked.load()
+        group = mlib.isg_gatv2_layer_conv_group(N, E, H, cap)
+    sparse = bool(sparse_out and CFG.sparse_conv_out and masked and want_rowmax and group > 1 and
+                  CFG.dense_tail_rows == TILE_CONV_NODES)      # the tail's tiles are the convolution's
+    shared, out, alpha, rowmax = _tile_conv_operands(plan, ntiles, cap, att, bias, node_mask, edge_mask, H, HC, want_rowmax, dev,
+                                                     want_alpha=want_alpha, poison=sparse and CFG.poison_sparse_out)
     # a masked launch also says which (row, head) kept all-zero accumulators: those rows of `out` are +0 + bias, all alike, and
     # mgat_dense_tail runs x_proj once for them.  Rows of a mixed plan's oversize graphs are written elsewhere: never flagged.
     row_dead = None
@@ -1545,12 +1570,9 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
         row_dead = (torch.empty if whole else torch.zeros)(N, H, dtype=torch.uint8, device=dev)
     # a masked launch on groups of tiles reads every tile's live tables from memory: one pre-pass builds them for all heads
     # (include/isg_masked.h).  Rebuilt on every call -- the mask is the step's -- in a buffer of this call, on the launch stream.
-    mlib, tables = None, None
-    if (node_mask is not None or edge_mask is not None) and cap > 0:
-        from . import _lib_masked
-        mlib = _lib_masked.load()
-        if mlib.isg_layer_conv_live_tables_enabled() and mlib.isg_gatv2_layer_conv_group(N, E, H, cap) > 1:
-            tables = torch.empty(mlib.isg_layer_conv_live_tables_bytes(cap), dtype=torch.uint8, device=dev)
+    tables = None
+    if mlib is not None and mlib.isg_layer_conv_live_tables_enabled() and group > 1:
+        tables = torch.empty(mlib.isg_layer_conv_live_tables_bytes(cap), dtype=torch.uint8, device=dev)
     timer, ev1 = MP_TIMER, None
     if timer is not None:
         ev0, ev1 = timer.bracket({"N": N, "E": E, "H": H, "C": C, "K": K, "masked": node_mask is not None or edge_mask is not None,
@@ -1558,12 +1580,17 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
         ev0.record()
     front = (x.planes.data_ptr(), x.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(), ep_inv.data_ptr(),
              we.data_ptr(), we_inv.data_ptr(), *shared, 0 if row_dead is None else row_dead.data_ptr())
-    if tables is None:
-        rc = lib.isg_gatv2_layer_conv(*front, N, E, H, C, K_in, K, float(negative_slope), _stream())
-    else:
+    if tables is not None:
         _, _, rowptr_p, eid_p, src_p, dst_p, tile_info_p, ntiles_p, _, nm_p, em_p = shared[:11]
         _lib.check(mlib.isg_layer_conv_live_tables(rowptr_p, eid_p, src_p, dst_p, ep_inv.data_ptr(), tile_info_p, ntiles_p, cap,
                                                    nm_p, em_p, tables.data_ptr(), N, E, _stream()), "isg_layer_conv_live_tables")
+    if sparse:
+        from . import _lib_sparse_out
+        rc = _lib_sparse_out.load().isg_gatv2_layer_conv_sparse(*front, 0 if tables is None else tables.data_ptr(), ISG_LC_SPARSE_OUT, N, E, H, C, K_in, K,
+                                              float(negative_slope), _stream())
+    elif tables is None:
+        rc = lib.isg_gatv2_layer_conv(*front, N, E, H, C, K_in, K, float(negative_slope), _stream())
+    else:
         rc = mlib.isg_gatv2_layer_conv_tables(*front, tables.data_ptr(), N, E, H, C, K_in, K, float(negative_slope), _stream())
     if not _launched(rc, "isg_gatv2_layer_conv", timer, ev1):
         return None
@@ -1579,6 +1606,8 @@ def gatv2_layer_conv(x, lin_l, lin_r, edge_attr: Tensor, w_edge: Tensor, att: Te
         attach_row_maxima(out, rowmax)
     if row_dead is not None:
         attach_dead_rows(out, row_dead)
+    if sparse:
+        _attach(out, "_isg_sparse_out", None if bias is None else bias.detach())
     return out, alpha
 
 
@@ -2111,6 +2140,11 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
     per `group` tiles, on their live rows plus one dead row; group = None: dense_tail_group's rule."""
     lib = _lib.load()
     N, K1 = conv_out.shape
+    dead = dead_rows(conv_out)
+    if dead is not None and (tuple(dead.shape) != (N, 4) or dead.dtype != torch.uint8 or not dead.is_contiguous()):
+        dead = None
+    if dead is None or dense_tail_dense_rows():
+        conv_out = dense_conv_out(conv_out)       # the form that reads every row (identity unless a sparse launch left conv_out)
     rm = row_maxima(conv_out)
     if rm is None or rm.dim() != 2 or rm.size(0) != N or rm.stride(1) != 1 or rm.dtype != torch.float32:
         return None
@@ -2123,9 +2157,6 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
     # one tile plan per batch: the convolution's (64 nodes / 256 slots) serves this kernel too when it exists
     # one tile plan per batch, the convolution's (64 nodes / 256 slots): the same graphs are "oversize" for every tile kernel
     tile_ptr, ntiles, cap, tile_info = plan.tiles(CFG.dense_tail_rows, TILE_CONV_EDGES if plan.rowptr is not None else 0)
-    dead = dead_rows(conv_out)
-    if dead is not None and (tuple(dead.shape) != (N, 4) or dead.dtype != torch.uint8 or not dead.is_contiguous()):
-        dead = None
     if dead is not None and group is None:
         group = dense_tail_group(N, plan.E if plan.rowptr is not None else 0, h.device)
     h_out = torch.empty_like(h)
@@ -2150,7 +2181,7 @@ def mgat_dense_tail(conv_out: Tensor, x_proj: torch.nn.Sequential, ins: Tensor, 
     sub = _mixed_sub(plan)
     if sub is not None:
         # mgat.py:156-177 on the graphs the tile kernel passed over: x_proj, the per-graph layer tail, the next gate
-        cs = mlp(x_proj, conv_out.index_select(0, sub.nodes))
+        cs = mlp(x_proj, dense_conv_out(conv_out).index_select(0, sub.nodes))
         nm = None if node_mask is None else node_mask.reshape(-1).index_select(0, sub.nodes).view(-1, 1)
         hs = mgat_layer_tail(ins.index_select(0, sub.gids), cs.contiguous(), h.index_select(0, sub.nodes), sub.plan, weight, bias,
                              mean_scale, eps, node_mask=nm)
@@ -2614,7 +2645,53 @@ def dead_rows(x: Tensor) -> Optional[Tensor]:
     return _attached(x, "_isg_row_dead")
 
 
+def is_sparse_conv_out(x: Tensor) -> bool:
+    """Did a sparse gatv2_layer_conv launch leave `x`?  (The marker is tied to x's version like the flags it goes with.)"""
+    hit = getattr(x, "_isg_sparse_out", None)
+    return hit is not None and hit[0] == _stamp(x) and dead_rows(x) is not None
+
+
+def dense_conv_out(x: Tensor) -> Tensor:
+    """`x` itself unless a sparse gatv2_layer_conv launch left it (sparse_out=True); then a tensor with every row: the rows whose
+    flags are set in every head -- of which the launch wrote one per tile -- are `0 + bias`, their maxima that vector's per head,
+    which is what a dense launch writes there bit for bit.  The result carries its maxima and flags and no marker."""
+    if not is_sparse_conv_out(x):
+        return x
+    bias, dead, rm = x._isg_sparse_out[1], dead_rows(x), row_maxima(x)
+    H = dead.size(1)
+    const = torch.zeros(x.size(1), dtype=x.dtype, device=x.device)
+    if bias is not None:
+        const = const + bias.reshape(-1).to(x.dtype)         # an addition, as in the kernel: +0 + -0 = +0
+    flagged = (dead != 0).all(dim=1, keepdim=True)
+    full = torch.where(flagged, const.unsqueeze(0), x)
+    if rm is not None:
+        attach_row_maxima(full, torch.where(flagged, const.view(H, -1).abs().amax(dim=1).unsqueeze(0), rm))
+    return attach_dead_rows(full, dead)
+
+
 _CUS = {}
+
+
+_DT_DENSE_ROWS = None
+
+
+def dense_tail_dense_rows() -> bool:
+    """ISG_DT_DENSE_ROWS=1 as isg_mgat_dense_tail reads it (once per process): x_proj over every row whatever the flags say."""
+    global _DT_DENSE_ROWS
+    if _DT_DENSE_ROWS is None:
+        e = os.environ.get("ISG_DT_DENSE_ROWS", "")
+        try:
+            _DT_DENSE_ROWS = int(e.strip() or 0) != 0
+        except ValueError:
+            _DT_DENSE_ROWS = False                   # atoi of a word is 0
+    return _DT_DENSE_ROWS
+
+
+def sparse_conv_out_rule(masked: bool, tail_supported: bool, explainer: bool, dense_rows: bool, conv: str) -> bool:
+    """May a layer's convolution leave the rows without a live in-slot unwritten (gatv2_layer_conv sparse_out)?  Only when the one
+    reader of its result is mgat_dense_tail's live-row form: a masked layer whose fused tail will run, outside the explainer,
+    without ISG_DT_DENSE_ROWS, on the layer_conv route.  Pure: MGAT.forward asks it once per layer."""
+    return bool(masked and tail_supported and not explainer and not dense_rows and conv == "layer_conv")
 
 
 def dense_tail_group(N: int, E: int, device) -> int:

@@ -47,7 +47,23 @@ if mode in ("logits", "tile", "layer"):
         torch.manual_seed(0)
         lin_l, lin_r = GlorotLinear(C, H * C).to(dev), GlorotLinear(C, H * C).to(dev)
         xin = torch.randn(N, C, device=dev, generator=g)
-        fn = lambda xl_, xr_, ea_, w_, att_, plan_, H_, **kw: ops.gatv2_layer_conv(xin, lin_l, lin_r, ea_, w_, att_, plan_, H_, **kw)
+        # as MGAT.forward issues it: no attention weights, and the masked launch with sparse output
+        fn = lambda xl_, xr_, ea_, w_, att_, plan_, H_, **kw: ops.gatv2_layer_conv(
+            xin, lin_l, lin_r, ea_, w_, att_, plan_, H_, want_alpha=False, sparse_out=kw.get("node_mask") is not None, **kw)
+        plan.require_csr()
+        # ... under a mask of the product's kind: two or three nodes of every graph, 2.7 on average (configs[1]'s masked layer
+        # keeps 11 052 of 82 286 nodes: tools/count_live_rows.py), not three nodes in ten anywhere -- with those a group of six
+        # tiles names more than 64 rows and runs tile by tile, which the product's masked layer never does
+        order = torch.argsort(wl.batch.double() * 2 + torch.rand(N, device=dev, generator=g).double())
+        first = torch.cumsum(torch.bincount(wl.batch, minlength=graphs), 0) - torch.bincount(wl.batch, minlength=graphs)
+        mask = torch.zeros(N, 1, device=dev)
+        keep = 2 + (wl.batch[order] % 10 < 7).long()
+        mask[order[(torch.arange(N, device=dev) - first[wl.batch[order]]) < keep]] = 1.0
+        live = (mask[plan.src.long(), 0] * mask[plan.dst.long(), 0]) != 0
+        with_live = torch.zeros(N, dtype=torch.bool, device=dev)
+        with_live[plan.dst.long()[live]] = True
+        print(f"rows_without_a_live_in_slot={int((~with_live).sum())} of N={N} (x {4 * H * C + 4 * H} bytes of out and maxima each, "
+              f"less one row per tile)")
     if mode in ("tile", "layer"):
         plan.tiles(ops.TILE_CONV_NODES, ops.TILE_CONV_EDGES)      # the tile plan is built once per batch, not per layer
         torch.cuda.synchronize()

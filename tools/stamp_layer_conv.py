@@ -8,7 +8,9 @@ The masked launch is the grouped form unless ISG_LC_GROUP=1 is
 --tables (with --masked): the tiles' live tables come from isg_layer_conv_live_tables, whose launch the stamps
 do not cover: the first phase is then the fetch of the images, and compaction builds no live lists.
 The grouped form ends in the constant fill and the list pass, each with a line of its own; with
-ISG_LC_AGG_ALL_ROWS=1 it ends in the per-tile aggregation over all rows instead, as before."""
+ISG_LC_AGG_ALL_ROWS=1 it ends in the per-tile aggregation over all rows instead, as before.
+--sparse (with --masked): the launch goes through isg_gatv2_layer_conv_sparse with ISG_LC_SPARSE_OUT and a flag buffer, without
+attention weights, as MGAT.forward issues it: the fill stores one row per tile."""
 import ctypes
 import os
 import sys
@@ -19,11 +21,12 @@ OUT = os.path.join(ROOT, "tools", "_build", "libisg_dt_stamp.so")
 
 import torch
 
-from isubgvqa_amd import _lib, _lib_masked, ops, synthetic
+from isubgvqa_amd import _lib, _lib_masked, _lib_sparse_out, ops, synthetic
 
 stamp = ctypes.CDLL(OUT)
 stamp.isg_gatv2_layer_conv.restype, stamp.isg_gatv2_layer_conv.argtypes = _lib.SIGNATURES["isg_gatv2_layer_conv"]
 stamp.isg_lc_set_stamp_buffer.argtypes = [ctypes.c_void_p]
+stamp.isg_gatv2_layer_conv_sparse.restype, stamp.isg_gatv2_layer_conv_sparse.argtypes = _lib_sparse_out.SIGNATURES["isg_gatv2_layer_conv_sparse"]
 for sym in ("isg_gatv2_layer_conv_tables", "isg_layer_conv_live_tables", "isg_layer_conv_live_tables_bytes"):
     getattr(stamp, sym).restype, getattr(stamp, sym).argtypes = _lib_masked.SIGNATURES[sym]
 dev = torch.device("cuda:0")
@@ -78,17 +81,25 @@ att = conv.att.detach().reshape(-1).contiguous()
 use_tables = bool(nm_arg) and "--tables" in sys.argv
 tables = torch.empty(stamp.isg_layer_conv_live_tables_bytes(cap) if use_tables else 0, dtype=torch.uint8, device=dev)
 st = torch.cuda.current_stream().cuda_stream
+sparse = bool(nm_arg) and "--sparse" in sys.argv
+row_dead = torch.empty(N, H, dtype=torch.uint8, device=dev)
 for rep in range(2):
     buf.zero_()
     front = (xp.planes.data_ptr(), xp.inv.data_ptr(), wn.data_ptr(), wn_inv.data_ptr(), cat_b.data_ptr(), ep.data_ptr(),
              ep_inv.data_ptr(), we.data_ptr(), we_inv.data_ptr(), att.data_ptr(), conv.bias.data_ptr(),
              plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
-             tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, alpha.data_ptr(), rowmax.data_ptr(), 0)
+             tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0, out.data_ptr(), H * C, 0 if sparse else alpha.data_ptr(),
+             rowmax.data_ptr(), row_dead.data_ptr() if sparse else 0)
     if use_tables:
         assert stamp.isg_layer_conv_live_tables(plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
                                                 ep_inv.data_ptr(), tile_info.data_ptr(), ntiles.data_ptr(), cap, nm_arg, 0,
                                                 tables.data_ptr(), N, E, st) == 0
-        rc = stamp.isg_gatv2_layer_conv_tables(*front, tables.data_ptr(), N, E, H, C, 128, 128, 0.2, st)
+        if sparse:
+            rc = stamp.isg_gatv2_layer_conv_sparse(*front, tables.data_ptr(), ops.ISG_LC_SPARSE_OUT, N, E, H, C, 128, 128, 0.2, st)
+        else:
+            rc = stamp.isg_gatv2_layer_conv_tables(*front, tables.data_ptr(), N, E, H, C, 128, 128, 0.2, st)
+    elif sparse:
+        rc = stamp.isg_gatv2_layer_conv_sparse(*front, 0, ops.ISG_LC_SPARSE_OUT, N, E, H, C, 128, 128, 0.2, st)
     else:
         rc = stamp.isg_gatv2_layer_conv(*front, N, E, H, C, 128, 128, 0.2, st)
     assert rc == 0
