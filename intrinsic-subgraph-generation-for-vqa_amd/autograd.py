@@ -652,6 +652,112 @@ def gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, neg
                           dropout_seed)
 
 
+def _identity_linear_backward(g, x, weight, want_dx, want_dw, want_db):
+    """(dx, dW, db) of y = x W^T + b from its upstream gradient g: the calls _Linear.backward makes for a Linear without an
+    activation, under either state of LINEAR_BWD_KERNELS.  g's rows may be strided (a column slice)."""
+    db = None
+    if LINEAR_BWD_KERNELS:
+        ops.COUNTERS["linear_bwd_kernels"] += 1
+        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
+            g = g.contiguous()
+        if want_db:
+            db = ops.linear_bwd_prep(g, None, 0, want_dz=False, want_db=True)[1]
+        if not g.is_contiguous():
+            g = g.contiguous()
+    else:
+        g = g.contiguous()
+    dx = None
+    if want_dx:
+        dx = ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False) if (g.size(1) & 3) == 0 else g @ weight
+    dw = None
+    if want_dw:
+        if g.size(0) < WGRAD_MIN_ROWS:
+            dw = g.t() @ x
+        else:
+            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if LINEAR_BWD_KERNELS else ops.linear_wgrad(g, x.contiguous())
+    if want_db and db is None:
+        db = g.sum(0)
+    return dx, dw, db
+
+
+class _ConvHalfRows(torch.autograd.Function):
+    """One GATv2 layer's projections, message passing and output rounding on fp16 feature rows (MaskingGATv2Conv.feature_dtype =
+    torch.float16, BASELINE configs[4]) as ONE node of the autograd graph, fp32 at every differentiable input and output.
+
+    A half tensor must never be an edge of the graph: the engine casts a gradient to the dtype of the tensor it belongs to, and a
+    gradient rounded to half flushes below 6e-8.  So x_l | x_r, e_proj and the half `out` live inside this Function only.
+    Rule: each of the four roundings (x_l, x_r, e_proj, out) has derivative 1 -- what is differentiated is the fp32 function
+    evaluated AT the rounded rows, the rows the forward kernels read.
+    Forward: ops.linear(out_dtype=half) twice (lin_l | lin_r as one [N, 2 H C] projection; lin_edge), isg_gatv2_mp_fwd_f16 on the
+    half slices, out.float().  Backward: isg_gatv2_mp_bwd_f16 on the saved half rows, d_x_l | d_x_r written into one [N, 2 H C]
+    buffer that IS the fused projection's upstream gradient, then the Linear backwards as _Linear makes them."""
+
+    @staticmethod
+    def forward(ctx, x, edge_attr, w_l, b_l, w_r, b_r, w_e, att, bias, node_mask, edge_mask, plan, heads, slope):
+        shared = w_r is None
+        w, b = _ConvHalfRows._cat(w_l, b_l, w_r, b_r)
+        x_lr = ops.linear(x, w, b, out_dtype=torch.float16, cache_planes=False)
+        e_half = ops.linear(edge_attr, w_e, None, out_dtype=torch.float16, cache_planes=False)
+        HC = w_l.size(0)
+        x_l, x_r = (x_lr, x_lr) if shared else (x_lr[:, :HC], x_lr[:, HC:])
+        out, alpha = ops.gatv2_mp(x_l, x_r, e_half, att, plan, heads, bias=bias, node_mask=node_mask, edge_mask=edge_mask,
+                                  negative_slope=slope)
+        ctx.save_for_backward(x, edge_attr, w_l, b_l, w_r, b_r, w_e, att, x_lr, e_half, alpha, node_mask, edge_mask)
+        ctx.cfg = (plan, heads, slope, bias is not None)
+        ctx.mark_non_differentiable(alpha)
+        return out.float(), alpha
+
+    @staticmethod
+    def _cat(w_l, b_l, w_r, b_r):
+        """The fused lin_l | lin_r weight and bias (ops.linear_fused's), or lin_l's own when the layer shares its weights."""
+        if w_r is None:
+            return w_l, b_l
+        w = torch.cat([w_l, w_r], dim=0)
+        if b_l is None and b_r is None:
+            return w, None
+        zero = lambda m: torch.zeros(m.size(0), device=w.device)
+        return w, torch.cat([zero(w_l) if b_l is None else b_l, zero(w_r) if b_r is None else b_r])
+
+    @staticmethod
+    def backward(ctx, g_out, _g_alpha):
+        x, edge_attr, w_l, b_l, w_r, b_r, w_e, att, x_lr, e_half, alpha, node_mask, edge_mask = ctx.saved_tensors
+        plan, heads, slope, has_bias = ctx.cfg
+        need = ctx.needs_input_grad
+        shared = w_r is None
+        HC = w_l.size(0)
+        N = x.size(0)
+        x_l, x_r = (x_lr, x_lr) if shared else (x_lr[:, :HC], x_lr[:, HC:])
+        want_mask = (node_mask is not None and need[9]) or (edge_mask is not None and need[10])
+        buf = None if shared else torch.empty(N, 2 * HC, dtype=torch.float32, device=x.device)
+        d_xl, d_xr, d_e, d_att, d_bias, d_m = ops.gatv2_mp_backward_f16(
+            x_l, x_r, e_half, att, alpha, g_out, plan, heads, node_mask=node_mask, edge_mask=edge_mask, negative_slope=slope,
+            want_mask_grad=want_mask, d_x_lr=buf)
+        g = d_xl + d_xr if shared else buf
+        w, _ = _ConvHalfRows._cat(w_l.detach(), None, None if shared else w_r.detach(), None)
+        want_b = (b_l is not None and need[3]) or (b_r is not None and need[5])
+        dx, dw, db = _identity_linear_backward(g, x, w, need[0], need[2] or need[4], want_b)
+        d_ea, d_we, _ = _identity_linear_backward(d_e, edge_attr, w_e.detach(), need[1], need[6], False)
+        half = lambda t, lo: None if t is None else t[lo:lo + HC]
+        d_node = d_edge = None
+        if want_mask and node_mask is not None:       # the fused mask[src]*mask[dst] product keeps the reference's rule
+            d_node = ops.node_to_edge_mask_backward(d_m, plan).view_as(node_mask)
+        elif want_mask:
+            d_edge = d_m.view_as(edge_mask)
+        return (dx, d_ea, half(dw, 0) if need[2] else None, half(db, 0) if b_l is not None and need[3] else None,
+                half(dw, HC) if not shared and need[4] else None, half(db, HC) if b_r is not None and need[5] else None,
+                d_we, d_att.view_as(att) if need[7] else None, d_bias if has_bias and need[8] else None, d_node, d_edge,
+                None, None, None)
+
+
+def conv_half_rows(x, edge_attr, lin_l, lin_r, w_edge, att, bias, node_mask, edge_mask, plan, heads, negative_slope):
+    """(out fp32 [N, H*C] holding half-rounded values, alpha [E, H]) of a GATv2 layer trained on fp16 feature rows.  lin_l / lin_r:
+    modules with .weight and .bias; lin_r None or lin_l itself: the layer shares its weights (g = d_x_l + d_x_r)."""
+    shared = lin_r is None or lin_r is lin_l
+    return _ConvHalfRows.apply(x, edge_attr, lin_l.weight, lin_l.bias, None if shared else lin_r.weight,
+                               None if shared else lin_r.bias, w_edge, att, bias, node_mask, edge_mask, plan, heads,
+                               negative_slope)
+
+
 class _NodeToEdgeMask(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask, edge_index, plan):

@@ -24,8 +24,15 @@
 // With attention dropout (include/isg_mp_train.h; the DROP instantiations, p > 0), r_e = keep(e, h) / (1 - p) regenerated from
 // (seed, original edge id, head) and out_i = sum_e (alpha_e r_e) m_e x_l[j]:  dalpha_e = r_e m_e <g, x_l[j]>, the `raw` that feeds
 // d m_e is r_e <g, x_l[j]>, and K2's weight is (alpha_e r_e) m_e; S, da_e, ds_e, d att, d x_r, d ep follow from those unchanged.
+//
+// On fp16 feature rows (include/isg_mp_f16_train.h; the F16 instantiations of K1): x_l, x_r and e_proj are stored as IEEE half, possibly
+// as column slices under a row stride; K1 loads 4 channels as 8 bytes and converts them (exactly) where they are used, after which
+// every operation above is the fp32 one in the fp32 instantiation's order -- the results are those of the fp32 kernels on the rows
+// upcast, bit for bit.  K2 reads no saved row; its LDX form only stores d x_l under a row stride, so that d x_l | d x_r can be the
+// two column halves of one [N, 2 H C] buffer.  No dropout form.
 #include "isg_mp.hpp"
 #include "../../include/isg_mp_train.h"
+#include "../../include/isg_mp_f16_train.h"
 
 namespace isg {
 
@@ -41,10 +48,24 @@ struct MpBwdArgs {
   float slope;
   float drop_p, drop_inv;                  // attention dropout: p and 1.0f / (1.0f - p) (0 and 1: none, the plain instantiations)
   uint64_t drop_seed;
+  // the half-row instantiations alone (include/isg_mp_f16_train.h) read these: row strides in units of 4 channels (8 bytes of x_l /
+  // x_r / e_proj, one float4 of d_x_l / d_x_r).  The fp32 instantiations keep the dense H * C / 4 they compute from C and H
+  int ld_l4, ld_r4, ld_e4, ld_dl4, ld_dr4;
 };
 
-template <int H, int P, bool DROP = false>
+// row `row` of a saved operand: fp32 rows are dense (`dense` float4 per row); half rows (F16: 4 channels = 8 bytes, read through
+// ldraw<true> / cvtq of isg_mp.hpp) lie `ld4` such quads apart -- a column half of one fused [N, 2 H C] projection
+template <bool F16>
+__device__ __forceinline__ const float4 *mp_bwd_row(const float4 *base, size_t row, int dense, int ld4) {
+  if constexpr (F16) return reinterpret_cast<const float4 *>(reinterpret_cast<const u32x2 *>(base) + row * (size_t)ld4);
+  else return base + row * dense;
+}
+
+// F16: x_l / x_r / e_proj hold IEEE half (converted at the point of use, every product and sum in fp32 and in the fp32
+// instantiation's order), and x_l / x_r / e_proj / d_x_r have the row strides of MpBwdArgs.  No dropout form of it exists.
+template <int H, int P, bool F16 = false, bool DROP = false>
 __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdArgs a) {
+  static_assert(!(F16 && DROP), "attention dropout exists on fp32 rows only");
   constexpr int G = 64 / H;
   __shared__ int s_rowptr[MP_NPB + 1];
   __shared__ int s_src[MP_ECAP];
@@ -87,7 +108,8 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
     float4 xr4[P], g4[P], dxr[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      xr4[p] = ok[p] ? a.x_r[(size_t)i * R + off[p]] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (F16) xr4[p] = ok[p] ? ldq<true>(mp_bwd_row<true>(a.x_r, (size_t)i, R, a.ld_r4), off[p]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      else xr4[p] = ok[p] ? a.x_r[(size_t)i * R + off[p]] : make_float4(0.f, 0.f, 0.f, 0.f);
       g4[p] = ok[p] ? a.grad_out[(size_t)i * R + off[p]] : make_float4(0.f, 0.f, 0.f, 0.f);
       dxr[p] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -102,11 +124,16 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
       float me = 1.f;
       if (mode == 1) me = a.node_mask[j] * mi;
       else if (mode == 2) me = a.edge_mask[e];
-      const float4 *xl = a.x_l + (size_t)j * R;
+      const float4 *xl = mp_bwd_row<F16>(a.x_l, (size_t)j, R, a.ld_l4);
       float part = 0.f;
 #pragma unroll
-      for (int p = 0; p < P; ++p)
-        if (ok[p]) part += dot4(g4[p], xl[off[p]]);
+      for (int p = 0; p < P; ++p) {   // half rows: an 8-byte load, converted where the dot product takes it
+        if constexpr (F16) {
+          if (ok[p]) part += dot4(g4[p], cvtq(ldraw<true>(xl, off[p])));
+        } else {
+          if (ok[p]) part += dot4(g4[p], xl[off[p]]);
+        }
+      }
       float raw = group_sum<G>(part);
       if (DROP) {   // the slot's edge id is wave-uniform: one Philox block per edge and four heads; pass 2 reads what is stored here
         uint32_t c[4];
@@ -155,13 +182,13 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
       const float al = a.alpha[(size_t)e * H + g];
       const float da = al * (dal - S);
       float dm_part = 0.f;
-      const float4 *xl = a.x_l + (size_t)j * R;
-      const float4 *ep = a.e_proj + (size_t)e * R;
+      const float4 *xl = mp_bwd_row<F16>(a.x_l, (size_t)j, R, a.ld_l4);
+      const float4 *ep = mp_bwd_row<F16>(a.e_proj, (size_t)e, R, a.ld_e4);
       float4 *dep = a.d_e_proj + (size_t)e * R;
 #pragma unroll
       for (int p = 0; p < P; ++p) {
         if (ok[p]) {
-          const float4 u = xl[off[p]], v = ep[off[p]];
+          const float4 u = cvtq(ldraw<F16>(xl, off[p])), v = cvtq(ldraw<F16>(ep, off[p]));
           float s[4] = {(xr4[p].x + u.x) + v.x, (xr4[p].y + u.y) + v.y, (xr4[p].z + u.z) + v.z, (xr4[p].w + u.w) + v.w};
           const float at[4] = {att4[p].x, att4[p].y, att4[p].z, att4[p].w};
           float ds[4], uu[4];
@@ -188,7 +215,7 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
     }
 #pragma unroll
     for (int p = 0; p < P; ++p)
-      if (ok[p]) a.d_x_r[(size_t)i * R + off[p]] = dxr[p];
+      if (ok[p]) a.d_x_r[(size_t)i * (F16 ? a.ld_dr4 : R) + off[p]] = dxr[p];
     __builtin_amdgcn_wave_barrier();
   }
 
@@ -211,8 +238,9 @@ __global__ __launch_bounds__(MP_WAVES * 64) void gatv2_mp_bwd_dst_kernel(MpBwdAr
   }
 }
 
-// K2: one wave per source node; d x_l[j] = sum_{e in out(j)} (d ep[e] + alpha_e m_e g[dst_e]), ascending edge id
-template <int H, int P, bool DROP = false>
+// K2: one wave per source node; d x_l[j] = sum_{e in out(j)} (d ep[e] + alpha_e m_e g[dst_e]), ascending edge id.  It reads no
+// saved row; LDX (the launches behind the half-row K1): d_x_l has the row stride of MpBwdArgs
+template <int H, int P, bool LDX = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gatv2_mp_bwd_src_kernel(MpBwdArgs a) {
   constexpr int G = 64 / H;
   const int lane = threadIdx.x & 63;
@@ -260,7 +288,7 @@ __global__ __launch_bounds__(256) void gatv2_mp_bwd_src_kernel(MpBwdArgs a) {
   }
 #pragma unroll
   for (int p = 0; p < P; ++p)
-    if (ok[p]) a.d_x_l[(size_t)j * R + off[p]] = acc[p];
+    if (ok[p]) a.d_x_l[(size_t)j * (LDX ? a.ld_dl4 : R) + off[p]] = acc[p];
 }
 
 // NodeMaskToEdgeMask.backward (ISubGVQA/sampling/node_edge_masks.py:13-19): the reference scatters the edge-mask
@@ -274,7 +302,7 @@ __global__ void node_mask_bwd_kernel(const float *__restrict__ d_edge, const int
   d_node[i] = acc;
 }
 
-template <int H>
+template <int H, bool F16 = false>
 static int launch_bwd(const MpBwdArgs &a, hipStream_t st) {
   constexpr int G = 64 / H;
   const int Q = a.C >> 2;
@@ -282,15 +310,17 @@ static int launch_bwd(const MpBwdArgs &a, hipStream_t st) {
   const int blocks = (a.N + MP_NPB - 1) / MP_NPB;
 #define ISG_BW(p, D)                                                                           \
   case p:                                                                                      \
-    gatv2_mp_bwd_dst_kernel<H, p, D><<<blocks, MP_WAVES * 64, 0, st>>>(a);                     \
-    gatv2_mp_bwd_src_kernel<H, p, D><<<(a.N + 3) / 4, 256, 0, st>>>(a);                        \
+    gatv2_mp_bwd_dst_kernel<H, p, F16, D><<<blocks, MP_WAVES * 64, 0, st>>>(a);                \
+    gatv2_mp_bwd_src_kernel<H, p, F16, D><<<(a.N + 3) / 4, 256, 0, st>>>(a);                   \
     break;
-  if (a.drop_p > 0.f) {
-    switch (P) {
-      ISG_BW(1, true) ISG_BW(2, true) ISG_BW(3, true) ISG_BW(4, true) ISG_BW(5, true) ISG_BW(6, true) ISG_BW(7, true) ISG_BW(8, true)
-      default: return ISG_EUNSUPPORTED;
+  if constexpr (!F16) {   // no DROP instantiation of the half form
+    if (a.drop_p > 0.f) {
+      switch (P) {
+        ISG_BW(1, true) ISG_BW(2, true) ISG_BW(3, true) ISG_BW(4, true) ISG_BW(5, true) ISG_BW(6, true) ISG_BW(7, true) ISG_BW(8, true)
+        default: return ISG_EUNSUPPORTED;
+      }
+      return check_launch();
     }
-    return check_launch();
   }
   switch (P) {
     ISG_BW(1, false) ISG_BW(2, false) ISG_BW(3, false) ISG_BW(4, false) ISG_BW(5, false) ISG_BW(6, false) ISG_BW(7, false)
@@ -305,8 +335,10 @@ static int launch_bwd(const MpBwdArgs &a, hipStream_t st) {
 
 using namespace isg;
 
-static int mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const float *att, const float *alpha,
-                  const float *grad_out, const int32_t *rowptr, const int32_t *eid, const int32_t *src, const int32_t *rowptr_s,
+// f16: the three saved rows hold IEEE half and the five strides apply (x_l / x_r / e_proj in halves, d_x_l / d_x_r in floats; 0 =
+// dense H * C, else 4 | ld and ld >= H * C); fp32 rows are dense and the strides are not looked at
+static int mp_bwd(const void *x_l, const void *x_r, const void *e_proj, bool f16, int32_t ld_l, int32_t ld_r, int32_t ld_e,
+                  int32_t ld_dl, int32_t ld_dr, const float *att, const float *alpha, const float *grad_out, const int32_t *rowptr, const int32_t *eid, const int32_t *src, const int32_t *rowptr_s,
                   const int32_t *eid_s, const int32_t *dst_s, const float *node_mask, const float *edge_mask, float *d_x_l,
                   float *d_x_r, float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E, int32_t H,
                   int32_t C, float negative_slope, float drop_p, uint64_t drop_seed, void *stream) {
@@ -315,6 +347,9 @@ static int mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const
   if (!x_l || !x_r || !att || !grad_out || !rowptr || !rowptr_s || !d_x_l || !d_x_r || !d_att_partial) return ISG_EINVAL;
   if (E > 0 && (!e_proj || !alpha || !eid || !src || !eid_s || !dst_s || !d_e_proj)) return ISG_EINVAL;
   if ((C & 3) != 0 || N >= (1ll << 31) || E >= (1ll << 31)) return ISG_EUNSUPPORTED;
+  const int64_t HC = (int64_t)H * C;
+  if (HC >= (1ll << 31)) return ISG_EUNSUPPORTED;
+  if (!f16) ld_l = ld_r = ld_e = ld_dl = ld_dr = 0;
   // every field named, in declaration order: -Werror=missing-field-initializers (HIP_FLAGS) refuses a field left out
   MpBwdArgs a = {
       .x_l = (const float4 *)x_l, .x_r = (const float4 *)x_r, .e_proj = (const float4 *)e_proj, .att = (const float4 *)att,
@@ -322,11 +357,31 @@ static int mp_bwd(const float *x_l, const float *x_r, const float *e_proj, const
       .eid_s = eid_s, .dst_s = dst_s, .node_mask = node_mask, .edge_mask = edge_mask, .d_e_proj = (float4 *)d_e_proj,
       .d_x_r = (float4 *)d_x_r, .d_x_l = (float4 *)d_x_l, .d_att_partial = (float4 *)d_att_partial, .d_edge_mask = d_edge_mask,
       .N = (int)N, .C = C, .H = H, .slope = negative_slope, .drop_p = drop_p, .drop_inv = 1.0f / (1.0f - drop_p),
-      .drop_seed = drop_seed};
+      .drop_seed = drop_seed, .ld_l4 = (int)(ld_l ? ld_l : HC) >> 2, .ld_r4 = (int)(ld_r ? ld_r : HC) >> 2,
+      .ld_e4 = (int)(ld_e ? ld_e : HC) >> 2, .ld_dl4 = (int)(ld_dl ? ld_dl : HC) >> 2, .ld_dr4 = (int)(ld_dr ? ld_dr : HC) >> 2};
   if (!a.x_l || !a.x_r || !a.att || !a.grad_out || !a.rowptr || !a.rowptr_s || !a.d_x_l || !a.d_x_r || !a.d_att_partial ||
       (E > 0 && (!a.e_proj || !a.alpha || !a.eid || !a.src || !a.eid_s || !a.dst_s || !a.d_e_proj)))
     return ISG_EINVAL;                         // the struct the kernels dereference, not the parameters it was filled from
   hipStream_t st = as_stream(stream);
+  if (f16) {
+    // a stride the kernels can index with: whole quads (the shift above lost nothing), no narrower than a row; and the vector
+    // accesses aligned -- 8 bytes of a half row, 16 of a gradient row (a column half of a [N, 2 H C] buffer keeps both)
+    for (int32_t ld : {ld_l, ld_r, ld_e, ld_dl, ld_dr})
+      if (ld != 0 && ((ld & 3) != 0 || ld < HC)) return ISG_EINVAL;
+    if ((int64_t)a.ld_l4 * 4 < HC || (int64_t)a.ld_r4 * 4 < HC || (int64_t)a.ld_e4 * 4 < HC || (int64_t)a.ld_dl4 * 4 < HC ||
+        (int64_t)a.ld_dr4 * 4 < HC)
+      return ISG_EINVAL;
+    if (((uintptr_t)a.x_l & 7) || ((uintptr_t)a.x_r & 7) || ((uintptr_t)a.e_proj & 7) || ((uintptr_t)a.d_x_l & 15) ||
+        ((uintptr_t)a.d_x_r & 15))
+      return ISG_EINVAL;
+    switch (H) {
+      case 1: return launch_bwd<1, true>(a, st);
+      case 2: return launch_bwd<2, true>(a, st);
+      case 4: return launch_bwd<4, true>(a, st);
+      case 8: return launch_bwd<8, true>(a, st);
+      default: return ISG_EUNSUPPORTED;
+    }
+  }
   switch (H) {
     case 1: return launch_bwd<1>(a, st);
     case 2: return launch_bwd<2>(a, st);
@@ -342,8 +397,24 @@ extern "C" int isg_gatv2_mp_bwd(const float *x_l, const float *x_r, const float 
                                 const float *node_mask, const float *edge_mask, float *d_x_l, float *d_x_r,
                                 float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
                                 int32_t H, int32_t C, float negative_slope, void *stream) {
-  return mp_bwd(x_l, x_r, e_proj, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask, edge_mask, d_x_l,
-                d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, 0.f, 0, stream);
+  return mp_bwd(x_l, x_r, e_proj, false, 0, 0, 0, 0, 0, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask,
+                edge_mask, d_x_l, d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, 0.f, 0, stream);
+}
+
+// include/isg_mp_f16_train.h: isg_gatv2_mp_bwd on saved rows stored as IEEE half, with row strides
+extern "C" int isg_mp_f16_train_abi_version(void) { return ISG_MP_F16_TRAIN_ABI_VERSION; }
+
+extern "C" int isg_gatv2_mp_bwd_f16(const uint16_t *x_l, const uint16_t *x_r, const uint16_t *e_proj, const float *att,
+                                    const float *alpha, const float *grad_out, const int32_t *rowptr, const int32_t *eid,
+                                    const int32_t *src, const int32_t *rowptr_s, const int32_t *eid_s, const int32_t *dst_s,
+                                    const float *node_mask, const float *edge_mask, float *d_x_l, float *d_x_r,
+                                    float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
+                                    int32_t H, int32_t C, float negative_slope, int32_t ld_l, int32_t ld_r, int32_t ld_e,
+                                    int32_t ld_dl, int32_t ld_dr, void *stream) {
+  if (ld_l < 0 || ld_r < 0 || ld_e < 0 || ld_dl < 0 || ld_dr < 0) return ISG_EINVAL;
+  return mp_bwd(x_l, x_r, e_proj, true, ld_l, ld_r, ld_e, ld_dl, ld_dr, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s,
+                dst_s, node_mask, edge_mask, d_x_l, d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, 0.f, 0,
+                stream);
 }
 
 // isg_gatv2_mp_bwd behind isg_gatv2_mp_fwd_dropout: the mask is drawn again from (seed, edge id, head).  p == 0: isg_gatv2_mp_bwd's
@@ -355,8 +426,9 @@ extern "C" int isg_gatv2_mp_bwd_dropout(const float *x_l, const float *x_r, cons
                                         float *d_e_proj, float *d_att_partial, float *d_edge_mask, int64_t N, int64_t E,
                                         int32_t H, int32_t C, float negative_slope, float p, uint64_t seed, void *stream) {
   if (!(p >= 0.f && p < 1.f)) return ISG_EINVAL;     // a NaN fails both comparisons
-  return mp_bwd(x_l, x_r, e_proj, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask, edge_mask, d_x_l,
-                d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, p, p > 0.f ? seed : 0, stream);
+  return mp_bwd(x_l, x_r, e_proj, false, 0, 0, 0, 0, 0, att, alpha, grad_out, rowptr, eid, src, rowptr_s, eid_s, dst_s, node_mask,
+                edge_mask, d_x_l, d_x_r, d_e_proj, d_att_partial, d_edge_mask, N, E, H, C, negative_slope, p, p > 0.f ? seed : 0,
+                stream);
 }
 
 extern "C" int isg_node_to_edge_mask_bwd(const float *d_edge_mask, const int32_t *rowptr, const int32_t *eid,

@@ -9,6 +9,9 @@ Device work per call:
   three dense projections        lin_l, lin_r (C -> H*C, +bias), lin_edge (no bias)     (:177,181,259)
   isg_gatv2_mp_fwd               message + segment softmax + aggregate + bias, with the node->edge
                                  mask product of NodeMaskToEdgeMask fused in            (:169-171,215-232,243-279)
+  autograd.conv_half_rows        feature_dtype = half under autograd: both projections, isg_gatv2_mp_fwd_f16 and the rounding of
+                                 `out` as one autograd node with fp32 ends; its backward reads the saved half rows
+                                 (isg_gatv2_mp_bwd_f16, include/isg_mp_f16_train.h)
   isg_gatv2_mp_fwd_dropout       the same in train() with dropout > 0: alpha = F.dropout(alpha, p, training) between the
                                  softmax and the aggregation, keep or drop drawn from (seed, edge id, head)  (:274-279)
 Which of these launches a layer makes on a batch -- message passing as one persistent launch on graph tiles, with lin_l | lin_r
@@ -72,7 +75,9 @@ class MaskingGATv2Conv(torch.nn.Module):
                                  beta=beta, tau=tau, sample_ratio=sample_ratio, sample_k_min=sample_k_min)
         self.masking = NodeMaskToEdgeMask.apply
         # storage type of the projected rows x_l / x_r / e_proj and of the aggregated output (fp32 arithmetic either way):
-        # torch.float16 is BASELINE configs[4] ("fp16 features / fp32 accumulate"), inference only
+        # torch.float16 is BASELINE configs[4] ("fp16 features / fp32 accumulate").  Inference reads and writes half rows in every
+        # kernel that has the form; under autograd the un-fused route keeps them as the layer's saved tensors and differentiates
+        # the fp32 function at the rounded rows (trains_on_half_rows, autograd.conv_half_rows).  Attention dropout needs fp32 rows
         self.feature_dtype = torch.float32
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout={dropout}: the attention dropout needs 0 <= dropout < 1")
@@ -100,6 +105,14 @@ class MaskingGATv2Conv(torch.nn.Module):
         if fdt == torch.float16 and plan is not None and (plan.nmax > ops.GK_NCAP_L or plan.emax > ops.GK_ECAP_L):
             return torch.float32
         return fdt
+
+    def trains_on_half_rows(self, plan, conv: str, recording: bool, e_proj_given: bool) -> bool:
+        """Does this call run as autograd.conv_half_rows -- projections, message passing and the rounding of `out` as ONE autograd
+        node that saves half rows?  The un-fused route, half rows on this batch (rows_dtype: an oversize graph keeps fp32 rows),
+        autograd recording through an operand of the layer, e_proj not handed in (it would be a half tensor on the autograd
+        graph's edge), no attention dropout (fp32 rows only).  Otherwise every line of forward() runs as it did."""
+        return bool(conv == "unfused" and self.rows_dtype(plan) == torch.float16 and recording and not e_proj_given
+                    and not self.attn_dropout_active())
 
     def route(self, plan, in_channels: int, edge_attr, e_proj=None, imle_att=None) -> "ops.ConvRoute":
         """ops.conv_route for this layer on this batch, kept on the plan.  GraphPlan.tile_mode can cost a device-to-host sync: it is
@@ -200,6 +213,15 @@ class MaskingGATv2Conv(torch.nn.Module):
                 raise RuntimeError("isg_gatv2_layer_conv refused a shape ops.conv_route accepted, and the gated input "
                                    "exists only as planes")
             how = "tile_conv"
+        if (edge_attr is not None and self.lin_edge is not None and
+                self.trains_on_half_rows(plan, how, ops._rec(x, edge_attr, mask, self.att, self.bias, *self.lin_l.parameters(),
+                                                             *self.lin_r.parameters(), *self.lin_edge.parameters()),
+                                         e_proj is not None)):
+            from .. import autograd
+            if edge_attr.dim() == 1:
+                edge_attr = edge_attr.view(-1, 1)
+            return done(*autograd.conv_half_rows(x, edge_attr.float().contiguous(), self.lin_l, self.lin_r, self.lin_edge.weight,
+                                                 self.att, self.bias, mask, None, plan, H, self.negative_slope))
         if self.share_weights:
             x_l = x_r = ops.linear(x, self.lin_l.weight, self.lin_l.bias, out_dtype=fdt)  # :177-179
         else:   # lin_l and lin_r share their input: one [N, 2*H*C] projection, x_l / x_r are its column halves

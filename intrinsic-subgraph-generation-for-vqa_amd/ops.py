@@ -140,7 +140,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "linear_bwd_kernels": 0,                   # autograd._Linear backwards on csrc/isg_linear_bwd.hip (autograd.LINEAR_BWD_KERNELS)
             "simple_bwd_kernel": 0,                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
             "topk_rows": 0,                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
-            "mp_dropout": 0}                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
+            "mp_dropout": 0,                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
+            "mp_f16_train": 0}                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
 
 
 def reset_counters() -> None:
@@ -1693,6 +1694,58 @@ def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alp
         _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
         d_x_l.data_ptr(), d_x_r.data_ptr(), d_e.data_ptr(), part.data_ptr(), 0 if d_m is None else d_m.data_ptr(),
         N, E, H, C, float(negative_slope), *drop, _stream()), name)
+    return d_x_l, d_x_r, d_e, part.sum(0), grad_out.sum(0), d_m
+
+
+def gatv2_mp_backward_f16(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
+                          plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
+                          edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
+                          dropout_p: float = 0.0, dropout_seed: int = 0, d_x_lr: Optional[Tensor] = None):
+    """gatv2_mp_backward on saved rows stored as IEEE half (include/isg_mp_f16_train.h): the same tuple, every gradient fp32,
+    the bits of gatv2_mp_backward on the same rows upcast.  x_l / x_r / e_proj may be column slices (rows strided by a multiple
+    of 4 halves, columns contiguous): the halves of the fused [N, 2*H*C] projection are read where they lie.
+    d_x_lr: a caller-owned fp32 [N, 2*H*C] buffer; d_x_l and d_x_r are then written into its column halves and returned as
+    views of it -- the upstream gradient of the fused lin_l | lin_r Linear, with no torch.cat.  Its other contents are kept.
+    Attention dropout has no half-row form (dropout_p > 0 raises)."""
+    dropout_p, dropout_seed = _drop_args(dropout_p, dropout_seed)
+    if dropout_p > 0.0:
+        raise _lib.IsgError("attention dropout exists on fp32 feature rows only (the half-row backward has no dropout form)")
+    from . import _lib_mp_f16_train
+    lib = _lib_mp_f16_train.load()
+    plan.require_csr()
+    N, HC = x_l.shape
+    H = int(heads)
+    C = HC // H
+    E = plan.E
+    dev = x_l.device
+    if N != plan.N or H * C != HC or tuple(x_r.shape) != (N, HC) or tuple(e_proj.shape) != (E, HC):
+        raise ValueError(f"x_l / x_r must be [N, H*C] and e_proj [E, H*C] of plan N={plan.N}, E={E}, heads={H}")
+    grad_out = grad_out.contiguous()
+    rowptr_s, eid_s, dst_s = plan.source_csr()
+    if d_x_lr is None:
+        d_x_l = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        d_x_r = torch.empty(N, HC, dtype=torch.float32, device=dev)
+    else:
+        if d_x_lr.dtype != torch.float32 or tuple(d_x_lr.shape) != (N, 2 * HC) or not d_x_lr.is_contiguous() or d_x_lr.device != dev:
+            raise ValueError(f"d_x_lr: expected a contiguous fp32 [{N}, {2 * HC}] buffer on {dev}")
+        d_x_l, d_x_r = d_x_lr[:, :HC], d_x_lr[:, HC:]
+    d_e = torch.empty(E, HC, dtype=torch.float32, device=dev)
+    part = torch.empty((N + 15) // 16, HC, dtype=torch.float32, device=dev)
+    d_m = torch.empty(E, dtype=torch.float32, device=dev) if want_mask_grad else None
+    ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else HC         # a single row has no pitch to speak of
+    COUNTERS["mp_f16_train"] += 1
+    _lib.check(lib.isg_gatv2_mp_bwd_f16(
+        _chk_rows(x_l, "x_l", torch.float16) if N > 0 else 0, _chk_rows(x_r, "x_r", torch.float16) if N > 0 else 0,
+        _chk_rows(e_proj, "e_proj", torch.float16) if E > 0 else 0,
+        _chk(att.reshape(-1), "att", torch.float32, (HC,)), _chk(alpha, "alpha", torch.float32, (E, H)) if E > 0 else 0,
+        _chk(grad_out, "grad_out", torch.float32, (N, HC)),
+        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
+        rowptr_s.data_ptr(), eid_s.data_ptr(), dst_s.data_ptr(),
+        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
+        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
+        d_x_l.data_ptr(), d_x_r.data_ptr(), d_e.data_ptr(), part.data_ptr(), 0 if d_m is None else d_m.data_ptr(),
+        N, E, H, C, float(negative_slope), ld(x_l), ld(x_r), ld(e_proj) if E > 0 else 0, ld(d_x_l), ld(d_x_r), _stream()),
+        "isg_gatv2_mp_bwd_f16")
     return d_x_l, d_x_r, d_e, part.sum(0), grad_out.sum(0), d_m
 
 
