@@ -454,6 +454,48 @@ def linear(x, weight, bias, gelu, relu=False):
     return _Linear.apply(x, weight, bias, gelu, relu)
 
 
+class _LinearRowBias(torch.autograd.Function):
+    """y = act(x W^T + P[seg]) (ops.linear_rowbias, include/isg_concat.h), in the mould of _Linear: the forward keeps the
+    pre-activation when an activation follows; dz from ops.linear_bwd_prep without a bias sum, dx on the transposed weight, dW on
+    the bf16 matrix cores from WGRAD_MIN_ROWS rows, and dP[s] = the sum of dz over segment s's rows -- contiguous ranges, summed
+    in row order by ops.segment_range_sum without atomics, so two calls agree bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, weight, P, seg, gelu, relu, rowptr):
+        z = ops.linear_rowbias(x, weight, P, seg, relu=relu, cache_planes=False)
+        ctx.gelu, ctx.relu, ctx.S = gelu, relu, P.size(0)
+        ctx.save_for_backward(x, weight, z if gelu or relu else None, seg, rowptr)
+        return F.gelu(z) if gelu else z
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, z, seg, rowptr = ctx.saved_tensors
+        mode = 1 if ctx.gelu else 2 if ctx.relu else 0
+        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
+            g = g.contiguous()
+        if mode != 0:
+            g = ops.linear_bwd_prep(g, z, mode, want_dz=True, want_db=False)[0]
+        elif not g.is_contiguous():
+            g = g.contiguous()
+        dx = dw = dp = None
+        if ctx.needs_input_grad[0]:
+            dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
+                  if (g.size(1) & 3) == 0 else g @ weight)
+        if ctx.needs_input_grad[1]:
+            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
+        if ctx.needs_input_grad[2]:
+            if rowptr is None:
+                rowptr = ops.segment_rowptr(seg, ctx.S)
+            dp = ops.segment_range_sum(rowptr, g)
+        return dx, dw, dp, None, None, None, None
+
+
+def linear_rowbias(x, weight, P, seg, gelu=False, relu=False, rowptr=None):
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
+    return _LinearRowBias.apply(x, weight, P, seg, gelu, relu, rowptr)
+
+
 # ------------------------------------------------------------------------------------------------
 # The loss (include/isg_optim.h)
 # ------------------------------------------------------------------------------------------------

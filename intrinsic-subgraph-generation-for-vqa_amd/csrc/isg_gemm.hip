@@ -20,6 +20,7 @@
 //           through a per-wave LDS patch -> 16-byte-per-lane row stores
 #include "isg_common.hpp"
 #include "isg_bf16x3.hpp"   // bf16_to_f32, split3
+#include "../../include/isg_concat.h"
 
 #include <stdlib.h>
 
@@ -70,10 +71,20 @@ __device__ __forceinline__ float4 gm_cvt(const gm_u32x2 &v) {
 // chain otherwise carries ~sqrt(6 K / 16) half-ulps of error (measured 4.2x a blocked CPU GEMM's at K = 1200, 4.4x at
 // K = 2048; 1.7x / 1.8x with the second accumulator).  Its 32 registers are paid for with one register image instead of
 // two (loads one k-tile ahead), which keeps 4 waves per SIMD.
-template <int ACT, int DBG, bool A16, bool D16, bool XCD, bool DUAL = false>   // ACT: 0 none, 1 exact GELU, 2 ReLU; XCD: tile order, see below
+//
+// ROWB (include/isg_concat.h): the bias is a ROW per segment instead of one vector -- `bias` is P [S, N] fp32 with row stride
+// rb.ldp, and row m of the result takes P[rb.seg[m], :].  The extra operands travel in a trailing argument that is EMPTY in every
+// other instantiation: their kernel arguments, and with them their instruction streams, are what they were without the flag.
+template <bool ROWB> struct GmRowBias {};
+template <> struct GmRowBias<true> {
+  const int *seg;   // [M], values in [0, S): trusted
+  int ldp;          // floats per row of P, >= N
+};
+template <int ACT, int DBG, bool A16, bool D16, bool XCD, bool DUAL = false, bool ROWB = false>   // ACT: 0 none, 1 exact GELU, 2 ReLU; XCD: tile order, see below
 __global__ __launch_bounds__(512, 4) void linear_bf16x6_kernel(const float *__restrict__ A, const __bf16 *__restrict__ Wp,
                                                             const float *__restrict__ bias, float *__restrict__ D, int M,
-                                                            int N, int K, int Kp, int lda, int ldd, int nt_store) {
+                                                            int N, int K, int Kp, int lda, int ldd, int nt_store,
+                                                            GmRowBias<ROWB> rb = {}) {
   typedef typename GmRawA<A16>::type RawA;
   const void *Av = A;   // fp16 variants: the same pointers, half elements
   void *Dv = D;
@@ -241,16 +252,36 @@ __global__ __launch_bounds__(512, 4) void linear_bf16x6_kernel(const float *__re
   __syncthreads();   // every wave is done with the operand tiles: the LDS is free
   float *patch = reinterpret_cast<float *>(&sm) + wave * (32 * 36);   // [32][32 + 4 pad] floats per wave
   const int h = lane >> 5;
+  // ROWB: the segment of each of this lane's 16 accumulator rows -- seg is read once per row for both column tiles; rows past
+  // M repeat the last row (never a conditional load), their results are never stored.  DUAL: the two accumulators are summed
+  // first (the same add, in the same place of the chain), which frees the registers the P values land in
+  int sg[ROWB ? 16 : 1];
+  if constexpr (ROWB) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sg[r] = rb.seg[min(m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, M - 1)];
+    if constexpr (DUAL) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][j][r] += acc2[j][r];
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int colb = n0 + wn * 64 + j * 32;
     const int col = colb + fr;
-    const float bv = (bias && col < N) ? bias[col] : 0.f;
+    float bv = 0.f;
+    if constexpr (!ROWB) bv = (bias && col < N) ? bias[col] : 0.f;
+    float pv[ROWB ? 16 : 1];
+    if constexpr (ROWB) {   // columns past N repeat the last column: their results are never stored either
+#pragma unroll
+      for (int r = 0; r < 16; ++r) pv[r] = bias[(int64_t)sg[r] * rb.ldp + min(col, N - 1)];
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float v = acc[0][j][r];
-      if constexpr (DUAL) v += acc2[j][r];
-      v += bv;
+      if constexpr (DUAL && !ROWB) v += acc2[j][r];
+      if constexpr (ROWB) v += pv[r]; else v += bv;
       if (ACT == 1) v = gelu_exact(v);
       if (ACT == 2) v = v < 0.f ? 0.f : v;   // ReLU (a NaN stays a NaN, as in torch)
       patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + fr] = v;
@@ -317,8 +348,10 @@ extern "C" int isg_split_bf16x3(const float *w, int64_t rows, int32_t K, uint16_
   return check_launch();
 }
 
+// seg != nullptr: the row-indexed form (include/isg_concat.h) -- `bias` is P [S, N] with row stride ldp, checked by the caller
 static int linear_launch(const void *a, int a16, const uint16_t *w_planes, const float *bias, void *d, int d16,
-                         int64_t M, int32_t N, int32_t K, int32_t lda, int32_t ldd, int32_t act, void *stream) {
+                         int64_t M, int32_t N, int32_t K, int32_t lda, int32_t ldd, int32_t act, void *stream,
+                         const int32_t *seg = nullptr, int32_t ldp = 0) {
   if (M < 0 || N <= 0 || K <= 0 || lda < K || ldd < N || act < 0 || act > 2) return ISG_EINVAL;
   if (M == 0) return ISG_OK;
   if (!a || !w_planes || !d) return ISG_EINVAL;
@@ -358,6 +391,23 @@ static int linear_launch(const void *a, int a16, const uint16_t *w_planes, const
     } else if (xcd) linear_bf16x6_kernel<ACT_, 0, A_, D_, true><<<gridx, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt); \
     else linear_bf16x6_kernel<ACT_, 0, A_, D_, false><<<grid, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt); \
   } while (0)
+  if (seg) {   // fp32 rows in; every launch form of the plain Linear, with the row term
+    if (a16) return ISG_EUNSUPPORTED;
+    const GmRowBias<true> rb = {seg, ldp};
+#define ISG_LIN_ROWB(ACT_, D_)                                                                                               \
+  do {                                                                                                                       \
+    if (dual) {                                                                                                              \
+      if (xcd) linear_bf16x6_kernel<ACT_, 0, false, D_, true, true, true><<<gridx, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt, rb); \
+      else linear_bf16x6_kernel<ACT_, 0, false, D_, false, true, true><<<grid, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt, rb); \
+    } else if (xcd) linear_bf16x6_kernel<ACT_, 0, false, D_, true, false, true><<<gridx, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt, rb); \
+    else linear_bf16x6_kernel<ACT_, 0, false, D_, false, false, true><<<grid, block, 0, st>>>((const float *)a, wp, bias, (float *)d, (int)M, N, K, Kp, lda, ldd, nt, rb); \
+  } while (0)
+    if (!d16) { if (act == 1) ISG_LIN_ROWB(1, false); else if (act == 2) ISG_LIN_ROWB(2, false); else ISG_LIN_ROWB(0, false); }
+    else if (act == 2) return ISG_EUNSUPPORTED;   // as the plain Linear: ReLU has no half-row form
+    else { if (act == 1) ISG_LIN_ROWB(1, true); else ISG_LIN_ROWB(0, true); }
+#undef ISG_LIN_ROWB
+    return check_launch();
+  }
   if (!a16 && !d16) { if (act == 1) ISG_LIN(1, false, false); else if (act == 2) ISG_LIN(2, false, false); else ISG_LIN(0, false, false); }
   else if (act == 2) return ISG_EUNSUPPORTED;   // ReLU exists for the fp32 text encoder only
   else if (a16 && !d16) { if (act == 1) ISG_LIN(1, true, false); else ISG_LIN(0, true, false); }
@@ -376,4 +426,15 @@ extern "C" int isg_linear_bf16x6_f16(const void *a, int32_t a_is_f16, const uint
                                      int32_t d_is_f16, int64_t M, int32_t N, int32_t K, int32_t lda, int32_t ldd,
                                      int32_t act, void *stream) {
   return linear_launch(a, a_is_f16 != 0, w_planes, bias, d, d_is_f16 != 0, M, N, K, lda, ldd, act, stream);
+}
+
+// ---- include/isg_concat.h: the Linear with a bias row per segment ----
+extern "C" int isg_concat_abi_version(void) { return ISG_CONCAT_ABI_VERSION; }
+
+extern "C" int isg_linear_bf16x6_rowbias(const float *a, const uint16_t *w_planes, const float *p, int32_t ldp, const int32_t *seg,
+                                         int32_t S, void *d, int32_t d_is_f16, int64_t M, int32_t N, int32_t K, int32_t lda,
+                                         int32_t ldd, int32_t act, void *stream) {
+  if (M < 0 || N <= 0 || ldp < N || S < 1) return ISG_EINVAL;
+  if (M > 0 && (!p || !seg)) return ISG_EINVAL;
+  return linear_launch(a, 0, w_planes, p, d, d_is_f16 != 0, M, N, K, lda, ldd, act, stream, seg, ldp);
 }

@@ -80,13 +80,25 @@ class MaskingModel(torch.nn.Module):
                 and u.dtype == torch.float32 and ops.node_gate_planes_supported(self.node_nn, u))
 
     def gate_scores(self, x: Tensor, u: Tensor, batch: Tensor, u_is_per_graph: bool = False, plan=None,
-                    x_planes=None, q: Optional[Tensor] = None) -> Tensor:
+                    x_planes=None, q: Optional[Tensor] = None, concat=None) -> Tensor:
         """masking.py:137,151-155 -> [N,1].  ``u_is_per_graph``: u is [B,C] and the caller would have passed
         u[batch]; the reference then indexes ques_nn(u[batch]) with batch AGAIN (quirk Q3), which equals
         ques_nn(u)[batch[batch]] row for row -- computed here without the N-row GEMM.  ``q``: ques_nn(u), from a caller that
-        ran it ahead of the layers (ops.small_mlps)."""
+        ran it ahead of the layers (ops.small_mlps).  ``concat`` = (instruction [B, C], seg int32 [N], ptr int32 [B + 1]): the
+        layer's input is cat(x, instruction[batch]) (concat_instr, dim_nodes = 2 C) and x holds its left half only -- node_nn runs
+        as the N-row GEMM at K = C with one bias row per graph (ops.linear_rowbias), the concatenation is never formed."""
         if q is None:
             q = ops.mlp(self.ques_nn, u)
+        if concat is not None:
+            ins, seg, ptr = concat
+            lin, C = self.node_nn[0], x.size(1)
+            if torch.is_grad_enabled() and ops._rec(x, ins, lin.weight, lin.bias):
+                w_x, w_u, b = lin.weight[:, :C], lin.weight[:, C:].contiguous(), lin.bias
+            else:
+                w_x, w_u, b = ops.derived_weight("concat_split", [lin.weight, lin.bias], lambda: (
+                    lin.weight[:, :C].contiguous(), lin.weight[:, C:].contiguous(), lin.bias.detach()))
+            xn = ops.linear_rowbias(x, w_x, ops.linear(ins, w_u, b), seg, gelu=True, rowptr=ptr)
+            return ops.node_gate(xn.contiguous(), q.contiguous(), batch, double_index=u_is_per_graph, plan=plan)
         if x_planes is not None and self.planes_ready(u):
             # node_nn + the reduction against q as one launch on the planes the convolution reads anyway
             return ops.node_gate_planes(x_planes, self.node_nn, q.contiguous(), batch, double_index=u_is_per_graph)
@@ -96,14 +108,14 @@ class MaskingModel(torch.nn.Module):
 
     def forward(self, x, u, batch, edge_index, size=None, use_all_instrs=True, plan: Optional[ops.GraphPlan] = None,
                 noise: Optional[Tensor] = None, seed: Optional[int] = None, u_is_per_graph: bool = False, x_planes=None,
-                q: Optional[Tensor] = None):
+                q: Optional[Tensor] = None, concat=None):
         if use_all_instrs:
             raise NotImplementedError("use_all_instrs=True (masking.py:141-149) is off by default and outside this path")
         if x is not None:
             x = x.unsqueeze(-1) if x.dim() == 1 else x
         if plan is None:
             plan = ops.GraphPlan.build(batch, None, num_graphs=size)
-        gate = self.gate_scores(x, u, batch, u_is_per_graph, plan, x_planes=x_planes, q=q)
+        gate = self.gate_scores(x, u, batch, u_is_per_graph, plan, x_planes=x_planes, q=q, concat=concat)
         if not self.use_topk:                                               # masking.py:195-198
             gate = F.dropout(gate, p=self.gate_dropout, training=self.training)
             return (torch.sigmoid(gate) > 0.5).to(dtype=gate.dtype)

@@ -166,7 +166,9 @@ class MGAT(torch.nn.Module):
             if isinstance(conv_res, Tensor) and conv_res.dtype == torch.float32 and tail_ok:
                 # x_proj + instruction attention + GraphNorm + residual (+ mask) + the NEXT layer's instruction gate: one
                 # launch on graph-aligned row tiles (csrc/isg_layer_tile.hip); :156-177 and mgat_v2_conv.py:156-157
-                nxt = instr_vectors[i + 1].contiguous() if i + 1 < L and self.convs[i + 1].use_instr else None
+                # (a concat_instr layer reads cat(h, ins) and gates nothing: the tail writes no gated input for it)
+                nxt = (instr_vectors[i + 1].contiguous()
+                       if i + 1 < L and self.convs[i + 1].use_instr and not self.convs[i + 1].concat_instr else None)
                 # the next layer's gated input: as planes when it runs as isg_gatv2_layer_conv, as fp32 rows when anything else
                 # reads it (a masked layer's node gate, the un-fused convolution)
                 nr = routes[i + 1] if nxt is not None else None

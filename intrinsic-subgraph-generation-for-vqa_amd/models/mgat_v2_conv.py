@@ -5,6 +5,9 @@ forward signature and return tuples are kept; ``plan``/``noise``/``seed`` are op
 
 Device work per call:
   isg_instr_gate                 x = gelu(x * instruction[batch])                       (:156-157)
+  isg_linear_bf16x6_rowbias      concat_instr: the layer reads cat(x, instruction[batch]), 2C wide (:153-154), and the
+                                 concatenation is never formed: cat(x, u[batch]) W^T + b = x W[:, :C]^T + (u W[:, C:]^T + b)[batch],
+                                 the N-row GEMM at K = C with one bias row per graph (CONCAT_SPLIT; include/isg_concat.h)
   MaskingModel (masked layers)   node gate + top-k sampler -> node mask [N,1]           (:161-168)
   three dense projections        lin_l, lin_r (C -> H*C, +bias), lin_edge (no bias)     (:177,181,259)
   isg_gatv2_mp_fwd               message + segment softmax + aggregate + bias, with the node->edge
@@ -36,6 +39,19 @@ from .masking import MaskingModel
 # The attention dropout of a layer draws from the stream of (layer seed + this): the sampler of the same layer draws from the
 # layer seed itself (MaskingModel), so an edge's keep decision never shares a Philox stream with a node's noise.
 ATTN_DROPOUT_SEED_OFFSET = 8192
+# concat_instr layers: lin_l | lin_r and the node gate's node_nn on the row-biased Linear (ops.linear_rowbias) instead of the
+# literal torch.cat((x, instruction[batch]), 1) in front of the existing Linears.  Off is the parity twin and the measured
+# baseline (tools/time_concat_instr.py).  An input width that is no multiple of 4 takes the literal form either way.
+CONCAT_SPLIT = True
+
+
+def _seg32(plan, batch: Tensor) -> Tensor:
+    """batch as the int32 segment vector the row-biased Linear reads, kept on the plan (one cast per batch, not per layer)."""
+    memo = plan.memo()
+    seg = memo.get("seg32")
+    if seg is None or seg.numel() != batch.numel():
+        seg = memo["seg32"] = batch.int().contiguous()
+    return seg
 
 
 class MaskingGATv2Conv(torch.nn.Module):
@@ -53,14 +69,18 @@ class MaskingGATv2Conv(torch.nn.Module):
                                       "self-loops already (datasets/scene_graph.py:309-343)")
         if not concat:
             raise NotImplementedError("concat=False (head averaging) is never used by ISubGVQA")
-        if concat_instr or use_all_instrs:
-            raise NotImplementedError("concat_instr / use_all_instrs are off by default (arg_parser.py:102,108) and "
-                                      "outside this path")
+        if use_all_instrs:
+            raise NotImplementedError("use_all_instrs is off by default (arg_parser.py:108) and outside this path: under use_topk "
+                                      "it hands the samplers a 2-D tensor they cannot unpack (deterministic_scheme.py:37)")
+        if concat_instr and use_instr and in_channels % 2 != 0:
+            raise ValueError(f"concat_instr: in_channels = {in_channels} is the width of cat(x, instruction[batch]), twice the node "
+                             "rows' (mgat_v2_conv.py:152-154)")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.negative_slope, self.dropout = concat, negative_slope, dropout
         self.add_self_loops, self.edge_dim, self.fill_value = add_self_loops, edge_dim, fill_value
         self.share_weights, self.use_instr = share_weights, use_instr
         self.concat_instr, self.use_all_instrs = concat_instr, use_all_instrs
+        self._cat = bool(concat_instr and use_instr)     # the flag acts under use_instr only (mgat_v2_conv.py:152-153)
 
         self.lin_l = GlorotLinear(in_channels, heads * out_channels, bias=bias)
         self.lin_r = self.lin_l if share_weights else GlorotLinear(in_channels, heads * out_channels, bias=bias)
@@ -118,12 +138,16 @@ class MaskingGATv2Conv(torch.nn.Module):
         """ops.conv_route for this layer on this batch, kept on the plan.  GraphPlan.tile_mode can cost a device-to-host sync: it is
         asked only when the route depends on it."""
         masked = self.mask.masking_threshold != 1.0
+        if self._cat:
+            in_channels = self.in_channels          # the true input width, whatever the caller read off the node rows
         facts = dict(heads=self.heads, channels=self.out_channels, in_channels=in_channels,
                      edge_dim=edge_attr.size(1) if edge_attr is not None and edge_attr.dim() == 2 else None,
                      rows_dtype=self.rows_dtype(plan), share_weights=self.share_weights, use_instr=self.use_instr, masked=masked,
                      gate_on_planes=masked and self.mask.planes_ready(imle_att), grad=torch.is_grad_enabled(),
                      e_proj_given=e_proj is not None, has_edge_lin=self.lin_edge is not None,
                      attn_dropout=self.attn_dropout_active())
+        if self._cat:
+            facts["concat_instr"] = True
         if plan is None:
             return ops.conv_route(N=0, B=0, E=0, nmax=0, has_csr=False, tile_mode="none", **facts)
         memo, key = plan.memo(), ("route", id(self), *facts.values())
@@ -169,7 +193,19 @@ class MaskingGATv2Conv(torch.nn.Module):
             route = self.route(plan, x.size(1), edge_attr, e_proj, imle_att)
         how, masked = route.conv, self.mask.masking_threshold != 1.0
         planes = None          # gelu(x * instruction[batch]) as the planes isg_gatv2_layer_conv reads (fp32 rows only where needed)
-        if (x_gated is not None or x_planes is not None) and self.use_instr:
+        split = None           # concat_instr on the row-biased Linear: (instruction [B, C], seg int32 [N], ptr int32 [B + 1])
+        if self._cat:                                                            # :153-154
+            if route.gate != "none" or how not in ("pair", "unfused"):
+                raise RuntimeError(f"a concat_instr layer runs un-gated on the pair or the un-fused kernels, not as {route}: a "
+                                   "route handed in must come from self.route() of this call")
+            x = x.float().contiguous()
+            if 2 * x.size(1) != self.in_channels or instruction is None or instruction.size(1) != x.size(1):
+                raise ValueError(f"concat_instr: x {tuple(x.shape)} and instruction must both be {self.in_channels // 2} wide")
+            if CONCAT_SPLIT and x.size(1) % 4 == 0:
+                split = (instruction.float().contiguous(), _seg32(plan, batch), plan.ptr)
+            else:
+                x = torch.cat((x, instruction.float()[batch]), dim=1)
+        elif (x_gated is not None or x_planes is not None) and self.use_instr:
             # gelu(x * instruction[batch]) was already written by the previous layer's fused tail (isg_mgat_dense_tail)
             x, planes = x_gated, x_planes
             if x is None and route.gate_rows:
@@ -188,7 +224,7 @@ class MaskingGATv2Conv(torch.nn.Module):
         mask = None
         if masked:                                                                       # :161
             mask = self.mask(x, imle_att, batch, edge_index, use_all_instrs=False, plan=plan, noise=noise,
-                             seed=seed, u_is_per_graph=not gate_rows_given, x_planes=planes, q=gate_q)   # :166-168
+                             seed=seed, u_is_per_graph=not gate_rows_given, x_planes=planes, q=gate_q, concat=split)   # :166-168
 
         def done(out, alpha):
             if isinstance(return_attention_weights, bool):
@@ -213,6 +249,10 @@ class MaskingGATv2Conv(torch.nn.Module):
                 raise RuntimeError("isg_gatv2_layer_conv refused a shape ops.conv_route accepted, and the gated input "
                                    "exists only as planes")
             how = "tile_conv"
+        if self._cat and fdt != torch.float32 and ops._rec(x, instruction, mask, *self.lin_l.parameters(),
+                                                                   *self.lin_r.parameters()):
+            raise ops._lib.IsgError("training a concat_instr layer on half rows (feature_dtype = torch.float16) is not supported: "
+                                    "the row-biased Linear differentiates fp32 rows only; train it with fp32 rows")
         if (edge_attr is not None and self.lin_edge is not None and
                 self.trains_on_half_rows(plan, how, ops._rec(x, edge_attr, mask, self.att, self.bias, *self.lin_l.parameters(),
                                                              *self.lin_r.parameters(), *self.lin_edge.parameters()),
@@ -222,7 +262,9 @@ class MaskingGATv2Conv(torch.nn.Module):
                 edge_attr = edge_attr.view(-1, 1)
             return done(*autograd.conv_half_rows(x, edge_attr.float().contiguous(), self.lin_l, self.lin_r, self.lin_edge.weight,
                                                  self.att, self.bias, mask, None, plan, H, self.negative_slope))
-        if self.share_weights:
+        if split is not None:
+            x_l, x_r = self._project_split(x, split, fdt)                                # :177-181 without the concatenation
+        elif self.share_weights:
             x_l = x_r = ops.linear(x, self.lin_l.weight, self.lin_l.bias, out_dtype=fdt)  # :177-179
         else:   # lin_l and lin_r share their input: one [N, 2*H*C] projection, x_l / x_r are its column halves
             x_l, x_r = ops.linear_fused(x, (self.lin_l, self.lin_r), out_dtype=fdt)      # :177,181
@@ -256,6 +298,33 @@ class MaskingGATv2Conv(torch.nn.Module):
                                       dropout_seed=base + ATTN_DROPOUT_SEED_OFFSET, **kw))
         return done(*ops.gatv2_mp(x_l, x_r, e_proj, self.att, plan, H, want_rowmax=not torch.is_grad_enabled(),
                                   want_planes=out_planes and not torch.is_grad_enabled(), **kw))          # :215-232
+
+    def _project_split(self, x: Tensor, split, fdt):
+        """x_l, x_r of cat(x, instruction[batch]) as ONE launch over the fused [N, 2 H C] projection (one [N, H C] projection with
+        share_weights): P = instruction . [W_l[:, C:]; W_r[:, C:]]^T + [b_l; b_r] is [B, 2 H C], one bias row per graph, and the
+        N-row GEMM runs at K = C.  Training: the parameters stay ONE tensor each in the reference's layout -- the fused weight is
+        their stack, sliced by column, and torch's slicing carries the gradients of both halves back."""
+        ins, seg, ptr = split
+        C, lins = x.size(1), ([self.lin_l] if self.share_weights else [self.lin_l, self.lin_r])
+        has_bias = lins[0].bias is not None
+
+        def fused():
+            w = lins[0].weight if len(lins) == 1 else torch.stack([m.weight for m in lins]).flatten(0, 1)
+            b = None if not has_bias else (lins[0].bias if len(lins) == 1 else torch.stack([m.bias for m in lins]).flatten())
+            return w, b
+
+        srcs = [m.weight for m in lins] + ([m.bias for m in lins] if has_bias else [])
+        if torch.is_grad_enabled() and ops._rec(x, ins, *srcs):
+            w, b = fused()
+            w_x, w_u = w[:, :C], w[:, C:].contiguous()
+        else:
+            def build():
+                w, b = fused()
+                return w[:, :C].contiguous(), w[:, C:].contiguous(), None if b is None else b.detach().contiguous()
+            w_x, w_u, b = ops.derived_weight("concat_split", srcs, build)
+        y = ops.linear_rowbias(x, w_x, ops.linear(ins, w_u, b), seg, out_dtype=fdt, rowptr=ptr)
+        HC = self.heads * self.out_channels
+        return (y, y) if self.share_weights else (y[:, :HC], y[:, HC:])
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, heads={self.heads})"

@@ -141,7 +141,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "simple_bwd_kernel": 0,                    # SIMPLE sampler backwards on csrc/isg_simple_bwd.hip (autograd.SIMPLE_BWD_KERNEL)
             "topk_rows": 0,                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
             "mp_dropout": 0,                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
-            "mp_f16_train": 0}                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
+            "mp_f16_train": 0,                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
+            "linear_rowbias": 0}                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
 
 
 def reset_counters() -> None:
@@ -2906,7 +2907,7 @@ def conv_route(*, heads: int, channels: int, in_channels: int, edge_dim: Optiona
                has_csr: bool, tile_mode: str, rows_dtype=torch.float32, share_weights: bool = False,
                use_instr: bool = True, masked: bool = False, gate_on_planes: bool = False, grad: bool = False,
                e_proj_given: bool = False, has_edge_lin: bool = True, cfg: Optional[Switches] = None,
-               attn_dropout: bool = False) -> ConvRoute:
+               attn_dropout: bool = False, concat_instr: bool = False) -> ConvRoute:
     """How a MaskingGATv2Conv layer (in_channels -> heads x channels, edge features edge_dim wide) runs on a batch of B graphs, N
     nodes (at most nmax per graph) and E edges: a pure function of plain values, the ONE place that decides.
 
@@ -2933,8 +2934,22 @@ def conv_route(*, heads: int, channels: int, in_channels: int, edge_dim: Optiona
       inference, fp32 rows, the lin_l | lin_r projection reads planes32      "planes32"  its operand (+ fp32 rows for a node gate)
       anything else                                                          "rows"
     gate_rows: everything but "layer_conv" reads rows, and so does a node gate that cannot run on the planes.  e_proj: conv is
-    "unfused" (a stack of layers then projects every layer's edge rows in one launch)."""
+    "unfused" (a stack of layers then projects every layer's edge rows in one launch).
+    concat_instr: the layer reads cat(x, instruction[batch]) instead of the gated rows (in_channels is then its TRUE input
+    width, 2 x the node rows' -- at C = 64 that is 128 and still no layer_conv shape).  It never gates ("none"), projects lin_l |
+    lin_r ahead of the message passing on the row-biased Linear (ops.linear_rowbias) and so reads rows; the graph-tile kernels
+    have no such projection: conv is "unfused" by the first two rules, on half rows as above, and "pair" otherwise."""
     cfg = CFG if cfg is None else cfg
+    if concat_instr:
+        if e_proj_given or edge_dim is None or not has_edge_lin or grad or attn_dropout:
+            conv = "unfused"
+        elif not _fused_logits_ok(heads, channels, edge_dim, B, E, nmax, has_csr, cfg):
+            conv = "unfused"
+        elif rows_dtype != torch.float32:
+            conv = "pair" if rows_dtype == torch.float16 and edge_dim >= 128 else "unfused"
+        else:
+            conv = "pair"
+        return ConvRoute(conv, "none", True, conv == "unfused")
     if e_proj_given or edge_dim is None or not has_edge_lin or grad or attn_dropout:
         conv = "unfused"
     elif not _fused_logits_ok(heads, channels, edge_dim, B, E, nmax, has_csr, cfg):
@@ -3894,3 +3909,88 @@ def linear_fused(x: Tensor, layers, out_dtype=torch.float32) -> Tuple[Tensor, ..
         outs.append(y[:, o:o + n])
         o += n
     return tuple(outs)
+
+
+# ------------------------------------------------------------------------------------------------
+# concat_instr (include/isg_concat.h): cat(x, u[batch]) W^T + b = x W[:, :C]^T + (u W[:, C:]^T + b)[batch]
+# ------------------------------------------------------------------------------------------------
+def _rowbias_planes(weight: Tensor) -> Tensor:
+    """The bf16x6 planes of a weight that is a column slice W[:, :C] of a parameter (or a tensor of its own), cached on the
+    tensor the slice is a view of: a slice is a new object at every call, its base is not."""
+    base = weight._base if weight._base is not None else weight
+    tag = ("rowbias_planes", weight.storage_offset(), tuple(weight.shape), tuple(weight.stride()))
+    return derived_weight(tag, (base,), lambda: _split_weight(weight, "tile"))
+
+
+def segment_rowptr(seg: Tensor, S: int) -> Tensor:
+    """int32 [S + 1]: where each segment's rows begin in a non-decreasing seg [M] (a batch vector) -- GraphPlan.ptr of it."""
+    return torch.searchsorted(seg, torch.arange(S + 1, dtype=seg.dtype, device=seg.device)).int()
+
+
+def segment_range_sum(rowptr: Tensor, G: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """out[s] = the sum of G's rows [rowptr[s], rowptr[s + 1]) in row order -> [S, C]  (isg_segment_range_sum: one workgroup per
+    segment and block of columns, no atomics).  rowptr: int32 [S + 1], non-decreasing within [0, rows of G] -- a plan's ptr.  G,
+    out: fp32 rows with contiguous columns (column slices of wider tensors are fine)."""
+    from . import _lib_concat
+    S = rowptr.numel() - 1
+    if S < 0 or G.dim() != 2:
+        raise ValueError(f"segment_range_sum: rowptr of {rowptr.numel()} entries, G {tuple(G.shape)}")
+    M, C = G.shape
+    if out is None:
+        out = torch.empty(S, C, dtype=torch.float32, device=G.device)
+    elif tuple(out.shape) != (S, C):
+        raise ValueError(f"segment_range_sum: out {tuple(out.shape)}, expected {(S, C)}")
+    if S == 0 or C == 0:
+        return out
+    _lib.check(_lib_concat.load().isg_segment_range_sum(_chk(rowptr, "rowptr", torch.int32), _chk_rows4(G, "G"), _pitch(G),
+                                                        _chk_rows4(out, "out"), _pitch(out), S, M, C, _stream()),
+               "isg_segment_range_sum")
+    return out
+
+
+def linear_rowbias(x: Tensor, weight: Tensor, P: Tensor, seg: Tensor, gelu: bool = False, relu: bool = False,
+                   out_dtype=torch.float32, out: Optional[Tensor] = None, rowptr: Optional[Tensor] = None,
+                   cache_planes: bool = True) -> Tensor:
+    """act(x @ weight^T + P[seg]): x [M, K] fp32 rows, weight [N, K] (a column slice W[:, :K] of a parameter, or a tensor of its
+    own), P [S, N] fp32 with contiguous columns (a column slice of a wider tensor is fine), seg int32 [M] with values in [0, S) --
+    one launch of isg_linear_bf16x6_rowbias, whose epilogue adds the row P[seg[m]] where isg_linear_bf16x6 adds the bias.
+    out_dtype = torch.float16: the result rounded once to half rows.  out: [M, N] rows of out_dtype to write (a column slice of a
+    wider tensor).  Under autograd it is autograd.linear_rowbias (fp32 only; seg non-decreasing; rowptr: int32 [S + 1], where
+    each segment's rows begin -- a plan's ptr -- derived from seg when it is not given)."""
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
+    if x.dim() != 2 or weight.dim() != 2 or P.dim() != 2 or weight.size(1) != x.size(1) or P.size(1) != weight.size(0):
+        raise ValueError(f"linear_rowbias: x {tuple(x.shape)}, weight {tuple(weight.shape)}, P {tuple(P.shape)}")
+    M, K = x.shape
+    N, S = weight.size(0), P.size(0)
+    if seg.dtype != torch.int32 or seg.dim() != 1 or seg.numel() != M:
+        raise ValueError(f"linear_rowbias: seg is int32 [{M}], got {seg.dtype} {tuple(seg.shape)}")
+    if torch.is_grad_enabled() and _rec(x, weight, P):
+        if out_dtype != torch.float32 or out is not None:
+            raise _lib.IsgError("linear_rowbias: training a concat_instr layer on half rows (or into a caller's rows) is not "
+                                "supported; the row-biased Linear differentiates fp32 rows only")
+        from . import autograd
+        return autograd.linear_rowbias(x, weight, P, seg, gelu, relu, rowptr)
+    if CFG.gemm_backend != "bf16x6":
+        raise _lib.IsgError("linear_rowbias exists on the bf16x6 kernel only (gemm_backend)")
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or (M > 1 and out.stride(0) < N):
+        raise ValueError(f"linear_rowbias: out is {out_dtype} [{M}, {N}] with contiguous columns, got {out.dtype} {tuple(out.shape)}")
+    if M == 0:
+        return out
+    if S < 1:
+        raise ValueError("linear_rowbias: P has no rows")
+    from . import _lib_concat
+    lib = _lib_concat.load()
+    planes = _rowbias_planes(weight) if cache_planes else _split_weight(weight, "tile")
+    if not x.is_cuda or not out.is_cuda:
+        raise _lib.IsgError(f"x must live on the GPU (got {x.device}); this path has no CPU fallback")
+    if x.dtype != torch.float32 or (K > 1 and x.stride(1) != 1):
+        raise ValueError("linear_rowbias: x is fp32 rows with contiguous columns")
+    COUNTERS["linear_rowbias"] += 1
+    _lib.check(lib.isg_linear_bf16x6_rowbias(x.data_ptr(), planes.data_ptr(), _chk_rows4(P.detach(), "P"), _pitch(P), _chk(seg, "seg", torch.int32),
+                                             S, out.data_ptr(), 1 if out_dtype == torch.float16 else 0, M, N, K,
+                                             max(int(x.stride(0)), K) if M > 1 else K, _pitch(out), 2 if relu else (1 if gelu else 0),
+                                             _stream()), "isg_linear_bf16x6_rowbias")
+    return out

@@ -148,14 +148,16 @@ class AnswerModel(torch.nn.Module):
 
     def __init__(self, channels: int, layers: int, masks, sampler: str, sample_k: int, heads: int = 4,
                  interpretable_mode: bool = False, tau: float = 1.0, num_answers: int = 1842,
-                 attn_dropout: float = 0.0, sample_ratio: Optional[float] = None, sample_k_min: int = 1):
+                 concat_instr: bool = False, attn_dropout: float = 0.0, sample_ratio: Optional[float] = None,
+                 sample_k_min: int = 1):
         super().__init__()
         from .models.att_pooling import GlobalAttention
         from .models.mgat import MGAT
         self.gat_seq = MGAT(channels=channels, num_ins=layers, heads=heads, use_instr=True,
                             masking_thresholds=list(masks), use_topk=True, interpretable_mode=interpretable_mode,
                             sampler_type=sampler, sample_k=sample_k, nb_samples=1, alpha=1.0, beta=10.0, tau=tau,
-                            attn_dropout=attn_dropout, sample_ratio=sample_ratio, sample_k_min=sample_k_min)
+                            attn_dropout=attn_dropout, sample_ratio=sample_ratio, sample_k_min=sample_k_min,
+                            concat_instr=bool(concat_instr))
         self.graph_global_attention_pooling = GlobalAttention(channels, channels)
         self.embedding = torch.nn.Sequential(torch.nn.Linear(channels * 3, 512), torch.nn.GELU(),
                                              torch.nn.Dropout(p=0.2))
