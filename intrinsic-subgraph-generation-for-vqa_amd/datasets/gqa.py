@@ -13,13 +13,15 @@ from typing import Callable, Optional, Sequence
 import torch
 
 
-def gqa_collate(data: Sequence[tuple], scene_graphs, tokenizer: Optional[Callable] = None, pin_memory: Optional[bool] = None):
+def gqa_collate(data: Sequence[tuple], scene_graphs, tokenizer: Optional[Callable] = None, pin_memory: Optional[bool] = None,
+                distinct: bool = False):
     """data: (questionID, image_id, question_text, qst_types, short_answer_label, image_id) tuples (gqa.py:186-193 with the
-    scene graph replaced by its image id).  Returns the reference's 7-tuple (gqa.py:262-270)."""
+    scene graph replaced by its image id).  Returns the reference's 7-tuple (gqa.py:262-270).  distinct=True: the scene-graph
+    batch holds every image once and carries the questions' graph_index (SceneGraphStore.collate); the tuple is the same."""
     question_id, graph_ids, question_text, qst_types, labels, img = zip(*data)
     qsts_padded = qsts_attention_mask = None
     if tokenizer is not None:
         q = tokenizer(list(question_text), return_tensors="pt", padding=True)            # :252-256
         qsts_padded, qsts_attention_mask = q["input_ids"], q["attention_mask"]
-    scene_graph = scene_graphs.collate(list(graph_ids), pin_memory)                      # :258
+    scene_graph = scene_graphs.collate(list(graph_ids), pin_memory, distinct=distinct)   # :258
     return (question_id, scene_graph, qsts_padded, qsts_attention_mask, torch.LongTensor(labels), img, qst_types)

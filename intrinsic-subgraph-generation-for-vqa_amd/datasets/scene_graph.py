@@ -51,5 +51,5 @@ class GQASceneGraphs:
         return SimpleNamespace(x=b.x, edge_index=b.edge_index, edge_attr=b.edge_attr.view(-1, 1),
                                added_sym_edge=b.added_sym_edge, x_bbox=b.x_bbox)
 
-    def collate(self, image_ids: Sequence[str], pin_memory: Optional[bool] = None) -> loader.SceneGraphBatch:
-        return self.store.collate(image_ids, pin_memory)
+    def collate(self, image_ids: Sequence[str], pin_memory: Optional[bool] = None, distinct: bool = False) -> loader.SceneGraphBatch:
+        return self.store.collate(image_ids, pin_memory, distinct=distinct)

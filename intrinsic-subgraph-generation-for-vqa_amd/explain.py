@@ -211,6 +211,8 @@ class EvalBatch(NamedTuple):
     qtok: Optional[Tensor] = None      # TokenTables.question_words(...) on the device
     qflags: Optional[Tensor] = None
     names: Optional[Tensor] = None     # int64 [N] name ids; default inputs.x[:, 0]
+    graph_index: Optional[Tensor] = None   # int64 [Q]: `inputs` holds G DISTINCT graphs and Q question rows; question q asks about
+                                           # graph graph_index[q] (ISubGVQA.encode_scene / ask; the full model only)
 
 
 def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0) -> CooReport:
@@ -223,13 +225,21 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
         for b in batches:
             inp = b.inputs
             B = int(inp.questions.size(0) if full else inp.glf.size(0))
-            plan = ops.GraphPlan.build(inp.batch, inp.edge_index, num_graphs=B, max_nodes=inp.max_nodes or None,
-                                       max_edges=inp.max_edges or None, graph_sizes=inp.graph_sizes)
-            if full:
-                out = model(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.questions, inp.att_mask, return_masks=True,
-                            scene_graphs=inp.scene_graphs(), plan=plan)
+            names = inp.x[:, 0] if b.names is None else b.names
+            if b.graph_index is not None:           # many questions per graph: encode once, score the instances' names
+                if not full:
+                    raise ValueError("EvalBatch.graph_index: the full model only (an AnswerModel has no encoder to share)")
+                state = model.encode_scene(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.scene_graphs())
+                out, inst = model.ask(state, inp.questions, inp.att_mask, b.graph_index)
+                plan, names = inst.plan(), inst.gather_nodes(names).contiguous()
             else:
-                out = model(inp, plan=plan)
+                plan = ops.GraphPlan.build(inp.batch, inp.edge_index, num_graphs=B, max_nodes=inp.max_nodes or None,
+                                           max_edges=inp.max_edges or None, graph_sizes=inp.graph_sizes)
+                if full:
+                    out = model(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.questions, inp.att_mask, return_masks=True,
+                                scene_graphs=inp.scene_graphs(), plan=plan)
+                else:
+                    out = model(inp, plan=plan)
             logits, mask = out[0], out[1]
             mask_text = out[4] if full and len(out) > 4 else None
             if totals is None:
@@ -238,7 +248,7 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
             if mask_text is not None:
                 ttok = tables.text_tokens(inp.questions)
                 tkeep = mask_text.reshape(B, -1).float().contiguous()
-            ops.token_coo(inp.x[:, 0] if b.names is None else b.names, mask, plan, logits.argmax(dim=1), b.label,
+            ops.token_coo(names, mask, plan, logits.argmax(dim=1), b.label,
                           tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
     if totals is None:
         totals = torch.zeros(ops.COO_TOTALS, dtype=torch.int64)

@@ -102,12 +102,13 @@ class SceneGraphBatch:
     max_edges: int
     graph_sizes: Optional[Tensor] = None      # HOST int64 [2, B] nodes / in-edges per graph, when some graph lies beyond a graph tile
                                               # (ops.GraphPlan.build's hint: the list of such graphs is then made without a sync)
+    graph_index: Optional[Tensor] = None      # HOST int64 [Q]: collate(distinct=True) -- the graph of this batch every question asks
 
     def to(self, device, non_blocking: bool = True) -> "SceneGraphBatch":
         mv = lambda t: t.to(device, non_blocking=non_blocking)
         return SceneGraphBatch(mv(self.x), mv(self.edge_index), mv(self.edge_attr), mv(self.x_bbox),
                                mv(self.added_sym_edge), mv(self.batch), mv(self.ptr), self.num_graphs,
-                               self.max_nodes, self.max_edges, self.graph_sizes)
+                               self.max_nodes, self.max_edges, self.graph_sizes, self.graph_index)
 
 
 class BatchBuffers:
@@ -163,12 +164,20 @@ class SceneGraphStore:
         return out
 
     def collate(self, image_ids, pin_memory: Optional[bool] = None, out: Optional["BatchBuffers"] = None,
-                threads: int = 4) -> SceneGraphBatch:
+                threads: int = 4, distinct: bool = False) -> SceneGraphBatch:
         """query_and_translate per graph + Batch.from_data_list, written into (pinned) host tensors.
-        ``image_ids``: id strings, or an int64 tensor of slots from ``slots()``.  ``out``: reusable buffers."""
+        ``image_ids``: id strings, or an int64 tensor of slots from ``slots()``.  ``out``: reusable buffers.
+        ``distinct``: the batch holds every distinct slot ONCE, in the order of first occurrence (all unknown ids share the one
+        dummy graph); ``graph_index[q]`` is then the graph of the batch that image_ids[q] names, and ``graph_sizes`` is always
+        filled -- what ISubGVQA.encode_scene / ask take for several questions per image."""
         lib = load()
         slots = image_ids if torch.is_tensor(image_ids) else self.slots(image_ids)
         slots = slots.contiguous()
+        graph_index = None
+        if distinct:
+            first = {}
+            graph_index = torch.tensor([first.setdefault(s, len(first)) for s in slots.clamp(min=-1).tolist()], dtype=torch.int64)
+            slots = torch.tensor(list(first), dtype=torch.int64)
         B = slots.numel()
         tot = (c_int64 * 3)()
         _check(lib.isg_sg_collate_sizes(self._h, slots.data_ptr(), B, tot), "isg_sg_collate_sizes")
@@ -182,10 +191,10 @@ class SceneGraphStore:
                                   bb.data_ptr(), sym.data_ptr(), batch.data_ptr(), ptr.data_ptr(), bounds,
                                   int(threads)), "isg_sg_collate")
         sizes = None
-        if int(bounds[0]) > 64 or int(bounds[1]) > 256:      # a graph beyond the 64-node / 256-in-edge tiles of the kernels
+        if distinct or int(bounds[0]) > 64 or int(bounds[1]) > 256:      # a graph beyond the 64-node / 256-in-edge tiles of the kernels
             sizes = torch.stack([ptr[1:] - ptr[:-1], torch.bincount(batch[ei[1]], minlength=B)]) if E > 0 else \
                 torch.stack([ptr[1:] - ptr[:-1], torch.zeros(B, dtype=torch.int64)])
-        return SceneGraphBatch(x, ei, ea, bb, sym, batch, ptr, B, int(bounds[0]), int(bounds[1]), sizes)
+        return SceneGraphBatch(x, ei, ea, bb, sym, batch, ptr, B, int(bounds[0]), int(bounds[1]), sizes, graph_index)
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:

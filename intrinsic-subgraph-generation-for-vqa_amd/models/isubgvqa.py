@@ -9,6 +9,7 @@ optional ``noises``/``seed`` pair to make the stochastic samplers reproducible a
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import math
@@ -23,6 +24,17 @@ from .scene_graph_encoder import SceneGraphEncoder
 from .text_encoder import DECODER_SEED_OFFSET, CLIPTextEmbeddings, QuestionDecoder, QuestionEncoder
 
 NUM_ANSWERS = 1842   # isubgvqa.py:207
+
+
+@dataclass
+class SceneState:
+    """What ISubGVQA.encode_scene leaves for any number of ISubGVQA.ask calls: the encoder's rows of a batch of G distinct scene
+    graphs -- nothing in them depends on a question."""
+    x_enc: Tensor                       # fp32 [N, C]
+    e_enc: Tensor                       # fp32 [E, C]
+    edge_index: Tensor                  # int64 [2, E]
+    plan: "ops.GraphPlan"               # of the G graphs
+    sizes: Optional[Tensor] = None      # HOST int64 [2, G] (nodes, edges per graph) when the collate handed them over
 
 
 class ISubGVQA(torch.nn.Module):
@@ -113,6 +125,52 @@ class ISubGVQA(torch.nn.Module):
                                                           return_mask=True, node_mask=imle_mask, plan=plan, q=pool_q)
         feats = ops.cat_mul_mlp(self.embedding, embed, glf, want_rowmax=True)           # :288-291 (row maxima: for logit_fc)
         return ops.linear(feats, self.logit_fc.weight, self.logit_fc.bias), imle_mask, gate, node_logits_layers   # :292
+
+    # -- many questions per scene graph: encode once, ask often ------------------------
+    def encode_scene(self, node_embeddings, edge_index, edge_embeddings, batch, scene_graphs, plan: Optional[ops.GraphPlan] = None
+                     ) -> SceneState:
+        """The scene-graph encoder on a batch of G DISTINCT graphs (loader.SceneGraphStore.collate(distinct=True)), for ask().
+        The number of graphs comes from `plan`, else from scene_graphs.num_graphs or .graph_sizes, else from the batch vector (a
+        device-to-host sync, and trailing graphs without nodes are then not counted)."""
+        if self.training:
+            raise ValueError("encode_scene / ask are inference forms: in train() the encoder's BatchNorm layers use the statistics of "
+                             "the batch, in which a graph asked five times would weigh once -- call eval(), or train through forward()")
+        if plan is None:
+            sizes = getattr(scene_graphs, "graph_sizes", None)
+            G = getattr(scene_graphs, "num_graphs", None)
+            if G is None and sizes is not None:
+                G = sizes.size(1)
+            plan = ops.GraphPlan.build(batch, edge_index, num_graphs=G, max_nodes=getattr(scene_graphs, "max_nodes", None),
+                                       max_edges=getattr(scene_graphs, "max_edges", None), graph_sizes=sizes)
+        x_enc, e_enc = self.scene_graph_encoder(node_embeddings, edge_index=edge_index, edge_attr=edge_embeddings, batch=batch,
+                                                gt_scene_graphs=scene_graphs, plan=plan)
+        return SceneState(x_enc, e_enc, edge_index, plan, plan.sizes_host)
+
+    def ask(self, state: SceneState, questions, qsts_att_mask, graph_index, noises: Optional[Dict[int, Tensor]] = None,
+            seed: Optional[int] = None, text_uniform: Optional[Tensor] = None, capture=False, explainer=False,
+            explainer_stage=False, expl_bypass_x=False):
+        """Q questions about the graphs graph_index[q] of an encoded batch: (forward's 5-tuple, ops.GraphInstances).  The question
+        side runs as in forward (same seed offset); the graph side of answer_graphs runs on the batch of Q graph INSTANCES that
+        ops.graph_instances expands on the device -- only answer_graphs' inputs are expanded, the encoder ran on the G graphs.
+        imle_mask and gate have one row per instance node: the returned GraphInstances maps them back (.node_src, .ptr).
+        added_sym_edge flipped edges of the DISTINCT batch's global edge list (quirk Q6); every instance inherits its graph's."""
+        if self.training:
+            raise ValueError("ask() is an inference form: the shared encoding was made without batch statistics of the questions' "
+                             "batch (encode_scene) -- call eval(), or train through forward()")
+        if capture:
+            raise ValueError("ask(): capture is not supported (the instance batch's sizes are read between two launches)")
+        if explainer or explainer_stage or expl_bypass_x is not False:
+            raise ValueError("ask(): the explainer arguments are not supported (they replace the encoder's input per question, "
+                             "which a shared encoding does not have); use forward()")
+        if questions.size(0) != graph_index.numel():
+            raise ValueError(f"ask(): {questions.size(0)} questions, {graph_index.numel()} entries of graph_index")
+        glf, instr_vectors = self.language_features(questions, qsts_att_mask, text_uniform, None if seed is None else seed + 7919)
+        mask_text = self.last_mask_text
+        inst = ops.graph_instances(state.plan, state.edge_index, graph_index, sizes=state.sizes)
+        x, e = inst.gather_rows(state.x_enc, state.e_enc)
+        logits, imle_mask, gate, node_logits_layers = self.answer_graphs(x, inst.edge_index, e, inst.batch, instr_vectors, glf,
+                                                                         inst.plan(), True, noises, seed)
+        return (logits, imle_mask, gate, node_logits_layers, mask_text), inst
 
     def _captured(self, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, explainer, explainer_stage,
                   scene_graphs, noises, seed, plan, text_uniform):

@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -142,7 +142,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "topk_rows": 0,                            # sampler launches with a k per row (csrc/isg_topk_rows.hip; the budget launch is not one)
             "mp_dropout": 0,                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
             "mp_f16_train": 0,                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
-            "linear_rowbias": 0}                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
+            "linear_rowbias": 0,                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
+            "graph_instances": 0}                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
 
 
 def reset_counters() -> None:
@@ -851,6 +852,134 @@ def subgraph_cut(node_mask: Tensor, edge_index: Tensor, plan: "GraphPlan", thres
     return SubgraphCut(plan, i32[o_nn:o_nn + N], i32[o_en:o_en + E], i64[o_nid:o_nid + N], i64[o_eid:o_eid + E],
                        i64[o_ei:o_ei + 2 * E].view(2, E), i64[o_b:o_b + N], i32[o_ptr:o_ptr + B + 1],
                        i32[o_sel:o_sel + B * k].view(B, k) if k else None, i32[o_cnt:o_cnt + 2])
+
+
+# ------------------------------------------------------------------------------------------------
+# Many questions per scene graph: G distinct graphs, Q instances
+# ------------------------------------------------------------------------------------------------
+INSTANCES_SCAN_BLOCK = 1024      # instances one step of the size pass's scan takes (INST_SCAN_BLOCK in csrc/isg_instances.hip)
+INSTANCES_FLAGS = ("bad_index", "bad_grouping")      # words 2 and 3 of GraphInstances.status
+
+
+class GraphInstances:
+    """What isg_instances_size / isg_instances_fill left on the device: the batch of Q graph instances that Q questions would have
+    brought along as copies of the parent batch's graphs index[q] (include/isg_instances.h).
+
+    ptr / eptr int32 [Q + 1]: node / edge range of every instance; batch int64 [N'] (value q on instance q's nodes); edge_index
+    int64 [2, E'] between the instance batch's node numbers; node_src int64 [N'] / edge_src int64 [E']: the row of the parent
+    batch every instance row is a copy of; status int32 [4] = (N', E', bad_index, bad_grouping) on the device; index int32 [Q] on
+    the device.  sizes_host: host int64 [2, Q] (nodes, edges per instance) when the caller knew the parent's on the host."""
+
+    def __init__(self, parent: "GraphPlan", index, ptr, eptr, batch, edge_index, node_src, edge_src, status, sizes_host=None,
+                 parent_edges=None):
+        self.parent, self.index, self.ptr, self.eptr, self.status, self.sizes_host = parent, index, ptr, eptr, status, sizes_host
+        self.batch, self.edge_index, self.node_src, self.edge_src = batch, edge_index, node_src, edge_src
+        self.parent_edges = parent.E if parent_edges is None else int(parent_edges)      # (a plan may have been built without edges)
+        self._plan = None
+
+    @property
+    def Q(self) -> int:
+        return self.ptr.numel() - 1
+
+    def gather_nodes(self, t: Tensor) -> Tensor:
+        """t[node_src] for a tensor with one row per node of the parent batch (any dtype)."""
+        return t.index_select(0, self.node_src)
+
+    def gather_edges(self, t: Tensor) -> Tensor:
+        """t[edge_src] for a tensor with one row per edge of the parent batch (any dtype)."""
+        return t.index_select(0, self.edge_src)
+
+    def gather_rows(self, x: Tensor, e: Tensor) -> Tuple[Tensor, Tensor]:
+        """(x[node_src], e[edge_src]) for fp32 rows in ONE launch (isg_instance_rows): x [N, Cx], e [E, Ce], widths and row strides
+        multiples of 4, rows 16-byte aligned."""
+        lib = _lib_instances.load()
+        px, pe = _chk_rows(x, "x"), _chk_rows(e, "e")
+        if x.size(0) != self.parent.N or e.size(0) != self.parent_edges:
+            raise ValueError(f"gather_rows: expected {self.parent.N} node rows and {self.parent_edges} edge rows, got {x.size(0)} and {e.size(0)}")
+        if (x.size(1) & 3) or (e.size(1) & 3):
+            raise ValueError(f"gather_rows: row widths must be multiples of 4, got {x.size(1)} and {e.size(1)}")
+        n, m = self.node_src.numel(), self.edge_src.numel()
+        xo = torch.empty(n, x.size(1), dtype=torch.float32, device=x.device)
+        eo = torch.empty(m, e.size(1), dtype=torch.float32, device=e.device)
+        # (pointers of EMPTY tensors are null: the entry point does not look at a half without rows)
+        _lib.check(lib.isg_instance_rows(px, x.stride(0), x.size(0), self.node_src.data_ptr(), n, xo.data_ptr(), x.size(1), x.size(1),
+                                         pe, e.stride(0), e.size(0), self.edge_src.data_ptr(), m, eo.data_ptr(), e.size(1), e.size(1),
+                                         _stream()), "isg_instance_rows")
+        return xo, eo
+
+    def plan(self) -> "GraphPlan":
+        """The GraphPlan of the instance batch (num_graphs = Q).  An instance is a copy of a graph of the parent, so the parent's
+        bounds serve as hints; with host sizes the list of graphs beyond a tile is made without a device-to-host sync too."""
+        if self._plan is None:
+            self._plan = GraphPlan.build(self.batch, self.edge_index, num_graphs=self.Q, max_nodes=self.parent.nmax,
+                                         max_edges=self.parent.emax, graph_sizes=self.sizes_host)
+        return self._plan
+
+    def verify(self) -> None:
+        """Read `status` (one device-to-host copy) and raise IsgError naming the flag that is set, or the sizes where the host's
+        disagree with the device's.  The model paths never call it."""
+        n, e, *flags = (int(v) for v in self.status.tolist())
+        bad = [name for name, f in zip(INSTANCES_FLAGS, flags) if f]
+        if bad:
+            why = {"bad_index": "an index lies outside [0, G); that instance is empty",
+                   "bad_grouping": "the edges of a graph are not contiguous and in graph order, or an edge leaves its graph"}
+            raise _lib.IsgError("graph_instances: " + "; ".join(f"{b} ({why[b]})" for b in bad))
+        if (n, e) != (self.node_src.numel(), self.edge_src.numel()):
+            raise _lib.IsgError(f"graph_instances: the sizes given on the host make {self.node_src.numel()} nodes / "
+                                f"{self.edge_src.numel()} edges, the device counted {n} / {e}")
+
+
+def graph_instances(plan: "GraphPlan", edge_index: Tensor, index: Tensor, sizes: Optional[Tensor] = None) -> GraphInstances:
+    """The batch of Q instances of the graphs index[q] of `plan`'s batch, expanded on the device (isg_instances_size: a 16-byte
+    clear and two launches; isg_instances_fill: one).  plan: the distinct batch's GraphPlan, built from its batch vector;
+    edge_index int64 [2, E], the edges of one graph contiguous and the graphs in order; index: int32 or int64 [Q], on the host or
+    on the device.  sizes: HOST int64 [2, G] (nodes, edges per graph, what a collate knows): with it and a host index N' and E' are
+    computed on the host; otherwise they come from one 8-byte device-to-host copy between the two passes."""
+    lib = _lib_instances.load()
+    p_ei = _chk(edge_index, "edge_index", torch.int64)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"edge_index must be [2,E], got {tuple(edge_index.shape)}")
+    if plan.batch is None:
+        raise ValueError("graph_instances needs a GraphPlan built from the batch vector")
+    N, E, G = plan.N, edge_index.size(1), plan.B
+    p_batch = _chk(plan.batch, "plan.batch", torch.int64, (N,))
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (G + 1,))
+    if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index: expected int32 or int64 [Q], got {index.dtype} {tuple(index.shape)}")
+    dev = edge_index.device
+    Q = index.numel()
+    sizes_host = totals = None
+    if sizes is not None:
+        if sizes.device.type != "cpu" or tuple(sizes.shape) != (2, G):
+            raise ValueError(f"sizes: a HOST tensor [2, {G}] (nodes, edges per graph), got {sizes.device} {tuple(sizes.shape)}")
+        if index.device.type == "cpu":
+            if Q and (int(index.min()) < 0 or int(index.max()) >= G):
+                raise ValueError(f"index: values outside [0, {G})")
+            sizes_host = sizes.long().index_select(1, index.long())
+            totals = (int(sizes_host[0].sum()), int(sizes_host[1].sum()))
+    idx = index.to(device=dev, dtype=torch.int32).contiguous()
+    COUNTERS["graph_instances"] += 1
+    ws_bytes = lib.isg_instances_workspace_bytes(G)
+    n32 = 2 * (Q + 1) + 4
+    i32 = torch.empty(n32 + (ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    ptr, eptr, status = i32[:Q + 1], i32[Q + 1:2 * Q + 2], i32[2 * Q + 2:n32]
+    if Q == 0:
+        i32[:n32].zero_()
+        totals = (0, 0)
+    b32 = i32.data_ptr()
+    _lib.check(lib.isg_instances_size(p_ptr, p_batch, p_ei, idx.data_ptr(), N, E, G, Q, b32, b32 + 4 * (Q + 1), b32 + 8 * (Q + 1),
+                                      b32 + 4 * n32, ws_bytes, _stream()), "isg_instances_size")
+    if totals is None:
+        n, e = status[:2].tolist()                  # the operator's only device-to-host copy
+        totals = (int(n), int(e))
+    Np, Ep = totals
+    i64 = torch.empty(max(2 * Np + 3 * Ep, 1), dtype=torch.int64, device=dev)
+    b64 = i64.data_ptr()
+    _lib.check(lib.isg_instances_fill(p_ptr, p_ei, idx.data_ptr(), N, E, G, Q, b32, b32 + 4 * (Q + 1), b32 + 4 * n32, ws_bytes, Np, Ep,
+                                      b64, b64 + 8 * (2 * Np), b64 + 8 * Np, b64 + 8 * (2 * Np + 2 * Ep), _stream()),
+               "isg_instances_fill")
+    return GraphInstances(plan, idx, ptr, eptr, i64[:Np], i64[2 * Np:2 * Np + 2 * Ep].view(2, Ep), i64[Np:2 * Np],
+                          i64[2 * Np + 2 * Ep:2 * Np + 3 * Ep], status, sizes_host, E)
 
 
 # ------------------------------------------------------------------------------------------------

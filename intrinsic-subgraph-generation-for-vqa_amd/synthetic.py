@@ -267,17 +267,41 @@ class FullWorkload:
     max_nodes: int
     max_edges: int
     graph_sizes: Optional[Tensor] = None      # HOST int64 [2, B] (nodes, in-edges per graph), as loader.collate hands them over
+    graph_index: Optional[Tensor] = None      # HOST int64 [Q] (make_shared_workload): the graph every question row asks; the
+                                              # graph tensors then hold G distinct graphs, for ISubGVQA.encode_scene / ask
 
     def to(self, device) -> "FullWorkload":
         mv = lambda t: t.to(device)
         return FullWorkload(mv(self.x), mv(self.edge_index), mv(self.edge_attr), mv(self.batch), mv(self.x_bbox),
                             mv(self.added_sym_edge), mv(self.questions), mv(self.att_mask), self.max_nodes, self.max_edges,
-                            self.graph_sizes)
+                            self.graph_sizes, self.graph_index)
 
     def scene_graphs(self):
         import argparse
         return argparse.Namespace(x_bbox=self.x_bbox, added_sym_edge=self.added_sym_edge, max_nodes=self.max_nodes,
                                   max_edges=self.max_edges, graph_sizes=self.graph_sizes)
+
+    def replicated(self) -> "FullWorkload":
+        """A shared workload (graph_index set) with every question's graph copied out: the batch forward() takes for the same
+        questions.  Host tensors, plain torch indexing.  added_sym_edge holds positions in the global edge list (quirk Q6) and
+        cannot follow the copies: it has to be empty."""
+        if self.graph_index is None or self.graph_sizes is None or self.x.is_cuda:
+            raise ValueError("replicated(): a shared workload on the host (graph_index and graph_sizes set)")
+        if self.added_sym_edge.numel():
+            raise ValueError("replicated(): added_sym_edge positions are not offset per graph (quirk Q6) and cannot be replicated")
+        idx = self.graph_index
+        n, e = self.graph_sizes[0], self.graph_sizes[1]
+        nptr, eptr = torch.cat([n.new_zeros(1), n.cumsum(0)]), torch.cat([e.new_zeros(1), e.cumsum(0)])
+        nq, eq = n[idx], e[idx]
+        iptr = torch.cat([nq.new_zeros(1), nq.cumsum(0)])
+        batch = torch.repeat_interleave(torch.arange(idx.numel()), nq)
+        node_src = torch.arange(int(nq.sum())) - iptr[:-1][batch] + nptr[idx][batch]
+        ebatch = torch.repeat_interleave(torch.arange(idx.numel()), eq)
+        eoff = torch.cat([eq.new_zeros(1), eq.cumsum(0)])
+        edge_src = torch.arange(int(eq.sum())) - eoff[:-1][ebatch] + eptr[idx][ebatch]
+        ei = self.edge_index[:, edge_src] + (iptr[:-1] - nptr[idx])[ebatch]
+        return FullWorkload(self.x[node_src], ei, self.edge_attr[edge_src], batch, self.x_bbox[node_src], self.added_sym_edge,
+                            self.questions, self.att_mask, self.max_nodes, self.max_edges, torch.stack([nq, eq]), None)
 
 
 def make_full_workload(num_graphs: int, tokens: int = 12, seed: int = 7, sg_vocab: int = 2578,
@@ -297,3 +321,20 @@ def make_full_workload(num_graphs: int, tokens: int = 12, seed: int = 7, sg_voca
     epg = torch.bincount(batch[ei[1]], minlength=num_graphs)
     return FullWorkload(x, ei, edge_attr, batch, x_bbox, sym, q, qmask, nmax, int(epg.max()),
                         torch.stack([torch.bincount(batch, minlength=num_graphs), epg]))
+
+
+def make_shared_workload(num_graphs: int, questions_per_graph: int, tokens: int = 12, seed: int = 7, sg_vocab: int = 2578,
+                         text_vocab: int = 49408, sizes=None, shuffle: bool = True) -> FullWorkload:
+    """G distinct graphs, Q = G x questions_per_graph question rows and the host index that names every question's graph
+    (FullWorkload.graph_index): what an evaluation loop grouped by image hands to ISubGVQA.encode_scene / ask.  The graph side is
+    make_full_workload(num_graphs)'s; shuffle: the questions come in a seeded random order, not grouped by graph."""
+    wl = make_full_workload(num_graphs, tokens, seed, sg_vocab, text_vocab, sizes)
+    gen = torch.Generator().manual_seed(seed + 2)
+    Q = num_graphs * int(questions_per_graph)
+    index = torch.arange(num_graphs).repeat_interleave(int(questions_per_graph))
+    if shuffle:
+        index = index[torch.randperm(Q, generator=gen)]
+    q = torch.randint(0, text_vocab, (Q, tokens), generator=gen)
+    lens = torch.randint(max(1, tokens // 2), tokens + 1, (Q,), generator=gen)
+    wl.questions, wl.att_mask, wl.graph_index = q, (torch.arange(tokens)[None] < lens[:, None]).long(), index
+    return wl
