@@ -25,3 +25,61 @@ def gqa_collate(data: Sequence[tuple], scene_graphs, tokenizer: Optional[Callabl
         qsts_padded, qsts_attention_mask = q["input_ids"], q["attention_mask"]
     scene_graph = scene_graphs.collate(list(graph_ids), pin_memory, distinct=distinct)   # :258
     return (question_id, scene_graph, qsts_padded, qsts_attention_mask, torch.LongTensor(labels), img, qst_types)
+
+
+class QuestionTypes:
+    """The id space of the questions' types for an evaluation by type (include/isg_eval.h): every name of every facet gets ONE id
+    in [0, num_groups), facet after facet, so two facets never share an id and one device table holds them all.
+
+    The reference's dataset hands every question's `types` dict ({"structural": ..., "semantic": ..., "detailed": ...},
+    gqa.py:186-193) through its collate as the last entry of the 7-tuple; encode() takes that entry as it is.
+    names: {facet: [name, ...]} fixes the ids; with names=None the id space is empty until fit() has seen the dicts."""
+
+    def __init__(self, facets: Sequence[str] = ("structural", "semantic"), names: Optional[dict] = None):
+        self.facets = tuple(facets)
+        if not 1 <= len(self.facets) <= 4:
+            raise ValueError(f"QuestionTypes: 1 to 4 facets (the device table's F), got {len(self.facets)}")
+        self._names = {f: [] for f in self.facets}
+        self._ids: dict = {}
+        if names is not None:
+            for f in self.facets:
+                for n in names[f]:
+                    self._add(f, n)
+            self._renumber()
+
+    def _add(self, facet: str, name) -> None:
+        if name not in self._names[facet]:
+            self._names[facet].append(name)
+
+    def _renumber(self) -> None:
+        self._ids, nxt = {}, 0
+        for f in self.facets:
+            for n in self._names[f]:
+                self._ids[(f, n)] = nxt
+                nxt += 1
+        if nxt > 256:
+            raise ValueError(f"QuestionTypes: {nxt} groups; the device table holds 256 (drop a facet such as `detailed`)")
+
+    def fit(self, qst_types: Sequence[dict]) -> "QuestionTypes":
+        """Add the names of these dicts, each facet in order of first occurrence, behind the names already known."""
+        for t in qst_types:
+            for f in self.facets:
+                if isinstance(t, dict) and t.get(f) is not None:
+                    self._add(f, t[f])
+        self._renumber()
+        return self
+
+    @property
+    def num_groups(self) -> int:
+        return len(self._ids)
+
+    @property
+    def group_names(self) -> list:
+        """[(facet, name)] by id."""
+        return list(self._ids)
+
+    def encode(self, qst_types: Sequence[dict]) -> torch.Tensor:
+        """Host int32 [B, F] of group ids, -1 for an unknown name or a missing key; pinned when CUDA is there."""
+        rows = [[self._ids.get((f, t.get(f) if isinstance(t, dict) else None), -1) for f in self.facets] for t in qst_types]
+        out = torch.tensor(rows, dtype=torch.int32).view(len(rows), len(self.facets))
+        return out.pin_memory() if torch.cuda.is_available() else out

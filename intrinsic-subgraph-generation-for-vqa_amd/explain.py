@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import argparse
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 from typing import Dict, Iterable, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -180,6 +180,7 @@ class CooReport:
     ans_tok_coo: float         # the answer's name is among the picked nodes; over correct, non-"color" questions whose answer names a node
     qst_tok_coo: float         # mean over correct questions of (question words naming a picked node / naming a node)
     text_tok_coo: float        # the same over the kept tokens of the text explanation
+    by_type: Optional[Dict[str, Dict[str, "CooReport"]]] = field(default=None, compare=False)   # evaluate(types=...): {facet: {name: report}}
 
     @staticmethod
     def _ratio_sum(totals: Sequence[int], which: int) -> float:
@@ -189,8 +190,8 @@ class CooReport:
         return math.fsum(h / m for m, h in enumerate(hits) if m > 0 and h)
 
     @classmethod
-    def from_totals(cls, totals: Tensor) -> "CooReport":
-        t = tuple(int(v) for v in totals.tolist())          # an evaluation's one device-to-host copy
+    def from_totals(cls, totals) -> "CooReport":
+        t = tuple(int(v) for v in (totals.tolist() if torch.is_tensor(totals) else totals))   # an evaluation's one device-to-host copy
         if len(t) != ops.COO_TOTALS:
             raise ValueError(f"totals: expected {ops.COO_TOTALS} entries, got {len(t)}")
         return cls(t, _mean(t[1], t[0]), _mean(t[3], t[2]), _mean(t[5], t[4]), _mean(cls._ratio_sum(t, 0), t[6]),
@@ -215,12 +216,39 @@ class EvalBatch(NamedTuple):
                                            # graph graph_index[q] (ISubGVQA.encode_scene / ask; the full model only)
 
 
-def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0) -> CooReport:
+_EvalBatchFields = EvalBatch
+
+
+class EvalBatch(_EvalBatchFields):         # noqa: F811 -- the tuple above, with one keyword beside its fields
+    """The batch of evaluate().  `groups` (int32 [B, F]: QuestionTypes.encode(...) of the questions, for evaluate(types=...)) is a
+    keyword and an attribute, not a seventh tuple field: the tuple's fields, their order and `_fields` stay what callers unpack."""
+    groups: Optional[Tensor] = None
+
+    def __new__(cls, *args, groups: Optional[Tensor] = None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.groups = groups
+        return self
+
+    def _replace(self, **kw):
+        groups = kw.pop("groups", self.groups)
+        out = super()._replace(**kw)
+        out.groups = groups
+        return out
+
+
+def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0, types=None) -> CooReport:
     """run_token_coo.py's experiment over whole batches: forward, argmax, ops.token_coo into ONE running totals tensor; nothing is
     copied to the host before the last batch has been queued.  With --text_sampling the forward's token mask is scored against
-    tables.clip_sg."""
+    tables.clip_sg.
+    types (a datasets.gqa.QuestionTypes; every batch then carries `groups`): the report also has by_type, {facet: {name: CooReport}}
+    of the questions of every group (ops.token_coo_groups, one launch more per batch).  The overall totals and the [G, COO_TOTALS]
+    table are ONE tensor: the evaluation stays one device-to-host copy."""
     full = not isinstance(model, synthetic.AnswerModel)
     totals = None
+    G = 0 if types is None else int(types.num_groups)
+    if types is not None and not 1 <= G <= ops.EVAL_GROUPS_MAX:
+        raise ValueError(f"evaluate: {G} groups (1 to {ops.EVAL_GROUPS_MAX})")
+    both = None
     with torch.no_grad():
         for b in batches:
             inp = b.inputs
@@ -243,13 +271,25 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
             logits, mask = out[0], out[1]
             mask_text = out[4] if full and len(out) > 4 else None
             if totals is None:
-                totals = torch.zeros(ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
+                both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
+                totals = both[0]
             ttok = tkeep = None
             if mask_text is not None:
                 ttok = tables.text_tokens(inp.questions)
                 tkeep = mask_text.reshape(B, -1).float().contiguous()
-            ops.token_coo(names, mask, plan, logits.argmax(dim=1), b.label,
-                          tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
-    if totals is None:
-        totals = torch.zeros(ops.COO_TOTALS, dtype=torch.int64)
-    return CooReport.from_totals(totals)
+            coo = ops.token_coo(names, mask, plan, logits.argmax(dim=1), b.label,
+                                tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
+            if types is not None:
+                groups = getattr(b, "groups", None)
+                if groups is None:
+                    raise ValueError("evaluate(types=...): every EvalBatch carries groups (QuestionTypes.encode)")
+                ops.token_coo_groups(coo.table, b.qflags, groups.to(logits.device, non_blocking=True), both[1:])
+    if both is None:
+        both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64)
+    if types is None:
+        return CooReport.from_totals(both[0])
+    rows = both.tolist()                                     # overall and every group: the evaluation's one device-to-host copy
+    by_type = {f: {} for f in types.facets}
+    for g, (facet, name) in enumerate(types.group_names):
+        by_type[facet][name] = CooReport.from_totals(rows[1 + g])
+    return replace(CooReport.from_totals(rows[0]), by_type=by_type)

@@ -143,7 +143,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "mp_dropout": 0,                           # message-passing forwards with attention dropout, p > 0 (include/isg_mp_train.h)
             "mp_f16_train": 0,                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
             "linear_rowbias": 0,                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
-            "graph_instances": 0}                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
+            "graph_instances": 0,                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
+            "eval_groups": 0}                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
 
 
 def reset_counters() -> None:
@@ -3824,6 +3825,102 @@ def cross_entropy_backward(logits: Tensor, labels: Tensor, lse: Tensor, stats: T
                                               0 if grad is None else grad.data_ptr(), d.data_ptr(), A, B, A, _stream()),
                "isg_xent_bwd")
     return d
+
+
+# ------------------------------------------------------------------------------------------------
+# Evaluation by question type (include/isg_eval.h): the answer's rank, grouped meters, grouped co-occurrence totals
+# ------------------------------------------------------------------------------------------------
+EVAL_TOPK_MAX, EVAL_FACETS_MAX, EVAL_GROUPS_MAX, GROUP_SLOTS = 8, 4, 256, 8      # ISG_EVAL_*_MAX, ISG_GRP_SLOTS
+
+
+class AnswerRank(NamedTuple):
+    """What ops.answer_rank returns, all on the device."""
+    rank: Tensor                 # [B] int32: classes that beat the label; -1 ignored row; A for a bad label or a NaN row
+    top_ids: Optional[Tensor]    # [B, k] int64: the k best classes, value descending, index ascending among equals; -1 beyond A
+    top_prob: Optional[Tensor]   # [B, k] fp32: their softmax probabilities (needs `lse`), 0 where the id is -1
+
+
+def answer_rank(logits: Tensor, labels: Tensor, k: int = 5, ignore_index: int = -100, lse: Optional[Tensor] = None,
+                want_top: bool = False) -> AnswerRank:
+    """The rank of every row's label among its logits (isg_answer_rank: one launch, a wave per row, no sync): the reference's
+    accuracy(output, target, topk) counts a row as a hit at k exactly where 0 <= rank < k.  With want_top the k best classes come
+    along (1 <= k <= 8), and their probabilities when `lse` (ops.cross_entropy(...).lse) is given."""
+    from . import _lib_eval
+    B, A, ld = _xent_operands(logits, labels)
+    k = int(k)
+    if want_top and not 1 <= k <= EVAL_TOPK_MAX:
+        raise ValueError(f"answer_rank: the {k} best classes were asked for; the kernel lists 1 to {EVAL_TOPK_MAX}")
+    dev = logits.device
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    top_ids = torch.empty(B, k, dtype=torch.int64, device=dev) if want_top else None
+    top_prob = torch.empty(B, k, dtype=torch.float32, device=dev) if want_top and lse is not None else None
+    _lib.check(_lib_eval.load().isg_answer_rank(logits.data_ptr(), ld, labels.data_ptr(), int(ignore_index),
+                                                _chk(lse, "lse", torch.float64, (B,), optional=True), rank.data_ptr(),
+                                                0 if top_ids is None else top_ids.data_ptr(),
+                                                0 if top_prob is None else top_prob.data_ptr(), k if want_top else 0, B, A, _stream()),
+               "isg_answer_rank")
+    return AnswerRank(rank, top_ids, top_prob)
+
+
+def _groups_operand(groups: Tensor, B: int, what: str) -> int:
+    if groups.dim() != 2 or groups.size(0) != B or not 1 <= groups.size(1) <= EVAL_FACETS_MAX:
+        raise ValueError(f"{what}: groups are int32 [{B}, F] with 1 <= F <= {EVAL_FACETS_MAX}, got {tuple(groups.shape)}")
+    return groups.size(1)
+
+
+def _group_totals(totals: Tensor, slots: int, dtype, what: str) -> int:
+    if totals.dim() != 2 or totals.size(1) != slots or not 1 <= totals.size(0) <= EVAL_GROUPS_MAX:
+        raise ValueError(f"{what}: totals are {dtype} [G, {slots}] with 1 <= G <= {EVAL_GROUPS_MAX}, got {tuple(totals.shape)}")
+    return totals.size(0)
+
+
+def group_meters_parts(B: int, G: int) -> int:
+    """Doubles of the workspace isg_group_meters needs for B rows and G groups (a host-only call)."""
+    from . import _lib_eval
+    return int(_lib_eval.load().isg_group_meters_parts(int(B), int(G)))
+
+
+def group_meters(row_loss: Tensor, rank: Tensor, groups: Tensor, totals: Tensor, k: int = 5, status: Optional[Tensor] = None,
+                 overall: Optional[Tensor] = None) -> Tensor:
+    """Running meters per group of questions (isg_group_meters: two launches, no sync): `totals` (float64 [G, 8], slots ISG_GRP_*
+    of include/isg_eval.h: rows, loss sum, nonfinite losses, hits at 1, hits at k) has this batch ADDED to it.  row_loss fp32 [B]
+    and rank int32 [B] are ops.cross_entropy's and ops.answer_rank's; groups int32 [B, F] holds ids in [0, G), -1 for none.
+    `status` (int32 [2], zeroed once per evaluation): bad ids seen and the first row that held one.  `overall` (float64 [8]): the
+    same slots over all rows, each counted once whatever its groups.  Returns totals."""
+    from . import _lib_eval
+    B = row_loss.numel()
+    G = _group_totals(totals, GROUP_SLOTS, torch.float64, "group_meters")
+    F = _groups_operand(groups, B, "group_meters")
+    if int(k) < 1:
+        raise ValueError(f"group_meters: k = {k}")
+    n = group_meters_parts(B, G)
+    parts = torch.empty(n, dtype=torch.float64, device=totals.device)
+    _lib.check(_lib_eval.load().isg_group_meters(_chk(row_loss, "row_loss", torch.float32, (B,)),
+                                                 _chk(rank, "rank", torch.int32, (B,)),
+                                                 _chk(groups, "groups", torch.int32), F, G, int(k),
+                                                 _chk(totals, "totals", torch.float64),
+                                                 _chk(overall, "overall", torch.float64, (GROUP_SLOTS,), optional=True),
+                                                 parts.data_ptr(), n, _chk(status, "status", torch.int32, (2,), optional=True), B,
+                                                 _stream()), "isg_group_meters")
+    COUNTERS["eval_groups"] += 1
+    return totals
+
+
+def token_coo_groups(table: Tensor, qflags: Optional[Tensor], groups: Tensor, totals: Tensor, status: Optional[Tensor] = None) -> Tensor:
+    """Token co-occurrence totals per group of questions (isg_token_coo_groups: one launch, no sync): row g of `totals` (int64
+    [G, COO_TOTALS]) has added to it exactly what ops.token_coo adds to its totals for the questions of group g alone.  `table`
+    is ops.token_coo(...).table; groups and status as ops.group_meters takes them.  Returns totals."""
+    from . import _lib_eval
+    B = table.size(0)
+    G = _group_totals(totals, COO_TOTALS, torch.int64, "token_coo_groups")
+    F = _groups_operand(groups, B, "token_coo_groups")
+    _lib.check(_lib_eval.load().isg_token_coo_groups(_chk(table, "table", torch.int32, (B, 8)),
+                                                     _chk(qflags, "qflags", torch.int32, (B,), optional=True),
+                                                     _chk(groups, "groups", torch.int32), F, G, _chk(totals, "totals", torch.int64),
+                                                     _chk(status, "status", torch.int32, (2,), optional=True), B, _stream()),
+               "isg_token_coo_groups")
+    COUNTERS["eval_groups"] += 1
+    return totals
 
 
 def cat_mul(a: Tensor, b: Tensor) -> Tensor:

@@ -53,6 +53,59 @@ class Meters:
         return self.summarize(totals.cpu().tolist())
 
 
+class TypedMeters(Meters):
+    """Meters with a device float64 [G, 8] table beside the [8] one: a row per group of `types` (a datasets.gqa.QuestionTypes), slots
+    ISG_GRP_* of include/isg_eval.h, advanced by ops.group_meters in validate(); `overall` holds the same slots over all rows (its
+    hits at k give the overall acc@k).  The three blocks are ONE allocation, so report() stays a single device-to-host copy (and a
+    single all-reduce).  `status` (int32 [2]) counts group ids outside the id space; it is not part of the report."""
+
+    def __init__(self, device, types, k: int = 5):
+        self.types, self.k = types, int(k)
+        G = int(types.num_groups)
+        if not 1 <= G <= ops.EVAL_GROUPS_MAX or self.k < 1:
+            raise ValueError(f"TypedMeters: {G} groups (1 to {ops.EVAL_GROUPS_MAX}), k = {k} (>= 1)")
+        self._all = torch.zeros(16 + G * ops.GROUP_SLOTS, dtype=torch.float64, device=device)
+        self.totals = self._all[:8]
+        self.overall = self._all[8:16]
+        self.groups = self._all[16:].view(G, ops.GROUP_SLOTS)
+        self.status = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def reset(self) -> None:
+        self._all.zero_()
+        self.status.zero_()
+
+    def summarize(self, totals: Sequence[float]) -> dict:
+        """Meters.summarize of the first 8 entries, then `acc@k` = 100 * hits at k / rows of the pass (the reference's
+        accuracy(topk=(1, k)) through its AverageMeter) from the next 8, and `by_type`: {facet: {name: {loss, acc1, acc@k, rows}}}
+        from the [G, 8] rows behind them.  A group without rows reports 0, as an AverageMeter that was never updated;
+        its loss is the mean of the finite row losses (the overall `loss` is the reference's mean of batch means)."""
+        t = [float(v) for v in totals]
+        out = Meters.summarize(t[:8])
+        key = f"acc@{self.k}"
+        by_type, base = {f: {} for f in self.types.facets}, 16
+        for g, (facet, name) in enumerate(self.types.group_names):
+            rows, loss, bad, hit1, hitk = t[base + g * ops.GROUP_SLOTS:base + g * ops.GROUP_SLOTS + 5]
+            by_type[facet][name] = {"loss": loss / (rows - bad) if rows - bad > 0 else 0.0,
+                                    "acc1": 100.0 * hit1 / rows if rows > 0 else 0.0,
+                                    key: 100.0 * hitk / rows if rows > 0 else 0.0, "rows": int(rows)}
+        out[key] = 100.0 * t[8 + 4] / t[3] if t[3] > 0 else 0.0
+        out["by_type"] = by_type
+        return out
+
+    def report(self, group=None) -> dict:
+        """As Meters.report; with a process group the overall block and the [G, 8] table are summed over the ranks in the same
+        single all-reduce as slots 0-3 and 5."""
+        both = self._all
+        if group is not None:
+            import torch.distributed as dist
+            idx = torch.cat([torch.tensor([0, 1, 2, 3, 5], device=both.device), torch.arange(8, both.numel(), device=both.device)])
+            summed = both[idx]
+            dist.all_reduce(summed, group=group)
+            both = both.clone()
+            both[idx] = summed
+        return self.summarize(both.cpu().tolist())
+
+
 def _logits(model, inputs, seed: Optional[int]) -> Tensor:
     kw = {} if seed is None else {"seed": seed}
     if isinstance(inputs, dict):
@@ -108,14 +161,28 @@ def validate(model, batches: Iterable, meters: Meters, seed: Optional[int] = Non
     """The reference's validate_epoch: eval mode, no_grad, forward and loss of every (inputs, labels) of `batches` into the meters.
     The model's mode is restored.  Nothing here waits for the device -- unless a process group is given: then every rank ran its
     own share of the batches, and meters.report(group), the meters summed over the ranks as AverageMeter.synchronize_between_processes
-    sums them, is returned."""
+    sums them, is returned.
+
+    A batch may be (inputs, labels, groups): groups is the int32 [B, F] of QuestionTypes.encode, on the host (pinned: the copy is
+    asynchronous) or already on the device.  With a TypedMeters the pass adds ops.answer_rank and ops.group_meters behind the loss:
+    three launches more per batch, still no wait.  With plain Meters the groups are not looked at."""
+    typed = isinstance(meters, TypedMeters)
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
-            for inputs, labels in batches:
+            for batch in batches:
+                inputs, labels = batch[0], batch[1]
                 model.n_valid_steps = getattr(model, "n_valid_steps", 0) + labels.size(0)
-                ops.cross_entropy(_logits(model, inputs, seed), labels, totals=meters.totals)
+                logits = _logits(model, inputs, seed)
+                res = ops.cross_entropy(logits, labels, totals=meters.totals)
+                if typed:
+                    if len(batch) < 3 or batch[2] is None:
+                        raise ValueError("validate: TypedMeters needs (inputs, labels, groups) batches (QuestionTypes.encode)")
+                    groups = batch[2].to(logits.device, non_blocking=True)
+                    rank = ops.answer_rank(logits, labels, k=meters.k).rank
+                    ops.group_meters(res.row_loss, rank, groups, meters.groups, k=meters.k, status=meters.status,
+                                     overall=meters.overall)
     finally:
         model.train(was_training)
     return None if group is None else meters.report(group)
