@@ -8,6 +8,7 @@
 // absent from the file.  Attributes: first-occurrence order of the distinct strings (the reference iterates a Python
 // set, whose order is hash-seed dependent).
 #include "../../include/isg_loader.h"
+#include "../../include/isg_loader_objects.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -193,6 +194,7 @@ struct Obj {
 
 struct Graph {   // converted tensors of one image, offsets into the store's pools
   int64_t node0 = 0, n = 0, edge0 = 0, e = 0, sym0 = 0, s = 0;
+  int64_t id0 = -1;   // where its n + 1 offsets into the id pool start (isg_loader_objects.h); -1: a dummy, which keeps no ids
 };
 
 }  // namespace
@@ -205,9 +207,11 @@ struct isg_sg_store {
   std::vector<Graph> graphs;
   std::unordered_map<std::string, int64_t> slot;
   Graph missing;                          // query_and_translate's 6-node dummy
+  std::string ids;                        // the object id strings of every converted image, in node order, back to back
+  std::vector<int64_t> id_off;            // per image n + 1 offsets into `ids` (Graph::id0): id of node i = [off[i], off[i + 1])
 
   // convert_one_gqa_scene_graph (scene_graph.py:231-389) on already tokenised objects
-  int convert(std::vector<Obj> &objs, Graph &g) {
+  int convert(std::vector<Obj> &objs, Graph &g, bool keep_ids = false) {
     std::sort(objs.begin(), objs.end(), [](const Obj &a, const Obj &b) { return a.id < b.id; });   // :234
     const int n = (int)objs.size();
     auto node_of = [&](const std::string &id) -> int {
@@ -246,6 +250,15 @@ struct isg_sg_store {
     g.n = n;
     g.e = (int64_t)ea.size() - g.edge0;
     g.s = (int64_t)sym.size() - g.sym0;
+    g.id0 = -1;
+    if (keep_ids) {                       // the sorted order IS the node order
+      g.id0 = (int64_t)id_off.size();
+      id_off.push_back((int64_t)ids.size());
+      for (const Obj &o : objs) {
+        ids += o.id;
+        id_off.push_back((int64_t)ids.size());
+      }
+    }
     return ISG_LD_OK;
   }
 
@@ -367,7 +380,7 @@ struct isg_sg_store {
           static const int two[2] = {1, 0};
           rc = add_dummy(two, 2, g);
         } else {
-          rc = convert(objs, g);
+          rc = convert(objs, g, true);
         }
         if (rc != ISG_LD_OK) { g_err = "image '" + image_id + "': " + g_err; return rc; }
         auto found = slot.find(image_id);
@@ -386,6 +399,22 @@ struct isg_sg_store {
     if (slot_id < 0 || slot_id >= (int64_t)graphs.size()) return missing;
     const Graph &g = graphs[slot_id];
     return g.e == 1 ? missing : g;
+  }
+
+  // the local node index of object `id` in the graph a collate of `slot_id` gives, or ISG_LD_NO_NODE
+  int32_t node_of(int64_t slot_id, const char *id) const {
+    if (!id) return ISG_LD_NO_NODE;
+    const Graph &g = query(slot_id);
+    if (g.id0 < 0) return ISG_LD_NO_NODE;               // absent, or a dummy
+    const std::string_view key(id);
+    const int64_t *off = id_off.data() + g.id0;
+    auto name = [&](int64_t i) { return std::string_view(ids.data() + off[i], (size_t)(off[i + 1] - off[i])); };
+    int64_t lo = 0, hi = g.n;                           // the ids ascend in std::string order, which string_view shares
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (name(mid) < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < g.n && name(lo) == key ? (int32_t)lo : ISG_LD_NO_NODE;
   }
 };
 
@@ -549,6 +578,26 @@ int isg_sg_collate(const isg_sg_store *s, const int64_t *slots, int64_t B, int64
   }
   if (bounds) { bounds[0] = nmax; bounds[1] = emax; }
   return ISG_LD_OK;
+}
+
+int isg_loader_objects_abi_version(void) { return ISG_LOADER_OBJECTS_ABI_VERSION; }
+
+int isg_sg_store_object_nodes(const isg_sg_store *s, const int64_t *slots, int64_t B, const int64_t *id_ptr,
+                              const char *const *object_ids, int32_t *nodes) {
+  if (!s || B < 0 || (B > 0 && (!slots || !id_ptr))) return fail(ISG_LD_EINVAL, "isg_sg_store_object_nodes: bad arguments");
+  if (B == 0) return ISG_LD_OK;
+  if (id_ptr[0] != 0) return fail(ISG_LD_EINVAL, "isg_sg_store_object_nodes: id_ptr[0] is not 0");
+  for (int64_t b = 0; b < B; ++b)
+    if (id_ptr[b + 1] < id_ptr[b])
+      return fail(ISG_LD_EINVAL, "isg_sg_store_object_nodes: id_ptr descends at question " + std::to_string(b));
+  if (id_ptr[B] > 0 && (!object_ids || !nodes)) return fail(ISG_LD_EINVAL, "isg_sg_store_object_nodes: NULL object_ids or nodes");
+  for (int64_t b = 0; b < B; ++b)
+    for (int64_t i = id_ptr[b]; i < id_ptr[b + 1]; ++i) nodes[i] = s->node_of(slots[b], object_ids[i]);
+  return ISG_LD_OK;
+}
+
+int64_t isg_sg_store_object_bytes(const isg_sg_store *s) {
+  return s ? (int64_t)(s->ids.size() + s->id_off.size() * sizeof(int64_t)) : -1;
 }
 
 }  // extern "C"

@@ -14,17 +14,26 @@ import torch
 
 
 def gqa_collate(data: Sequence[tuple], scene_graphs, tokenizer: Optional[Callable] = None, pin_memory: Optional[bool] = None,
-                distinct: bool = False):
+                distinct: bool = False, annotations: Optional["ObjectAnnotations"] = None):
     """data: (questionID, image_id, question_text, qst_types, short_answer_label, image_id) tuples (gqa.py:186-193 with the
     scene graph replaced by its image id).  Returns the reference's 7-tuple (gqa.py:262-270).  distinct=True: the scene-graph
-    batch holds every image once and carries the questions' graph_index (SceneGraphStore.collate); the tuple is the same."""
-    question_id, graph_ids, question_text, qst_types, labels, img = zip(*data)
+    batch holds every image once and carries the questions' graph_index (SceneGraphStore.collate); the tuple is the same.
+    annotations (an ObjectAnnotations): every item carries the question record's `annotations` dict as a SEVENTH field, and the
+    tuple gets an eighth entry, the gold table int32 [B, F, M] of annotations.encode -- indices local to a graph, so the same
+    table serves distinct=True."""
+    if annotations is not None:
+        question_id, graph_ids, question_text, qst_types, labels, img, annos = zip(*data)
+    else:
+        question_id, graph_ids, question_text, qst_types, labels, img = zip(*data)
     qsts_padded = qsts_attention_mask = None
     if tokenizer is not None:
         q = tokenizer(list(question_text), return_tensors="pt", padding=True)            # :252-256
         qsts_padded, qsts_attention_mask = q["input_ids"], q["attention_mask"]
     scene_graph = scene_graphs.collate(list(graph_ids), pin_memory, distinct=distinct)   # :258
-    return (question_id, scene_graph, qsts_padded, qsts_attention_mask, torch.LongTensor(labels), img, qst_types)
+    out = (question_id, scene_graph, qsts_padded, qsts_attention_mask, torch.LongTensor(labels), img, qst_types)
+    if annotations is None:
+        return out
+    return out + (annotations.encode(annos, list(graph_ids), getattr(scene_graphs, "store", scene_graphs)),)
 
 
 class QuestionTypes:
@@ -82,4 +91,61 @@ class QuestionTypes:
         """Host int32 [B, F] of group ids, -1 for an unknown name or a missing key; pinned when CUDA is there."""
         rows = [[self._ids.get((f, t.get(f) if isinstance(t, dict) else None), -1) for f in self.facets] for t in qst_types]
         out = torch.tensor(rows, dtype=torch.int32).view(len(rows), len(self.facets))
+        return out.pin_memory() if torch.cuda.is_available() else out
+
+
+class ObjectAnnotations:
+    """GQA's object annotations as node indices, for the grounding score (include/isg_grounding.h; the sibling of QuestionTypes).
+
+    Every GQA question record carries `annotations`: {"question": {...}, "answer": {...}, "fullAnswer": {...}}, each facet mapping
+    word positions ("4", "2:4") to the id of the scene-graph object the words refer to.  Only the values are used, in the dict's
+    order.  A value may be an id string, several ids separated by commas, or a list of id strings."""
+
+    def __init__(self, facets: Sequence[str] = ("question", "answer", "fullAnswer"), max_gold: int = 64):
+        self.facets = tuple(facets)
+        if not 1 <= len(self.facets) <= 3:
+            raise ValueError(f"ObjectAnnotations: 1 to 3 facets (the device table's F), got {len(self.facets)}")
+        if not 1 <= int(max_gold) <= 64:
+            raise ValueError(f"ObjectAnnotations: max_gold = {max_gold}; a facet of the device table holds 1 to 64 entries")
+        self.max_gold = int(max_gold)
+
+    @staticmethod
+    def _ids(value) -> list:
+        if isinstance(value, (list, tuple)):
+            return [i for v in value for i in ObjectAnnotations._ids(v)]
+        return [p.strip() for p in str(value).split(",") if p.strip()]
+
+    def object_ids(self, annotations: Sequence[dict]) -> list:
+        """[[ids of facet 0, ids of facet 1, ...] per question]: the annotated object ids as strings, values in dict order."""
+        out = []
+        for q, a in enumerate(annotations):
+            row = []
+            for f in self.facets:
+                words = a.get(f) if isinstance(a, dict) else None
+                ids = [i for v in words.values() for i in self._ids(v)] if isinstance(words, dict) else []
+                if len(ids) > self.max_gold:
+                    raise ValueError(f"ObjectAnnotations: question {q} annotates {len(ids)} objects in `{f}`, more than "
+                                     f"max_gold = {self.max_gold}")
+                row.append(ids)
+            out.append(row)
+        return out
+
+    def encode(self, annotations: Sequence[dict], image_ids, store) -> torch.Tensor:
+        """Host int32 [B, F, M] of LOCAL node indices (store.object_nodes: loader.SceneGraphStore, or anything with that method),
+        M = the longest facet list of the batch (at least 1); -1 pads, -2 = annotated but not a node of the graph.  Pinned when
+        CUDA is there."""
+        ids = self.object_ids(annotations)
+        B, F = len(ids), len(self.facets)
+        if len(image_ids) != B:
+            raise ValueError(f"ObjectAnnotations.encode: {B} annotations, {len(image_ids)} image ids")
+        M = max([len(f) for row in ids for f in row] + [1])
+        out = torch.full((B, F, M), -1, dtype=torch.int32)
+        if B:
+            nodes, ptr = store.object_nodes(image_ids, [[i for f in row for i in f] for row in ids])
+            at = ptr.tolist()
+            for q, row in enumerate(ids):
+                lo = at[q]
+                for f, lst in enumerate(row):
+                    out[q, f, :len(lst)] = nodes[lo:lo + len(lst)]
+                    lo += len(lst)
         return out.pin_memory() if torch.cuda.is_available() else out

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import math
+import operator
 from dataclasses import dataclass, field, replace
 from typing import Dict, Iterable, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
@@ -181,6 +182,7 @@ class CooReport:
     qst_tok_coo: float         # mean over correct questions of (question words naming a picked node / naming a node)
     text_tok_coo: float        # the same over the kept tokens of the text explanation
     by_type: Optional[Dict[str, Dict[str, "CooReport"]]] = field(default=None, compare=False)   # evaluate(types=...): {facet: {name: report}}
+    grounding: Optional["GroundingReport"] = field(default=None, compare=False)                 # evaluate(grounding=True)
 
     @staticmethod
     def _ratio_sum(totals: Sequence[int], which: int) -> float:
@@ -219,32 +221,94 @@ class EvalBatch(NamedTuple):
 _EvalBatchFields = EvalBatch
 
 
-class EvalBatch(_EvalBatchFields):         # noqa: F811 -- the tuple above, with one keyword beside its fields
-    """The batch of evaluate().  `groups` (int32 [B, F]: QuestionTypes.encode(...) of the questions, for evaluate(types=...)) is a
-    keyword and an attribute, not a seventh tuple field: the tuple's fields, their order and `_fields` stay what callers unpack."""
+class EvalBatch(_EvalBatchFields):         # noqa: F811 -- the tuple above, with two keywords beside its fields
+    """The batch of evaluate().  `groups` (int32 [B, F]: QuestionTypes.encode(...) of the questions, for evaluate(types=...)) and
+    `gold` (int32 [B, F, M]: ObjectAnnotations.encode(...), for evaluate(grounding=True)) are keywords and attributes, not further
+    tuple fields: the tuple's fields, their order and `_fields` stay what callers unpack."""
     groups: Optional[Tensor] = None
+    gold: Optional[Tensor] = None
 
-    def __new__(cls, *args, groups: Optional[Tensor] = None, **kw):
+    def __new__(cls, *args, groups: Optional[Tensor] = None, gold: Optional[Tensor] = None, **kw):
         self = super().__new__(cls, *args, **kw)
         self.groups = groups
+        self.gold = gold
         return self
 
     def _replace(self, **kw):
         groups = kw.pop("groups", self.groups)
+        gold = kw.pop("gold", self.gold)
         out = super()._replace(**kw)
         out.groups = groups
+        out.gold = gold
         return out
 
 
-def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0, types=None) -> CooReport:
+# ---------------------------------------------------------------------------------------------------------------------
+# Grounding in GQA's object annotations
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class GroundingFigures:
+    """One set of annotated objects (a facet, or the union `any`) over one population of questions; NaN where the denominator is 0."""
+    questions: int             # questions whose set holds at least one object of the graph
+    precision: float           # picked nodes that are annotated objects: sum hits / sum |P|  (micro)
+    recall: float              # annotated objects that were picked: sum hits / sum |G|  (micro)
+    macro_recall: float        # mean over the questions of hits / |G|
+    f1: float                  # of the two micro figures
+    pointing: float            # questions with at least one annotated object picked
+    full_recall: float         # questions with every annotated object picked
+    chance: float              # sum |P| / sum n_g: the recall of a random subset of the same size
+
+
+@dataclass(frozen=True)
+class GroundingReport:
+    """isg_grounding's running totals (one row of them) as figures: sets[name][population], name in `question`, `answer`,
+    `fullAnswer` (the facets given) and `any` (their union), population `all` or `correct`."""
+    totals: Tuple[int, ...]
+    questions: int
+    correct: int
+    unresolved: int            # annotated objects that are no node of their graph (entries -2)
+    bad: int                   # entries that are neither a pad, nor unresolved, nor a node index of the graph
+    sets: Dict[str, Dict[str, GroundingFigures]] = field(default_factory=dict, compare=False)
+    by_type: Optional[Dict[str, Dict[str, "GroundingReport"]]] = field(default=None, compare=False)
+
+    @staticmethod
+    def _figures(blk: Sequence[int]) -> GroundingFigures:
+        H = ops.GROUND_HIST
+        q, kept, nodes, gold, hits, some, every = blk[:7]
+        macro = math.fsum(map(operator.truediv, blk[9 + H:8 + 2 * H], range(1, H)))      # sum over m >= 1 of hits[m] / m: exact terms, exact sum
+        p, r = _mean(hits, kept), _mean(hits, gold)
+        f1 = float("nan") if p != p or r != r else (2 * p * r / (p + r) if p + r else 0.0)
+        return GroundingFigures(q, p, r, _mean(macro, q), f1, _mean(some, q), _mean(every, q), _mean(kept, nodes))
+
+    @classmethod
+    def from_totals(cls, totals, facets: Sequence[str] = ("question", "answer", "fullAnswer")) -> "GroundingReport":
+        t = tuple(totals.tolist()) if torch.is_tensor(totals) else tuple(int(v) for v in totals)
+        if len(t) != ops.GROUND_TOTALS:
+            raise ValueError(f"totals: expected {ops.GROUND_TOTALS} entries, got {len(t)}")
+        if not 1 <= len(facets) <= ops.GROUND_FACETS:
+            raise ValueError(f"facets: 1 to {ops.GROUND_FACETS}, got {len(facets)}")
+        names = {s: f for s, f in enumerate(facets)}
+        names[ops.GROUND_SETS - 1] = "any"
+        sets = {}
+        for s, name in names.items():
+            at = lambda c: t[ops.GROUND_HEAD + (2 * s + c) * ops.GROUND_BLOCK:ops.GROUND_HEAD + (2 * s + c + 1) * ops.GROUND_BLOCK]
+            sets[name] = {"all": cls._figures(at(0)), "correct": cls._figures(at(1))}
+        return cls(t, t[0], t[1], t[2], t[3], sets)
+
+
+def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold: float = 0.0, types=None,
+             grounding: bool = False) -> CooReport:
     """run_token_coo.py's experiment over whole batches: forward, argmax, ops.token_coo into ONE running totals tensor; nothing is
     copied to the host before the last batch has been queued.  With --text_sampling the forward's token mask is scored against
     tables.clip_sg.
     types (a datasets.gqa.QuestionTypes; every batch then carries `groups`): the report also has by_type, {facet: {name: CooReport}}
     of the questions of every group (ops.token_coo_groups, one launch more per batch).  The overall totals and the [G, COO_TOTALS]
-    table are ONE tensor: the evaluation stays one device-to-host copy."""
+    table are ONE tensor: the evaluation stays one device-to-host copy.
+    grounding (every batch then carries `gold`, ObjectAnnotations.encode of its questions): the report also has .grounding, a
+    GroundingReport of ops.grounding over the same masks and predictions (two launches more per batch), with by_type when types
+    is given.  Its totals lie behind the co-occurrence totals in the SAME int64 buffer: still one device-to-host copy."""
     full = not isinstance(model, synthetic.AnswerModel)
-    totals = None
+    totals = flat = ground = None
     G = 0 if types is None else int(types.num_groups)
     if types is not None and not 1 <= G <= ops.EVAL_GROUPS_MAX:
         raise ValueError(f"evaluate: {G} groups (1 to {ops.EVAL_GROUPS_MAX})")
@@ -271,25 +335,54 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
             logits, mask = out[0], out[1]
             mask_text = out[4] if full and len(out) > 4 else None
             if totals is None:
-                both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
+                if grounding:                       # one buffer, one copy: [1 + G, COO_TOTALS] then [1 + G, GROUND_TOTALS]
+                    flat = torch.zeros((1 + G) * (ops.COO_TOTALS + ops.GROUND_TOTALS), dtype=torch.int64, device=logits.device)
+                    both = flat[:(1 + G) * ops.COO_TOTALS].view(1 + G, ops.COO_TOTALS)
+                    ground = flat[(1 + G) * ops.COO_TOTALS:].view(1 + G, ops.GROUND_TOTALS)
+                else:
+                    both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
                 totals = both[0]
             ttok = tkeep = None
             if mask_text is not None:
                 ttok = tables.text_tokens(inp.questions)
                 tkeep = mask_text.reshape(B, -1).float().contiguous()
-            coo = ops.token_coo(names, mask, plan, logits.argmax(dim=1), b.label,
+            pred = logits.argmax(dim=1)
+            coo = ops.token_coo(names, mask, plan, pred, b.label,
                                 tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
+            groups = None
             if types is not None:
                 groups = getattr(b, "groups", None)
                 if groups is None:
                     raise ValueError("evaluate(types=...): every EvalBatch carries groups (QuestionTypes.encode)")
-                ops.token_coo_groups(coo.table, b.qflags, groups.to(logits.device, non_blocking=True), both[1:])
+                groups = groups.to(logits.device, non_blocking=True)
+                ops.token_coo_groups(coo.table, b.qflags, groups, both[1:])
+            if grounding:
+                gold = getattr(b, "gold", None)
+                if gold is None:
+                    raise ValueError("evaluate(grounding=True): every EvalBatch carries gold (ObjectAnnotations.encode)")
+                ops.grounding(mask, plan, gold.to(logits.device, non_blocking=True), pred, b.label, groups, G, threshold=threshold,
+                              totals=ground)
     if both is None:
-        both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64)
-    if types is None:
+        flat = torch.zeros((1 + G) * (ops.COO_TOTALS + (ops.GROUND_TOTALS if grounding else 0)), dtype=torch.int64)
+        both = flat[:(1 + G) * ops.COO_TOTALS].view(1 + G, ops.COO_TOTALS)
+    if types is None and not grounding:
         return CooReport.from_totals(both[0])
-    rows = both.tolist()                                     # overall and every group: the evaluation's one device-to-host copy
-    by_type = {f: {} for f in types.facets}
-    for g, (facet, name) in enumerate(types.group_names):
-        by_type[facet][name] = CooReport.from_totals(rows[1 + g])
-    return replace(CooReport.from_totals(rows[0]), by_type=by_type)
+    if not grounding:
+        rows = both.tolist()                                 # overall and every group: the evaluation's one device-to-host copy
+        by_type = {f: {} for f in types.facets}
+        for g, (facet, name) in enumerate(types.group_names):
+            by_type[facet][name] = CooReport.from_totals(rows[1 + g])
+        return replace(CooReport.from_totals(rows[0]), by_type=by_type)
+    host = flat.cpu()                                        # both tables, overall and every group: the one device-to-host copy
+    n_coo = (1 + G) * ops.COO_TOTALS
+    rows = host[:n_coo].view(1 + G, ops.COO_TOTALS).tolist()
+    grows = host[n_coo:].view(1 + G, ops.GROUND_TOTALS)     # rows stay tensors: from_totals turns each into ints in one call
+    report, ground_report = CooReport.from_totals(rows[0]), GroundingReport.from_totals(grows[0])
+    if types is not None:
+        by_type, ground_by_type = {f: {} for f in types.facets}, {f: {} for f in types.facets}
+        for g, (facet, name) in enumerate(types.group_names):
+            by_type[facet][name] = CooReport.from_totals(rows[1 + g])
+            ground_by_type[facet][name] = GroundingReport.from_totals(grows[1 + g])
+        report = replace(report, by_type=by_type)
+        ground_report = replace(ground_report, by_type=ground_by_type)
+    return replace(report, grounding=ground_report)

@@ -31,6 +31,11 @@ class LoaderError(RuntimeError):
 # name -> (restype, argtypes) of every symbol include/isg_loader.h declares; ISG_LOADER_ABI_VERSION
 SIGNATURES, ABI_VERSION = read_header(os.path.join(os.path.dirname(_HERE), "include", "isg_loader.h"), LoaderError)
 
+# the same of include/isg_loader_objects.h (object id -> node index), a table and an ABI version of its own: SIGNATURES stays
+# exactly what isg_loader.h declares
+OBJECT_SIGNATURES, OBJECT_ABI_VERSION = read_header(os.path.join(os.path.dirname(_HERE), "include", "isg_loader_objects.h"), LoaderError)
+NO_NODE = -2               # ISG_LD_NO_NODE: the object is not a node of the graph a collate of that image gives
+
 _lib = None
 
 
@@ -44,6 +49,12 @@ def load():
     lib = bind(ctypes.CDLL(LIB_PATH), SIGNATURES)
     if lib.isg_loader_abi_version() != ABI_VERSION:
         raise LoaderError(f"libisg_loader.so ABI {lib.isg_loader_abi_version()}, binding expects {ABI_VERSION}")
+    try:
+        bind(lib, OBJECT_SIGNATURES)
+    except AttributeError as e:
+        raise LoaderError(f"{LIB_PATH} lacks a symbol of include/isg_loader_objects.h ({e}): rebuild it (build())") from None
+    if lib.isg_loader_objects_abi_version() != OBJECT_ABI_VERSION:
+        raise LoaderError(f"libisg_loader.so objects ABI {lib.isg_loader_objects_abi_version()}, binding expects {OBJECT_ABI_VERSION}")
     _lib = lib
     return lib
 
@@ -54,7 +65,7 @@ def _check(rc: int, what: str) -> None:
 
 
 def _c_strings(items: Sequence[str]):
-    arr = (c_char_p * len(items))(*[s.encode("utf-8") for s in items])
+    arr = (c_char_p * len(items))(*[None if s is None else s.encode("utf-8") for s in items])      # None: a NULL string
     return arr
 
 
@@ -195,6 +206,29 @@ class SceneGraphStore:
             sizes = torch.stack([ptr[1:] - ptr[:-1], torch.bincount(batch[ei[1]], minlength=B)]) if E > 0 else \
                 torch.stack([ptr[1:] - ptr[:-1], torch.zeros(B, dtype=torch.int64)])
         return SceneGraphBatch(x, ei, ea, bb, sym, batch, ptr, B, int(bounds[0]), int(bounds[1]), sizes, graph_index)
+
+    def object_nodes(self, image_ids, object_ids: Sequence[Sequence[str]]):
+        """(nodes int32 [total], ptr int64 [B + 1]): for question b, nodes[ptr[b]:ptr[b + 1]] are the LOCAL node indices of the GQA
+        object ids object_ids[b] in the graph of image_ids[b] as collate() numbers it (objects by ascending id STRING), NO_NODE
+        (-2) where the image is unknown, its graph is a dummy, it has no such object, or the id is None.  ``image_ids``: id
+        strings, or an int64 tensor of slots from ``slots()``."""
+        slots = image_ids if torch.is_tensor(image_ids) else self.slots(image_ids)
+        slots = slots.to(torch.int64).contiguous()
+        B = slots.numel()
+        if len(object_ids) != B:
+            raise ValueError(f"object_nodes: {B} images, {len(object_ids)} id lists")
+        flat = [None if i is None else str(i) for ids in object_ids for i in ids]
+        ptr = torch.zeros(B + 1, dtype=torch.int64)
+        if B:
+            ptr[1:] = torch.tensor([len(ids) for ids in object_ids], dtype=torch.int64).cumsum(0)
+        nodes = torch.empty(len(flat), dtype=torch.int32)
+        _check(load().isg_sg_store_object_nodes(self._h, slots.data_ptr(), B, ptr.data_ptr(), _c_strings(flat), nodes.data_ptr()),
+               "isg_sg_store_object_nodes")
+        return nodes, ptr
+
+    def object_bytes(self) -> int:
+        """Bytes the store keeps to resolve object ids: the id pool and its offsets."""
+        return int(load().isg_sg_store_object_bytes(self._h))
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:

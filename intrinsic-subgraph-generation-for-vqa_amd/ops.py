@@ -144,7 +144,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "mp_f16_train": 0,                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
             "linear_rowbias": 0,                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
             "graph_instances": 0,                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
-            "eval_groups": 0}                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
+            "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
+            "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
 
 def reset_counters() -> None:
@@ -3921,6 +3922,62 @@ def token_coo_groups(table: Tensor, qflags: Optional[Tensor], groups: Tensor, to
                "isg_token_coo_groups")
     COUNTERS["eval_groups"] += 1
     return totals
+
+
+# ------------------------------------------------------------------------------------------------
+# Grounding of the sampled subgraph in GQA's object annotations (include/isg_grounding.h)
+# ------------------------------------------------------------------------------------------------
+from ._lib_grounding import CONSTANTS as _GROUND      # noqa: E402 -- the header's numbers; reading them loads no library
+
+GROUND_COLS, GROUND_TOTALS, GROUND_GOLD_MAX = _GROUND["ISG_GROUND_COLS"], _GROUND["ISG_GROUND_TOTALS"], _GROUND["ISG_GROUND_GOLD_MAX"]
+GROUND_FACETS, GROUND_SETS, GROUND_HEAD = _GROUND["ISG_GROUND_FACETS"], _GROUND["ISG_GROUND_SETS"], _GROUND["ISG_GROUND_HEAD"]
+GROUND_BLOCK, GROUND_HIST = _GROUND["ISG_GROUND_BLOCK"], _GROUND["ISG_GROUND_HIST"]
+
+
+class Grounding(NamedTuple):
+    table: Tensor                # int32 [B, GROUND_COLS]: the row of every question (include/isg_grounding.h)
+    totals: Optional[Tensor]     # int64 [1 + G, GROUND_TOTALS]: the caller's running totals with this batch added, or None
+
+
+def grounding(mask: Tensor, plan: "GraphPlan", gold: Tensor, pred: Optional[Tensor] = None, label: Optional[Tensor] = None,
+              groups: Optional[Tensor] = None, num_groups: int = 0, threshold: float = 0.0, totals: Optional[Tensor] = None,
+              status: Optional[Tensor] = None) -> Grounding:
+    """How many of the annotated objects are among the kept nodes (isg_grounding: two launches, one without totals; no sync, no
+    copy).  mask fp32 [N] or [N, 1] (a forward's imle_mask); gold int32 [B, F, M] of LOCAL node indices, -1 pad, -2 annotated but
+    not in the graph (datasets.gqa.ObjectAnnotations.encode); pred, label int64 [B], both or neither; groups int32 [B, Fg] with
+    num_groups = G as ops.group_meters takes them.  `totals` (int64 [1 + G, GROUND_TOTALS], zeroed by the caller once per
+    evaluation; a plain [GROUND_TOTALS] without groups) has this batch ADDED to it; `status` as ops.group_meters."""
+    from . import _lib_grounding
+    lib = _lib_grounding.load()
+    if (pred is None) != (label is None):
+        raise ValueError("pred and label come together")
+    if mask.dim() == 2 and mask.size(1) == 1:
+        mask = mask.squeeze(1)
+    N, B = plan.N, plan.B
+    if gold.dim() != 3 or gold.size(0) != B or not 1 <= gold.size(1) <= GROUND_FACETS or not 1 <= gold.size(2) <= GROUND_GOLD_MAX:
+        raise ValueError(f"gold: expected int32 [{B}, F, M] with 1 <= F <= {GROUND_FACETS} and 1 <= M <= {GROUND_GOLD_MAX}, "
+                         f"got {tuple(gold.shape)}")
+    G = int(num_groups)
+    Fg = 0
+    if groups is None:
+        if G != 0:
+            raise ValueError(f"grounding: num_groups = {G} without groups")
+    else:
+        if not 1 <= G <= EVAL_GROUPS_MAX:
+            raise ValueError(f"grounding: num_groups = {G} (1 to {EVAL_GROUPS_MAX})")
+        Fg = _groups_operand(groups, B, "grounding")
+    if totals is not None and tuple(totals.shape) not in ((1 + G, GROUND_TOTALS),) + (((GROUND_TOTALS,),) if G == 0 else ()):
+        raise ValueError(f"totals: expected int64 [{1 + G}, {GROUND_TOTALS}], got {tuple(totals.shape)}")
+    table = torch.empty(B, GROUND_COLS, dtype=torch.int32, device=mask.device)
+    _lib.check(lib.isg_grounding(_chk(mask, "mask", torch.float32, (N,)), float(threshold),
+                                 _chk(plan.ptr, "plan.ptr", torch.int32, (B + 1,)), _chk(gold, "gold", torch.int32),
+                                 gold.size(1), gold.size(2), _chk(pred, "pred", torch.int64, (B,), optional=True),
+                                 _chk(label, "label", torch.int64, (B,), optional=True),
+                                 _chk(groups, "groups", torch.int32, optional=True), Fg, G, _chk(table, "table", torch.int32),
+                                 _chk(totals, "totals", torch.int64, optional=True),
+                                 _chk(status, "status", torch.int32, (2,), optional=True), N, B, _stream()), "isg_grounding")
+    COUNTERS["grounding"] += 1
+    return Grounding(table, totals)
 
 
 def cat_mul(a: Tensor, b: Tensor) -> Tensor:

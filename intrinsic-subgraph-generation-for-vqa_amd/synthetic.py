@@ -338,3 +338,23 @@ def make_shared_workload(num_graphs: int, questions_per_graph: int, tokens: int 
     lens = torch.randint(max(1, tokens // 2), tokens + 1, (Q,), generator=gen)
     wl.questions, wl.att_mask, wl.graph_index = q, (torch.arange(tokens)[None] < lens[:, None]).long(), index
     return wl
+
+
+def make_gold(nodes_per_question, facets: int = 3, entries: int = 6, seed: int = 0, repeat: float = 0.2,
+              unresolved: float = 0.1) -> Tensor:
+    """A seeded gold table int32 [B, facets, entries] for ops.grounding / explain.evaluate(grounding=True), shaped like
+    datasets.gqa.ObjectAnnotations.encode's: LOCAL node indices in [0, n_q), every facet list of a random length padded with -1,
+    a share `repeat` of the entries repeating the question's first index (duplicates inside a facet and across facets), a share
+    `unresolved` equal to -2 (annotated, not in the graph).  A question without nodes has -2 and -1 only.
+    nodes_per_question: the node count of every question's graph (Workload.graph_sizes[0]; graph_sizes[0][graph_index] for a
+    shared workload)."""
+    gen = torch.Generator().manual_seed(seed)
+    n = torch.as_tensor(nodes_per_question, dtype=torch.long).view(-1, 1, 1)
+    B, F, M = n.size(0), int(facets), int(entries)
+    idx = (torch.rand(B, F, M, generator=gen) * n.float()).floor().long()
+    idx = torch.minimum(idx, (n - 1).clamp_min(0).expand(B, F, M))
+    idx = torch.where(torch.rand(B, F, M, generator=gen) < repeat, idx[:, :1, :1].expand(B, F, M), idx)
+    idx[(torch.rand(B, F, M, generator=gen) < unresolved) | (n == 0).expand(B, F, M)] = -2
+    count = torch.randint(0, M + 1, (B, F), generator=gen)
+    idx[torch.arange(M).view(1, 1, M) >= count.view(B, F, 1)] = -1
+    return idx.to(torch.int32)
