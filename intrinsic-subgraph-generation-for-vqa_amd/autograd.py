@@ -38,6 +38,22 @@ from . import ops
 # ------------------------------------------------------------------------------------------------
 # Generic: fused forward, recomputed torch backward
 # ------------------------------------------------------------------------------------------------
+def _restated_grads(restate, tensors, need, gouts):
+    """One gradient (or None) per tensor: autograd through restate(*tensors), a torch-op restatement of a fused forward,
+    evaluated again on detached copies.  need: which tensors want a gradient; gouts: the upstream gradient of each of the
+    restatement's outputs, None where there is none."""
+    with torch.enable_grad():
+        ins = [None if t is None else (t.detach().requires_grad_(True) if n else t.detach())
+               for t, n in zip(tensors, need)]
+        outs = restate(*ins)
+        outs = outs if isinstance(outs, tuple) else (outs,)
+        pairs = [(o, g) for o, g in zip(outs, gouts) if g is not None and o.requires_grad]
+        wanted = [i for i, n in zip(ins, need) if n]
+        grads = torch.autograd.grad([o for o, _ in pairs], wanted, [g for _, g in pairs], allow_unused=True)
+    it = iter(grads)
+    return tuple(next(it) if n else None for n in need)
+
+
 class _Recomputed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fused, restate, consts, *tensors):
@@ -48,18 +64,9 @@ class _Recomputed(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        tensors = ctx.saved_tensors
-        need = ctx.needs_input_grad[3:]
-        with torch.enable_grad():
-            ins = [None if t is None else (t.detach().requires_grad_(True) if n else t.detach())
-                   for t, n in zip(tensors, need)]
-            outs = ctx.restate(*ins, *ctx.consts)
-            outs = outs if isinstance(outs, tuple) else (outs,)
-            pairs = [(o, g) for o, g in zip(outs, gouts) if g is not None and o.requires_grad]
-            wanted = [i for i, n in zip(ins, need) if n]
-            grads = torch.autograd.grad([o for o, _ in pairs], wanted, [g for _, g in pairs], allow_unused=True)
-        it = iter(grads)
-        return (None, None, None) + tuple(next(it) if n else None for n in need)
+        restate, consts = ctx.restate, ctx.consts
+        return (None, None, None) + _restated_grads(lambda *ins: restate(*ins, *consts), ctx.saved_tensors,
+                                                    ctx.needs_input_grad[3:], gouts)
 
 
 def _seg_sum(v: Tensor, batch: Tensor, B: int) -> Tensor:
@@ -140,10 +147,6 @@ def _layer_tail_t(ins, c, h, weight, bias, mean_scale, node_mask, batch, B, eps)
     return y if node_mask is None else node_mask.view(-1, 1) * y
 
 
-def _layer_tail_f(ins, c, h, weight, bias, mean_scale, node_mask, plan, eps):
-    return ops.mgat_layer_tail(ins, c, h, plan, weight, bias, mean_scale, eps, node_mask=node_mask)
-
-
 class _LayerTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ins, c, h, weight, bias, mean_scale, node_mask, plan, eps):
@@ -169,10 +172,6 @@ def _pool_t(xn, q, node_mask, batch, B):
     x = xn if node_mask is None else xn * node_mask.view(-1, 1)
     gate = _seg_softmax((x * q[batch]).sum(-1) / math.sqrt(x.size(1)), batch, B, 1e-16).unsqueeze(1)
     return _seg_sum(gate * x, batch, B), gate
-
-
-def _pool_f(xn, q, node_mask, plan):
-    return ops.global_attn_pool(xn, q, plan, node_mask)
 
 
 class _Pool(torch.autograd.Function):
@@ -392,6 +391,44 @@ WGRAD_MIN_ROWS = 2048
 LINEAR_BWD_KERNELS = True
 
 
+def _linear_backward(g, x, weight, saved, mode, want_dx, want_dw, want_db, kernels):
+    """(dz, dx, dW, db) of y = act(x W^T + b) from its upstream gradient g, whose rows may be strided (a column slice): the one
+    place that knows a Linear's backward.  mode: ops.LINEAR_BWD_MODES -- 0 identity, 1 GELU (saved = the pre-activation), 2 ReLU
+    (saved = its result).  kernels: dz and db in one pass of ops.linear_bwd_prep and dW on the bf16 matrix cores
+    (csrc/isg_linear_bwd.hip); False: the torch passes and the fp32 split-M kernel of before.  The CALLER reads
+    LINEAR_BWD_KERNELS and counts in ops.COUNTERS["linear_bwd_kernels"], so what each node does with the switch stands at its call."""
+    db = None
+    if kernels:
+        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
+            g = g.contiguous()
+        if mode == 0:                   # identity: the bias gradient alone, g is not copied
+            if want_db:
+                db = ops.linear_bwd_prep(g, None, 0, want_dz=False, want_db=True)[1]
+            if not g.is_contiguous():
+                g = g.contiguous()
+        else:
+            g, db = ops.linear_bwd_prep(g, saved, mode, want_dz=True, want_db=want_db)
+    else:
+        g = g.contiguous()
+        if mode == 1:
+            g = torch.ops.aten.gelu_backward(g, saved)
+        elif mode == 2:
+            g = g * (saved > 0)
+    dx = None
+    if want_dx:                         # dX = g W: the same matrix-core kernel on the transposed weight
+        dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
+              if (g.size(1) & 3) == 0 else g @ weight)
+    dw = None
+    if want_dw:                         # long-and-thin reductions on a split-M kernel; short ones are hipBLASLt's home turf
+        if g.size(0) < WGRAD_MIN_ROWS:
+            dw = g.t() @ x
+        else:
+            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if kernels else ops.linear_wgrad(g, x.contiguous())
+    if want_db and not kernels:
+        db = g.sum(0)
+    return g, dx, dw, db
+
+
 class _Linear(torch.autograd.Function):
     """y = act(x W^T + b): forward on isg_linear_bf16x6 (pre-activation kept when act = GELU; ReLU fused into the kernel's epilogue
     and its RESULT kept: y > 0 is all the backward needs of it); backward on csrc/isg_linear_bwd.hip (LINEAR_BWD_KERNELS), or as
@@ -400,7 +437,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gelu, relu=False):
         z = ops.linear(x, weight, bias, gelu=False, cache_planes=False, relu=relu)
-        ctx.gelu, ctx.relu = gelu, relu
+        ctx.mode = 1 if gelu else 2 if relu else 0
         ctx.save_for_backward(x, weight, z if gelu or relu else None)
         ctx.has_bias = bias is not None
         return F.gelu(z) if gelu else z
@@ -408,43 +445,11 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, z = ctx.saved_tensors
+        need = ctx.needs_input_grad
         if LINEAR_BWD_KERNELS:
-            return _Linear._backward_kernels(ctx, g, x, weight, z)
-        g = g.contiguous()
-        if ctx.gelu:
-            g = torch.ops.aten.gelu_backward(g, z)
-        elif ctx.relu:
-            g = g * (z > 0)
-        dx = None
-        if ctx.needs_input_grad[0]:     # dX = g W: the same matrix-core kernel on the transposed weight
-            dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
-                  if (g.size(1) & 3) == 0 else g @ weight)
-        dw = None
-        if ctx.needs_input_grad[1]:   # long-and-thin reductions on the split-M kernel; short ones are hipBLASLt's home turf
-            dw = ops.linear_wgrad(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
-        db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        return dx, dw, db, None, None
-
-    @staticmethod
-    def _backward_kernels(ctx, g, x, weight, z):
-        ops.COUNTERS["linear_bwd_kernels"] += 1
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        mode = 1 if ctx.gelu else 2 if ctx.relu else 0
-        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
-            g = g.contiguous()
-        if mode == 0:                   # identity: the bias gradient alone, g is not copied
-            db = ops.linear_bwd_prep(g, None, 0, want_dz=False, want_db=True)[1] if want_db else None
-            if not g.is_contiguous():
-                g = g.contiguous()
-        else:
-            g, db = ops.linear_bwd_prep(g, z, mode, want_dz=True, want_db=want_db)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
-                  if (g.size(1) & 3) == 0 else g @ weight)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
+            ops.COUNTERS["linear_bwd_kernels"] += 1
+        _, dx, dw, db = _linear_backward(g, x, weight, z, ctx.mode, need[0], need[1], ctx.has_bias and need[2],
+                                         kernels=LINEAR_BWD_KERNELS)
         return dx, dw, db, None, None
 
 
@@ -456,43 +461,32 @@ def linear(x, weight, bias, gelu, relu=False):
 
 class _LinearRowBias(torch.autograd.Function):
     """y = act(x W^T + P[seg]) (ops.linear_rowbias, include/isg_concat.h), in the mould of _Linear: the forward keeps the
-    pre-activation when an activation follows; dz from ops.linear_bwd_prep without a bias sum, dx on the transposed weight, dW on
-    the bf16 matrix cores from WGRAD_MIN_ROWS rows, and dP[s] = the sum of dz over segment s's rows -- contiguous ranges, summed
-    in row order by ops.segment_range_sum without atomics, so two calls agree bit for bit."""
+    pre-activation when an activation follows; the backward is _linear_backward's without a bias sum, and dP[s] = the sum of dz
+    over segment s's rows -- contiguous ranges, summed in row order by ops.segment_range_sum without atomics, so two calls agree
+    bit for bit.  It runs the kernel path whatever LINEAR_BWD_KERNELS says and does not count in "linear_bwd_kernels"."""
 
     @staticmethod
     def forward(ctx, x, weight, P, seg, gelu, relu, rowptr):
         z = ops.linear_rowbias(x, weight, P, seg, relu=relu, cache_planes=False)
-        ctx.gelu, ctx.relu, ctx.S = gelu, relu, P.size(0)
+        ctx.mode, ctx.S = 1 if gelu else 2 if relu else 0, P.size(0)
         ctx.save_for_backward(x, weight, z if gelu or relu else None, seg, rowptr)
         return F.gelu(z) if gelu else z
 
     @staticmethod
     def backward(ctx, g):
         x, weight, z, seg, rowptr = ctx.saved_tensors
-        mode = 1 if ctx.gelu else 2 if ctx.relu else 0
-        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
-            g = g.contiguous()
-        if mode != 0:
-            g = ops.linear_bwd_prep(g, z, mode, want_dz=True, want_db=False)[0]
-        elif not g.is_contiguous():
-            g = g.contiguous()
-        dx = dw = dp = None
-        if ctx.needs_input_grad[0]:
-            dx = (ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False)
-                  if (g.size(1) & 3) == 0 else g @ weight)
-        if ctx.needs_input_grad[1]:
-            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if g.size(0) >= WGRAD_MIN_ROWS else g.t() @ x
-        if ctx.needs_input_grad[2]:
+        need = ctx.needs_input_grad
+        dz, dx, dw, _ = _linear_backward(g, x, weight, z, ctx.mode, need[0], need[1], False, kernels=True)
+        dp = None
+        if need[2]:
             if rowptr is None:
                 rowptr = ops.segment_rowptr(seg, ctx.S)
-            dp = ops.segment_range_sum(rowptr, g)
+            dp = ops.segment_range_sum(rowptr, dz)
         return dx, dw, dp, None, None, None, None
 
 
 def linear_rowbias(x, weight, P, seg, gelu=False, relu=False, rowptr=None):
-    if relu and gelu:
-        raise ValueError("relu excludes gelu")
+    """ops.linear_rowbias under autograd; that entry has checked the operands (relu excludes gelu among them)."""
     return _LinearRowBias.apply(x, weight, P, seg, gelu, relu, rowptr)
 
 
@@ -659,6 +653,19 @@ def add_layernorm(x, residual, norm, p=0.0, seed=0):
 # ------------------------------------------------------------------------------------------------
 # Message passing and the node -> edge mask
 # ------------------------------------------------------------------------------------------------
+def _mask_grad_wanted(node_mask, edge_mask, need_node, need_edge):
+    return (node_mask is not None and need_node) or (edge_mask is not None and need_edge)
+
+
+def _mask_grads(d_m, node_mask, edge_mask, plan, need_node, need_edge):
+    """(d_node_mask, d_edge_mask) from the message passing's d_m [E], the gradient of the mask each edge was scaled by."""
+    if not _mask_grad_wanted(node_mask, edge_mask, need_node, need_edge):
+        return None, None
+    if node_mask is not None:                         # the fused mask[src]*mask[dst] product keeps the reference's rule
+        return ops.node_to_edge_mask_backward(d_m, plan).view_as(node_mask), None
+    return None, d_m.view_as(edge_mask)
+
+
 class _GatV2MP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, slope, kernel, drop_p=0.0, drop_seed=0):
@@ -676,15 +683,11 @@ class _GatV2MP(torch.autograd.Function):
         x_l, x_r, e_proj, att, alpha, node_mask, edge_mask = ctx.saved_tensors
         plan, heads, slope, has_bias = ctx.cfg
         need = ctx.needs_input_grad
-        want_mask = (node_mask is not None and need[5]) or (edge_mask is not None and need[6])
         d_xl, d_xr, d_e, d_att, d_bias, d_m = ops.gatv2_mp_backward(
             x_l, x_r, e_proj, att, alpha, g_out, plan, heads, node_mask=node_mask, edge_mask=edge_mask,
-            negative_slope=slope, want_mask_grad=want_mask, dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1])
-        d_node = d_edge = None
-        if want_mask and node_mask is not None:       # the fused mask[src]*mask[dst] product keeps the reference's rule
-            d_node = ops.node_to_edge_mask_backward(d_m, plan).view_as(node_mask)
-        elif want_mask:
-            d_edge = d_m.view_as(edge_mask)
+            negative_slope=slope, want_mask_grad=_mask_grad_wanted(node_mask, edge_mask, need[5], need[6]),
+            dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1])
+        d_node, d_edge = _mask_grads(d_m, node_mask, edge_mask, plan, need[5], need[6])
         return (d_xl, d_xr, d_e, d_att.view_as(att), d_bias if has_bias else None, d_node, d_edge,
                 None, None, None, None, None, None)
 
@@ -692,34 +695,6 @@ class _GatV2MP(torch.autograd.Function):
 def gatv2_mp(x_l, x_r, e_proj, att, plan, heads, bias, node_mask, edge_mask, negative_slope, kernel, dropout_p=0.0, dropout_seed=0):
     return _GatV2MP.apply(x_l, x_r, e_proj, att, bias, node_mask, edge_mask, plan, heads, negative_slope, kernel, dropout_p,
                           dropout_seed)
-
-
-def _identity_linear_backward(g, x, weight, want_dx, want_dw, want_db):
-    """(dx, dW, db) of y = x W^T + b from its upstream gradient g: the calls _Linear.backward makes for a Linear without an
-    activation, under either state of LINEAR_BWD_KERNELS.  g's rows may be strided (a column slice)."""
-    db = None
-    if LINEAR_BWD_KERNELS:
-        ops.COUNTERS["linear_bwd_kernels"] += 1
-        if g.dim() != 2 or g.stride(1) != 1 or g.stride(0) < g.size(1):
-            g = g.contiguous()
-        if want_db:
-            db = ops.linear_bwd_prep(g, None, 0, want_dz=False, want_db=True)[1]
-        if not g.is_contiguous():
-            g = g.contiguous()
-    else:
-        g = g.contiguous()
-    dx = None
-    if want_dx:
-        dx = ops.linear(g, weight.detach().t().contiguous(), None, cache_planes=False) if (g.size(1) & 3) == 0 else g @ weight
-    dw = None
-    if want_dw:
-        if g.size(0) < WGRAD_MIN_ROWS:
-            dw = g.t() @ x
-        else:
-            dw = ops.linear_wgrad_bf16x6(g, x.contiguous()) if LINEAR_BWD_KERNELS else ops.linear_wgrad(g, x.contiguous())
-    if want_db and db is None:
-        db = g.sum(0)
-    return dx, dw, db
 
 
 class _ConvHalfRows(torch.autograd.Function):
@@ -737,7 +712,7 @@ class _ConvHalfRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, edge_attr, w_l, b_l, w_r, b_r, w_e, att, bias, node_mask, edge_mask, plan, heads, slope):
         shared = w_r is None
-        w, b = _ConvHalfRows._cat(w_l, b_l, w_r, b_r)
+        w, b = (w_l, b_l) if shared else ops.fused_weight((w_l, w_r), (b_l, b_r))
         x_lr = ops.linear(x, w, b, out_dtype=torch.float16, cache_planes=False)
         e_half = ops.linear(edge_attr, w_e, None, out_dtype=torch.float16, cache_planes=False)
         HC = w_l.size(0)
@@ -750,17 +725,6 @@ class _ConvHalfRows(torch.autograd.Function):
         return out.float(), alpha
 
     @staticmethod
-    def _cat(w_l, b_l, w_r, b_r):
-        """The fused lin_l | lin_r weight and bias (ops.linear_fused's), or lin_l's own when the layer shares its weights."""
-        if w_r is None:
-            return w_l, b_l
-        w = torch.cat([w_l, w_r], dim=0)
-        if b_l is None and b_r is None:
-            return w, None
-        zero = lambda m: torch.zeros(m.size(0), device=w.device)
-        return w, torch.cat([zero(w_l) if b_l is None else b_l, zero(w_r) if b_r is None else b_r])
-
-    @staticmethod
     def backward(ctx, g_out, _g_alpha):
         x, edge_attr, w_l, b_l, w_r, b_r, w_e, att, x_lr, e_half, alpha, node_mask, edge_mask = ctx.saved_tensors
         plan, heads, slope, has_bias = ctx.cfg
@@ -769,22 +733,20 @@ class _ConvHalfRows(torch.autograd.Function):
         HC = w_l.size(0)
         N = x.size(0)
         x_l, x_r = (x_lr, x_lr) if shared else (x_lr[:, :HC], x_lr[:, HC:])
-        want_mask = (node_mask is not None and need[9]) or (edge_mask is not None and need[10])
         buf = None if shared else torch.empty(N, 2 * HC, dtype=torch.float32, device=x.device)
         d_xl, d_xr, d_e, d_att, d_bias, d_m = ops.gatv2_mp_backward_f16(
             x_l, x_r, e_half, att, alpha, g_out, plan, heads, node_mask=node_mask, edge_mask=edge_mask, negative_slope=slope,
-            want_mask_grad=want_mask, d_x_lr=buf)
+            want_mask_grad=_mask_grad_wanted(node_mask, edge_mask, need[9], need[10]), d_x_lr=buf)
         g = d_xl + d_xr if shared else buf
-        w, _ = _ConvHalfRows._cat(w_l.detach(), None, None if shared else w_r.detach(), None)
+        w = w_l.detach() if shared else ops.fused_weight((w_l.detach(), w_r.detach()), (None, None))[0]
         want_b = (b_l is not None and need[3]) or (b_r is not None and need[5])
-        dx, dw, db = _identity_linear_backward(g, x, w, need[0], need[2] or need[4], want_b)
-        d_ea, d_we, _ = _identity_linear_backward(d_e, edge_attr, w_e.detach(), need[1], need[6], False)
+        kernels = LINEAR_BWD_KERNELS                    # two Linears without an activation, each counted as _Linear counts one
+        ops.COUNTERS["linear_bwd_kernels"] += int(kernels)
+        _, dx, dw, db = _linear_backward(g, x, w, None, 0, need[0], need[2] or need[4], want_b, kernels=kernels)
+        ops.COUNTERS["linear_bwd_kernels"] += int(kernels)
+        _, d_ea, d_we, _ = _linear_backward(d_e, edge_attr, w_e.detach(), None, 0, need[1], need[6], False, kernels=kernels)
         half = lambda t, lo: None if t is None else t[lo:lo + HC]
-        d_node = d_edge = None
-        if want_mask and node_mask is not None:       # the fused mask[src]*mask[dst] product keeps the reference's rule
-            d_node = ops.node_to_edge_mask_backward(d_m, plan).view_as(node_mask)
-        elif want_mask:
-            d_edge = d_m.view_as(edge_mask)
+        d_node, d_edge = _mask_grads(d_m, node_mask, edge_mask, plan, need[9], need[10])
         return (dx, d_ea, half(dw, 0) if need[2] else None, half(db, 0) if b_l is not None and need[3] else None,
                 half(dw, HC) if not shared and need[4] else None, half(db, HC) if b_r is not None and need[5] else None,
                 d_we, d_att.view_as(att) if need[7] else None, d_bias if has_bias and need[8] else None, d_node, d_edge,
@@ -887,12 +849,7 @@ class _SimpleTopK(torch.autograd.Function):
         d = ops.simple_topk_backward(scores, k, plan, None if g_out is None else g_out.contiguous(),
                                      None if g_marg is None else g_marg.contiguous())
         if d is None:                                   # a row beyond the kernel's LDS rule: the restatement, as with the switch off
-            with torch.enable_grad():
-                sc = scores.detach().requires_grad_(True)
-                outs = _simple_restatement(sc, k, plan, return_marginals)(sc)
-                outs = outs if isinstance(outs, tuple) else (outs,)
-                pairs = [(o, g) for o, g in zip(outs, (g_out, g_marg)) if g is not None]
-                d, = torch.autograd.grad([o for o, _ in pairs], [sc], [g for _, g in pairs])
+            d, = _restated_grads(_simple_restatement(scores, k, plan, return_marginals), (scores,), (True,), (g_out, g_marg))
         return (d,) + (None,) * 5
 
 

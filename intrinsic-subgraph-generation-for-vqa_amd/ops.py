@@ -1784,74 +1784,46 @@ def gatv2_tile_conv(x_l: Tensor, x_r: Tensor, edge_attr: Tensor, w_edge: Tensor,
     return out, alpha
 
 
-def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
-                      plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
-                      edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
-                      dropout_p: float = 0.0, dropout_seed: int = 0):
-    """Backward of gatv2_mp: (d_x_l, d_x_r, d_e_proj, d_att[H*C], d_bias[H*C], d_edge_mask[E] or None).
-    dropout_p / dropout_seed: those of the forward; the kernels draw its mask again (include/isg_mp_train.h).
-
-    No reference counterpart file: the reference relies on autograd through PyG's propagate
-    (mgat_v2_conv.py:215-279); the formulas are derived in csrc/isg_mp_bwd.hip.
-    """
-    dropout_p, dropout_seed = _drop_args(dropout_p, dropout_seed)
-    lib = _lib.load()
-    plan.require_csr()
+def _mp_rows_f32(x_l: Tensor, x_r: Tensor, e_proj: Tensor, plan: GraphPlan, H: int):
+    """fp32 feature rows of the message-passing backward, dense: (x_l, x_r, e_proj as read, their three addresses)."""
     N, HC = x_l.shape
-    H = int(heads)
-    C = HC // H
     E = plan.E
-    dev = x_l.device
-    x_l, x_r, e_proj, grad_out = x_l.contiguous(), x_r.contiguous(), e_proj.contiguous(), grad_out.contiguous()
-    rowptr_s, eid_s, dst_s = plan.source_csr()
-    d_x_l = torch.empty(N, HC, dtype=torch.float32, device=dev)
-    d_x_r = torch.empty(N, HC, dtype=torch.float32, device=dev)
-    d_e = torch.empty(E, HC, dtype=torch.float32, device=dev)
-    blocks = (N + 15) // 16
-    part = torch.empty(blocks, HC, dtype=torch.float32, device=dev)
-    d_m = torch.empty(E, dtype=torch.float32, device=dev) if want_mask_grad else None
-    if dropout_p > 0.0:
-        from . import _lib_mp_train
-        entry, name, drop = _lib_mp_train.load().isg_gatv2_mp_bwd_dropout, "isg_gatv2_mp_bwd_dropout", (dropout_p, dropout_seed)
-    else:
-        entry, name, drop = lib.isg_gatv2_mp_bwd, "isg_gatv2_mp_bwd", ()
-    _lib.check(entry(
-        _chk(x_l, "x_l", torch.float32, (N, HC)), _chk(x_r, "x_r", torch.float32, (N, HC)),
-        _chk(e_proj, "e_proj", torch.float32, (E, HC)) if E > 0 else 0,
-        _chk(att.reshape(-1), "att", torch.float32, (HC,)), _chk(alpha, "alpha", torch.float32, (E, H)) if E > 0 else 0,
-        _chk(grad_out, "grad_out", torch.float32, (N, HC)),
-        plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
-        rowptr_s.data_ptr(), eid_s.data_ptr(), dst_s.data_ptr(),
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
-        d_x_l.data_ptr(), d_x_r.data_ptr(), d_e.data_ptr(), part.data_ptr(), 0 if d_m is None else d_m.data_ptr(),
-        N, E, H, C, float(negative_slope), *drop, _stream()), name)
-    return d_x_l, d_x_r, d_e, part.sum(0), grad_out.sum(0), d_m
+    x_l, x_r, e_proj = x_l.contiguous(), x_r.contiguous(), e_proj.contiguous()
+    return (x_l, x_r, e_proj, _chk(x_l, "x_l", torch.float32, (N, HC)), _chk(x_r, "x_r", torch.float32, (N, HC)),
+            _chk(e_proj, "e_proj", torch.float32, (E, HC)) if E > 0 else 0)
 
 
-def gatv2_mp_backward_f16(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
-                          plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
-                          edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
-                          dropout_p: float = 0.0, dropout_seed: int = 0, d_x_lr: Optional[Tensor] = None):
-    """gatv2_mp_backward on saved rows stored as IEEE half (include/isg_mp_f16_train.h): the same tuple, every gradient fp32,
-    the bits of gatv2_mp_backward on the same rows upcast.  x_l / x_r / e_proj may be column slices (rows strided by a multiple
-    of 4 halves, columns contiguous): the halves of the fused [N, 2*H*C] projection are read where they lie.
-    d_x_lr: a caller-owned fp32 [N, 2*H*C] buffer; d_x_l and d_x_r are then written into its column halves and returned as
-    views of it -- the upstream gradient of the fused lin_l | lin_r Linear, with no torch.cat.  Its other contents are kept.
-    Attention dropout has no half-row form (dropout_p > 0 raises)."""
-    dropout_p, dropout_seed = _drop_args(dropout_p, dropout_seed)
-    if dropout_p > 0.0:
-        raise _lib.IsgError("attention dropout exists on fp32 feature rows only (the half-row backward has no dropout form)")
-    from . import _lib_mp_f16_train
-    lib = _lib_mp_f16_train.load()
-    plan.require_csr()
+def _mp_rows_f16(x_l: Tensor, x_r: Tensor, e_proj: Tensor, plan: GraphPlan, H: int):
+    """Half feature rows, read where they lie (rows strided by a multiple of 4 halves, columns contiguous)."""
     N, HC = x_l.shape
-    H = int(heads)
-    C = HC // H
     E = plan.E
-    dev = x_l.device
-    if N != plan.N or H * C != HC or tuple(x_r.shape) != (N, HC) or tuple(e_proj.shape) != (E, HC):
+    if N != plan.N or H * (HC // H) != HC or tuple(x_r.shape) != (N, HC) or tuple(e_proj.shape) != (E, HC):
         raise ValueError(f"x_l / x_r must be [N, H*C] and e_proj [E, H*C] of plan N={plan.N}, E={E}, heads={H}")
+    return (x_l, x_r, e_proj, _chk_rows(x_l, "x_l", torch.float16) if N > 0 else 0, _chk_rows(x_r, "x_r", torch.float16) if N > 0 else 0,
+            _chk_rows(e_proj, "e_proj", torch.float16) if E > 0 else 0)
+
+
+def _mp_pitches(x_l: Tensor, x_r: Tensor, e_proj: Tensor, d_x_l: Tensor, d_x_r: Tensor):
+    """isg_gatv2_mp_bwd_f16's ld_l, ld_r, ld_e (halves), ld_dl, ld_dr (floats)."""
+    HC = x_l.size(1)
+    ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else HC         # a single row has no pitch to speak of
+    return ld(x_l), ld(x_r), ld(e_proj) if e_proj.size(0) > 0 else 0, ld(d_x_l), ld(d_x_r)
+
+
+def _mp_backward(entry, name: str, rows, tail, x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
+                 plan: GraphPlan, heads: int, node_mask: Optional[Tensor], edge_mask: Optional[Tensor], negative_slope: float,
+                 want_mask_grad: bool, d_x_lr: Optional[Tensor] = None):
+    """The message-passing backward marshalled once for its three entry points (isg_gatv2_mp_bwd, isg_gatv2_mp_bwd_dropout,
+    isg_gatv2_mp_bwd_f16), which share their operand list up to the slope.  rows: _mp_rows_f32 or _mp_rows_f16, the feature rows
+    checked; tail(x_l, x_r, e_proj, d_x_l, d_x_r): the entry point's arguments between the slope and the stream.  d_x_lr: see
+    gatv2_mp_backward_f16.  Every tensor whose address is passed is a local here, held until the launch is queued."""
+    plan.require_csr()
+    N, HC = x_l.shape
+    H = int(heads)
+    C = HC // H
+    E = plan.E
+    dev = x_l.device
+    x_l, x_r, e_proj, p_l, p_r, p_e = rows(x_l, x_r, e_proj, plan, H)
     grad_out = grad_out.contiguous()
     rowptr_s, eid_s, dst_s = plan.source_csr()
     if d_x_lr is None:
@@ -1864,21 +1836,59 @@ def gatv2_mp_backward_f16(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor,
     d_e = torch.empty(E, HC, dtype=torch.float32, device=dev)
     part = torch.empty((N + 15) // 16, HC, dtype=torch.float32, device=dev)
     d_m = torch.empty(E, dtype=torch.float32, device=dev) if want_mask_grad else None
-    ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else HC         # a single row has no pitch to speak of
-    COUNTERS["mp_f16_train"] += 1
-    _lib.check(lib.isg_gatv2_mp_bwd_f16(
-        _chk_rows(x_l, "x_l", torch.float16) if N > 0 else 0, _chk_rows(x_r, "x_r", torch.float16) if N > 0 else 0,
-        _chk_rows(e_proj, "e_proj", torch.float16) if E > 0 else 0,
-        _chk(att.reshape(-1), "att", torch.float32, (HC,)), _chk(alpha, "alpha", torch.float32, (E, H)) if E > 0 else 0,
+    att_flat = att.reshape(-1)
+    node_flat = None if node_mask is None else node_mask.reshape(-1)
+    edge_flat = None if edge_mask is None else edge_mask.reshape(-1)
+    _lib.check(entry(
+        p_l, p_r, p_e,
+        _chk(att_flat, "att", torch.float32, (HC,)), _chk(alpha, "alpha", torch.float32, (E, H)) if E > 0 else 0,
         _chk(grad_out, "grad_out", torch.float32, (N, HC)),
         plan.rowptr.data_ptr(), plan.eid.data_ptr(), plan.src.data_ptr(),
         rowptr_s.data_ptr(), eid_s.data_ptr(), dst_s.data_ptr(),
-        _chk(None if node_mask is None else node_mask.reshape(-1), "node_mask", torch.float32, (N,), optional=True),
-        _chk(None if edge_mask is None else edge_mask.reshape(-1), "edge_mask", torch.float32, (E,), optional=True),
+        _chk(node_flat, "node_mask", torch.float32, (N,), optional=True),
+        _chk(edge_flat, "edge_mask", torch.float32, (E,), optional=True),
         d_x_l.data_ptr(), d_x_r.data_ptr(), d_e.data_ptr(), part.data_ptr(), 0 if d_m is None else d_m.data_ptr(),
-        N, E, H, C, float(negative_slope), ld(x_l), ld(x_r), ld(e_proj) if E > 0 else 0, ld(d_x_l), ld(d_x_r), _stream()),
-        "isg_gatv2_mp_bwd_f16")
+        N, E, H, C, float(negative_slope), *tail(x_l, x_r, e_proj, d_x_l, d_x_r), _stream()), name)
     return d_x_l, d_x_r, d_e, part.sum(0), grad_out.sum(0), d_m
+
+
+def gatv2_mp_backward(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
+                      plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
+                      edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
+                      dropout_p: float = 0.0, dropout_seed: int = 0):
+    """Backward of gatv2_mp: (d_x_l, d_x_r, d_e_proj, d_att[H*C], d_bias[H*C], d_edge_mask[E] or None).
+    dropout_p / dropout_seed: those of the forward; the kernels draw its mask again (include/isg_mp_train.h).
+
+    No reference counterpart file: the reference relies on autograd through PyG's propagate
+    (mgat_v2_conv.py:215-279); the formulas are derived in csrc/isg_mp_bwd.hip.
+    """
+    drop = _drop_args(dropout_p, dropout_seed)
+    if drop[0] > 0.0:
+        from . import _lib_mp_train
+        entry, name = _lib_mp_train.load().isg_gatv2_mp_bwd_dropout, "isg_gatv2_mp_bwd_dropout"
+    else:
+        entry, name, drop = _lib.load().isg_gatv2_mp_bwd, "isg_gatv2_mp_bwd", ()
+    return _mp_backward(entry, name, _mp_rows_f32, lambda *_: drop, x_l, x_r, e_proj, att, alpha, grad_out, plan, heads, node_mask,
+                        edge_mask, negative_slope, want_mask_grad)
+
+
+def gatv2_mp_backward_f16(x_l: Tensor, x_r: Tensor, e_proj: Tensor, att: Tensor, alpha: Tensor, grad_out: Tensor,
+                          plan: GraphPlan, heads: int, node_mask: Optional[Tensor] = None,
+                          edge_mask: Optional[Tensor] = None, negative_slope: float = 0.2, want_mask_grad: bool = False,
+                          dropout_p: float = 0.0, dropout_seed: int = 0, d_x_lr: Optional[Tensor] = None):
+    """gatv2_mp_backward on saved rows stored as IEEE half (include/isg_mp_f16_train.h): the same tuple, every gradient fp32,
+    the bits of gatv2_mp_backward on the same rows upcast.  x_l / x_r / e_proj may be column slices (rows strided by a multiple
+    of 4 halves, columns contiguous): the halves of the fused [N, 2*H*C] projection are read where they lie.
+    d_x_lr: a caller-owned fp32 [N, 2*H*C] buffer; d_x_l and d_x_r are then written into its column halves and returned as
+    views of it -- the upstream gradient of the fused lin_l | lin_r Linear, with no torch.cat.  Its other contents are kept.
+    Attention dropout has no half-row form (dropout_p > 0 raises)."""
+    if _drop_args(dropout_p, dropout_seed)[0] > 0.0:
+        raise _lib.IsgError("attention dropout exists on fp32 feature rows only (the half-row backward has no dropout form)")
+    from . import _lib_mp_f16_train
+    res = _mp_backward(_lib_mp_f16_train.load().isg_gatv2_mp_bwd_f16, "isg_gatv2_mp_bwd_f16", _mp_rows_f16, _mp_pitches, x_l, x_r,
+                       e_proj, att, alpha, grad_out, plan, heads, node_mask, edge_mask, negative_slope, want_mask_grad, d_x_lr)
+    COUNTERS["mp_f16_train"] += 1
+    return res
 
 
 def node_to_edge_mask_backward(d_edge_mask: Tensor, plan: GraphPlan) -> Tensor:
@@ -4173,15 +4183,20 @@ def small_mlps(chains, strict: bool = True) -> Optional[list]:
     return outs
 
 
-def linear_fused(x: Tensor, layers, out_dtype=torch.float32) -> Tuple[Tensor, ...]:
-    """Several Linear layers that share their input as ONE projection (weights concatenated along the output dim, a derived
-    weight); returns one column-slice view of the fused output per layer (row stride = total width)."""
-    biases = [m.bias for m in layers if m.bias is not None]
+def fused_weight(weights, biases):
+    """(weight, bias) of Linears that share their input, as ONE projection: the weights stacked along the output dim, and the
+    biases in a row with zeros for a layer that has none -- None when no layer has one."""
+    w = torch.cat(list(weights), dim=0)
+    if all(b is None for b in biases):
+        return w, None
+    return w, torch.cat([torch.zeros(m.size(0), device=w.device) if b is None else b for m, b in zip(weights, biases)])
 
-    def cat():
-        w = torch.cat([m.weight for m in layers], dim=0)
-        return w, torch.cat([m.bias if m.bias is not None else torch.zeros(m.weight.size(0), device=w.device)
-                             for m in layers]) if biases else None
+
+def linear_fused(x: Tensor, layers, out_dtype=torch.float32) -> Tuple[Tensor, ...]:
+    """Several Linear layers that share their input as ONE projection (fused_weight, a derived weight); returns one column-slice
+    view of the fused output per layer (row stride = total width)."""
+    biases = [m.bias for m in layers if m.bias is not None]
+    cat = lambda: fused_weight([m.weight for m in layers], [m.bias for m in layers])
     if _rec(*([] if isinstance(x, Planes32) else [x]), *[m.weight for m in layers]):      # training: differentiable, nothing cached
         y = linear(x, *cat())
     else:
