@@ -1,10 +1,11 @@
-"""ctypes binding of libisg_hip.so (C ABI declared in include/isg.h).
+"""ctypes binding of libisg_hip.so (C ABI declared in include/isg.h and the include/isg_*.h of HEADERS).
 
 The product path has no CPU fallback: if the shared library is missing or a tensor is not on
 an MI355X, the ops raise.  Build the library with ``python -c "import __graft_entry__ as g; g.build()"``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import re
@@ -87,24 +88,83 @@ def read_header(path: str, error=IsgError):
         return parse_header(f.read())
 
 
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "isg.h")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+# Every device header of libisg_hip.so, in the order they were added: file -> (its version symbol, the noun its messages use).
+# Each has an ABI version of its own, so none of the others moves when an entry point of one does; the symbols live in the one
+# shared library, and load() binds and checks them all on the one handle.  (The loader's two headers declare another library:
+# loader.py.)
+HEADERS = {
+    "isg.h": ("isg_abi_version", ""),
+    "isg_train.h": ("isg_train_abi_version", "training "),
+    "isg_optim.h": ("isg_optim_abi_version", "optimizer "),
+    "isg_fused.h": ("isg_fused_abi_version", "fused-launch "),
+    "isg_sgenc_train.h": ("isg_sgenc_train_abi_version", "scene-graph training "),
+    "isg_dist.h": ("isg_dist_abi_version", "data-parallel "),
+    "isg_linear_train.h": ("isg_linear_train_abi_version", "Linear-backward "),
+    "isg_masked.h": ("isg_masked_abi_version", "masked-layer "),
+    "isg_sampler_train.h": ("isg_sampler_train_abi_version", "sampler-training "),
+    "isg_topk_rows.h": ("isg_topk_rows_abi_version", "per-row top-k "),
+    "isg_mp_train.h": ("isg_mp_train_abi_version", "attention-dropout "),
+    "isg_sparse_out.h": ("isg_sparse_out_abi_version", "sparse-output "),
+    "isg_mp_f16_train.h": ("isg_mp_f16_train_abi_version", "half-row training "),
+    "isg_concat.h": ("isg_concat_abi_version", "concat_instr "),
+    "isg_instances.h": ("isg_instances_abi_version", "instances "),
+    "isg_eval.h": ("isg_eval_abi_version", "eval "),
+    "isg_grounding.h": ("isg_grounding_abi_version", "grounding "),
+}
+_parsed, _declared_in = {}, {}                      # file -> header(file); symbol -> the file that declares it
+
+
+def header(file: str):
+    """(path, {name: (restype, argtypes)}, ABI version) of one header of HEADERS, read once.  The headers share one library and
+    one handle, so a symbol that two of them declare raises, naming both."""
+    if file not in _parsed:
+        path = os.path.join(INCLUDE, file)
+        signatures, abi = read_header(path)
+        for name in signatures:
+            if _declared_in.setdefault(name, file) != file:
+                raise IsgError(f"`{name}` is declared in include/{_declared_in[name]} and in include/{file}")
+        _parsed[file] = (path, signatures, abi)
+    return _parsed[file]
+
+
 # name -> (restype, argtypes), one entry per symbol declared in include/isg.h; ISG_ABI_VERSION
-SIGNATURES, ABI_VERSION = read_header(HEADER_PATH)
+HEADER_PATH, SIGNATURES, ABI_VERSION = header("isg.h")
+for _file in HEADERS:
+    header(_file)
 
 _lib = None
 
 
 def bind(lib, signatures=None):
-    """Set restype / argtypes of every declared symbol on a CDLL (the product library, or a variant build of it)."""
-    for name, (res, args) in (SIGNATURES if signatures is None else signatures).items():
-        fn = getattr(lib, name)   # AttributeError here = header and library disagree
-        fn.restype = res
-        fn.argtypes = args
+    """Set restype / argtypes of the given symbols -- without `signatures`, of every symbol of every header -- on a CDLL (the
+    product library, or a variant build of it)."""
+    for sigs in ([header(f)[1] for f in HEADERS] if signatures is None else [signatures]):
+        for name, (res, args) in sigs.items():
+            fn = getattr(lib, name)   # AttributeError here = header and library disagree
+            fn.restype = res
+            fn.argtypes = args
+    return lib
+
+
+def checked(lib):
+    """bind() header by header, each followed by its version check: the handle, or the IsgError that names the header at fault."""
+    for file, (version, noun) in HEADERS.items():
+        _, signatures, abi = header(file)
+        try:
+            bind(lib, signatures)
+        except AttributeError as e:
+            raise IsgError(f"{LIB_PATH} lacks a symbol of include/{file} ({e}): rebuild it (build())") from None
+        v = getattr(lib, version)()
+        if v != abi:
+            raise IsgError(f"libisg_hip.so {noun}ABI version {v}, binding expects {abi}")
     return lib
 
 
 def load():
-    """Load libisg_hip.so once; raise (never fall back) when it is absent or has the wrong ABI."""
+    """Load libisg_hip.so once, with every header bound and checked; raise (never fall back) when it is absent, lacks a symbol or
+    has the wrong ABI.  The one handle of the package: every _lib_<name>.load() returns it, so assigning `_lib._lib` (or using())
+    swaps the library under every entry point."""
     global _lib
     if _lib is not None:
         return _lib
@@ -112,12 +172,20 @@ def load():
         raise IsgError(
             f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
             "g.build()\"` (hipcc --offload-arch=gfx950). There is no CPU fallback for this path.")
-    lib = bind(ctypes.CDLL(LIB_PATH))
-    v = lib.isg_abi_version()
-    if v != ABI_VERSION:
-        raise IsgError(f"libisg_hip.so ABI version {v}, binding expects {ABI_VERSION}")
-    _lib = lib
-    return lib
+    _lib = checked(ctypes.CDLL(LIB_PATH))
+    return _lib
+
+
+@contextlib.contextmanager
+def using(handle):
+    """Run the block on another handle -- a variant build from bind(ctypes.CDLL(path)), or a proxy around one -- and put back
+    what was there."""
+    global _lib
+    keep, _lib = load(), handle
+    try:
+        yield handle
+    finally:
+        _lib = keep
 
 
 def check(status: int, what: str) -> None:

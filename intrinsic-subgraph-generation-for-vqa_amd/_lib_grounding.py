@@ -3,18 +3,18 @@
 The seventeenth device header has an ABI version of its own (ISG_GROUNDING_ABI_VERSION): none of the other headers moves when
 the entry point here does.  The symbols live in the same shared library.  The layout constants (ISG_GROUND_*) are read from the
 header too: the header is the contract, and nothing in Python restates a number of it.
+
+One of the headers of _lib.HEADERS: parsed, bound and version-checked there, on the one handle of the package, so
+`load() is _lib.load()`, always -- a library swapped in through `_lib._lib` is the library here too.
 """
 from __future__ import annotations
 
-import ctypes
-import os
 import re
 
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib._HERE), "include", "isg_grounding.h")
 # name -> (restype, argtypes) of every symbol include/isg_grounding.h declares; ISG_GROUNDING_ABI_VERSION
-SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
+HEADER_PATH, SIGNATURES, ABI_VERSION = _lib.header("isg_grounding.h")
 
 
 def read_constants(path: str = HEADER_PATH) -> dict:
@@ -30,22 +30,7 @@ def read_constants(path: str = HEADER_PATH) -> dict:
 
 CONSTANTS = read_constants()
 
-_bound = None
-
 
 def load():
-    """The product library with the grounding symbols bound; raises (never falls back) when one is missing."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    _lib.load()                                   # existence, the inference ABI
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    try:
-        _lib.bind(lib, SIGNATURES)
-    except AttributeError as e:
-        raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/isg_grounding.h ({e}): rebuild it (build())") from None
-    v = lib.isg_grounding_abi_version()
-    if v != ABI_VERSION:
-        raise _lib.IsgError(f"libisg_hip.so grounding ABI version {v}, binding expects {ABI_VERSION}")
-    _bound = lib
-    return lib
+    """The package's handle (_lib.load(), looked up when called), where the grounding symbols are bound beside all others."""
+    return _lib.load()

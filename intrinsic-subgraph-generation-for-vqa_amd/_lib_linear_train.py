@@ -2,34 +2,18 @@
 
 The header has an ABI version of its own (ISG_LINEAR_TRAIN_ABI_VERSION): no other header moves when the backward's kernels do.  The
 symbols live in the same shared library (csrc/isg_linear_bwd.hip).
+
+One of the headers of _lib.HEADERS: parsed, bound and version-checked there, on the one handle of the package, so
+`load() is _lib.load()`, always -- a library swapped in through `_lib._lib` is the library here too.
 """
 from __future__ import annotations
 
-import ctypes
-import os
-
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib._HERE), "include", "isg_linear_train.h")
 # name -> (restype, argtypes) of every symbol include/isg_linear_train.h declares; ISG_LINEAR_TRAIN_ABI_VERSION
-SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
-
-_bound = None
+HEADER_PATH, SIGNATURES, ABI_VERSION = _lib.header("isg_linear_train.h")
 
 
 def load():
-    """The product library with the Linear-backward symbols bound; raises (never falls back) when one is missing."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    _lib.load()                                   # existence, the inference ABI
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    try:
-        _lib.bind(lib, SIGNATURES)
-    except AttributeError as e:
-        raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/isg_linear_train.h ({e}): rebuild it (build())") from None
-    v = lib.isg_linear_train_abi_version()
-    if v != ABI_VERSION:
-        raise _lib.IsgError(f"libisg_hip.so Linear-backward ABI version {v}, binding expects {ABI_VERSION}")
-    _bound = lib
-    return lib
+    """The package's handle (_lib.load(), looked up when called), where the Linear-backward symbols are bound beside all others."""
+    return _lib.load()

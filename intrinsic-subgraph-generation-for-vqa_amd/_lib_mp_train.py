@@ -3,34 +3,18 @@ _lib's.
 
 The eleventh device header has an ABI version of its own (ISG_MP_TRAIN_ABI_VERSION): none of the other headers moves when an entry
 point here does.  The symbols live in the same shared library.
+
+One of the headers of _lib.HEADERS: parsed, bound and version-checked there, on the one handle of the package, so
+`load() is _lib.load()`, always -- a library swapped in through `_lib._lib` is the library here too.
 """
 from __future__ import annotations
 
-import ctypes
-import os
-
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib._HERE), "include", "isg_mp_train.h")
 # name -> (restype, argtypes) of every symbol include/isg_mp_train.h declares; ISG_MP_TRAIN_ABI_VERSION
-SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
-
-_bound = None
+HEADER_PATH, SIGNATURES, ABI_VERSION = _lib.header("isg_mp_train.h")
 
 
 def load():
-    """The product library with the attention-dropout symbols bound; raises (never falls back) when one is missing."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    _lib.load()                                   # existence, the inference ABI
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    try:
-        _lib.bind(lib, SIGNATURES)
-    except AttributeError as e:
-        raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/isg_mp_train.h ({e}): rebuild it (build())") from None
-    v = lib.isg_mp_train_abi_version()
-    if v != ABI_VERSION:
-        raise _lib.IsgError(f"libisg_hip.so attention-dropout ABI version {v}, binding expects {ABI_VERSION}")
-    _bound = lib
-    return lib
+    """The package's handle (_lib.load(), looked up when called), where the attention-dropout symbols are bound beside all others."""
+    return _lib.load()

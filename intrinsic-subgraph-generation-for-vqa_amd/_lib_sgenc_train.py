@@ -2,34 +2,18 @@
 
 The fifth device header has an ABI version of its own (ISG_SGENC_TRAIN_ABI_VERSION): include/isg.h and the other three headers do
 not move when one of these entry points does.  The symbols live in the same shared library (csrc/isg_sgenc_bwd.hip).
+
+One of the headers of _lib.HEADERS: parsed, bound and version-checked there, on the one handle of the package, so
+`load() is _lib.load()`, always -- a library swapped in through `_lib._lib` is the library here too.
 """
 from __future__ import annotations
 
-import ctypes
-import os
-
 from . import _lib
 
-HEADER_PATH = os.path.join(os.path.dirname(_lib._HERE), "include", "isg_sgenc_train.h")
 # name -> (restype, argtypes) of every symbol include/isg_sgenc_train.h declares; ISG_SGENC_TRAIN_ABI_VERSION
-SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
-
-_bound = None
+HEADER_PATH, SIGNATURES, ABI_VERSION = _lib.header("isg_sgenc_train.h")
 
 
 def load():
-    """The product library with the scene-graph training symbols bound; raises (never falls back) when one is missing."""
-    global _bound
-    if _bound is not None:
-        return _bound
-    _lib.load()                                   # existence, the inference ABI
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    try:
-        _lib.bind(lib, SIGNATURES)
-    except AttributeError as e:
-        raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/isg_sgenc_train.h ({e}): rebuild it (build())") from None
-    v = lib.isg_sgenc_train_abi_version()
-    if v != ABI_VERSION:
-        raise _lib.IsgError(f"libisg_hip.so scene-graph training ABI version {v}, binding expects {ABI_VERSION}")
-    _bound = lib
-    return lib
+    """The package's handle (_lib.load(), looked up when called), where the scene-graph training symbols are bound beside all others."""
+    return _lib.load()

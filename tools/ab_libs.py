@@ -42,16 +42,16 @@ else:
 
 
 def run(lib, n):
-    _lib._lib = lib              # (derived weights are data, the same for both builds: the caches stay)
-    torch.cuda.synchronize()
-    for i in range(3):
-        out = step(i)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n):
-        out = step(i)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3, out
+    with _lib.using(lib):        # (derived weights are data, the same for both builds: the caches stay)
+        torch.cuda.synchronize()
+        for i in range(3):
+            out = step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n):
+            out = step(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, out
 
 
 with torch.no_grad():
@@ -62,7 +62,6 @@ with torch.no_grad():
             ms, out = run(lib, 20 if "--full" not in sys.argv else 5)
             res[name].append(ms)
             outs[name] = out
-    _lib._lib = shipped
 same = torch.equal(outs["shipped"], outs["variant"])
 for name, v in res.items():
     v = v[2:]

@@ -26,11 +26,10 @@ for C in (128, 300, 20):
     nm = (torch.rand(N, 1, generator=gen) > 0.5).float().to(dev)
     res = {}
     for name, lib in (("shipped", shipped), ("variant", variant)):
-        _lib._lib = lib
-        res[name] = [ops.scatter_attention(ins, c, plan), ops.graph_norm(c, plan, w, b, ms),
-                     ops.mgat_layer_tail(ins, c, h, plan, w, b, ms), ops.mgat_layer_tail(ins, c, h, plan, w, b, ms, node_mask=nm),
-                     *ops.global_attn_pool(c, q, plan, None), *ops.global_attn_pool(c, q, plan, nm)]
-        torch.cuda.synchronize()
-    _lib._lib = shipped
+        with _lib.using(lib):
+            res[name] = [ops.scatter_attention(ins, c, plan), ops.graph_norm(c, plan, w, b, ms),
+                         ops.mgat_layer_tail(ins, c, h, plan, w, b, ms), ops.mgat_layer_tail(ins, c, h, plan, w, b, ms, node_mask=nm),
+                         *ops.global_attn_pool(c, q, plan, None), *ops.global_attn_pool(c, q, plan, nm)]
+            torch.cuda.synchronize()
     names = ["scatter_attention", "graph_norm", "layer_tail", "layer_tail masked", "pool out", "pool gate", "pool out masked", "pool gate masked"]
     print(C, {n: ("same" if torch.equal(a, v) else f"{(a - v).abs().max().item():.2e}") for n, a, v in zip(names, res["shipped"], res["variant"])})

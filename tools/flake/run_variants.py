@@ -47,11 +47,8 @@ torch.cuda.synchronize()
 
 
 def use(path):
-    if path is None:
-        _lib._lib = shipped
-        return
-    variant = _lib.bind(ctypes.CDLL(os.path.abspath(path)))
-    _lib._lib = variant
+    """`with use(path):` runs the block on that variant library (None: the shipped one), every header's entry points included."""
+    return _lib.using(shipped if path is None else _lib.bind(ctypes.CDLL(os.path.abspath(path))))
 
 
 def conv(s):
@@ -89,9 +86,9 @@ def explain(s, right, wrong, alpha):
 
 report = {"device": torch.cuda.get_device_name(0), "launches_per_set": launches, "sets": nsets, "variants": {}}
 rolled = os.path.join(ROOT, "tools", "_build", "libisg_agg_rolled.so")
-use(rolled if os.path.exists(rolled) else None)
-reference = [conv(s) for s in sets]
-torch.cuda.synchronize()
+with use(rolled if os.path.exists(rolled) else None):
+    reference = [conv(s) for s in sets]
+    torch.cuda.synchronize()
 libs = sorted(glob.glob(os.path.join(ROOT, "tools", "_build", "libisg_agg_*.so")))
 order = ["unroll2", "pairs", "two_acc", "nops", "opaque_w", "scalar", "between_nop", "unroll2_no_inflight", "rolled"]
 if "--shipped-only" in sys.argv:
@@ -101,30 +98,29 @@ vname = lambda p: "shipped" if p is None else os.path.basename(p)[len("libisg_ag
 libs.sort(key=lambda p: order.index(vname(p)) if vname(p) in order else 99)
 for lib in libs:
     name = vname(lib)
-    use(lib)
     t0 = time.time()
     wrong_launches, records, vs_rolled = 0, [], None
-    for si, s in enumerate(sets):
-        first = conv(s)
+    with use(lib):
+        for si, s in enumerate(sets):
+            first = conv(s)
+            torch.cuda.synchronize()
+            if vs_rolled is None:
+                vs_rolled = bool(torch.equal(first[0], reference[si][0]))      # two_acc rounds differently by design
+            # the variant's own majority value: three launches agreeing
+            for _ in range(3):
+                again = conv(s)
+                if not torch.equal(again[0], first[0]):
+                    first = again
+            for li in range(launches):
+                out = conv(s)
+                if not torch.equal(out[0], first[0]):
+                    wrong_launches += 1
+                    if len(records) < 12:
+                        rec = explain(s, first[0], out[0], out[1])
+                        rec.update(set=si, launch=li)
+                        records.append(rec)
         torch.cuda.synchronize()
-        if vs_rolled is None:
-            vs_rolled = bool(torch.equal(first[0], reference[si][0]))      # two_acc rounds differently by design
-        # the variant's own majority value: three launches agreeing
-        for _ in range(3):
-            again = conv(s)
-            if not torch.equal(again[0], first[0]):
-                first = again
-        for li in range(launches):
-            out = conv(s)
-            if not torch.equal(out[0], first[0]):
-                wrong_launches += 1
-                if len(records) < 12:
-                    rec = explain(s, first[0], out[0], out[1])
-                    rec.update(set=si, launch=li)
-                    records.append(rec)
-    torch.cuda.synchronize()
     report["variants"][name] = dict(launches=launches * nsets, wrong_launches=wrong_launches, first_launch_equals_rolled=vs_rolled,
                                     seconds=round(time.time() - t0, 1), records=records)
     print(f"[flake] {name}: {wrong_launches} wrong of {launches * nsets} launches ({time.time() - t0:.1f} s)", file=sys.stderr, flush=True)
-use(None)
 print(json.dumps(report, indent=1))

@@ -36,12 +36,8 @@ def run(cfg, label):
             model(wl, seed=3 + i)
         torch.cuda.synchronize()
         tr = Tracer()
-        _lib._lib = tr
-        try:
-            with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU]) as prof:
-                model(wl, seed=9)
-        finally:
-            _lib._lib = real
+        with _lib.using(tr), torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU]) as prof:
+            model(wl, seed=9)                       # every header's entry points come from the one handle: all are seen
         torch.cuda.synchronize()
     aten = [e.key for e in prof.key_averages() if e.key.startswith("aten::")]
     n_aten = sum(e.count for e in prof.key_averages() if e.key.startswith("aten::"))
