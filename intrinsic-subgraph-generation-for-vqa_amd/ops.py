@@ -3342,6 +3342,8 @@ def linear_skinny(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gelu
     weight read as it is).  None when the operands' layout is not the kernel's (the caller takes the tile kernels)."""
     # (host time matters here -- a forward at this size is ~70 of these calls and the GPU needs ~10 us for each: every tensor
     # property is read once, nothing is detached or viewed)
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
     if x.dim() != 2 or weight.dim() != 2:
         return None
     M, K = x.shape
@@ -3429,6 +3431,8 @@ def linear_h3p(x, weight: Tensor, bias: Optional[Tensor] = None, gelu: bool = Fa
     """act(x @ weight^T + bias) on the planes32 engine.  x: Planes32 or fp32 rows (split here, once per tensor version).
     planes_out: the result as Planes32 (its columns padded with zeros to a multiple of 32), scaled by the bound known before the
     product -- the input of the next Linear with no pass over it; otherwise fp32 [M, N]."""
+    if relu and gelu:
+        raise ValueError("relu excludes gelu")
     lib = _lib.load()
     xp = x if isinstance(x, Planes32) else split_planes32(x)
     M, K = xp.rows, xp.cols
