@@ -244,6 +244,27 @@ def scatter_mean(msg, plan):
 
 
 # ------------------------------------------------------------------------------------------------
+# Training through shared scene encodings (include/ext/isg_instances_train.h)
+# ------------------------------------------------------------------------------------------------
+class _InstanceRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inst, x, e):
+        ctx.inst = inst
+        return inst.gather_rows(x, e)
+
+    @staticmethod
+    def backward(ctx, g_x, g_e):
+        d_x, d_e = ops.instance_rows_backward(ctx.inst, g_x.contiguous(), g_e.contiguous())
+        return None, d_x, d_e
+
+
+def instance_rows(inst, x, e):
+    """(x[inst.node_src], e[inst.edge_src]) of an ops.GraphInstances, one launch each way: forward isg_instance_rows, backward
+    isg_instance_rows_bwd -- per distinct row the sum of its copies' gradient rows in ascending instance number, no atomics."""
+    return _InstanceRows.apply(inst, x, e)
+
+
+# ------------------------------------------------------------------------------------------------
 # Scene-graph encoder without its concatenations (include/isg_sgenc_train.h)
 # ------------------------------------------------------------------------------------------------
 def _column_slice(t):

@@ -36,6 +36,72 @@ def gqa_collate(data: Sequence[tuple], scene_graphs, tokenizer: Optional[Callabl
     return out + (annotations.encode(annos, list(graph_ids), getattr(scene_graphs, "store", scene_graphs)),)
 
 
+class GroupedBatchSampler:
+    """A batch sampler (torch.utils.data.DataLoader(batch_sampler=...)) whose batches REPEAT scene graphs: every batch holds
+    `images_per_batch` images and up to `questions_per_image` questions of each -- what SceneGraphStore.collate(distinct=True)
+    and ISubGVQA.forward_shared are for; a shuffled sampler over GQA's questions almost never draws an image twice in one batch.
+
+    image_ids: the image of every dataset item, in item order (any hashable).  Per epoch the questions of an image are shuffled
+    and cut into groups of at most questions_per_image (the last group of an image is what is left over); the groups of all
+    images are shuffled and dealt into batches, and a group whose image already sits in the batch waits for the next one -- so a
+    batch never holds more than questions_per_image questions of an image.  Every question appears exactly once per epoch
+    (drop_last=True drops the batches with fewer than images_per_batch groups).  Deterministic per (seed, epoch): set_epoch()
+    as with torch's DistributedSampler.  Host only."""
+
+    def __init__(self, image_ids: Sequence, images_per_batch: int, questions_per_image: int, seed: int, drop_last: bool = False):
+        if int(images_per_batch) < 1 or int(questions_per_image) < 1:
+            raise ValueError(f"GroupedBatchSampler: images_per_batch = {images_per_batch}, questions_per_image = {questions_per_image}")
+        self.images_per_batch, self.questions_per_image = int(images_per_batch), int(questions_per_image)
+        self.seed, self.drop_last, self.epoch = int(seed), bool(drop_last), 0
+        by_image = {}
+        for i, image in enumerate(image_ids):
+            by_image.setdefault(image, []).append(i)
+        self._items = list(by_image.values())             # images in the order of their first question
+        self._made = None                                 # (epoch, batches)
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def _batches(self) -> list:
+        if self._made is not None and self._made[0] == self.epoch:
+            return self._made[1]
+        gen = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
+        groups = []                                       # (image number, item indices)
+        for image, items in enumerate(self._items):
+            order = torch.randperm(len(items), generator=gen).tolist()
+            for lo in range(0, len(items), self.questions_per_image):
+                groups.append((image, [items[j] for j in order[lo:lo + self.questions_per_image]]))
+        stream = [groups[j] for j in torch.randperm(len(groups), generator=gen).tolist()]
+        batches, waiting, pos = [], [], 0
+        while pos < len(stream) or waiting:
+            images, batch, still = set(), [], []
+            for group in waiting:                         # the groups that waited go first, in their order
+                if len(images) < self.images_per_batch and group[0] not in images:
+                    images.add(group[0])
+                    batch += group[1]
+                else:
+                    still.append(group)
+            while pos < len(stream) and len(images) < self.images_per_batch:
+                group = stream[pos]
+                pos += 1
+                if group[0] in images:
+                    still.append(group)
+                else:
+                    images.add(group[0])
+                    batch += group[1]
+            waiting = still
+            if len(images) == self.images_per_batch or not self.drop_last:
+                batches.append(batch)
+        self._made = (self.epoch, batches)
+        return batches
+
+    def __iter__(self):
+        return iter([list(b) for b in self._batches()])
+
+    def __len__(self) -> int:
+        return len(self._batches())
+
+
 class QuestionTypes:
     """The id space of the questions' types for an evaluation by type (include/isg_eval.h): every name of every facet gets ONE id
     in [0, num_groups), facet after facet, so two facets never share an id and one device table holds them all.

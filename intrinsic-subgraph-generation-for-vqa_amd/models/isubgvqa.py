@@ -172,6 +172,40 @@ class ISubGVQA(torch.nn.Module):
                                                                          inst.plan(), True, noises, seed)
         return (logits, imle_mask, gate, node_logits_layers, mask_text), inst
 
+    def forward_shared(self, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, graph_index,
+                       scene_graphs=None, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                       plan: Optional[ops.GraphPlan] = None, text_uniform: Optional[Tensor] = None):
+        """Q questions about the graphs graph_index[q] of a batch of G DISTINCT graphs, in either mode: (forward's 5-tuple,
+        ops.GraphInstances).
+        eval(): exactly encode_scene + ask, the same bits.
+        train(): the encoder runs ONCE per distinct graph with multiplicity = the number of questions per graph, so that its
+        BatchNorm layers see the statistics of the batch with every graph copied out; its rows are expanded into the instance
+        batch by autograd.instance_rows, whose backward sums a row's copies without atomics, and answer_graphs runs on the
+        instances as in ask().  A graph that no question names takes no part in the statistics and receives zero gradient from
+        the expansion.  `plan`: the distinct batch's GraphPlan (built here when None, as in encode_scene)."""
+        if not self.training:
+            state = self.encode_scene(node_embeddings, edge_index, edge_embeddings, batch, scene_graphs, plan)
+            return self.ask(state, questions, qsts_att_mask, graph_index, noises=noises, seed=seed, text_uniform=text_uniform)
+        if questions.size(0) != graph_index.numel():
+            raise ValueError(f"forward_shared(): {questions.size(0)} questions, {graph_index.numel()} entries of graph_index")
+        from .. import autograd
+        glf, instr_vectors = self.language_features(questions, qsts_att_mask, text_uniform, None if seed is None else seed + 7919)
+        mask_text = self.last_mask_text
+        if plan is None:
+            sizes = getattr(scene_graphs, "graph_sizes", None)
+            G = getattr(scene_graphs, "num_graphs", None)
+            if G is None and sizes is not None:
+                G = sizes.size(1)
+            plan = ops.GraphPlan.build(batch, edge_index, num_graphs=G, max_nodes=getattr(scene_graphs, "max_nodes", None),
+                                       max_edges=getattr(scene_graphs, "max_edges", None), graph_sizes=sizes)
+        inst = ops.graph_instances(plan, edge_index, graph_index, sizes=plan.sizes_host)
+        x_enc, e_enc = self.scene_graph_encoder(node_embeddings, edge_index=edge_index, edge_attr=edge_embeddings, batch=batch,
+                                                gt_scene_graphs=scene_graphs, plan=plan, multiplicity=inst.counts())
+        x, e = autograd.instance_rows(inst, x_enc, e_enc)
+        logits, imle_mask, gate, node_logits_layers = self.answer_graphs(x, inst.edge_index, e, inst.batch, instr_vectors, glf,
+                                                                         inst.plan(), True, noises, seed)
+        return (logits, imle_mask, gate, node_logits_layers, mask_text), inst
+
     def _captured(self, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, explainer, explainer_stage,
                   scene_graphs, noises, seed, plan, text_uniform):
         """forward() as a replayed hipGraph (ops.StepCapture), one capture per batch SHAPE -- the opt-in for evaluation loops whose

@@ -133,6 +133,39 @@ class _MetaLayer(torch.nn.Module):
         return ops.mlp(self.node_model.node_mlp_2, torch.cat([x, agg], dim=1)), e_new   # :142-143
 
 
+def weighted_batch_norm(bn: torch.nn.BatchNorm1d, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """A BatchNorm1d in train() over rows [N, C] of which row n stands for w[n] >= 0 equal rows: W = sum w, mean = sum w x / W,
+    biased var = sum w (x - mean)^2 / W -- the statistics, the result and (under autograd) the gradients of the module applied
+    to the rows physically repeated, up to rounding; a row of weight 0 takes no part.  The running statistics move as torch
+    moves them at W rows (unbiased factor W / (W - 1), `momentum` or the cumulative average, num_batches_tracked).  Torch ops:
+    these are reductions over [N, 4], [N, 16] and [N, 332], not a hot path.  Nothing here waits for the device (so W <= 1,
+    which torch refuses, is not looked for)."""
+    wc = w.to(x.dtype).unsqueeze(1)
+    W = wc.sum()
+    mean = (wc * x).sum(0) / W
+    xc = x - mean
+    var = (wc * xc * xc).sum(0) / W
+    if bn.track_running_stats and bn.running_mean is not None:
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+            f = 1.0 / bn.num_batches_tracked.to(x.dtype) if bn.momentum is None else bn.momentum
+            bn.running_mean.mul_(1.0 - f).add_(f * mean.detach().to(bn.running_mean.dtype))
+            bn.running_var.mul_(1.0 - f).add_(f * (var.detach() * (W / (W - 1.0))).to(bn.running_var.dtype))
+    y = xc * torch.rsqrt(var + bn.eps)
+    return y * bn.weight + bn.bias if bn.affine else y
+
+
+class _WeightedBatchNorm:
+    """What stands in for a BatchNorm1d of a Sequential handed to ops.mlp while a multiplicity is in force (no `weight` of its
+    own: ops.mlp calls it like any module that is no Linear)."""
+
+    def __init__(self, bn, w):
+        self.bn, self.w = bn, w
+
+    def __call__(self, x):
+        return weighted_batch_norm(self.bn, x, self.w)
+
+
 class SceneGraphEncoder(torch.nn.Module):
     def __init__(self, hidden_dim, dist=False, vocab_size: int = SG_VOCAB_SIZE, pad_idx: Optional[int] = 1):
         super().__init__()
@@ -149,14 +182,25 @@ class SceneGraphEncoder(torch.nn.Module):
                                               torch.nn.Linear(self.sg_emb_dim + 32, self.sg_emb_dim), torch.nn.GELU())
 
     def forward(self, x, edge_index, edge_attr, batch, explainer=False, explainer_stage=False, gt_scene_graphs=None,
-                plan: Optional[ops.GraphPlan] = None):
+                plan: Optional[ops.GraphPlan] = None, *, multiplicity: Optional[torch.Tensor] = None):
         # train(): the BatchNorm layers use batch statistics like the reference's (torch modules); the HIP operators of this
         # encoder (embedding sum, gather-add, scatter_mean, fp64 GraphNorm) differentiate through autograd.py
+        # multiplicity: int32 [G], how often every graph of this DISTINCT batch is asked (ops.GraphInstances.counts()).  In train()
+        # the three BatchNorm layers then weigh a node's row by its graph's count, which gives the statistics of the batch with
+        # every graph copied out (weighted_batch_norm); in eval() the layers run as they are.  None: nothing changes.
+        bbox_encoding, feat_reduc = self.bbox_encoding, self.feat_reduc
+        if multiplicity is not None and self.dist:
+            raise ValueError("SceneGraphEncoder: a multiplicity with SyncBatchNorm (dist=True) is not supported -- the weighted "
+                             "statistics would need a weighted all-reduce")
+        if multiplicity is not None and self.training:
+            w = multiplicity.index_select(0, batch)
+            weighted = lambda seq: [_WeightedBatchNorm(m, w) if isinstance(m, torch.nn.BatchNorm1d) else m for m in seq]
+            bbox_encoding, feat_reduc = weighted(bbox_encoding), weighted(feat_reduc)
         first = explainer and (explainer_stage == 0)
         x_embed_sum = x if first else ops.embedding_sum(self.sg_vocab_embedding.weight, x,     # :63-70 (sum of the token rows)
                                                         self.sg_vocab_embedding.padding_idx)
-        x_bbox = ops.mlp(self.bbox_encoding, gt_scene_graphs.x_bbox.to(dtype=x_embed_sum.dtype))   # :72
-        x_embed_sum = ops.mlp(self.feat_reduc, torch.cat((x_embed_sum, x_bbox), dim=1))  # :73-74
+        x_bbox = ops.mlp(bbox_encoding, gt_scene_graphs.x_bbox.to(dtype=x_embed_sum.dtype))   # :72
+        x_embed_sum = ops.mlp(feat_reduc, torch.cat((x_embed_sum, x_bbox), dim=1))  # :73-74
         sym = gt_scene_graphs.added_sym_edge
         if plan is None:
             plan = ops.GraphPlan.build(batch, edge_index)

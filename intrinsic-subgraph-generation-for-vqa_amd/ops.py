@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib, _lib_instances
+from . import _ext_instances_train, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -144,6 +144,7 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "mp_f16_train": 0,                         # message-passing backwards on saved half rows (include/isg_mp_f16_train.h)
             "linear_rowbias": 0,                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
             "graph_instances": 0,                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
+            "instance_rows_bwd": 0,                    # backwards of the instance-row gather (include/ext/isg_instances_train.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -870,14 +871,17 @@ class GraphInstances:
     ptr / eptr int32 [Q + 1]: node / edge range of every instance; batch int64 [N'] (value q on instance q's nodes); edge_index
     int64 [2, E'] between the instance batch's node numbers; node_src int64 [N'] / edge_src int64 [E']: the row of the parent
     batch every instance row is a copy of; status int32 [4] = (N', E', bad_index, bad_grouping) on the device; index int32 [Q] on
-    the device.  sizes_host: host int64 [2, Q] (nodes, edges per instance) when the caller knew the parent's on the host."""
+    the device.  sizes_host: host int64 [2, Q] (nodes, edges per instance) when the caller knew the parent's on the host.
+    erange int32 [G + 1]: the edge range of every graph of the parent batch, as the size pass left it in its workspace (the
+    backward of gather_rows reads it); index_host: the index as the caller gave it, when it came from the host."""
 
     def __init__(self, parent: "GraphPlan", index, ptr, eptr, batch, edge_index, node_src, edge_src, status, sizes_host=None,
-                 parent_edges=None):
+                 parent_edges=None, erange=None, index_host=None):
         self.parent, self.index, self.ptr, self.eptr, self.status, self.sizes_host = parent, index, ptr, eptr, status, sizes_host
         self.batch, self.edge_index, self.node_src, self.edge_src = batch, edge_index, node_src, edge_src
         self.parent_edges = parent.E if parent_edges is None else int(parent_edges)      # (a plan may have been built without edges)
-        self._plan = None
+        self.erange, self.index_host = erange, index_host
+        self._plan = self._by_graph = None
 
     @property
     def Q(self) -> int:
@@ -891,9 +895,32 @@ class GraphInstances:
         """t[edge_src] for a tensor with one row per edge of the parent batch (any dtype)."""
         return t.index_select(0, self.edge_src)
 
+    def by_graph(self) -> Tuple[Tensor, Tensor]:
+        """(gptr int32 [G + 1], glist int32 [Q]) on the device: glist[gptr[g] : gptr[g + 1]] are the instances of graph g in
+        ascending q -- the inverse of `index`, cached.  Made on the host when the index came from the host; otherwise by a stable
+        device sort of the [Q] index (the counts read off the sorted keys by a binary search, which unlike bincount does not wait
+        for the device).  An index outside [0, G) belongs to no graph: it sorts behind all of them."""
+        if self._by_graph is None:
+            G, dev = self.parent.B, self.index.device
+            idx = (self.index if self.index_host is None else self.index_host).long()
+            key = torch.where((idx >= 0) & (idx < G), idx, torch.full_like(idx, G))
+            key, order = torch.sort(key, stable=True)
+            gptr = torch.searchsorted(key, torch.arange(G + 1, dtype=torch.int64, device=key.device))
+            self._by_graph = (gptr.to(device=dev, dtype=torch.int32), order.to(device=dev, dtype=torch.int32))
+        return self._by_graph
+
+    def counts(self) -> Tensor:
+        """int32 [G] on the device: the number of instances of every graph of the parent batch."""
+        gptr = self.by_graph()[0]
+        return gptr[1:] - gptr[:-1]
+
     def gather_rows(self, x: Tensor, e: Tensor) -> Tuple[Tensor, Tensor]:
         """(x[node_src], e[edge_src]) for fp32 rows in ONE launch (isg_instance_rows): x [N, Cx], e [E, Ce], widths and row strides
-        multiples of 4, rows 16-byte aligned."""
+        multiples of 4, rows 16-byte aligned.  When autograd records through x or e: autograd.instance_rows, whose backward is
+        instance_rows_backward."""
+        if _rec(x, e):
+            from . import autograd
+            return autograd.instance_rows(self, x, e)
         lib = _lib_instances.load()
         px, pe = _chk_rows(x, "x"), _chk_rows(e, "e")
         if x.size(0) != self.parent.N or e.size(0) != self.parent_edges:
@@ -981,7 +1008,37 @@ def graph_instances(plan: "GraphPlan", edge_index: Tensor, index: Tensor, sizes:
                                       b64, b64 + 8 * (2 * Np), b64 + 8 * Np, b64 + 8 * (2 * Np + 2 * Ep), _stream()),
                "isg_instances_fill")
     return GraphInstances(plan, idx, ptr, eptr, i64[:Np], i64[2 * Np:2 * Np + 2 * Ep].view(2, Ep), i64[Np:2 * Np],
-                          i64[2 * Np + 2 * Ep:2 * Np + 3 * Ep], status, sizes_host, E)
+                          i64[2 * Np + 2 * Ep:2 * Np + 3 * Ep], status, sizes_host, E, erange=i32[n32:n32 + G + 1] if Q else None,
+                          index_host=index if index.device.type == "cpu" else None)
+
+
+def instance_rows_backward(inst: GraphInstances, g_x: Tensor, g_e: Tensor) -> Tuple[Tensor, Tensor]:
+    """The backward of GraphInstances.gather_rows in ONE launch (isg_instance_rows_bwd): g_x fp32 [N', Cx] and g_e fp32 [E', Ce],
+    gradients of the instance batch's rows -> (d_x [N, Cx], d_e [E, Ce]) of the parent batch's: per distinct row the sum of its
+    copies' rows in ascending instance number, plain fp32 adds, no atomics -- two calls agree bit for bit.  Every row is written;
+    the rows of a graph that no instance names are +0."""
+    lib = _ext_instances_train.load()
+    pgx, pge = _chk_rows(g_x, "g_x"), _chk_rows(g_e, "g_e")
+    n, m = inst.node_src.numel(), inst.edge_src.numel()
+    if g_x.size(0) != n or g_e.size(0) != m:
+        raise ValueError(f"instance_rows_backward: expected {n} node rows and {m} edge rows, got {g_x.size(0)} and {g_e.size(0)}")
+    if (g_x.size(1) & 3) or (g_e.size(1) & 3):
+        raise ValueError(f"instance_rows_backward: row widths must be multiples of 4, got {g_x.size(1)} and {g_e.size(1)}")
+    N, E, G, Q = inst.parent.N, inst.parent_edges, inst.parent.B, inst.Q
+    dx = torch.empty(N, g_x.size(1), dtype=torch.float32, device=g_x.device)
+    de = torch.empty(E, g_e.size(1), dtype=torch.float32, device=g_e.device)
+    if Q == 0 or inst.erange is None:            # nothing was expanded: no copies, every sum is empty
+        return dx.zero_(), de.zero_()
+    gptr, glist = inst.by_graph()
+    COUNTERS["instance_rows_bwd"] += 1
+    _lib.check(lib.isg_instance_rows_bwd(pgx, g_x.stride(0), n, dx.data_ptr(), g_x.size(1), N, g_x.size(1),
+                                         pge, g_e.stride(0), m, de.data_ptr(), g_e.size(1), E, g_e.size(1),
+                                         _chk(inst.parent.ptr, "plan.ptr", torch.int32, (G + 1,)),
+                                         _chk(inst.erange, "erange", torch.int32, (G + 1,)),
+                                         _chk(inst.ptr, "inst.ptr", torch.int32, (Q + 1,)), _chk(inst.eptr, "inst.eptr", torch.int32, (Q + 1,)),
+                                         _chk(gptr, "gptr", torch.int32, (G + 1,)), _chk(glist, "glist", torch.int32, (Q,)), G, Q,
+                                         _stream()), "isg_instance_rows_bwd")
+    return dx, de
 
 
 # ------------------------------------------------------------------------------------------------
@@ -4063,7 +4120,8 @@ def cat_mul_mlp(seq: torch.nn.Sequential, a: Tensor, b: Tensor, want_rowmax: boo
 
 
 def mlp(seq: torch.nn.Sequential, x: Tensor, want_rowmax: bool = False) -> Tensor:   # x may be fp16 feature rows; the output is fp32
-    """Run an nn.Sequential of Linear / GELU / Dropout(eval) modules with every Linear(+GELU) pair as one launch.
+    """Run an nn.Sequential of Linear / GELU / Dropout(eval) modules with every Linear(+GELU) pair as one launch (or a plain list
+    of its modules, some replaced by callables: the scene-graph encoder's weighted BatchNorm; what is no Linear is simply called).
     ``want_rowmax``: the caller feeds the result to another Linear (the last launch's epilogue leaves its row maxima on it)."""
     mods = list(seq)
     i = 0

@@ -117,6 +117,35 @@ def _logits(model, inputs, seed: Optional[int]) -> Tensor:
     return out[0] if isinstance(out, tuple) else out
 
 
+class SharedScenes(torch.nn.Module):
+    """A model seen through ISubGVQA.forward_shared: forward(**inputs) returns its 5-tuple (the GraphInstances is dropped), so
+    train_step and validate drive a batch of distinct scene graphs with a graph index like any other batch.  The step counters
+    are the wrapped model's."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    @property
+    def n_train_steps(self):
+        return self.model.n_train_steps
+
+    @n_train_steps.setter
+    def n_train_steps(self, value):
+        self.model.n_train_steps = value
+
+    @property
+    def n_valid_steps(self):
+        return self.model.n_valid_steps
+
+    @n_valid_steps.setter
+    def n_valid_steps(self, value):
+        self.model.n_valid_steps = value
+
+    def forward(self, **inputs):
+        return self.model.forward_shared(**inputs)[0]
+
+
 def train_step(model, optimizer, inputs, labels: Tensor, meters: Meters, seed: Optional[int] = None, sync=None, accumulate: int = 1,
                micro: int = 0) -> ops.CrossEntropy:
     """One step of the reference's train_epoch body, in its order: n_train_steps += B, the forward (`inputs`: a dict of keyword

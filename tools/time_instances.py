@@ -13,7 +13,16 @@ Before anything is timed the two forwards are compared: questions whose top-k ma
 scores lie within 1e-4 of each other for a few questions in a thousand, and the encoder's Linears take other kernels at G rows than
 at Q rows), and on all other questions the logits must agree within 1e-4 and the gates within 1e-5.
 One sample = REPS calls between two events; per round the arms run one after the other; median, minimum and maximum over the
-rounds (two more are run first and discarded).  A record, not a gate."""
+rounds (two more are run first and discarded).  A record, not a gate.
+
+  python tools/time_instances.py --train [--questions 4096] [--rounds 6] [--out profiles/<name>.json]
+
+Training through shared encodings (include/ext/isg_instances_train.h), the same method in train(): forward +
+backward of the replicated step (forward() on the batch with every graph copied out) against the shared one
+(ISubGVQA.forward_shared: the encoder once per distinct graph with weighted BatchNorm statistics, the instance rows' backward as
+one launch) at 1, 4 and 12 questions per graph.  Besides the two steps: the new launch alone (isg_instance_rows_bwd), a device
+copy_ of the same rows (the rate it is held against) and the generic route it replaces, ops.token_csr over the N' + E' row numbers
++ isg_segment_rows_sum (two stable device sorts per step)."""
 import json
 import os
 import sys
@@ -53,6 +62,86 @@ def rounds(arms):
                 us[a].append(t)
     return {a: {"median_us": round(median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)} for a, v in us.items()}
 
+
+def train_main():
+    torch.manual_seed(0)
+    model = build_model(synthetic.full_model_args(sampler_type="gumbel"), None).to(dev).train()
+    out = {"device": torch.cuda.get_device_name(0), "mode": "train(): forward + backward, Gumbel sampler, dropout as configured",
+           "method": f"HIP events around {REPS} calls; {ROUNDS} rounds behind {SKIP} discarded ones, the arms alternating inside a "
+                     f"round; median (min-max) us per call", "settings": {}}
+    for qpg in (1, 4, 12):
+        G = QUESTIONS // qpg
+        wl = synthetic.make_shared_workload(G, qpg, seed=7)
+        wl.added_sym_edge = wl.added_sym_edge[:0]          # the two forms are equal only without the un-offset flips (quirk Q6)
+        rep = wl.replicated()
+        Q = wl.graph_index.numel()
+        d, dr, index = wl.to(dev), rep.to(dev), wl.graph_index
+        sg, sgr = d.scene_graphs(), dr.scene_graphs()
+        w = torch.randn(Q, 1842, generator=torch.Generator().manual_seed(1)).to(dev)
+
+        def replicated_step():
+            model.zero_grad(set_to_none=True)
+            res = model(dr.x, dr.edge_index, dr.edge_attr, dr.batch, dr.questions, dr.att_mask, return_masks=True, scene_graphs=sgr, seed=3)
+            (res[0] * w).sum().backward()
+
+        def shared_step():
+            model.zero_grad(set_to_none=True)
+            res, _ = model.forward_shared(d.x, d.edge_index, d.edge_attr, d.batch, d.questions, d.att_mask, index, scene_graphs=sg, seed=3)
+            (res[0] * w).sum().backward()
+
+        plan = ops.GraphPlan.build(d.batch, d.edge_index, num_graphs=G, max_nodes=wl.max_nodes, max_edges=wl.max_edges,
+                                   graph_sizes=wl.graph_sizes)
+        inst = ops.graph_instances(plan, d.edge_index, index, sizes=wl.graph_sizes)
+        inst.by_graph()
+        N, E, Np, Ep, C = wl.x.size(0), wl.edge_index.size(1), inst.node_src.numel(), inst.edge_src.numel(), 300
+        gx, ge = torch.randn(Np, C, device=dev), torch.randn(Ep, C, device=dev)
+        x_dst, e_dst = torch.empty_like(gx), torch.empty_like(ge)
+
+        def generic():
+            rp, eid = ops.token_csr(inst.node_src, N)
+            dx = ops.segment_rows_sum(rp, eid, gx)
+            rp, eid = ops.token_csr(inst.edge_src, E)
+            return dx, ops.segment_rows_sum(rp, eid, ge)
+
+        with torch.no_grad():
+            dx, de = ops.instance_rows_backward(inst, gx, ge)
+            gdx, gde = generic()
+            torch.cuda.synchronize()
+            err = max(float((dx - gdx).abs().max()), float((de - gde).abs().max()))
+            assert err < 1e-4, err                              # the same sums, in another order
+        arms = {"replicated_step": replicated_step, "shared_step": shared_step}
+        row = rounds(arms)
+        with torch.no_grad():
+            row.update(rounds({"rows_backward": lambda: ops.instance_rows_backward(inst, gx, ge),
+                               "inverse_lists": lambda: (setattr(inst, "_by_graph", None), inst.by_graph()),
+                               "row_copy": lambda: (x_dst.copy_(gx), e_dst.copy_(ge)),
+                               "token_csr_and_segment_rows_sum": generic}))
+        ops.check_plans()
+        bwd_bytes = (Np + Ep + N + E) * C * 4                  # every gradient row read once, every distinct row written once
+        copy_bytes = (Np + Ep) * 2 * C * 4
+        rf, sh = row["replicated_step"]["median_us"], row["shared_step"]["median_us"]
+        spread = max(row[a]["max_us"] - row[a]["min_us"] for a in ("replicated_step", "shared_step"))
+        row.update({"graphs": G, "questions": Q, "N": N, "E": E, "N_instances": Np, "E_instances": Ep,
+                    "shared_over_replicated": round(sh / rf, 4), "diff_us": round(sh - rf, 1), "larger_round_spread_us": round(spread, 1),
+                    "verdict": "faster" if sh - rf < -spread else "slower" if sh - rf > spread else "within the round spread",
+                    "rows_backward_GB_per_s": round(bwd_bytes / row["rows_backward"]["median_us"] / 1e3, 1),
+                    "copy_GB_per_s": round(copy_bytes / row["row_copy"]["median_us"] / 1e3, 1),
+                    "max_abs_diff_to_the_generic_route": err})
+        out["settings"][f"{qpg} questions per graph"] = row
+        print(f"train, {qpg} per graph (G={G}, Q={Q}, N'={Np}, E'={Ep}): replicated step {rf:.0f} us, shared step {sh:.0f} us "
+              f"({row['shared_over_replicated']:.3f}, {row['verdict']}); rows backward {row['rows_backward']['median_us']:.0f} us "
+              f"({row['rows_backward_GB_per_s']} GB/s; copy of the rows {row['row_copy']['median_us']:.0f} us, {row['copy_GB_per_s']} GB/s; "
+              f"token_csr + segment_rows_sum {row['token_csr_and_segment_rows_sum']['median_us']:.0f} us; inverse lists "
+              f"{row['inverse_lists']['median_us']:.0f} us)", flush=True)
+        del d, dr, inst, gx, ge, x_dst, e_dst, plan
+    if "--out" in opt:
+        with open(opt["--out"], "w") as fh:
+            fh.write(json.dumps(out, indent=1) + "\n")
+
+
+if "--train" in argv:
+    train_main()
+    sys.exit(0)
 
 torch.manual_seed(0)
 model = build_model(synthetic.full_model_args(), None).to(dev).eval()
