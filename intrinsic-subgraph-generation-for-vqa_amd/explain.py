@@ -10,6 +10,10 @@ The reference's third question is lexical (run_token_coo.py:145-185, utils/token
 nodes, and how many of the question's words that name an object of the graph were picked.  `TokenTables` turns the strings into
 vocabulary ids once, `ops.token_coo` scores whole batches on the device into running totals, `CooReport` reads them -- the one
 device-to-host copy of an evaluation (`evaluate`).
+
+Something to hold the intrinsic mask against: `occlusion` gives leave-one-out attributions -- a forward-only post-hoc baseline on
+the batch of instances `ops.induced_instances` makes in one pass --, `faithfulness_of_mask` asks the two fidelity questions of ANY
+node mask, and `compare` reports the model's own mask, the occlusion mask and a random one by the same yardsticks.
 """
 from __future__ import annotations
 
@@ -83,29 +87,46 @@ def _per_graph_any(flags: Tensor, batch: Tensor, B: int) -> Tensor:
     return torch.zeros(B, dtype=torch.int64, device=flags.device).index_add_(0, batch, flags.long()) > 0
 
 
-def faithfulness(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
-                 threshold: float = 0.0) -> Faithfulness:
-    """One forward, the keep-cut and the removal-cut of its node mask, one forward on each.  `inputs`: a synthetic.Workload for
-    an AnswerModel, a synthetic.FullWorkload (or any object with its fields and scene_graphs()) for ISubGVQA.  A graph that a cut
-    would leave without nodes goes through that forward whole (the flags are adjusted before the cut): the model never sees an
-    empty graph it was not given."""
+def _forwarder(model, inputs, noises, seed):
+    """(full, B, forward) of a model and its batch: forward(x, edge_index, edge_attr, batch, sg, plan, rows=None, noises=...) ->
+    (logits, mask) on a batch cut at the model's input.  rows: int64 [B'] -- row r of the question side is question rows[r] of
+    `inputs` (a batch of instances); None: the questions as they are."""
     full = not isinstance(model, synthetic.AnswerModel)
     B = int(inputs.questions.size(0) if full else inputs.glf.size(0))
+
+    def forward(x, edge_index, edge_attr, batch, sg, p, rows=None, nz=noises):
+        if full:
+            q, am = (inputs.questions, inputs.att_mask) if rows is None else (inputs.questions.index_select(0, rows),
+                                                                            inputs.att_mask.index_select(0, rows))
+            out = model(x, edge_index, edge_attr, batch, q, am, return_masks=True, scene_graphs=sg, noises=nz, seed=seed, plan=p)
+        else:
+            instr, glf = (inputs.instr, inputs.glf) if rows is None else (inputs.instr.index_select(1, rows).contiguous(),
+                                                                          inputs.glf.index_select(0, rows))
+            out = model(synthetic.Workload(x, edge_index, edge_attr, batch, instr, glf, glf.size(0), inputs.max_nodes,
+                                           inputs.max_edges, None), noises=nz, seed=seed, plan=p)
+        return out[0], out[1]
+
+    return full, B, forward
+
+
+def _input_plan(inputs, B: int) -> "ops.GraphPlan":
+    return ops.GraphPlan.build(inputs.batch, inputs.edge_index, num_graphs=B, max_nodes=inputs.max_nodes or None,
+                               max_edges=inputs.max_edges or None, graph_sizes=inputs.graph_sizes)
+
+
+def faithfulness_of_mask(model, inputs, mask: Tensor, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                         threshold: float = 0.0, logits: Optional[Tensor] = None, plan: Optional["ops.GraphPlan"] = None) -> Faithfulness:
+    """faithfulness() for ANY node mask (fp32 [N] or [N, 1]; kept where > threshold): the keep-cut and the removal-cut of the
+    mask, one forward on each, scored against the model's answer on the whole batch -- `logits` when the caller has them (with
+    the `plan` of that forward), else one forward more.  This is how an explainer other than the model's own sampler (occlusion,
+    a random baseline) is measured with the intrinsic mask's yardstick."""
+    full, B, forward = _forwarder(model, inputs, noises, seed)
     with torch.no_grad():
-        plan = ops.GraphPlan.build(inputs.batch, inputs.edge_index, num_graphs=B, max_nodes=inputs.max_nodes or None,
-                                   max_edges=inputs.max_edges or None, graph_sizes=inputs.graph_sizes)
-
-        def forward(x, edge_index, edge_attr, batch, sg, p):
-            if full:
-                out = model(x, edge_index, edge_attr, batch, inputs.questions, inputs.att_mask, return_masks=True,
-                            scene_graphs=sg, noises=noises, seed=seed, plan=p)
-            else:
-                out = model(synthetic.Workload(x, edge_index, edge_attr, batch, inputs.instr, inputs.glf, B, inputs.max_nodes,
-                                               inputs.max_edges, None), noises=noises, seed=seed, plan=p)
-            return out[0], out[1]
-
+        if plan is None:
+            plan = _input_plan(inputs, B)
         sg = inputs.scene_graphs() if full else None
-        logits, mask = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan)
+        if logits is None:
+            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan)[0]
         flat = mask.reshape(-1)
         keep = flat > threshold
         has_nodes = (plan.ptr[1:] > plan.ptr[:-1])
@@ -126,6 +147,124 @@ def faithfulness(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, s
         scores = fidelity_scores(logits, outs[0], outs[1], emptied)
         scores = scores._replace(fid_minus=torch.where(kept_none, torch.full_like(scores.p, float("nan")), scores.fid_minus))
     return Faithfulness(scores, logits, outs[0], outs[1], mask, kept_none, cuts[0], cuts[1])
+
+
+def faithfulness(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                 threshold: float = 0.0) -> Faithfulness:
+    """One forward, the keep-cut and the removal-cut of its node mask, one forward on each.  `inputs`: a synthetic.Workload for
+    an AnswerModel, a synthetic.FullWorkload (or any object with its fields and scene_graphs()) for ISubGVQA.  A graph that a cut
+    would leave without nodes goes through that forward whole (the flags are adjusted before the cut): the model never sees an
+    empty graph it was not given.  (The forward, then faithfulness_of_mask on its mask.)"""
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        plan = _input_plan(inputs, B)
+        logits, mask = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
+                               plan)
+    return faithfulness_of_mask(model, inputs, mask, noises=noises, seed=seed, threshold=threshold, logits=logits, plan=plan)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A post-hoc baseline: leave-one-out (occlusion) attributions
+# ---------------------------------------------------------------------------------------------------------------------
+def shifted_attributions(attribution: Tensor, batch: Tensor, B: int) -> Tensor:
+    """fp32 [N]: the attributions moved per graph so that the smallest of a graph is 1 (a - min_g + 1) -- scores for
+    ops.topk_threshold, in whose padded rows the pads hold 0 and compete: after the shift no pad beats a node, however negative
+    its attribution.  The order inside a graph is kept; two attributions closer than the fp32 spacing near their shifted value
+    (1.2e-7 to 2.4e-7 for probabilities) become a tie, and a threshold top-k keeps both."""
+    a = attribution.float().reshape(-1)
+    low = torch.full((B,), float("inf"), dtype=torch.float32, device=a.device).scatter_reduce(0, batch, a, "amin")
+    return a - low.index_select(0, batch) + 1.0
+
+
+def instance_sym_edges(sym: Optional[Tensor], edge_src: Tensor, E: int) -> Optional[Tensor]:
+    """added_sym_edge across a batch of instances: the positions (ascending) of every instance edge whose parent edge the old list
+    names.  The old list holds positions in the parent's GLOBAL edge list (quirk Q6); those beyond it name nothing, and an edge
+    named several times is flipped once by the encoder, so one entry per instance edge is the same flip."""
+    if sym is None:
+        return None
+    p = sym.long()
+    p = p[(p >= 0) & (p < E)]
+    named = torch.zeros(E, dtype=torch.bool, device=edge_src.device)
+    named[p] = True
+    return torch.nonzero(named.index_select(0, edge_src)).reshape(-1)
+
+
+def instance_inputs(inputs, inst: "ops.GraphInstances", full: bool):
+    """(x, edge_index, edge_attr, batch, scene_graphs or None) of a batch of instances of `inputs`' graphs, cut at the model's
+    input as faithfulness() cuts it: node and edge rows through node_src / edge_src, x_bbox gathered, added_sym_edge following
+    its edges (instance_sym_edges).  The question side is gathered by the caller through inst.index."""
+    x, ea = inst.gather_nodes(inputs.x), inst.gather_edges(inputs.edge_attr)
+    sg = None
+    if full:
+        src = inputs.scene_graphs()
+        sg = argparse.Namespace(x_bbox=inst.gather_nodes(src.x_bbox),
+                                added_sym_edge=instance_sym_edges(getattr(src, "added_sym_edge", None), inst.edge_src,
+                                                                  inputs.edge_index.size(1)),
+                                max_nodes=getattr(src, "max_nodes", None), max_edges=getattr(src, "max_edges", None))
+    return x, inst.edge_index, ea, inst.batch, sg
+
+
+@dataclass
+class Occlusion:
+    """Leave-one-out attributions of one batch (occlusion())."""
+    pred: Tensor                   # int64 [B]: the class predicted on the whole graph
+    p: Tensor                      # fp32 [B]: its softmax probability on the whole graph
+    attribution: Tensor            # fp32 [N]: p[g] - (that class's probability with node n removed); 0 on the nodes of `single` graphs
+    single: Tensor                 # bool [B]: fewer than 2 nodes -- no node can be removed, the graph got no instance
+    index: Tensor                  # int32 [Q]: the graph of every leave-one-out instance
+    inst_node: Tensor              # int64 [Q]: the node (row of the batch) every instance lacks
+    p_without: Tensor              # fp32 [Q]: the predicted class's probability on every instance
+    logits: Tensor                 # [B, classes] of the whole batch
+    plan: "ops.GraphPlan"
+    chunks: List["ops.InducedInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph whose removal costs the answer most --
+        ops.topk_threshold on shifted_attributions (the samplers' zero pads compete and lose).  A graph with fewer than k nodes
+        keeps them all; ties at the k-th value are all kept, as the samplers' threshold keeps them."""
+        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+
+def occlusion(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+              max_instances: Optional[int] = None) -> Occlusion:
+    """Leave-one-out (occlusion) attribution of every node: the change of the predicted answer's probability when that node is
+    removed from its scene graph -- a forward-only post-hoc baseline for the intrinsic mask.  One forward on the batch for `pred`
+    and `p`; then the batch of leave-one-out instances (ops.keep_bits_leave_one_out, ops.induced_instances: graph g gives n_g
+    instances, each without one node and its edges), cut at the model's input as faithfulness() cuts it, forwarded in chunks of
+    at most `max_instances` instances (None: all at once).  `inputs` as for faithfulness().  The removed node is removed BEFORE
+    the encoder (the full model encodes every instance).
+
+    A graph with fewer than 2 nodes has no instance: its attribution is 0 and it is flagged in `single`.  With a noisy sampler
+    (gumbel, simple; `noises` rows are handed to an instance by its graph, where the columns behind the removed node name the next
+    node) the attribution carries sampling noise: the difference of two draws, not of two expectations.  The eval solve of the
+    imle / aimle samplers is noise-free."""
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    if max_instances is not None and int(max_instances) < 1:
+        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    with torch.no_grad():
+        plan = _input_plan(inputs, B)
+        sg = inputs.scene_graphs() if full else None
+        logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan)[0]
+        prob = torch.softmax(logits.float(), dim=1)
+        pred = prob.argmax(dim=1)
+        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
+        index, keep, inst_node = ops.keep_bits_leave_one_out(plan)
+        Q = index.numel()
+        step = Q if max_instances is None else int(max_instances)
+        chunks, parts = [], []
+        for lo in range(0, Q, max(step, 1)):
+            rows = index[lo:lo + step].long()
+            inst = ops.induced_instances(plan, inputs.edge_index, index[lo:lo + step].contiguous(), keep[lo:lo + step].contiguous())
+            nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
+            out = forward(*instance_inputs(inputs, inst, full), inst.plan(), rows, nz)[0]
+            parts.append(torch.softmax(out.float(), dim=1).gather(1, pred.index_select(0, rows).unsqueeze(1)).squeeze(1))
+            chunks.append(inst)
+        p_without = torch.cat(parts) if parts else p.new_zeros(0)
+        attribution = torch.zeros(plan.N, dtype=torch.float32, device=logits.device)
+        attribution[inst_node] = p.index_select(0, index.long()) - p_without
+        single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
+    return Occlusion(pred, p, attribution, single, index, inst_node, p_without, logits, plan, chunks)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -386,3 +525,109 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
         report = replace(report, by_type=by_type)
         ground_report = replace(ground_report, by_type=ground_by_type)
     return replace(report, grounding=ground_report)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The intrinsic mask beside post-hoc baselines
+# ---------------------------------------------------------------------------------------------------------------------
+EXPLAINERS = ("intrinsic", "occlusion", "random")
+COMPARE_SUMS = 6       # float64 per explainer: sum fid_plus, questions that have one, sum fid_minus, questions that have one,
+                       # sum of the Jaccard overlaps with the intrinsic mask, graphs that have one
+
+
+@dataclass(frozen=True)
+class ExplainerReport:
+    """One explainer's masks over an evaluation (compare()); NaN where no question has the quantity."""
+    coo: CooReport                           # token co-occurrence of its masks (the model's predictions are the same for all)
+    grounding: Optional[GroundingReport]     # against the annotated objects, when every batch carried `gold`
+    fid_plus: float                          # mean over the questions that have one (faithfulness_of_mask)
+    fid_minus: float
+    jaccard: float                           # mean over the graphs of |mask & intrinsic| / |mask | intrinsic| (graphs where both are empty: none)
+    sums: Tuple[float, ...]                  # the COMPARE_SUMS totals behind the three means
+
+
+def random_mask(plan: "ops.GraphPlan", k, seed: int) -> Tensor:
+    """fp32 [N, 1], k-hot per graph: ops.topk_threshold on seeded noise alone (uniform in [1, 2), so no zero pad is picked)."""
+    gen = torch.Generator(device=plan.ptr.device).manual_seed(int(seed))
+    scores = 1.0 + torch.rand(plan.N, 1, generator=gen, device=plan.ptr.device)
+    return ops.topk_threshold(scores, k, plan=plan)
+
+
+def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: float = 0.0) -> Tensor:
+    """float64 [2] on the device: (sum over the graphs of |a & b| / |a | b|, graphs where a | b is not empty)."""
+    a, b = mask.reshape(-1) > threshold, other.reshape(-1) > threshold
+    z = torch.zeros(B, dtype=torch.float64, device=batch.device)
+    inter, union = z.index_add(0, batch, (a & b).double()), z.index_add(0, batch, (a | b).double())
+    some = union > 0
+    return torch.stack([torch.where(some, inter / union.clamp_min(1.0), torch.zeros_like(z)).sum(), some.double().sum()])
+
+
+def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
+            threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None) -> Dict[str, ExplainerReport]:
+    """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
+    explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
+    mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
+    intrinsic: the forward's own mask; occlusion: occlusion().mask(k); random: random_mask(plan, k, seed + batch number).
+    Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate()."""
+    names_x = tuple(explainers)
+    unknown = [x for x in names_x if x not in EXPLAINERS]
+    if unknown or not names_x:
+        raise ValueError(f"compare: explainers from {EXPLAINERS}, got {names_x}")
+    X = len(names_x)
+    full = not isinstance(model, synthetic.AnswerModel)
+    flat = coo = ground = sums = None
+    with_gold = None
+    per = ops.COO_TOTALS + ops.GROUND_TOTALS + COMPARE_SUMS
+    with torch.no_grad():
+        for number, b in enumerate(batches):
+            inp = b.inputs
+            if b.graph_index is not None:
+                raise ValueError("compare: one graph per question (occlusion on shared encodings would leave the removed node "
+                                 "seen by the encoder)")
+            B = int(inp.questions.size(0) if full else inp.glf.size(0))
+            plan = _input_plan(inp, B)
+            _, _, forward = _forwarder(model, inp, None, None)
+            logits, intrinsic = forward(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.scene_graphs() if full else None, plan)
+            gold = getattr(b, "gold", None)
+            if with_gold is None:
+                with_gold = gold is not None
+                flat = torch.zeros(X * per, dtype=torch.int64, device=logits.device)      # int64 words; the sums are float64 in theirs
+                coo = flat[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS)
+                ground = flat[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
+                sums = flat[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):].view(torch.float64).view(X, COMPARE_SUMS)
+            elif with_gold != (gold is not None):
+                raise ValueError("compare: every EvalBatch carries gold, or none does")
+            names = inp.x[:, 0] if b.names is None else b.names
+            pred = logits.argmax(dim=1)
+            for x, name in enumerate(names_x):
+                if name == "intrinsic":
+                    mask = intrinsic
+                elif name == "occlusion":
+                    mask = occlusion(model, inp, max_instances=max_instances).mask(k)
+                else:
+                    mask = random_mask(plan, k, seed + number)
+                ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,
+                              threshold=threshold, totals=coo[x])
+                if with_gold:
+                    ops.grounding(mask, plan, gold.to(logits.device, non_blocking=True), pred, b.label, threshold=threshold,
+                                  totals=ground[x])
+                f = faithfulness_of_mask(model, inp, mask, threshold=threshold, logits=logits, plan=plan).scores
+                has_p, has_m = ~torch.isnan(f.fid_plus), ~torch.isnan(f.fid_minus)
+                sums[x] += torch.cat([torch.stack([torch.where(has_p, f.fid_plus, torch.zeros_like(f.fid_plus)).double().sum(),
+                                                   has_p.double().sum(),
+                                                   torch.where(has_m, f.fid_minus, torch.zeros_like(f.fid_minus)).double().sum(),
+                                                   has_m.double().sum()]),
+                                      jaccard_sums(mask, intrinsic, inp.batch, B, threshold)])
+    if flat is None:
+        flat = torch.zeros(X * per, dtype=torch.int64)
+        with_gold = False
+    host = flat.cpu()                                        # every explainer's totals: the one device-to-host copy
+    coo_h = host[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS).tolist()
+    ground_h = host[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
+    sums_h = host[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):].view(torch.float64).view(X, COMPARE_SUMS).tolist()
+    out = {}
+    for x, name in enumerate(names_x):
+        s = tuple(float(v) for v in sums_h[x])
+        out[name] = ExplainerReport(CooReport.from_totals(coo_h[x]), GroundingReport.from_totals(ground_h[x]) if with_gold else None,
+                                    _mean(s[0], s[1]), _mean(s[2], s[3]), _mean(s[4], s[5]), s)
+    return out

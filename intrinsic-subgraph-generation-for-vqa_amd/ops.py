@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _ext_instances_train, _lib, _lib_instances
+from . import _ext_induced, _ext_instances_train, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -145,6 +145,7 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "linear_rowbias": 0,                       # Linears with a bias row per graph (include/isg_concat.h; concat_instr layers)
             "graph_instances": 0,                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
             "instance_rows_bwd": 0,                    # backwards of the instance-row gather (include/ext/isg_instances_train.h)
+            "induced_instances": 0,                    # batches of induced-subgraph instances (include/ext/isg_induced.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1039,6 +1040,145 @@ def instance_rows_backward(inst: GraphInstances, g_x: Tensor, g_e: Tensor) -> Tu
                                          _chk(gptr, "gptr", torch.int32, (G + 1,)), _chk(glist, "glist", torch.int32, (Q,)), G, Q,
                                          _stream()), "isg_instance_rows_bwd")
     return dx, de
+
+
+# ------------------------------------------------------------------------------------------------
+# Induced-subgraph instances: every instance a graph of the parent batch minus some of its nodes
+# ------------------------------------------------------------------------------------------------
+INDUCED_WORDS_MAX = 64      # words of keep bits per instance, one per lane of the instance's wave (IND_WORDS_MAX in csrc/isg_induced.hip)
+
+
+class InducedInstances(GraphInstances):
+    """What isg_induced_size / isg_induced_fill left on the device (include/ext/isg_induced.h): instance q is graph index[q] of
+    the parent batch with the nodes its row of `keep` names, and the edges among them.  The fields are GraphInstances'; node_src /
+    edge_src name the parent row of every instance row, so gather_nodes / gather_edges / gather_rows (without autograd), plan()
+    and verify() work as on the parent class -- an instance is no larger than its graph, the parent's bounds stay valid hints.
+    keep uint32 [Q, W] on the device, or None (every node kept).
+
+    These are inference forms: the instance-row backward assumes whole copies of a graph's rows at computable addresses, so
+    gather_rows under autograd, by_graph() and counts() raise."""
+
+    def __init__(self, *args, keep=None, **kw):
+        super().__init__(*args, **kw)
+        self.keep = keep
+
+    def gather_rows(self, x: Tensor, e: Tensor) -> Tuple[Tensor, Tensor]:
+        if _rec(x, e):
+            raise NotImplementedError("InducedInstances.gather_rows has no backward (the instance-row backward assumes whole copies "
+                                      "of a graph); wrap the call in torch.no_grad() or detach the inputs")
+        return super().gather_rows(x, e)
+
+    def by_graph(self):
+        raise NotImplementedError("InducedInstances.by_graph: the instances of a graph are no copies of it (an inference form)")
+
+    def counts(self):
+        raise NotImplementedError("InducedInstances.counts: the instances of a graph are no copies of it (an inference form)")
+
+
+def induced_instances(plan: "GraphPlan", edge_index: Tensor, index: Tensor, keep: Optional[Tensor],
+                      sizes: Optional[Tensor] = None) -> InducedInstances:
+    """The batch of Q induced-subgraph instances in one pass on the device (isg_induced_size: a 16-byte clear and three launches;
+    isg_induced_fill: one).  plan: the parent batch's GraphPlan, built from its batch vector; edge_index int64 [2, E], the edges
+    of one graph contiguous and the graphs in order; index int32 or int64 [Q], on the host or on the device; keep uint32-as-int32
+    [Q, W] on the device (bit i & 31 of word i >> 5 of row q: local node i of graph index[q] is in instance q; W <= 64), or None:
+    every node is kept and the result is ops.graph_instances'.  N' and E' come from one 16-byte device-to-host copy between the
+    passes (E' depends on the bits: it cannot be known on the host).  sizes: HOST int64 [2, G] (nodes, edges per graph); it is
+    only checked -- the instances' own sizes are not known on the host, so the plan of the instance batch is built without them."""
+    lib = _ext_induced.load()
+    p_ei = _chk(edge_index, "edge_index", torch.int64)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"edge_index must be [2,E], got {tuple(edge_index.shape)}")
+    if plan.batch is None:
+        raise ValueError("induced_instances needs a GraphPlan built from the batch vector")
+    N, E, G = plan.N, edge_index.size(1), plan.B
+    p_batch = _chk(plan.batch, "plan.batch", torch.int64, (N,))
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (G + 1,))
+    if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"index: expected int32 or int64 [Q], got {index.dtype} {tuple(index.shape)}")
+    if sizes is not None and (sizes.device.type != "cpu" or tuple(sizes.shape) != (2, G)):
+        raise ValueError(f"sizes: a HOST tensor [2, {G}] (nodes, edges per graph), got {sizes.device} {tuple(sizes.shape)}")
+    dev = edge_index.device
+    Q = index.numel()
+    W, p_keep = 0, 0
+    if keep is not None:
+        if keep.dim() != 2 or keep.size(0) != Q or keep.dtype != torch.int32:
+            raise ValueError(f"keep: expected int32 words [{Q}, W], got {keep.dtype} {tuple(keep.shape)}")
+        W = keep.size(1)
+        if not 1 <= W <= INDUCED_WORDS_MAX:
+            raise _lib.IsgError(f"keep: {W} words per instance (1 to {INDUCED_WORDS_MAX}: {32 * INDUCED_WORDS_MAX} nodes per graph)")
+        p_keep = _chk(keep, "keep", torch.int32) if Q else 0
+    idx = index.to(device=dev, dtype=torch.int32).contiguous()
+    COUNTERS["induced_instances"] += 1
+    ws_bytes = lib.isg_induced_workspace_bytes(G, Q)
+    n32 = 2 * (Q + 1) + 4
+    i32 = torch.empty(n32 + (ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    ptr, eptr, status = i32[:Q + 1], i32[Q + 1:2 * Q + 2], i32[2 * Q + 2:n32]
+    b32 = i32.data_ptr()
+    if Q == 0:
+        i32[:n32].zero_()
+        Np = Ep = 0
+    else:
+        _lib.check(lib.isg_induced_size(p_ptr, p_batch, p_ei, idx.data_ptr(), p_keep, W, N, E, G, Q, b32, b32 + 4 * (Q + 1),
+                                        b32 + 8 * (Q + 1), b32 + 4 * n32, ws_bytes, _stream()), "isg_induced_size")
+        Np, Ep = (int(v) for v in status.tolist()[:2])          # the operator's only device-to-host copy: the 16 bytes of status
+    i64 = torch.empty(max(2 * Np + 3 * Ep, 1), dtype=torch.int64, device=dev)
+    b64 = i64.data_ptr()
+    _lib.check(lib.isg_induced_fill(p_ptr, p_ei, idx.data_ptr(), p_keep, W, N, E, G, Q, b32, b32 + 4 * (Q + 1), b32 + 4 * n32,
+                                    ws_bytes, Np, Ep, b64, b64 + 8 * (2 * Np), b64 + 8 * Np, b64 + 8 * (2 * Np + 2 * Ep), _stream()),
+               "isg_induced_fill")
+    return InducedInstances(plan, idx, ptr, eptr, i64[:Np], i64[2 * Np:2 * Np + 2 * Ep].view(2, Ep), i64[Np:2 * Np],
+                            i64[2 * Np + 2 * Ep:2 * Np + 3 * Ep], status, None, E, erange=i32[n32:n32 + G + 1] if Q else None,
+                            index_host=index if index.device.type == "cpu" else None, keep=keep)
+
+
+def keep_words(max_nodes: int) -> int:
+    """Words of 32 keep bits that hold graphs of up to max_nodes nodes (at least one)."""
+    return max(1, (int(max_nodes) + 31) // 32)
+
+
+def _pack_bits(flags: Tensor, W: int) -> Tensor:
+    """bool [R, 32 W] -> int32 [R, W]: bit i & 31 of word i >> 5.  The sum runs in int64 and wraps into the int32 word."""
+    shifts = torch.arange(32, dtype=torch.int64, device=flags.device)
+    words = (flags.view(flags.size(0), W, 32).long() << shifts).sum(dim=2)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+
+
+def keep_bits_leave_one_out(plan: "GraphPlan", graphs: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(index int32 [Q], keep int32 [Q, W], inst_node int64 [Q]) of the leave-one-out batch, made with torch ops on the plan's
+    device (O(Q W) words): graph g gets n_g instances, instance j of them lacks local node j, inst_node is the removed node's row
+    in the parent batch; the instances of a graph are consecutive, the graphs in order.  A graph with fewer than 2 nodes gets no
+    instance (removing its node would leave an empty graph).  graphs: int64 [B'] -- only these graphs, in this order.
+    W = keep_words(plan.nmax).  One device-to-host copy (Q, to size the result)."""
+    ptr = plan.ptr.long()
+    n = ptr[1:] - ptr[:-1]
+    g_all = torch.arange(plan.B, dtype=torch.int64, device=ptr.device) if graphs is None else graphs.to(ptr.device).long()
+    reps = n.index_select(0, g_all)
+    reps = torch.where(reps >= 2, reps, torch.zeros_like(reps))
+    index = torch.repeat_interleave(g_all, reps)                 # (the copy: the output's length)
+    Q = index.numel()
+    first = torch.cumsum(reps, 0) - reps                         # the first instance of every listed graph
+    local = torch.arange(Q, dtype=torch.int64, device=ptr.device) - torch.repeat_interleave(first, reps, output_size=Q)
+    W = keep_words(plan.nmax)
+    bit = torch.arange(32 * W, dtype=torch.int64, device=ptr.device).view(1, -1)
+    flags = (bit < n.index_select(0, index).view(-1, 1)) & (bit != local.view(-1, 1))
+    return index.to(torch.int32), _pack_bits(flags, W), ptr.index_select(0, index) + local
+
+
+def keep_bits_from_mask(mask: Tensor, plan: "GraphPlan", threshold: float = 0.0, complement: bool = False) -> Tensor:
+    """keep int32 [B, W] for ops.induced_instances with the identity index: bit i of row g is (mask[ptr[g] + i] > threshold) !=
+    complement, ops.subgraph_cut's rule (a NaN compares false).  mask fp32 [N] or [N, 1]; W = keep_words(plan.nmax)."""
+    flat = mask.reshape(-1)
+    if flat.numel() != plan.N:
+        raise ValueError(f"mask: expected {plan.N} entries, got {flat.numel()}")
+    if plan.batch is None:
+        raise ValueError("keep_bits_from_mask needs a GraphPlan built from the batch vector")
+    W = keep_words(plan.nmax)
+    batch = plan.batch.long()
+    local = torch.arange(plan.N, dtype=torch.int64, device=flat.device) - plan.ptr.long().index_select(0, batch)
+    flags = torch.zeros(plan.B, 32 * W, dtype=torch.bool, device=flat.device)
+    inside = local < 32 * W
+    flags[batch[inside], local[inside]] = ((flat > threshold) != bool(complement))[inside]
+    return _pack_bits(flags, W)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""The intrinsic mask beside post-hoc baselines (explain.compare) on synthetic workloads: the AnswerModel of
+BASELINE configs[1] with the I-MLE sampler (its eval solve is noise-free), seeded batches, seeded names, question words, labels
+and annotated objects.  An untrained model on random graphs: the figures show that the yardsticks run and how the explainers
+differ on them, not how good an explanation is.
+
+  python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048] [--out profiles/<name>.json]"""
+import dataclasses
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from isubgvqa_amd import explain, synthetic
+
+dev = torch.device("cuda:0")
+argv = sys.argv[1:]
+opt = {a: b for a, b in zip(argv, argv[1:]) if a.startswith("--")}
+GRAPHS, BATCHES, K = int(opt.get("--graphs", 64)), int(opt.get("--batches", 2)), int(opt.get("--k", 5))
+MAX_INSTANCES = int(opt["--max-instances"]) if "--max-instances" in opt else None
+V, A = 2578, 1842
+
+cfg = dataclasses.replace(synthetic.CFG1, num_graphs=GRAPHS, sampler="imle", sample_k=K)
+model = synthetic.build_answer_model(cfg).eval().to(dev)
+tables = explain.TokenTables({f"w{i}": i for i in range(V)}, [f"w{(11 * a) % V}" if a % 3 == 0 else f"answer {a}" for a in range(A)])
+gen = torch.Generator().manual_seed(17)
+batches = []
+with torch.no_grad():
+    for b in range(BATCHES):
+        wl = synthetic.make_workload(dataclasses.replace(cfg, seed=cfg.seed + b))
+        d = wl.to(dev)
+        names = torch.randint(0, V, (wl.x.size(0),), generator=gen)
+        ptr = torch.cat([torch.zeros(1, dtype=torch.long), wl.graph_sizes[0].cumsum(0)])
+        label = model(d)[0].argmax(1).cpu()
+        label[2::3] = (label[2::3] + 1) % A                      # a third of the answers wrong
+        qtok = torch.full((GRAPHS, 6), -1, dtype=torch.int32)
+        for g in range(GRAPHS):                                  # question words: three name nodes of the graph, one names nothing
+            own = names[ptr[g]:ptr[g + 1]]
+            qtok[g, :3] = own[torch.randint(0, own.numel(), (3,), generator=gen)].int()
+            qtok[g, 3] = int(torch.randint(0, V, (1,), generator=gen))
+        gold = synthetic.make_gold(wl.graph_sizes[0], seed=b)
+        batches.append(explain.EvalBatch(d, label.to(dev), qtok.to(dev), (torch.arange(GRAPHS) % 4 == 0).int().to(dev), names.to(dev),
+                                         gold=gold.to(dev)))
+report = explain.compare(model, batches, tables, k=K, max_instances=MAX_INSTANCES)
+out = {"device": torch.cuda.get_device_name(0), "graphs_per_batch": GRAPHS, "batches": BATCHES, "k": K, "explainers": {}}
+for name, r in report.items():
+    g = r.grounding.sets["any"]["all"]
+    out["explainers"][name] = {"fid_plus": r.fid_plus, "fid_minus": r.fid_minus, "jaccard_with_intrinsic": r.jaccard,
+                               "accuracy": r.coo.accuracy, "ans_tok_coo": r.coo.ans_tok_coo, "qst_tok_coo": r.coo.qst_tok_coo,
+                               "grounding_precision": g.precision, "grounding_recall": g.recall, "grounding_chance": g.chance}
+    print(f"{name:10s} fid+ {r.fid_plus:.4f}  fid- {r.fid_minus:.4f}  jaccard {r.jaccard:.3f}  qst coo {r.coo.qst_tok_coo:.3f}  "
+          f"grounding p {g.precision:.3f} r {g.recall:.3f} (chance {g.chance:.3f})", flush=True)
+if "--out" in opt:
+    with open(opt["--out"], "w") as fh:
+        fh.write(json.dumps(out, indent=1) + "\n")
