@@ -18,6 +18,7 @@ node mask, and `compare` reports the model's own mask, the occlusion mask and a 
 from __future__ import annotations
 
 import argparse
+import functools
 import math
 import operator
 from dataclasses import dataclass, field, replace
@@ -94,16 +95,19 @@ def _forwarder(model, inputs, noises, seed):
     full = not isinstance(model, synthetic.AnswerModel)
     B = int(inputs.questions.size(0) if full else inputs.glf.size(0))
 
-    def forward(x, edge_index, edge_attr, batch, sg, p, rows=None, nz=noises):
+    def forward(x, edge_index, edge_attr, batch, sg, p, rows=None, nz=noises, trace=None):
+        extra = {} if trace is None else {"trace": trace}
         if full:
             q, am = (inputs.questions, inputs.att_mask) if rows is None else (inputs.questions.index_select(0, rows),
                                                                             inputs.att_mask.index_select(0, rows))
-            out = model(x, edge_index, edge_attr, batch, q, am, return_masks=True, scene_graphs=sg, noises=nz, seed=seed, plan=p)
+            # (ISubGVQA.forward keeps its signature: a trace goes through forward_traced)
+            call = model if trace is None else functools.partial(model.forward_traced, trace)
+            out = call(x, edge_index, edge_attr, batch, q, am, return_masks=True, scene_graphs=sg, noises=nz, seed=seed, plan=p)
         else:
             instr, glf = (inputs.instr, inputs.glf) if rows is None else (inputs.instr.index_select(1, rows).contiguous(),
                                                                           inputs.glf.index_select(0, rows))
             out = model(synthetic.Workload(x, edge_index, edge_attr, batch, instr, glf, glf.size(0), inputs.max_nodes,
-                                           inputs.max_edges, None), noises=nz, seed=seed, plan=p)
+                                           inputs.max_edges, None), noises=nz, seed=seed, plan=p, **extra)
         return out[0], out[1]
 
     return full, B, forward
@@ -265,6 +269,57 @@ def occlusion(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed
         attribution[inst_node] = p.index_select(0, index.long()) - p_without
         single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
     return Occlusion(pred, p, attribution, single, index, inst_node, p_without, logits, plan, chunks)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A one-forward baseline: attention rollout
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class AttentionTrace:
+    """What a forward with `trace=` leaves behind (MGAT.forward, AnswerModel.forward, ISubGVQA.answer_graphs / forward_traced): mutable,
+    filled by the call, once."""
+    alphas: Optional[List[Tensor]] = None           # L tensors fp32 [E, H]: every layer's attention weights, in the caller's edge order
+    masks: Optional[List[Optional[Tensor]]] = None  # L entries: a layer's node mask fp32 [N, 1], or None where the layer has none
+    mask: Optional[Tensor] = None                   # the forward's node mask (its second result)
+    gate: Optional[Tensor] = None                   # the read-out's pooling weights (its third result)
+
+
+@dataclass
+class Rollout:
+    """Attention-rollout attributions of one batch (attention_rollout())."""
+    attribution: Tensor            # fp32 [N]: the relevance of every node (include/ext/isg_rollout.h)
+    flow: Optional[Tensor]         # fp32 [L, E]: what every edge carried at every layer; None unless asked for
+    trace: AttentionTrace          # the forward's attention weights, layer masks, mask and gate
+    logits: Tensor                 # [B, classes] of the batch
+    plan: "ops.GraphPlan"
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k most relevant nodes of every graph -- ops.topk_threshold on
+        shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the k-th value are all
+        kept."""
+        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+
+def attention_rollout(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                      residual: float = 0.5, use_masks: bool = True, want_flow: bool = False) -> Rollout:
+    """Attention rollout (Abnar & Zuidema 2020) of every node: the read-out's pooling weights walked back through the layers'
+    head-averaged attention weights, a share `residual` of a node's relevance staying on it at every layer.  ONE forward with a
+    trace, under torch.no_grad(), and one launch (ops.attention_rollout); `inputs` as for faithfulness().
+    The walk starts from gate * mask (a masked node's pooled term is exactly zero, att_pooling.py), or from the gate alone when
+    the forward has no mask.  use_masks=False hands the kernel no layer masks: the attention weights alone decide."""
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    trace = AttentionTrace()
+    with torch.no_grad():
+        plan = _input_plan(inputs, B)
+        logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None, plan,
+                         trace=trace)[0]
+        start = trace.gate.float().reshape(-1)
+        if trace.mask is not None:
+            start = start * trace.mask.float().reshape(-1)
+        relevance, flow = ops.attention_rollout(plan, trace.alphas, start.contiguous(), trace.masks if use_masks else None,
+                                                residual=residual, want_flow=want_flow)
+    return Rollout(relevance, flow, trace, logits, plan)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -531,6 +586,7 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
 # The intrinsic mask beside post-hoc baselines
 # ---------------------------------------------------------------------------------------------------------------------
 EXPLAINERS = ("intrinsic", "occlusion", "random")
+EXPLAINERS_ALL = EXPLAINERS + ("attention",)       # what compare() accepts; EXPLAINERS stays its default
 COMPARE_SUMS = 6       # float64 per explainer: sum fid_plus, questions that have one, sum fid_minus, questions that have one,
                        # sum of the Jaccard overlaps with the intrinsic mask, graphs that have one
 
@@ -567,12 +623,13 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
     """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
     explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
     mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
-    intrinsic: the forward's own mask; occlusion: occlusion().mask(k); random: random_mask(plan, k, seed + batch number).
+    intrinsic: the forward's own mask; occlusion: occlusion().mask(k); random: random_mask(plan, k, seed + batch number);
+    attention (not among the default): attention_rollout().mask(k).
     Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate()."""
     names_x = tuple(explainers)
-    unknown = [x for x in names_x if x not in EXPLAINERS]
+    unknown = [x for x in names_x if x not in EXPLAINERS_ALL]
     if unknown or not names_x:
-        raise ValueError(f"compare: explainers from {EXPLAINERS}, got {names_x}")
+        raise ValueError(f"compare: explainers from {EXPLAINERS_ALL}, got {names_x}")
     X = len(names_x)
     full = not isinstance(model, synthetic.AnswerModel)
     flat = coo = ground = sums = None
@@ -604,6 +661,8 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                     mask = intrinsic
                 elif name == "occlusion":
                     mask = occlusion(model, inp, max_instances=max_instances).mask(k)
+                elif name == "attention":
+                    mask = attention_rollout(model, inp).mask(k)
                 else:
                     mask = random_mask(plan, k, seed + number)
                 ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,

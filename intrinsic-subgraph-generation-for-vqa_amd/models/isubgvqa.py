@@ -114,15 +114,19 @@ class ISubGVQA(torch.nn.Module):
 
     def answer_graphs(self, x_encoded, edge_index, edge_attr_encoded, batch, instr_vectors, glf, plan,
                       return_masks=True, noises=None, seed=None, explainer=False, explainer_stage=False,
-                      expl_bypass_x=False):
-        """MGAT -> pooling -> classifier (isubgvqa.py:267-292)."""
+                      expl_bypass_x=False, trace=None):
+        """MGAT -> pooling -> classifier (isubgvqa.py:267-292).  trace: an explain.AttentionTrace, which receives the layers'
+        attention weights and node masks, the mask and the gate; the results are the bits of the call without it."""
         gate_q, pool_q = self.gat_seq.question_side(glf, None, self.graph_global_attention_pooling)
         x_mgat, imle_mask, node_logits_layers, _ = self.gat_seq(
             x=x_encoded, edge_index=edge_index, edge_attr=edge_attr_encoded, instr_vectors=instr_vectors[:4],
             global_language_feats=glf, batch=batch, return_masks=return_masks, explainer=explainer,
-            explainer_stage=explainer_stage, expl_bypass_x=expl_bypass_x, plan=plan, noises=noises, seed=seed, gate_q=gate_q)
+            explainer_stage=explainer_stage, expl_bypass_x=expl_bypass_x, plan=plan, noises=noises, seed=seed, gate_q=gate_q,
+            trace=trace)
         embed, gate = self.graph_global_attention_pooling(x=x_mgat, u=glf, batch=batch, size=None,
                                                           return_mask=True, node_mask=imle_mask, plan=plan, q=pool_q)
+        if trace is not None:
+            trace.mask, trace.gate = imle_mask, gate
         feats = ops.cat_mul_mlp(self.embedding, embed, glf, want_rowmax=True)           # :288-291 (row maxima: for logit_fc)
         return ops.linear(feats, self.logit_fc.weight, self.logit_fc.bias), imle_mask, gate, node_logits_layers   # :292
 
@@ -277,6 +281,23 @@ class ISubGVQA(torch.nn.Module):
                 return_masks=False, explainer=False, explainer_stage=False, expl_bypass_x=False, scene_graphs=None,
                 noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
                 plan: Optional[ops.GraphPlan] = None, text_uniform: Optional[Tensor] = None, capture=False):
+        return self._forward(None, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask, return_masks,
+                             explainer, explainer_stage, expl_bypass_x, scene_graphs, noises, seed, plan, text_uniform, capture)
+
+    def forward_traced(self, trace, *args, **kwargs):
+        """forward(*args, **kwargs) with an explain.AttentionTrace, which receives the layers' attention weights and node masks,
+        the mask and the gate (see answer_graphs).  The return tuple and its bits are forward()'s; forward()'s own signature stays
+        as it is.  Together with capture= it raises ValueError: a replayed step keeps no attention weights."""
+        if trace is None:
+            raise ValueError("forward_traced needs a trace (an explain.AttentionTrace); without one, call forward()")
+        return self._forward(trace, *args, **kwargs)
+
+    def _forward(self, trace, node_embeddings, edge_index, edge_embeddings, batch, questions, qsts_att_mask,
+                 return_masks=False, explainer=False, explainer_stage=False, expl_bypass_x=False, scene_graphs=None,
+                 noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                 plan: Optional[ops.GraphPlan] = None, text_uniform: Optional[Tensor] = None, capture=False):
+        if trace is not None and capture:
+            raise ValueError("trace together with capture: a replayed step keeps no attention weights; run it eagerly")
         if not return_masks:
             # the reference unpacks two values from GlobalAttention.forward, which returns a bare tensor when
             # return_mask=False (isubgvqa.py:280, att_pooling.py:75-77): return_masks=True is mandatory there
@@ -304,7 +325,7 @@ class ISubGVQA(torch.nn.Module):
                                                 gt_scene_graphs=scene_graphs, plan=plan)  # :255
         logits, imle_mask, gate, node_logits_layers = self.answer_graphs(
             x_enc, edge_index, e_enc, batch, instr_vectors, glf, plan, return_masks, noises, seed, explainer,
-            explainer_stage, expl_bypass_x)
+            explainer_stage, expl_bypass_x, trace)
         if explainer:
             return logits                                                                # :294-295
         return logits, imle_mask, gate, node_logits_layers, mask_text                    # :297

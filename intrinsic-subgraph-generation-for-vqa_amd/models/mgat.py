@@ -106,7 +106,10 @@ class MGAT(torch.nn.Module):
                 explainer=False, explainer_stage=False, expl_bypass_x=False, plan: Optional[ops.GraphPlan] = None,
                 noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
                 return_attention: bool = False, gate_feats: Optional[Tensor] = None,
-                gate_q: Optional[Dict[int, Tensor]] = None):
+                gate_q: Optional[Dict[int, Tensor]] = None, trace=None):
+        # trace: an explain.AttentionTrace -- every layer is asked for its attention weights, and the object receives `alphas`
+        # (L tensors fp32 [E, H] in the caller's edge order) and `masks` (L entries, a layer's node mask [N, 1] or None); nothing
+        # else changes: the results are the bits of the call without it
         # gate_feats [B, C]: the rows the masked layers' node gates read, given per graph (ops.run_split's sub-batch); default:
         # global_language_feats under the reference's double index (masking.py:151-155, quirk Q3)
         # gate_q {layer: mask.ques_nn(those rows)}: from a caller that ran the question-side MLPs ahead (question_side)
@@ -118,6 +121,7 @@ class MGAT(torch.nn.Module):
         mask = None
         global_mask = None
         edge_attns = []
+        trace_alphas, trace_masks = [], []
         gate_u = glf if gate_feats is None else gate_feats.contiguous()
         # how every layer runs on this batch (ops.conv_route), asked once: the layers are handed their answer, the dense tail reads
         # the next layer's
@@ -146,7 +150,7 @@ class MGAT(torch.nn.Module):
             conv_res, mask, edge_att = self.convs[i](
                 x=h, edge_index=edge_index, edge_attr=edge_attr, instruction=ins, batch=batch,
                 return_masks=return_masks, return_attention_weights=True, imle_att=gate_u,
-                want_alpha=bool(return_attention) or not ops.CFG.skip_unread_alpha, sparse_out=sparse,
+                want_alpha=bool(return_attention) or trace is not None or not ops.CFG.skip_unread_alpha, sparse_out=sparse,
                 gate_rows_given=gate_feats is not None, all_instrs=instr_vectors, route=routes[i],
                 plan=plan, noise=None if noises is None else noises.get(i),
                 seed=None if seed is None else seed + i,
@@ -156,6 +160,11 @@ class MGAT(torch.nn.Module):
             x_gated = x_planes = None
             if return_attention:
                 edge_attns.append(edge_att)
+            if trace is not None:
+                if edge_att is None:
+                    raise RuntimeError(f"layer {i} returned no attention weights although they were asked for")
+                trace_alphas.append(edge_att[1])
+                trace_masks.append(mask)
             tail_mask = None
             if self.use_global_mask:                                                     # :161-162,174-175
                 global_mask = mask if global_mask is None else mask * global_mask
@@ -183,6 +192,8 @@ class MGAT(torch.nn.Module):
             conv_res = ops.mlp(self.x_proj[i], conv_res)                                 # :156 (Linear+GELU fused)
             h = ops.mgat_layer_tail(ins, conv_res.contiguous(), h, plan, bn.weight, bn.bias, bn.mean_scale, bn.eps,
                                     node_mask=tail_mask)                                 # :168-177
+        if trace is not None:
+            trace.alphas, trace.masks = trace_alphas, trace_masks
         if return_attention:
             return h, mask, [], [], edge_attns
         return h, mask, [], []

@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _ext_induced, _ext_instances_train, _lib, _lib_instances
+from . import _ext_induced, _ext_instances_train, _ext_rollout, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -146,6 +146,7 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "graph_instances": 0,                      # expansions of a distinct batch into graph instances (include/isg_instances.h)
             "instance_rows_bwd": 0,                    # backwards of the instance-row gather (include/ext/isg_instances_train.h)
             "induced_instances": 0,                    # batches of induced-subgraph instances (include/ext/isg_induced.h)
+            "attention_rollout": 0,                    # attention-rollout launches (include/ext/isg_rollout.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1043,6 +1044,70 @@ def instance_rows_backward(inst: GraphInstances, g_x: Tensor, g_e: Tensor) -> Tu
 
 
 # ------------------------------------------------------------------------------------------------
+# Attention rollout: the read-out's weights walked back through the layers' attention weights
+# ------------------------------------------------------------------------------------------------
+ROLLOUT_MAX_LAYERS = 8      # isg_rollout_max_layers() (ROLL_MAX_LAYERS in csrc/isg_rollout.hip)
+
+
+def attention_rollout(plan: "GraphPlan", alphas, start: Tensor, masks=None, residual: float = 0.5,
+                      want_flow: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """(relevance fp32 [N], flow fp32 [L, E] or None) of isg_attention_rollout (include/ext/isg_rollout.h, where the function is
+    stated): one launch, one wave per graph.  plan: the batch's GraphPlan, built with edge_index (its CSR by source is built on
+    first use); alphas: L fp32 [E, H] tensors in edge-id order, columns contiguous, the row stride free (a layer kernel's
+    `alpha`, or a column slice of a wider tensor); start fp32 [N] or [N, 1]; masks: None, or L entries each None or fp32 [N] /
+    [N, 1] (the layer's node mask); residual: the share of a node's relevance that stays on it at every layer, in [0, 1].
+    flow[l, e] is what edge e carried at layer l (zero for an edge that was skipped)."""
+    lib = _ext_rollout.load()
+    plan.require_csr()
+    alphas = list(alphas)
+    L, N, E, B = len(alphas), plan.N, plan.E, plan.B
+    if not 1 <= L <= ROLLOUT_MAX_LAYERS:
+        raise _lib.IsgError(f"attention_rollout: {L} layers (1 to {ROLLOUT_MAX_LAYERS})")
+    if masks is None:
+        masks = [None] * L
+    masks = list(masks)
+    if len(masks) != L:
+        raise ValueError(f"masks: expected None or {L} entries (one per layer, each a tensor or None), got {len(masks)}")
+    if not 0.0 <= float(residual) <= 1.0:            # (a NaN compares false)
+        raise ValueError(f"residual: expected a share in [0, 1], got {residual}")
+    if start.dim() == 2 and start.size(1) == 1:
+        start = start.reshape(-1)
+    p_start = _chk(start, "start", torch.float32, (N,))
+    H = alphas[0].size(1) if alphas[0].dim() == 2 else 0
+    if H < 1:
+        raise ValueError(f"alphas[0]: expected fp32 [{E}, H] with H >= 1, got {tuple(alphas[0].shape)}")
+    fields, keep = [], []
+    for l, (al, m) in enumerate(zip(alphas, masks)):
+        if not al.is_cuda:
+            raise _lib.IsgError(f"alphas[{l}] must live on the GPU (got {al.device}); this path has no CPU fallback")
+        if al.dtype != torch.float32 or tuple(al.shape) != (E, H) or (E > 0 and (al.stride(1) != 1 or al.stride(0) < H)):
+            raise ValueError(f"alphas[{l}]: expected fp32 [{E}, {H}] with contiguous columns, got {al.dtype} {tuple(al.shape)} "
+                             f"with strides {tuple(al.stride())}")
+        if _rec(al):
+            raise NotImplementedError(f"alphas[{l}] requires grad but this operator has no backward; wrap the call in "
+                                      "torch.no_grad() or detach the input")
+        if m is not None:
+            if m.dim() == 2 and m.size(1) == 1:
+                m = m.reshape(-1)
+            m = _f32(m)
+            keep.append(m)
+        fields += [al.data_ptr() if E > 0 else 0, al.stride(0) if E > 1 else H, _chk(m, f"masks[{l}]", torch.float32, (N,), optional=True)]
+    dev = start.device
+    by_src = plan.source_csr() if N > 0 else (plan.rowptr, plan.eid, plan.dst)
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (B + 1,))
+    COUNTERS["attention_rollout"] += 1
+    relevance = torch.empty(N, dtype=torch.float32, device=dev)
+    flow = torch.zeros(L, E, dtype=torch.float32, device=dev) if want_flow else None
+    import ctypes
+    table = (ctypes.c_int64 * len(fields))(*fields)
+    _lib.check(lib.isg_attention_rollout(p_ptr, by_src[0].data_ptr(), by_src[1].data_ptr(), by_src[2].data_ptr(),
+                                         ctypes.addressof(table), L, H, float(residual), p_start, N, E, B, plan.nmax,
+                                         relevance.data_ptr(), 0 if flow is None else flow.data_ptr(), _stream()),
+               "isg_attention_rollout")
+    return relevance, flow
+
+
+# ------------------------------------------------------------------------------------------------
 # Induced-subgraph instances: every instance a graph of the parent batch minus some of its nodes
 # ------------------------------------------------------------------------------------------------
 INDUCED_WORDS_MAX = 64      # words of keep bits per instance, one per lane of the instance's wave (IND_WORDS_MAX in csrc/isg_induced.hip)
@@ -1732,7 +1797,7 @@ def oversize_split(plan: "GraphPlan") -> Optional["OversizeGraphs"]:
 def run_split(plan: "GraphPlan", sub: "OversizeGraphs", core, x: Tensor, edge_index: Tensor, edge_attr: Tensor, batch: Tensor,
               instr: Tensor, glf: Tensor, noises=None, seed=None, kinds: str = "gnn"):
     """core(x, edge_index, edge_attr, batch, instr, glf, plan, noises, seed, gate_feats) -> tuple of tensors / lists / None, one per
-    letter of `kinds` ("g": a row per graph, "n": a row per node), run TWICE: on the whole batch with the tile kernels passing
+    letter of `kinds` ("g": a row per graph, "n": a row per node, "e": a row per edge, merged through sub.edges), run TWICE: on the whole batch with the tile kernels passing
     over the graphs beyond a tile (their rows stay unwritten: plan.holes), and on those graphs as a batch of their own (per-graph
     kernels; instr is [L, B, C]); the second result is then copied over the rows of the first.  Every op of the path is local to
     a graph (or a row), so nothing of a hole reaches another graph -- with ONE exception that the reference itself makes: a masked
@@ -1789,11 +1854,12 @@ def run_split(plan: "GraphPlan", sub: "OversizeGraphs", core, x: Tensor, edge_in
             return None
         if isinstance(m, (list, tuple)):
             return type(m)(merge(a, b, kind) for a, b in zip(m, s_))
-        idx = sub.gids if kind == "g" else sub.nodes
-        if m.size(0) != (plan.B if kind == "g" else plan.N) or s_.size(0) != idx.numel():
+        idx, rows = {"g": (sub.gids, plan.B), "n": (sub.nodes, plan.N), "e": (sub.edges, plan.E)}[kind]
+        if m.size(0) != rows or s_.size(0) != idx.numel():
             raise ValueError(f"run_split: a '{kind}' result of {tuple(m.shape)} / {tuple(s_.shape)} rows")
-        if m.dim() == 2 and kind == "n" and s_.dim() == 2 and m.size(1) != s_.size(1):
-            raise ValueError("run_split: per-node results of different widths")
+        if m.dim() == 2 and kind in ("n", "e") and s_.dim() == 2 and m.size(1) != s_.size(1):
+            raise ValueError("run_split: per-node results of different widths" if kind == "n" else
+                             "run_split: per-edge results of different widths")
         return m.index_copy_(0, idx, s_.to(m.dtype))
     return tuple(merge(m, s_, k) for m, s_, k in zip(main, side, kinds))
 

@@ -164,8 +164,12 @@ class AnswerModel(torch.nn.Module):
         self.logit_fc = torch.nn.Linear(512, num_answers)
 
     def forward(self, wl: Workload, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
-                plan=None, use_hints: bool = True, capture: bool = False):
+                plan=None, use_hints: bool = True, capture: bool = False, trace=None):
+        # trace: an explain.AttentionTrace; it receives the layers' attention weights and node masks, the mask and the gate of this
+        # call.  The return tuple and its bits do not change
         from . import ops
+        if trace is not None and capture:
+            raise ValueError("trace together with capture=True: a replayed step keeps no attention weights; run it eagerly")
         if capture:
             return self._captured(wl, noises, seed, plan)
         if plan is None:
@@ -175,8 +179,22 @@ class AnswerModel(torch.nn.Module):
                                        graph_sizes=wl.graph_sizes if use_hints else None)
         sub = ops.oversize_split(plan) if self.gat_seq.on_tiles(plan, wl.x.size(1), wl.edge_attr) else None
         if sub is None:
-            return self._answer(wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf, plan, noises, seed, None)
+            return self._answer(wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf, plan, noises, seed, None, trace)
         # a few graphs beyond a graph tile: they run as a batch of their own, the rest stays on the tile kernels
+        if trace is not None:
+            # each pass fills a trace of its own; the weights merge by edge, the layer masks by node, and the caller's trace is
+            # filled once, behind the merge
+            from .explain import AttentionTrace
+
+            def traced(*args):
+                t = AttentionTrace()
+                logits, mask, gate = self._answer(*args, t)
+                return logits, mask, gate, t.alphas, t.masks
+
+            logits, mask, gate, alphas, masks = ops.run_split(plan, sub, traced, wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr,
+                                                              wl.glf, noises, seed, kinds="gnnen")
+            trace.alphas, trace.masks, trace.mask, trace.gate = alphas, masks, mask, gate
+            return logits, mask, gate
         return ops.run_split(plan, sub, self._answer, wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf, noises, seed,
                              kinds="gnn")
 
@@ -211,14 +229,16 @@ class AnswerModel(torch.nn.Module):
         tensors = [wl.x, wl.edge_index, wl.edge_attr, wl.batch, wl.instr, wl.glf] + [noises[k] for k in keys]
         return cap.run(fn, tensors, key_extra=("answer", hints, tuple(keys), self.training), stamp=watch.stamp())
 
-    def _answer(self, x, edge_index, edge_attr, batch, instr, glf, plan, noises, seed, gate_feats):
+    def _answer(self, x, edge_index, edge_attr, batch, instr, glf, plan, noises, seed, gate_feats, trace=None):
         from . import ops as _ops
         gate_q, pool_q = self.gat_seq.question_side(glf, gate_feats, self.graph_global_attention_pooling)
         h, mask, _, _ = self.gat_seq(x=x, edge_index=edge_index, edge_attr=edge_attr, instr_vectors=instr[:4],
                                      global_language_feats=glf, batch=batch, return_masks=True, plan=plan, noises=noises, seed=seed,
-                                     gate_feats=gate_feats, gate_q=gate_q)
+                                     gate_feats=gate_feats, gate_q=gate_q, trace=trace)
         embed, gate = self.graph_global_attention_pooling(x=h, u=glf, batch=batch, size=None, return_mask=True,
                                                           node_mask=mask, plan=plan, q=pool_q)
+        if trace is not None:
+            trace.mask, trace.gate = mask, gate
         feats = _ops.cat_mul_mlp(self.embedding, embed, glf, want_rowmax=True)
         return _ops.linear(feats, self.logit_fc.weight, self.logit_fc.bias), mask, gate
 

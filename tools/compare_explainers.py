@@ -4,7 +4,9 @@ BASELINE configs[1] with the I-MLE sampler (its eval solve is noise-free), seede
 and annotated objects.  An untrained model on random graphs: the figures show that the yardsticks run and how the explainers
 differ on them, not how good an explanation is.
 
-  python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048] [--out profiles/<name>.json]"""
+  python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048]
+                                     [--explainers intrinsic,occlusion,random,attention] [--out profiles/<name>.json]
+--explainers: a comma-separated list from explain.EXPLAINERS_ALL (default: explain.EXPLAINERS)."""
 import dataclasses
 import json
 import os
@@ -20,6 +22,7 @@ argv = sys.argv[1:]
 opt = {a: b for a, b in zip(argv, argv[1:]) if a.startswith("--")}
 GRAPHS, BATCHES, K = int(opt.get("--graphs", 64)), int(opt.get("--batches", 2)), int(opt.get("--k", 5))
 MAX_INSTANCES = int(opt["--max-instances"]) if "--max-instances" in opt else None
+EXPLAINERS = tuple(n for n in opt["--explainers"].split(",") if n) if "--explainers" in opt else explain.EXPLAINERS
 V, A = 2578, 1842
 
 cfg = dataclasses.replace(synthetic.CFG1, num_graphs=GRAPHS, sampler="imle", sample_k=K)
@@ -43,7 +46,7 @@ with torch.no_grad():
         gold = synthetic.make_gold(wl.graph_sizes[0], seed=b)
         batches.append(explain.EvalBatch(d, label.to(dev), qtok.to(dev), (torch.arange(GRAPHS) % 4 == 0).int().to(dev), names.to(dev),
                                          gold=gold.to(dev)))
-report = explain.compare(model, batches, tables, k=K, max_instances=MAX_INSTANCES)
+report = explain.compare(model, batches, tables, explainers=EXPLAINERS, k=K, max_instances=MAX_INSTANCES)
 out = {"device": torch.cuda.get_device_name(0), "graphs_per_batch": GRAPHS, "batches": BATCHES, "k": K, "explainers": {}}
 for name, r in report.items():
     g = r.grounding.sets["any"]["all"]
