@@ -14,6 +14,8 @@ device-to-host copy of an evaluation (`evaluate`).
 Something to hold the intrinsic mask against: `occlusion` gives leave-one-out attributions -- a forward-only post-hoc baseline on
 the batch of instances `ops.induced_instances` makes in one pass --, `faithfulness_of_mask` asks the two fidelity questions of ANY
 node mask, and `compare` reports the model's own mask, the occlusion mask and a random one by the same yardsticks.
+`attention_rollout` is the one-forward baseline, `integrated_gradients` (with gradient x input as its one-point case) the gradient
+one: the points of a straight path as one batch of instances, their gradient rows reduced to attributions on the device.
 """
 from __future__ import annotations
 
@@ -323,6 +325,199 @@ def attention_rollout(model, inputs, *, noises: Optional[Dict[int, Tensor]] = No
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A gradient baseline: integrated gradients, with gradient x input as its one-point case
+# ---------------------------------------------------------------------------------------------------------------------
+QUADRATURE_RULES = ("gauss_legendre", "midpoint", "trapezoid", "endpoint")
+
+
+def quadrature(steps: int, rule: str = "gauss_legendre") -> Tuple[Tensor, Tensor]:
+    """(t, w): the nodes in [0, 1] and the weights of a rule for the path integral, HOST float64 [S]; the weights sum to 1.
+    midpoint: t_s = (s + 1/2) / S, w = 1 / S.  trapezoid (S >= 2): t_s = s / (S - 1), the two end points weigh half.
+    gauss_legendre: numpy.polynomial.legendre.leggauss mapped from [-1, 1]; exact for polynomials up to degree 2 S - 1.
+    endpoint (S = 1): t = 1, w = 1 -- gradient x (input - baseline)."""
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"quadrature: steps must be an integer >= 1, got {steps!r}")
+    S = int(steps)
+    if rule == "midpoint":
+        t = (torch.arange(S, dtype=torch.float64) + 0.5) / S
+        w = torch.full((S,), 1.0 / S, dtype=torch.float64)
+    elif rule == "trapezoid":
+        if S < 2:
+            raise ValueError("quadrature: the trapezoid rule needs steps >= 2")
+        t = torch.arange(S, dtype=torch.float64) / (S - 1)
+        w = torch.full((S,), 1.0 / (S - 1), dtype=torch.float64)
+        w[0] = w[-1] = 0.5 / (S - 1)
+    elif rule == "gauss_legendre":
+        import numpy as np
+        nodes, weights = np.polynomial.legendre.leggauss(S)
+        t = torch.from_numpy((nodes + 1.0) * 0.5).to(torch.float64)
+        w = torch.from_numpy(weights * 0.5).to(torch.float64)
+    elif rule == "endpoint":
+        if S != 1:
+            raise ValueError("quadrature: the endpoint rule is one step (gradient x input), got steps = %d" % S)
+        t, w = torch.ones(1, dtype=torch.float64), torch.ones(1, dtype=torch.float64)
+    else:
+        raise ValueError(f"quadrature: rule from {QUADRATURE_RULES}, got {rule!r}")
+    return t, w
+
+
+@dataclass
+class PathAttributions:
+    """Path (integrated-gradients) attributions of one batch (path_attributions(), integrated_gradients())."""
+    attribution: Tensor                    # fp32 [N]: sum over the channels of (x - baseline) * the path's weighted gradient
+    edge_attribution: Optional[Tensor]     # fp32 [E], when the edge rows were on the path
+    avg_grad: Optional[Tuple[Tensor, Optional[Tensor]]]    # (fp32 [N, Cx], fp32 [E, Ce] or None): the weighted gradient rows, when asked for
+    f_input: Tensor                        # fp32 [B]: the score at the input (t = 1)
+    f_baseline: Tensor                     # fp32 [B]: the score at the baseline (t = 0)
+    delta: Tensor                          # fp32 [B]: the graph's attributions summed - (f_input - f_baseline), the completeness gap
+    plan: "ops.GraphPlan"
+    steps: int
+    rule: str
+    chunks: List["ops.GraphInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
+    pred: Optional[Tensor] = None          # int64 [B]: the class that was explained (integrated_gradients)
+    logits: Optional[Tensor] = None        # [B, classes] of the whole batch (integrated_gradients)
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest attribution --
+        ops.topk_threshold on shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the
+        k-th value are all kept."""
+        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+
+def _step_instances(plan: "ops.GraphPlan", edge_index: Tensor, steps: int) -> "ops.GraphInstances":
+    """`steps` instances of every graph, the copies of one graph next to each other: index[q] = q // steps."""
+    index = torch.arange(plan.B * steps, dtype=torch.int64) // max(steps, 1)
+    return ops.graph_instances(plan, edge_index, index, sizes=plan.sizes_host)
+
+
+def path_attributions(score, x: Tensor, e: Tensor, plan: "ops.GraphPlan", edge_index: Tensor, *, steps: int = 16,
+                      rule: str = "gauss_legendre", baseline_x: Optional[Tensor] = None, baseline_e: Optional[Tensor] = None,
+                      edges: bool = False, rows: bool = False, max_instances: Optional[int] = None) -> PathAttributions:
+    """Integrated gradients of `score` along the straight path from a baseline to the rows (x, e) of a batch -- the model-free
+    core.  score(x_inst, e_inst, inst) -> fp32 [Q']: any differentiable function of an instance batch (inst: its
+    ops.GraphInstances) whose instances do not interact.  x fp32 [N, Cx], e fp32 [E, Ce] of the batch `plan` describes (built
+    from its batch vector); a baseline is None (zeros), one row [C] or rows [rows, C].
+
+    The S points of the rule (quadrature) become instances: per chunk of whole steps -- all B graphs x a run of steps, at most
+    `max_instances` instances but at least one step -- ops.graph_instances expands the batch, ops.ig_path_rows writes the
+    points' rows in one launch, the rows become leaves, ONE torch.autograd.grad call under torch.enable_grad() takes the gradient
+    of score(...).sum() with respect to them (no parameter's .grad is touched), and ops.ig_attribution reduces the gradient
+    rows to attributions in one launch, adding to the running result.  edges=True puts the edge rows on the path as well;
+    otherwise they stay at the input.  rows=True also returns the weighted gradient rows.  The score at t = 1 and t = 0 comes
+    from one two-step instance batch without a gradient; `delta` is computed on the device."""
+    t_host, w_host = quadrature(steps, rule)
+    S, B = int(steps), plan.B
+    if plan.batch is None:
+        raise ValueError("path_attributions needs a GraphPlan built from the batch vector")
+    if max_instances is not None and int(max_instances) < 1:
+        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    per = S if max_instances is None else max(1, min(S, int(max_instances) // max(B, 1)))
+    with torch.no_grad():
+        x, e = x.detach(), e.detach()
+        dev = x.device
+        bx = None if baseline_x is None else baseline_x.detach()
+        be = None if baseline_e is None or not edges else baseline_e.detach()
+        res, chunks = None, []
+        for lo in range(0, S, per):
+            sc = min(per, S - lo)
+            inst = _step_instances(plan, edge_index, sc)
+            t = t_host[lo:lo + sc].float().repeat(B).to(dev)
+            w = w_host[lo:lo + sc].float().repeat(B).to(dev)
+            x_inst, e_inst = ops.ig_path_rows(inst, x, e, t, bx, be, path_edges=edges)
+            leaves = [x_inst.requires_grad_(True)] + ([e_inst.requires_grad_(True)] if edges else [])
+            with torch.enable_grad():
+                total = score(x_inst, e_inst, inst).sum()
+                grads = torch.autograd.grad(total, leaves)
+            res = ops.ig_attribution(inst, grads[0].contiguous(), grads[1].contiguous() if edges else None, w, x, e, bx, be,
+                                     want_rows=rows, out=res)
+            chunks.append(inst)
+        ends = _step_instances(plan, edge_index, 2)
+        x_end, e_end = ops.ig_path_rows(ends, x, e, torch.tensor([1.0, 0.0]).repeat(B).to(dev), bx, be, path_edges=edges)
+        f = score(x_end, e_end, ends).float().reshape(B, 2)
+        f_input, f_baseline = f[:, 0].contiguous(), f[:, 1].contiguous()
+        total = torch.zeros(B, dtype=torch.float32, device=dev).index_add_(0, plan.batch, res.attr_x)
+        if edges:
+            total.index_add_(0, plan.batch.index_select(0, edge_index[1]), res.attr_e)
+        delta = total - (f_input - f_baseline)
+    return PathAttributions(res.attr_x, res.attr_e, (res.avg_x, res.avg_e) if rows else None, f_input, f_baseline, delta, plan, S,
+                            rule, chunks)
+
+
+def _graph_mean_rows(rows: Tensor, graph: Tensor, B: int) -> Tensor:
+    """fp32 [rows, C]: every row replaced by the mean row of its graph."""
+    sums = torch.zeros(B, rows.size(1), dtype=torch.float32, device=rows.device).index_add_(0, graph, rows.float())
+    count = torch.zeros(B, dtype=torch.float32, device=rows.device).index_add_(0, graph, torch.ones_like(graph, dtype=torch.float32))
+    return (sums / count.clamp_min(1.0).unsqueeze(1)).index_select(0, graph).contiguous()
+
+
+def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
+                         steps: int = 16, rule: str = "gauss_legendre", baseline="zero", target: str = "prob",
+                         edges: bool = False, max_instances: Optional[int] = None) -> PathAttributions:
+    """Integrated gradients (Sundararajan et al. 2017) of every node: the gradient of the predicted answer's score along the
+    straight path from a baseline to the rows the MGAT reads, integrated by `rule` over `steps` points and multiplied by
+    (row - baseline) -- a gradient post-hoc baseline for the intrinsic mask (path_attributions does the work).  steps=1 with
+    rule="endpoint" is gradient x input.  `inputs` as for occlusion().  One forward under no_grad gives `pred` and `logits`; the
+    score is the softmax probability (target="prob", occlusion's yardstick) or the logit (target="logit") of class pred[graph]
+    on every instance, the question side gathered by the instance's graph.
+
+    For an AnswerModel the path lies in inputs.x / inputs.edge_attr.  For ISubGVQA it lies in the scene-graph encoder's OUTPUT:
+    encode_scene and language_features run once, every chunk runs answer_graphs on the path's rows -- the token ids have no
+    straight path, so the attribution is that of the rows the MGAT reads, not of the tokens.
+    baseline: "zero", "mean" (every graph's mean row) or a tensor ([C] or [N, C]; a pair (x, e) with edges=True).
+
+    The model must be in eval().  The samplers along the path behave as the model's autograd defines there: imle / aimle give a
+    constant threshold mask (no gradient through the selection), gumbel is straight-through, simple differentiates its marginals.
+    The mask may CHANGE along the path (the score is then not smooth in t); `delta`, the completeness gap, reports what that and
+    the quadrature cost.  No parameter's .grad is touched."""
+    if model.training:
+        raise ValueError("integrated_gradients explains the model in eval(): in train() dropout and the training samplers would "
+                         "change the score from point to point -- call model.eval()")
+    if target not in ("prob", "logit"):
+        raise ValueError(f"target: 'prob' or 'logit', got {target!r}")
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        plan = _input_plan(inputs, B)
+        if full:
+            state = model.encode_scene(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs(), plan)
+            glf, instr = model.language_features(inputs.questions, inputs.att_mask, None, None if seed is None else seed + 7919)
+            x, e = state.x_enc.float().contiguous(), state.e_enc.float().contiguous()
+            logits = model.answer_graphs(x, inputs.edge_index, e, inputs.batch, instr, glf, plan, True, noises, seed)[0]
+        else:
+            glf, instr = inputs.glf, inputs.instr
+            x, e = inputs.x.float().contiguous(), inputs.edge_attr.float().contiguous()
+            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, None, plan)[0]
+        pred = torch.softmax(logits.float(), dim=1).argmax(dim=1)
+        graph_e = inputs.batch.index_select(0, inputs.edge_index[1])
+        if isinstance(baseline, str):
+            if baseline not in ("zero", "mean"):
+                raise ValueError(f"baseline: 'zero', 'mean' or a tensor, got {baseline!r}")
+            bx = None if baseline == "zero" else _graph_mean_rows(x, inputs.batch, B)
+            be = None if baseline == "zero" or not edges else _graph_mean_rows(e, graph_e, B)
+        elif isinstance(baseline, (tuple, list)):
+            bx, be = baseline
+        else:
+            bx, be = baseline, None
+
+    def score(x_inst, e_inst, inst):
+        rows = inst.index.long()
+        nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
+        ins, g = instr.index_select(1, rows).contiguous(), glf.index_select(0, rows)
+        if full:
+            out = model.answer_graphs(x_inst, inst.edge_index, e_inst, inst.batch, ins, g, inst.plan(), True, nz, seed)[0]
+        else:
+            out = model(synthetic.Workload(x_inst, inst.edge_index, e_inst, inst.batch, ins, g, g.size(0), inputs.max_nodes,
+                                           inputs.max_edges, None), noises=nz, seed=seed, plan=inst.plan())[0]
+        out = out.float()
+        pick = pred.index_select(0, rows).unsqueeze(1)
+        return (torch.softmax(out, dim=1) if target == "prob" else out).gather(1, pick).squeeze(1)
+
+    res = path_attributions(score, x, e, plan, inputs.edge_index, steps=steps, rule=rule, baseline_x=bx, baseline_e=be, edges=edges,
+                            max_instances=max_instances)
+    return replace(res, pred=pred, logits=logits)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Token co-occurrence
 # ---------------------------------------------------------------------------------------------------------------------
 class TokenTables:
@@ -586,7 +781,8 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
 # The intrinsic mask beside post-hoc baselines
 # ---------------------------------------------------------------------------------------------------------------------
 EXPLAINERS = ("intrinsic", "occlusion", "random")
-EXPLAINERS_ALL = EXPLAINERS + ("attention",)       # what compare() accepts; EXPLAINERS stays its default
+EXPLAINERS_ALL = EXPLAINERS + ("attention",)       # what compare() accepts beside the gradient explainers; EXPLAINERS stays its default
+EXPLAINERS_GRADIENT = ("integrated_gradients", "grad_x_input")      # compare() accepts these too (integrated_gradients())
 COMPARE_SUMS = 6       # float64 per explainer: sum fid_plus, questions that have one, sum fid_minus, questions that have one,
                        # sum of the Jaccard overlaps with the intrinsic mask, graphs that have one
 
@@ -619,17 +815,20 @@ def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: 
 
 
 def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
-            threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None) -> Dict[str, ExplainerReport]:
+            threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16
+            ) -> Dict[str, ExplainerReport]:
     """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
     explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
     mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
     intrinsic: the forward's own mask; occlusion: occlusion().mask(k); random: random_mask(plan, k, seed + batch number);
-    attention (not among the default): attention_rollout().mask(k).
+    attention (not among the default): attention_rollout().mask(k); integrated_gradients and grad_x_input (EXPLAINERS_GRADIENT,
+    not among the default): integrated_gradients(steps=ig_steps).mask(k) and its one-point case (steps=1, rule="endpoint") --
+    autograd records inside those calls only.
     Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate()."""
     names_x = tuple(explainers)
-    unknown = [x for x in names_x if x not in EXPLAINERS_ALL]
+    unknown = [x for x in names_x if x not in EXPLAINERS_ALL + EXPLAINERS_GRADIENT]
     if unknown or not names_x:
-        raise ValueError(f"compare: explainers from {EXPLAINERS_ALL}, got {names_x}")
+        raise ValueError(f"compare: explainers from {EXPLAINERS_ALL + EXPLAINERS_GRADIENT}, got {names_x}")
     X = len(names_x)
     full = not isinstance(model, synthetic.AnswerModel)
     flat = coo = ground = sums = None
@@ -663,6 +862,10 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                     mask = occlusion(model, inp, max_instances=max_instances).mask(k)
                 elif name == "attention":
                     mask = attention_rollout(model, inp).mask(k)
+                elif name == "integrated_gradients":
+                    mask = integrated_gradients(model, inp, steps=ig_steps, max_instances=max_instances).mask(k)
+                elif name == "grad_x_input":
+                    mask = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances).mask(k)
                 else:
                     mask = random_mask(plan, k, seed + number)
                 ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,

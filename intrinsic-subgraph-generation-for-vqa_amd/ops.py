@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _ext_induced, _ext_instances_train, _ext_rollout, _lib, _lib_instances
+from . import _ext_ig, _ext_induced, _ext_instances_train, _ext_rollout, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -147,6 +147,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "instance_rows_bwd": 0,                    # backwards of the instance-row gather (include/ext/isg_instances_train.h)
             "induced_instances": 0,                    # batches of induced-subgraph instances (include/ext/isg_induced.h)
             "attention_rollout": 0,                    # attention-rollout launches (include/ext/isg_rollout.h)
+            "ig_path_rows": 0,                         # path-row launches of integrated gradients (include/ext/isg_ig.h)
+            "ig_attribution": 0,                       # gradient rows reduced to attributions (include/ext/isg_ig.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1105,6 +1107,129 @@ def attention_rollout(plan: "GraphPlan", alphas, start: Tensor, masks=None, resi
                                          relevance.data_ptr(), 0 if flow is None else flow.data_ptr(), _stream()),
                "isg_attention_rollout")
     return relevance, flow
+
+
+# ------------------------------------------------------------------------------------------------
+# Integrated gradients: the path's rows as one instance batch, its gradient rows reduced to attributions
+# ------------------------------------------------------------------------------------------------
+class IgAttribution(NamedTuple):
+    attr_x: Tensor               # fp32 [N]: the attribution of every node of the parent batch
+    attr_e: Optional[Tensor]     # fp32 [E], or None when the edge half was skipped
+    avg_x: Optional[Tensor]      # fp32 [N, Cx]: the weighted sum of every node's gradient rows; None unless asked for
+    avg_e: Optional[Tensor]      # fp32 [E, Ce]
+
+
+def _ig_base(base: Optional[Tensor], rows: int, C: int, name: str) -> Tuple[int, int]:
+    """(address, row stride) of a baseline: None -> (0, 0); fp32 [C] -> one row, stride 0; fp32 [rows, C] -> its rows."""
+    if base is None:
+        return 0, 0
+    if base.dim() == 1:
+        return _chk(base, name, torch.float32, (C,)), 0
+    p = _chk_rows(base, name)
+    if tuple(base.shape) != (rows, C):
+        raise ValueError(f"{name}: expected None, fp32 [{C}] or fp32 [{rows}, {C}], got {tuple(base.shape)}")
+    return p, _ld(base)
+
+
+def _ig_rows(inst: GraphInstances, x: Tensor, e: Tensor, what: str) -> Tuple[int, int]:
+    px, pe = _chk_rows(x, "x"), _chk_rows(e, "e")
+    if x.size(0) != inst.parent.N or e.size(0) != inst.parent_edges:
+        raise ValueError(f"{what}: expected {inst.parent.N} node rows and {inst.parent_edges} edge rows, got {x.size(0)} and {e.size(0)}")
+    if (x.size(1) & 3) or (e.size(1) & 3):
+        raise ValueError(f"{what}: row widths must be multiples of 4, got {x.size(1)} and {e.size(1)}")
+    return px, pe
+
+
+def _ld(t: Tensor) -> int:
+    """The row stride the entry points are told.  A tensor of fewer than two rows may carry any (an expanded [1, C] gradient
+    has 0 and still counts as contiguous); its width serves."""
+    return t.stride(0) if t.size(0) > 1 else t.size(1)
+
+
+def ig_path_rows(inst: GraphInstances, x: Tensor, e: Tensor, t: Tensor, base_x: Optional[Tensor] = None,
+                 base_e: Optional[Tensor] = None, path_edges: bool = False) -> Tuple[Tensor, Tensor]:
+    """(x_inst [N', Cx], e_inst [E', Ce]) of isg_ig_path_rows (include/ext/isg_ig.h, where the function is stated): instance q's
+    rows are the point t[q] of the straight path from the baseline to the input, x_inst[i] = t x[node_src[i]] + (1 - t) base, in
+    ONE launch.  x fp32 [N, Cx], e fp32 [E, Ce] (strided rows as gather_rows takes them); t fp32 [Q] on the device; a baseline
+    is None (zeros), one row [C] or rows [rows, C].  path_edges=False copies the edge rows (they stay at the input; base_e is
+    then not looked at).  No backward: a tensor that requires grad raises."""
+    lib = _ext_ig.load()
+    px, pe = _ig_rows(inst, x, e, "ig_path_rows")
+    Q, Cx, Ce = inst.Q, x.size(1), e.size(1)
+    pt = _chk(t, "t", torch.float32, (Q,))
+    pbx, ldbx = _ig_base(base_x, x.size(0), Cx, "base_x")
+    pbe, ldbe = _ig_base(base_e, e.size(0), Ce, "base_e") if path_edges else (0, 0)
+    n, m = inst.node_src.numel(), inst.edge_src.numel()
+    xo = torch.empty(n, Cx, dtype=torch.float32, device=x.device)
+    eo = torch.empty(m, Ce, dtype=torch.float32, device=e.device)
+    einst = inst.batch.index_select(0, inst.edge_index[0]) if path_edges and m > 0 else None      # the instance of every edge row
+    COUNTERS["ig_path_rows"] += 1
+    _lib.check(lib.isg_ig_path_rows(px, _ld(x), x.size(0), pbx, ldbx, inst.node_src.data_ptr(), inst.batch.data_ptr(), n,
+                                    xo.data_ptr(), Cx, Cx,
+                                    pe, _ld(e), e.size(0), pbe, ldbe, inst.edge_src.data_ptr(),
+                                    0 if einst is None else einst.data_ptr(), m, eo.data_ptr(), Ce, Ce,
+                                    pt, Q, 1 if path_edges else 0, _stream()), "isg_ig_path_rows")
+    return xo, eo
+
+
+def ig_attribution(inst: GraphInstances, g_x: Tensor, g_e: Optional[Tensor], w: Tensor, x: Tensor, e: Tensor,
+                   base_x: Optional[Tensor] = None, base_e: Optional[Tensor] = None, want_rows: bool = False,
+                   out: Optional[IgAttribution] = None) -> IgAttribution:
+    """isg_ig_attribution (include/ext/isg_ig.h, where the function and its order of operations are stated) in ONE launch: g_x
+    fp32 [N', Cx] (and g_e fp32 [E', Ce], or None: the edge half is skipped) are the gradients of the instance batch's rows, w
+    fp32 [Q] the quadrature weight of every instance; per row of the parent batch the weighted sum of its copies' gradient rows,
+    dotted with (x - base).  want_rows also returns those weighted sums (avg_x, avg_e).  out=: a previous result of the same
+    shapes, which this call adds to (a path forwarded in chunks) and returns.  No atomics; two calls agree bit for bit."""
+    lib = _ext_ig.load()
+    px, pe = _ig_rows(inst, x, e, "ig_attribution")
+    N, E, G, Q, Cx, Ce = inst.parent.N, inst.parent_edges, inst.parent.B, inst.Q, x.size(1), e.size(1)
+    n, m = inst.node_src.numel(), inst.edge_src.numel()
+    edges = g_e is not None
+    pgx = _chk_rows(g_x, "g_x")
+    pge = _chk_rows(g_e, "g_e") if edges else 0
+    if tuple(g_x.shape) != (n, Cx) or (edges and tuple(g_e.shape) != (m, Ce)):
+        raise ValueError(f"ig_attribution: expected gradient rows [{n}, {Cx}] and [{m}, {Ce}] (or None), got {tuple(g_x.shape)} and "
+                         f"{None if g_e is None else tuple(g_e.shape)}")
+    pw = _chk(w, "w", torch.float32, (Q,))
+    pbx, ldbx = _ig_base(base_x, N, Cx, "base_x")
+    pbe, ldbe = _ig_base(base_e, E, Ce, "base_e") if edges else (0, 0)
+    dev = x.device
+    if out is None:
+        attr_x = torch.empty(N, dtype=torch.float32, device=dev)
+        attr_e = torch.empty(E, dtype=torch.float32, device=dev) if edges else None
+        avg_x = torch.empty(N, Cx, dtype=torch.float32, device=dev) if want_rows else None
+        avg_e = torch.empty(E, Ce, dtype=torch.float32, device=dev) if want_rows and edges else None
+    else:
+        attr_x, attr_e, avg_x, avg_e = out
+        if (attr_e is not None) != edges or (avg_x is not None) != bool(want_rows):
+            raise ValueError("ig_attribution: `out` was made with another g_e / want_rows")
+        _chk(attr_x, "out.attr_x", torch.float32, (N,))
+        if edges:
+            _chk(attr_e, "out.attr_e", torch.float32, (E,))
+        if want_rows:
+            _chk(avg_x, "out.avg_x", torch.float32, (N, Cx))
+            if edges:
+                _chk(avg_e, "out.avg_e", torch.float32, (E, Ce))
+    res = IgAttribution(attr_x, attr_e, avg_x, avg_e)
+    if Q == 0 or inst.erange is None:            # nothing was expanded: no copies, every sum is empty
+        if out is None:
+            for t_ in res:
+                if t_ is not None:
+                    t_.zero_()
+        return res
+    gptr, glist = inst.by_graph()
+    COUNTERS["ig_attribution"] += 1
+    _lib.check(lib.isg_ig_attribution(pgx, _ld(g_x), n, px, _ld(x), pbx, ldbx, attr_x.data_ptr(),
+                                      0 if avg_x is None else avg_x.data_ptr(), Cx, N, Cx,
+                                      pge, _ld(g_e) if edges else Ce, m if edges else 0, pe, _ld(e), pbe, ldbe,
+                                      attr_e.data_ptr() if edges else 0, 0 if avg_e is None else avg_e.data_ptr(), Ce,
+                                      E if edges else 0, Ce,
+                                      pw, _chk(inst.parent.ptr, "plan.ptr", torch.int32, (G + 1,)),
+                                      _chk(inst.erange, "erange", torch.int32, (G + 1,)),
+                                      _chk(inst.ptr, "inst.ptr", torch.int32, (Q + 1,)), _chk(inst.eptr, "inst.eptr", torch.int32, (Q + 1,)),
+                                      _chk(gptr, "gptr", torch.int32, (G + 1,)), _chk(glist, "glist", torch.int32, (Q,)), G, Q,
+                                      0 if out is None else 1, _stream()), "isg_ig_attribution")
+    return res
 
 
 # ------------------------------------------------------------------------------------------------
