@@ -16,6 +16,7 @@ the batch of instances `ops.induced_instances` makes in one pass --, `faithfulne
 node mask, and `compare` reports the model's own mask, the occlusion mask and a random one by the same yardsticks.
 `attention_rollout` is the one-forward baseline, `integrated_gradients` (with gradient x input as its one-point case) the gradient
 one: the points of a straight path as one batch of instances, their gradient rows reduced to attributions on the device.
+`mask_optimization` is the learned one (GNNExplainer): a soft node mask optimised by Adam, an iteration's arithmetic in one launch.
 """
 from __future__ import annotations
 
@@ -518,6 +519,136 @@ def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] =
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A learned baseline: mask optimisation (GNNExplainer)
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class MaskOptimization:
+    """The learned soft node mask of one batch (mask_optimize(), mask_optimization()): B independent GNNExplainer runs."""
+    theta: Tensor                          # fp32 [N]: the logit of every node after the last step
+    soft: Tensor                           # fp32 [N]: sigmoid(theta), the soft mask
+    nll: Tensor                            # fp32 [steps + 1, B] on the device: the score at the mask BEFORE step i (row 0: the initial
+                                           # mask) and, in the last row, at the final mask
+    plan: "ops.GraphPlan"
+    steps: int
+    edge_theta: Optional[Tensor] = None    # fp32 [E], when the edge rows had logits of their own (edges=True)
+    edge_soft: Optional[Tensor] = None
+    pred: Optional[Tensor] = None          # int64 [B]: the class that was explained
+    logits: Optional[Tensor] = None        # [B, classes] of the whole, unmasked batch (mask_optimization)
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest soft mask --
+        ops.topk_threshold on shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the
+        k-th value are all kept."""
+        scores = shifted_attributions(self.soft, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+
+def _edge_ranges(plan: "ops.GraphPlan", edge_index: Tensor) -> Tensor:
+    """int32 [B + 1] on the device: the range of every graph's rows in the caller's edge order (a graph's edges lie next to each
+    other, as a collated batch has them); counted on the device, nothing is copied to the host."""
+    count = torch.bincount(plan.batch.index_select(0, edge_index[1]), minlength=plan.B)
+    return torch.cat([count.new_zeros(1), count.cumsum(0)]).to(torch.int32).contiguous()
+
+
+def _initial_logits(init, rows: int, gen, dev, name: str) -> Tensor:
+    if torch.is_tensor(init):
+        if init.numel() != rows:
+            raise ValueError(f"mask_optimize: init for the {name} rows holds {init.numel()} logits, the batch has {rows}")
+        return init.detach().to(device=dev, dtype=torch.float32).reshape(-1).clone()
+    return float(init) * torch.randn(rows, generator=gen, device=dev, dtype=torch.float32)
+
+
+def mask_optimize(score, x: Tensor, e: Tensor, plan: "ops.GraphPlan", edge_index: Tensor, *, pred_rows: Optional[Tensor] = None,
+                  steps: int = 100, lr: float = 0.01, a_size: float = 1.0, a_ent: float = 0.1, init=0.1, init_seed: int = 0,
+                  edges: bool = False) -> MaskOptimization:
+    """GNNExplainer's optimisation (Ying et al. 2019, PyG's GNNExplainer with an object-level node mask) of `score` over the rows
+    (x, e) of a batch -- the model-free core.  score(x_m, e_m) -> fp32 [B]: any differentiable per-graph loss of the MASKED rows
+    whose graphs do not interact.  One logit theta[n] per node, the score reads sigmoid(theta[n]) * x[n]; per graph
+        score + a_size * mean_n sigmoid(theta) + a_ent * mean_n H(sigmoid(theta))
+    is minimised by `steps` Adam steps of rate `lr`; the batch loss is the sum over the graphs and Adam is elementwise, so the B
+    graphs are B independent runs.  edges=True learns a second logit per edge row, with the means over each graph's edge rows.
+
+    Per iteration: the masked rows become leaves, ONE torch.autograd.grad call under torch.enable_grad() takes the gradient of
+    score(...).sum() with respect to them (no parameter's .grad is touched), and ONE ops.maskopt_step per half turns the gradient
+    rows into d theta, takes the Adam step and writes the next masked rows (include/ext/isg_maskopt.h).  Nothing is copied to the
+    host inside the loop.  init: the std of seeded normal logits drawn on the device (init_seed), or a tensor of logits ([N]; a
+    pair ([N], [E]) with edges=True).  pred_rows (int64 [B]): the classes the score explains, kept in the result."""
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 0:
+        raise ValueError(f"mask_optimize: steps must be an integer >= 0, got {steps!r}")
+    if plan.batch is None:
+        raise ValueError("mask_optimize needs a GraphPlan built from the batch vector")
+    T, B = int(steps), plan.B
+    kw = dict(a_size=a_size, a_ent=a_ent, lr=lr)
+    with torch.no_grad():
+        x, e = x.detach(), e.detach()
+        dev = x.device
+        gen = torch.Generator(device=dev).manual_seed(int(init_seed))
+        init_x, init_e = init if isinstance(init, (tuple, list)) else (init, init)
+        halves = [(x, plan.ptr, _initial_logits(init_x, x.size(0), gen, dev, "node"))]
+        if edges:
+            halves.append((e, _edge_ranges(plan, edge_index), _initial_logits(init_e, e.size(0), gen, dev, "edge")))
+        moments = [(torch.zeros_like(th), torch.zeros_like(th)) for _, _, th in halves]
+        masked = [ops.maskopt_step(rows, None, seg, th, None, None, step=1, **kw)[0] for rows, seg, th in halves]
+        nll = torch.empty(T + 1, B, dtype=torch.float32, device=dev)
+        for it in range(1, T + 1):
+            leaves = [m.requires_grad_(True) for m in masked]
+            with torch.enable_grad():
+                f = score(leaves[0], leaves[1] if edges else e)
+                grads = torch.autograd.grad(f.sum(), leaves)
+            nll[it - 1] = f.detach().float().reshape(B)
+            masked = [ops.maskopt_step(rows, g.contiguous(), seg, th, mv[0], mv[1], step=it, **kw)[0]
+                      for (rows, seg, th), mv, g in zip(halves, moments, grads)]
+        nll[T] = score(masked[0], masked[1] if edges else e).float().reshape(B)
+        theta = halves[0][2]
+        edge_theta = halves[1][2] if edges else None
+    return MaskOptimization(theta, torch.sigmoid(theta), nll, plan, T, edge_theta, None if edge_theta is None else torch.sigmoid(edge_theta),
+                            pred_rows)
+
+
+def mask_optimization(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None, steps: int = 100,
+                      lr: float = 0.01, a_size: float = 1.0, a_ent: float = 0.1, init=0.1, init_seed: int = 0,
+                      edges: bool = False) -> MaskOptimization:
+    """GNNExplainer (Ying et al. 2019) of every node: a soft mask on the rows the MGAT reads, learned so that the masked graph
+    still gives the model's answer -- the learned post-hoc baseline for the intrinsic mask (mask_optimize does the work; PyG's
+    defaults).  `inputs` as for occlusion().  One forward under no_grad gives `pred` and `logits`; the score is
+    -log softmax(logits)[pred[graph]] of the masked batch.
+
+    For an AnswerModel the mask scales inputs.x (and inputs.edge_attr with edges=True).  For ISubGVQA it scales the scene-graph
+    encoder's OUTPUT rows, as integrated_gradients' path lies there: encode_scene and language_features run once, every iteration
+    runs answer_graphs.  The model must be in eval(); the samplers behave as integrated_gradients states for eval() under
+    autograd, and the model's own mask may change from one iteration to the next.  No parameter's .grad is touched."""
+    if model.training:
+        raise ValueError("mask_optimization explains the model in eval(): in train() dropout and the training samplers would "
+                         "change the score from iteration to iteration -- call model.eval()")
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        plan = _input_plan(inputs, B)
+        if full:
+            state = model.encode_scene(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs(), plan)
+            glf, instr = model.language_features(inputs.questions, inputs.att_mask, None, None if seed is None else seed + 7919)
+            x, e = state.x_enc.float().contiguous(), state.e_enc.float().contiguous()
+            logits = model.answer_graphs(x, inputs.edge_index, e, inputs.batch, instr, glf, plan, True, noises, seed)[0]
+        else:
+            glf, instr = inputs.glf, inputs.instr
+            x, e = inputs.x.float().contiguous(), inputs.edge_attr.float().contiguous()
+            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, None, plan)[0]
+        pred = torch.softmax(logits.float(), dim=1).argmax(dim=1)
+        pick = pred.unsqueeze(1)
+
+    def score(x_m, e_m):
+        if full:
+            out = model.answer_graphs(x_m, inputs.edge_index, e_m, inputs.batch, instr, glf, plan, True, noises, seed)[0]
+        else:
+            out = model(synthetic.Workload(x_m, inputs.edge_index, e_m, inputs.batch, instr, glf, B, inputs.max_nodes,
+                                           inputs.max_edges, None), noises=noises, seed=seed, plan=plan)[0]
+        return -torch.log_softmax(out.float(), dim=1).gather(1, pick).squeeze(1)
+
+    res = mask_optimize(score, x, e, plan, inputs.edge_index, pred_rows=pred, steps=steps, lr=lr, a_size=a_size, a_ent=a_ent,
+                        init=init, init_seed=init_seed, edges=edges)
+    return replace(res, logits=logits)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Token co-occurrence
 # ---------------------------------------------------------------------------------------------------------------------
 class TokenTables:
@@ -783,6 +914,7 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
 EXPLAINERS = ("intrinsic", "occlusion", "random")
 EXPLAINERS_ALL = EXPLAINERS + ("attention",)       # what compare() accepts beside the gradient explainers; EXPLAINERS stays its default
 EXPLAINERS_GRADIENT = ("integrated_gradients", "grad_x_input")      # compare() accepts these too (integrated_gradients())
+EXPLAINERS_LEARNED = ("mask_optimization",)                         # ... and this one (mask_optimization(): GNNExplainer)
 COMPARE_SUMS = 6       # float64 per explainer: sum fid_plus, questions that have one, sum fid_minus, questions that have one,
                        # sum of the Jaccard overlaps with the intrinsic mask, graphs that have one
 
@@ -815,20 +947,22 @@ def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: 
 
 
 def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
-            threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16
-            ) -> Dict[str, ExplainerReport]:
+            threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16,
+            mo_steps: int = 100) -> Dict[str, ExplainerReport]:
     """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
     explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
     mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
     intrinsic: the forward's own mask; occlusion: occlusion().mask(k); random: random_mask(plan, k, seed + batch number);
     attention (not among the default): attention_rollout().mask(k); integrated_gradients and grad_x_input (EXPLAINERS_GRADIENT,
     not among the default): integrated_gradients(steps=ig_steps).mask(k) and its one-point case (steps=1, rule="endpoint") --
-    autograd records inside those calls only.
+    autograd records inside those calls only; mask_optimization (EXPLAINERS_LEARNED, not among the default):
+    mask_optimization(steps=mo_steps, init_seed=seed + batch number).mask(k), GNNExplainer with PyG's defaults.
     Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate()."""
     names_x = tuple(explainers)
-    unknown = [x for x in names_x if x not in EXPLAINERS_ALL + EXPLAINERS_GRADIENT]
+    known = EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED
+    unknown = [x for x in names_x if x not in known]
     if unknown or not names_x:
-        raise ValueError(f"compare: explainers from {EXPLAINERS_ALL + EXPLAINERS_GRADIENT}, got {names_x}")
+        raise ValueError(f"compare: explainers from {known}, got {names_x}")
     X = len(names_x)
     full = not isinstance(model, synthetic.AnswerModel)
     flat = coo = ground = sums = None
@@ -866,6 +1000,8 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                     mask = integrated_gradients(model, inp, steps=ig_steps, max_instances=max_instances).mask(k)
                 elif name == "grad_x_input":
                     mask = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances).mask(k)
+                elif name == "mask_optimization":
+                    mask = mask_optimization(model, inp, steps=mo_steps, init_seed=seed + number).mask(k)
                 else:
                     mask = random_mask(plan, k, seed + number)
                 ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,

@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _ext_ig, _ext_induced, _ext_instances_train, _ext_rollout, _lib, _lib_instances
+from . import _ext_ig, _ext_induced, _ext_instances_train, _ext_maskopt, _ext_rollout, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -149,6 +149,7 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "attention_rollout": 0,                    # attention-rollout launches (include/ext/isg_rollout.h)
             "ig_path_rows": 0,                         # path-row launches of integrated gradients (include/ext/isg_ig.h)
             "ig_attribution": 0,                       # gradient rows reduced to attributions (include/ext/isg_ig.h)
+            "maskopt_step": 0,                         # mask-optimisation iterations (include/ext/isg_maskopt.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1230,6 +1231,58 @@ def ig_attribution(inst: GraphInstances, g_x: Tensor, g_e: Optional[Tensor], w: 
                                       _chk(gptr, "gptr", torch.int32, (G + 1,)), _chk(glist, "glist", torch.int32, (Q,)), G, Q,
                                       0 if out is None else 1, _stream()), "isg_ig_attribution")
     return res
+
+
+# ------------------------------------------------------------------------------------------------
+# Mask optimisation: one iteration's arithmetic of a GNNExplainer run as one launch
+# ------------------------------------------------------------------------------------------------
+def adam_bias_corrections(step: int, betas=(0.9, 0.999)) -> Tuple[float, float]:
+    """(1 - beta1^step, 1 - beta2^step) in double, as isg_mt_adam's prologue forms them (include/isg_optim.h)."""
+    if isinstance(step, bool) or int(step) != step or int(step) < 1:
+        raise ValueError(f"step must be an integer >= 1, got {step!r}")
+    return 1.0 - float(betas[0]) ** int(step), 1.0 - float(betas[1]) ** int(step)
+
+
+def maskopt_step(x: Tensor, g: Optional[Tensor], seg: Tensor, theta: Tensor, exp_avg: Optional[Tensor],
+                 exp_avg_sq: Optional[Tensor], *, step: int, a_size: float = 1.0, a_ent: float = 0.1, lr: float = 0.01,
+                 betas=(0.9, 0.999), eps: float = 1e-8, out: Optional[Tensor] = None, want_grad: bool = False
+                 ) -> Tuple[Tensor, Optional[Tensor]]:
+    """(x_masked [N, C], d_theta [N] or None) of isg_maskopt_step (include/ext/isg_maskopt.h, where the function and its order of
+    operations are stated) in ONE launch: x fp32 [N, C] the unmasked rows, g fp32 [N, C] the gradient of the summed loss with
+    respect to the masked rows (strided rows as gather_rows takes them), seg int32 [B + 1] the range starts of the rows' segments
+    (plan.ptr for node rows), theta / exp_avg / exp_avg_sq fp32 [N] updated IN PLACE by Adam's step number `step` (>= 1).
+    g=None is the apply-only form: nothing is updated (the moments may be None), x_masked = sigmoid(theta) * x.
+    out=: an fp32 [N, C] tensor to write the masked rows to; want_grad also returns d theta.  No backward: a tensor that requires
+    grad raises.  No atomics; two calls agree bit for bit."""
+    lib = _ext_maskopt.load()
+    px = _chk_rows(x, "x")
+    N, C = x.size(0), x.size(1)
+    if C & 3:
+        raise ValueError(f"maskopt_step: the row width must be a multiple of 4, got {C}")
+    pg, ldg = 0, C
+    if g is not None:
+        pg, ldg = _chk_rows(g, "g"), _ld(g)
+        if tuple(g.shape) != (N, C):
+            raise ValueError(f"maskopt_step: expected gradient rows [{N}, {C}], got {tuple(g.shape)}")
+    if seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError(f"maskopt_step: seg is int32 [B + 1], got {tuple(seg.shape)}")
+    B = seg.numel() - 1
+    pseg = _chk(seg, "seg", torch.int32)
+    pth = _chk(theta, "theta", torch.float32, (N,))
+    pm = _chk(exp_avg, "exp_avg", torch.float32, (N,), optional=g is None)
+    pv = _chk(exp_avg_sq, "exp_avg_sq", torch.float32, (N,), optional=g is None)
+    bc1, bc2 = adam_bias_corrections(step, betas)
+    if out is None:
+        out = torch.empty(N, C, dtype=torch.float32, device=x.device)
+    po = _chk_rows(out, "out")
+    if tuple(out.shape) != (N, C):
+        raise ValueError(f"maskopt_step: expected out [{N}, {C}], got {tuple(out.shape)}")
+    d_theta = torch.empty(N, dtype=torch.float32, device=x.device) if want_grad and g is not None else None
+    COUNTERS["maskopt_step"] += 1
+    _lib.check(lib.isg_maskopt_step(px, _ld(x), pg, ldg, pseg, B, pth, pm, pv, po, _ld(out),
+                                    0 if d_theta is None else d_theta.data_ptr(), N, C, float(a_size), float(a_ent), float(lr),
+                                    float(betas[0]), float(betas[1]), float(eps), bc1, bc2, _stream()), "isg_maskopt_step")
+    return out, d_theta
 
 
 # ------------------------------------------------------------------------------------------------

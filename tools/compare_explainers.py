@@ -5,10 +5,11 @@ and annotated objects.  An untrained model on random graphs: the figures show th
 differ on them, not how good an explanation is.
 
   python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048]
-                                     [--explainers intrinsic,occlusion,random,attention,integrated_gradients,grad_x_input]
-                                     [--ig-steps 16] [--out profiles/<name>.json]
---explainers: a comma-separated list from explain.EXPLAINERS_ALL + explain.EXPLAINERS_GRADIENT (default: explain.EXPLAINERS);
---ig-steps: the points of integrated_gradients' path."""
+                                     [--explainers intrinsic,occlusion,random,attention,integrated_gradients,grad_x_input,mask_optimization]
+                                     [--ig-steps 16] [--mo-steps 100] [--out profiles/<name>.json]
+--explainers: a comma-separated list from explain.EXPLAINERS_ALL + explain.EXPLAINERS_GRADIENT + explain.EXPLAINERS_LEARNED
+(default: explain.EXPLAINERS); --ig-steps: the points of integrated_gradients' path; --mo-steps: the Adam steps
+of mask_optimization."""
 import dataclasses
 import json
 import os
@@ -26,6 +27,7 @@ GRAPHS, BATCHES, K = int(opt.get("--graphs", 64)), int(opt.get("--batches", 2)),
 MAX_INSTANCES = int(opt["--max-instances"]) if "--max-instances" in opt else None
 EXPLAINERS = tuple(n for n in opt["--explainers"].split(",") if n) if "--explainers" in opt else explain.EXPLAINERS
 IG_STEPS = int(opt.get("--ig-steps", 16))
+MO_STEPS = int(opt.get("--mo-steps", 100))
 V, A = 2578, 1842
 
 cfg = dataclasses.replace(synthetic.CFG1, num_graphs=GRAPHS, sampler="imle", sample_k=K)
@@ -49,7 +51,8 @@ with torch.no_grad():
         gold = synthetic.make_gold(wl.graph_sizes[0], seed=b)
         batches.append(explain.EvalBatch(d, label.to(dev), qtok.to(dev), (torch.arange(GRAPHS) % 4 == 0).int().to(dev), names.to(dev),
                                          gold=gold.to(dev)))
-report = explain.compare(model, batches, tables, explainers=EXPLAINERS, k=K, max_instances=MAX_INSTANCES, ig_steps=IG_STEPS)
+report = explain.compare(model, batches, tables, explainers=EXPLAINERS, k=K, max_instances=MAX_INSTANCES, ig_steps=IG_STEPS,
+                         mo_steps=MO_STEPS)
 out = {"device": torch.cuda.get_device_name(0), "graphs_per_batch": GRAPHS, "batches": BATCHES, "k": K, "explainers": {}}
 for name, r in report.items():
     g = r.grounding.sets["any"]["all"]
