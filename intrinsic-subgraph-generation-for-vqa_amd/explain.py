@@ -211,6 +211,25 @@ def instance_inputs(inputs, inst: "ops.GraphInstances", full: bool):
     return x, inst.edge_index, ea, inst.batch, sg
 
 
+def _instance_probabilities(forward, inputs, full: bool, B: int, plan: "ops.GraphPlan", index: Tensor, keep: Tensor, pred: Tensor,
+                            p: Tensor, noises, max_instances: Optional[int]):
+    """(fp32 [Q]: the class pred[index[q]]'s probability on instance q, the instance batches in order) of the Q induced-subgraph
+    instances that rows of keep bits name (ops.induced_instances), cut at the model's input (instance_inputs), the question rows
+    gathered through index, the noises' rows handed to an instance by its graph, forwarded in chunks of at most max_instances
+    instances (None: all at once).  The loop that occlusion() and fidelity_curves() share; the caller holds torch.no_grad()."""
+    Q = index.numel()
+    step = Q if max_instances is None else int(max_instances)
+    chunks, parts = [], []
+    for lo in range(0, Q, max(step, 1)):
+        rows = index[lo:lo + step].long()
+        inst = ops.induced_instances(plan, inputs.edge_index, index[lo:lo + step].contiguous(), keep[lo:lo + step].contiguous())
+        nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
+        out = forward(*instance_inputs(inputs, inst, full), inst.plan(), rows, nz)[0]
+        parts.append(torch.softmax(out.float(), dim=1).gather(1, pred.index_select(0, rows).unsqueeze(1)).squeeze(1))
+        chunks.append(inst)
+    return (torch.cat(parts) if parts else p.new_zeros(0)), chunks
+
+
 @dataclass
 class Occlusion:
     """Leave-one-out attributions of one batch (occlusion())."""
@@ -224,6 +243,12 @@ class Occlusion:
     logits: Tensor                 # [B, classes] of the whole batch
     plan: "ops.GraphPlan"
     chunks: List["ops.InducedInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift -- the scores of a fidelity curve (fidelity_curves()).  mask(k) keeps
+        its threshold rule, under which ties at the k-th value keep MORE than k nodes; a curve's rank prefixes
+        (ops.curve_keep_bits) keep exactly k, ties going to the lower node."""
+        return self.attribution.float().reshape(-1)
 
     def mask(self, k) -> Tensor:
         """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph whose removal costs the answer most --
@@ -257,17 +282,7 @@ def occlusion(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed
         pred = prob.argmax(dim=1)
         p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
         index, keep, inst_node = ops.keep_bits_leave_one_out(plan)
-        Q = index.numel()
-        step = Q if max_instances is None else int(max_instances)
-        chunks, parts = [], []
-        for lo in range(0, Q, max(step, 1)):
-            rows = index[lo:lo + step].long()
-            inst = ops.induced_instances(plan, inputs.edge_index, index[lo:lo + step].contiguous(), keep[lo:lo + step].contiguous())
-            nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
-            out = forward(*instance_inputs(inputs, inst, full), inst.plan(), rows, nz)[0]
-            parts.append(torch.softmax(out.float(), dim=1).gather(1, pred.index_select(0, rows).unsqueeze(1)).squeeze(1))
-            chunks.append(inst)
-        p_without = torch.cat(parts) if parts else p.new_zeros(0)
+        p_without, chunks = _instance_probabilities(forward, inputs, full, B, plan, index, keep, pred, p, noises, max_instances)
         attribution = torch.zeros(plan.N, dtype=torch.float32, device=logits.device)
         attribution[inst_node] = p.index_select(0, index.long()) - p_without
         single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
@@ -295,6 +310,10 @@ class Rollout:
     trace: AttentionTrace          # the forward's attention weights, layer masks, mask and gate
     logits: Tensor                 # [B, classes] of the batch
     plan: "ops.GraphPlan"
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift (Occlusion.scores on the difference between the two rules)."""
+        return self.attribution.float().reshape(-1)
 
     def mask(self, k) -> Tensor:
         """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k most relevant nodes of every graph -- ops.topk_threshold on
@@ -377,6 +396,10 @@ class PathAttributions:
     chunks: List["ops.GraphInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
     pred: Optional[Tensor] = None          # int64 [B]: the class that was explained (integrated_gradients)
     logits: Optional[Tensor] = None        # [B, classes] of the whole batch (integrated_gradients)
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift (Occlusion.scores on the difference between the two rules)."""
+        return self.attribution.float().reshape(-1)
 
     def mask(self, k) -> Tensor:
         """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest attribution --
@@ -534,6 +557,11 @@ class MaskOptimization:
     edge_soft: Optional[Tensor] = None
     pred: Optional[Tensor] = None          # int64 [B]: the class that was explained
     logits: Optional[Tensor] = None        # [B, classes] of the whole, unmasked batch (mask_optimization)
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift: the soft mask (Occlusion.scores on the difference between the two
+        rules)."""
+        return self.soft.float().reshape(-1)
 
     def mask(self, k) -> Tensor:
         """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest soft mask --
@@ -909,6 +937,138 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Fidelity curves: the answer's probability along a node ranking, kept or removed
+# ---------------------------------------------------------------------------------------------------------------------
+CURVE_FRACTIONS = (0.0, 0.1, 0.2, 0.3, 0.5, 0.7, 1.0)
+CURVE_RULES = ("trapezoid", "mean")
+
+
+def curve_weights(x: Sequence[float], rule: str = "trapezoid") -> Tensor:
+    """float64 [L]: quadrature weights over the level axis x (non-decreasing; for fractions the fractions, for counts the counts
+    divided by their largest).  trapezoid: w_0 = (x_1 - x_0) / 2, w_j = (x_{j+1} - x_{j-1}) / 2, w_{L-1} = (x_{L-1} - x_{L-2}) / 2
+    -- the area under the polygon through the curve's points, x_{L-1} - x_0 for a curve that is 1 everywhere; a single level has
+    the weight 1 (the curve's one value).  mean: 1 / L each.  Formed in double; ops.curve_sums takes them rounded to fp32 once."""
+    xs = torch.tensor([float(v) for v in x], dtype=torch.float64)
+    L = xs.numel()
+    if L == 0 or bool(torch.isnan(xs).any()) or bool((xs[1:] < xs[:-1]).any()):
+        raise ValueError(f"curve_weights: a non-empty, non-decreasing level axis, got {list(x)}")
+    if rule == "mean":
+        return torch.full((L,), 1.0 / L, dtype=torch.float64)
+    if rule != "trapezoid":
+        raise ValueError(f"curve_weights: rule from {CURVE_RULES}, got {rule!r}")
+    if L == 1:
+        return torch.ones(1, dtype=torch.float64)
+    w = torch.zeros(L, dtype=torch.float64)
+    w[0], w[-1] = (xs[1] - xs[0]) / 2, (xs[-1] - xs[-2]) / 2
+    w[1:-1] = (xs[2:] - xs[:-2]) / 2
+    return w
+
+
+def _curve_levels(fractions, counts):
+    """(fractions or None, counts or None, the level axis x) of fidelity_curves' two keywords."""
+    if counts is None:
+        if fractions is None:
+            raise ValueError("fidelity_curves: fractions or counts")
+        fr = tuple(float(f) for f in fractions)
+        return fr, None, fr
+    if fractions is not None and tuple(fractions) != CURVE_FRACTIONS:
+        raise ValueError("fidelity_curves: fractions or counts, not both")
+    cn = tuple(operator.index(c) for c in counts)
+    top = max(cn) if cn else 0
+    return None, cn, tuple(c / top if top else 0.0 for c in cn)
+
+
+@dataclass
+class FidelityCurves:
+    """Deletion and insertion curves of one batch along one node ranking (fidelity_curves())."""
+    pred: Tensor                   # int64 [B]: the class predicted on the whole graph
+    p: Tensor                      # fp32 [B]: its softmax probability on the whole graph
+    rank: Tensor                   # int32 [N]: every node's rank inside its graph, 0 = the most important (ops.curve_keep_bits)
+    level_k: Tensor                # int32 [B, L, S]: the nodes ranked into (keep) or out of (remove) every instance; 0 for graphs without nodes
+    p_keep: Optional[Tensor]       # fp32 [B, L]: that class's probability on the level's top-ranked nodes ALONE; NaN for graphs without nodes
+    p_remove: Optional[Tensor]     # fp32 [B, L]: ... with the level's top-ranked nodes REMOVED
+    auc_keep: Optional[Tensor]     # fp32 [B]: the area under p_keep over the level axis (the weights of curve_weights); NaN where skipped
+    auc_remove: Optional[Tensor]   # fp32 [B]
+    totals: Tensor                 # float64 [S, L + 3] on the device: per side the L level sums, the sum of the areas, graphs counted, skipped
+    weights: Optional[Tensor] = None           # float64 [L] on the host: the quadrature weights
+    bits: Optional["ops.CurveBits"] = None     # the ranking's keep rows
+    chunks: List["ops.InducedInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
+
+
+def fidelity_curves(model, inputs, scores: Tensor, *, fractions=CURVE_FRACTIONS, counts=None, sides=ops.CURVE_SIDES,
+                    noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None, max_instances: Optional[int] = None,
+                    logits: Optional[Tensor] = None, plan: Optional["ops.GraphPlan"] = None, totals: Optional[Tensor] = None,
+                    rule: str = "trapezoid") -> FidelityCurves:
+    """The predicted answer's probability as the top-ranked nodes of `scores` (fp32 [N] or [N, 1], higher = more important; any
+    explainer's .scores()) are kept alone (p_keep: an insertion curve) or removed (p_remove: a deletion curve), at every level of
+    `fractions` (shares of a graph's nodes, ceil(fp32(f) * fp32(n))) or `counts` (numbers of nodes), with the area under each
+    curve.  One forward on the batch for `pred` and `p` (or `logits`, with the `plan` of that forward); ONE launch for the
+    ranking and all keep rows (ops.curve_keep_bits); the batch of 2 B L instances cut and forwarded exactly as occlusion() does it
+    (ops.induced_instances, instance_inputs, question rows through the index, noises by graph, chunks of at most max_instances);
+    ONE launch for the areas and the running totals (ops.curve_sums; `totals` float64 [S, L + 3] is accumulated into).
+
+    Ties go to the lower node and a level holds EXACTLY its k nodes (an explainer's .mask(k) keeps every tie at the k-th value).
+    The keep side never has fewer than 1 node and the remove side never removes the last one, so the model sees no empty graph:
+    at fraction 0 the keep curve is the best single node, at fraction 1 the remove curve leaves the worst single node.  Graphs
+    without nodes have NaN rows and are not counted.  The model must be in eval(); the call runs under torch.no_grad().  A result
+    depends on the composition of its instance batch (quirks Q1 / Q3 / Q4): curves from different max_instances may differ in
+    the last bits."""
+    if model.training:
+        raise ValueError("fidelity_curves scores the model in eval(): in train() dropout and the training samplers would change "
+                         "the answer from instance to instance -- call model.eval()")
+    if max_instances is not None and int(max_instances) < 1:
+        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    fr, cn, x = _curve_levels(fractions, counts)
+    weights = curve_weights(x, rule)
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        if plan is None:
+            plan = _input_plan(inputs, B)
+        if logits is None:
+            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
+                             plan)[0]
+        prob = torch.softmax(logits.float(), dim=1)
+        pred = prob.argmax(dim=1)
+        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
+        bits = ops.curve_keep_bits(scores.detach().float().reshape(-1).contiguous(), plan, fractions=fr, counts=cn, sides=sides)
+        p_inst, chunks = _instance_probabilities(forward, inputs, full, B, plan, bits.index, bits.keep, pred, p, noises, max_instances)
+        auc, totals = ops.curve_sums(p_inst, bits, weights.float().to(p.device), totals)
+        R, L, S = bits.R, bits.L, bits.S
+        listed = bits.graphs.long()
+        nan = float("nan")
+        per_side = p_inst.view(R, L, S)
+        level_k = torch.zeros(B, L, S, dtype=torch.int32, device=p.device).index_copy_(0, listed, bits.level_k)
+        curves, areas = {}, {}
+        for s, name in enumerate(n for b, n in enumerate(ops.CURVE_SIDES) if bits.sides >> b & 1):
+            curves[name] = torch.full((B, L), nan, dtype=torch.float32, device=p.device).index_copy_(0, listed, per_side[:, :, s].contiguous())
+            areas[name] = torch.full((B,), nan, dtype=torch.float32, device=p.device).index_copy_(0, listed, auc[:, s].contiguous())
+    return FidelityCurves(pred, p, bits.rank, level_k, curves.get("keep"), curves.get("remove"), areas.get("keep"),
+                          areas.get("remove"), totals, weights, bits, chunks)
+
+
+@dataclass(frozen=True)
+class CurveReport:
+    """One explainer's fidelity curves over an evaluation (compare(curves=...)): means over the graphs that were counted (those
+    with nodes and finite probabilities at every level of the side); NaN where none was."""
+    fractions: Tuple[float, ...]             # the level axis
+    p_keep: Tuple[float, ...]                # per level: the mean probability of the predicted answer on the top-ranked nodes alone
+    p_remove: Tuple[float, ...]              # per level: ... with the top-ranked nodes removed
+    auc_keep: float                          # the mean area under a graph's keep curve (curve_weights' trapezoid rule)
+    auc_remove: float
+    counted: Tuple[int, int]                 # graphs counted on the keep side, on the remove side
+    skipped: Tuple[int, int]                 # graphs skipped for a non-finite probability
+    sums: Tuple[Tuple[float, ...], ...] = ()         # the two rows of L + 3 totals behind the means
+
+    @classmethod
+    def from_totals(cls, fractions, rows) -> "CurveReport":
+        L = len(fractions)
+        keep, remove = (tuple(float(v) for v in r) for r in rows)
+        return cls(tuple(float(f) for f in fractions), tuple(_mean(v, keep[L + 1]) for v in keep[:L]),
+                   tuple(_mean(v, remove[L + 1]) for v in remove[:L]), _mean(keep[L], keep[L + 1]), _mean(remove[L], remove[L + 1]),
+                   (int(keep[L + 1]), int(remove[L + 1])), (int(keep[L + 2]), int(remove[L + 2])), (keep, remove))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The intrinsic mask beside post-hoc baselines
 # ---------------------------------------------------------------------------------------------------------------------
 EXPLAINERS = ("intrinsic", "occlusion", "random")
@@ -928,13 +1088,19 @@ class ExplainerReport:
     fid_minus: float
     jaccard: float                           # mean over the graphs of |mask & intrinsic| / |mask | intrinsic| (graphs where both are empty: none)
     sums: Tuple[float, ...]                  # the COMPARE_SUMS totals behind the three means
+    curves: Optional[CurveReport] = None     # its fidelity curves, when compare() was given `curves`
+
+
+def random_scores(plan: "ops.GraphPlan", seed: int) -> Tensor:
+    """fp32 [N, 1]: the seeded noise random_mask ranks (uniform in [1, 2), so no zero pad is picked) -- the random explainer's
+    scores for a fidelity curve."""
+    gen = torch.Generator(device=plan.ptr.device).manual_seed(int(seed))
+    return 1.0 + torch.rand(plan.N, 1, generator=gen, device=plan.ptr.device)
 
 
 def random_mask(plan: "ops.GraphPlan", k, seed: int) -> Tensor:
-    """fp32 [N, 1], k-hot per graph: ops.topk_threshold on seeded noise alone (uniform in [1, 2), so no zero pad is picked)."""
-    gen = torch.Generator(device=plan.ptr.device).manual_seed(int(seed))
-    scores = 1.0 + torch.rand(plan.N, 1, generator=gen, device=plan.ptr.device)
-    return ops.topk_threshold(scores, k, plan=plan)
+    """fp32 [N, 1], k-hot per graph: ops.topk_threshold on seeded noise alone (random_scores)."""
+    return ops.topk_threshold(random_scores(plan, seed), k, plan=plan)
 
 
 def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: float = 0.0) -> Tensor:
@@ -948,7 +1114,7 @@ def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: 
 
 def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
             threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16,
-            mo_steps: int = 100) -> Dict[str, ExplainerReport]:
+            mo_steps: int = 100, curves: Optional[Sequence[float]] = None) -> Dict[str, ExplainerReport]:
     """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
     explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
     mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
@@ -957,15 +1123,23 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
     not among the default): integrated_gradients(steps=ig_steps).mask(k) and its one-point case (steps=1, rule="endpoint") --
     autograd records inside those calls only; mask_optimization (EXPLAINERS_LEARNED, not among the default):
     mask_optimization(steps=mo_steps, init_seed=seed + batch number).mask(k), GNNExplainer with PyG's defaults.
-    Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate()."""
+    Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate().
+    curves: a tuple of fractions (CURVE_FRACTIONS, say) -- every explainer's ranking is also scored along the whole curve
+    (fidelity_curves on its .scores(); random: its seeded noise; intrinsic: the k-hot mask itself, so the picked nodes come first
+    and the rest fall to node order -- its curve says something at the level of k nodes only) and every report carries a
+    CurveReport; the curve totals ride in the same buffer.  None: no curve is computed and `curves` of every report is None."""
     names_x = tuple(explainers)
+    levels = None if curves is None else tuple(float(f) for f in curves)
+    if levels is not None:
+        curve_weights(levels)                                # (refuses an empty or decreasing axis before any forward)
+    cwords = 0 if levels is None else 2 * (len(levels) + 3)  # float64 per explainer: both sides' totals (ops.curve_sums)
     known = EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED
     unknown = [x for x in names_x if x not in known]
     if unknown or not names_x:
         raise ValueError(f"compare: explainers from {known}, got {names_x}")
     X = len(names_x)
     full = not isinstance(model, synthetic.AnswerModel)
-    flat = coo = ground = sums = None
+    flat = coo = ground = sums = ctot = None
     with_gold = None
     per = ops.COO_TOTALS + ops.GROUND_TOTALS + COMPARE_SUMS
     with torch.no_grad():
@@ -981,29 +1155,38 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
             gold = getattr(b, "gold", None)
             if with_gold is None:
                 with_gold = gold is not None
-                flat = torch.zeros(X * per, dtype=torch.int64, device=logits.device)      # int64 words; the sums are float64 in theirs
+                flat = torch.zeros(X * (per + cwords), dtype=torch.int64, device=logits.device)   # int64 words; the sums are float64 in theirs
                 coo = flat[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS)
                 ground = flat[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
-                sums = flat[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):].view(torch.float64).view(X, COMPARE_SUMS)
+                sums = flat[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):X * per].view(torch.float64).view(X, COMPARE_SUMS)
+                if levels is not None:
+                    ctot = flat[X * per:].view(torch.float64).view(X, 2, len(levels) + 3)
             elif with_gold != (gold is not None):
                 raise ValueError("compare: every EvalBatch carries gold, or none does")
             names = inp.x[:, 0] if b.names is None else b.names
             pred = logits.argmax(dim=1)
             for x, name in enumerate(names_x):
-                if name == "intrinsic":
-                    mask = intrinsic
-                elif name == "occlusion":
-                    mask = occlusion(model, inp, max_instances=max_instances).mask(k)
+                res = None
+                if name == "occlusion":
+                    res = occlusion(model, inp, max_instances=max_instances)
                 elif name == "attention":
-                    mask = attention_rollout(model, inp).mask(k)
+                    res = attention_rollout(model, inp)
                 elif name == "integrated_gradients":
-                    mask = integrated_gradients(model, inp, steps=ig_steps, max_instances=max_instances).mask(k)
+                    res = integrated_gradients(model, inp, steps=ig_steps, max_instances=max_instances)
                 elif name == "grad_x_input":
-                    mask = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances).mask(k)
+                    res = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances)
                 elif name == "mask_optimization":
-                    mask = mask_optimization(model, inp, steps=mo_steps, init_seed=seed + number).mask(k)
+                    res = mask_optimization(model, inp, steps=mo_steps, init_seed=seed + number)
+                if res is not None:
+                    mask = res.mask(k)
+                elif name == "intrinsic":
+                    mask = intrinsic
                 else:
                     mask = random_mask(plan, k, seed + number)
+                if levels is not None:
+                    ranked = res.scores() if res is not None else (intrinsic if name == "intrinsic" else random_scores(plan, seed + number))
+                    fidelity_curves(model, inp, ranked, fractions=levels, max_instances=max_instances, logits=logits, plan=plan,
+                                    totals=ctot[x])
                 ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,
                               threshold=threshold, totals=coo[x])
                 if with_gold:
@@ -1017,15 +1200,17 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                                                    has_m.double().sum()]),
                                       jaccard_sums(mask, intrinsic, inp.batch, B, threshold)])
     if flat is None:
-        flat = torch.zeros(X * per, dtype=torch.int64)
+        flat = torch.zeros(X * (per + cwords), dtype=torch.int64)
         with_gold = False
     host = flat.cpu()                                        # every explainer's totals: the one device-to-host copy
     coo_h = host[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS).tolist()
     ground_h = host[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
-    sums_h = host[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):].view(torch.float64).view(X, COMPARE_SUMS).tolist()
+    sums_h = host[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):X * per].view(torch.float64).view(X, COMPARE_SUMS).tolist()
+    curves_h = None if levels is None else host[X * per:].view(torch.float64).view(X, 2, len(levels) + 3).tolist()
     out = {}
     for x, name in enumerate(names_x):
         s = tuple(float(v) for v in sums_h[x])
         out[name] = ExplainerReport(CooReport.from_totals(coo_h[x]), GroundingReport.from_totals(ground_h[x]) if with_gold else None,
-                                    _mean(s[0], s[1]), _mean(s[2], s[3]), _mean(s[4], s[5]), s)
+                                    _mean(s[0], s[1]), _mean(s[2], s[3]), _mean(s[4], s[5]), s,
+                                    None if levels is None else CurveReport.from_totals(levels, curves_h[x]))
     return out

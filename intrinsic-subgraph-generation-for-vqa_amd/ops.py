@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _ext_ig, _ext_induced, _ext_instances_train, _ext_maskopt, _ext_rollout, _lib, _lib_instances
+from . import _ext_curves, _ext_ig, _ext_induced, _ext_instances_train, _ext_maskopt, _ext_rollout, _lib, _lib_instances
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -150,6 +150,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "ig_path_rows": 0,                         # path-row launches of integrated gradients (include/ext/isg_ig.h)
             "ig_attribution": 0,                       # gradient rows reduced to attributions (include/ext/isg_ig.h)
             "maskopt_step": 0,                         # mask-optimisation iterations (include/ext/isg_maskopt.h)
+            "curve_keep_bits": 0,                      # rankings with their keep rows of all levels (include/ext/isg_curves.h)
+            "curve_sums": 0,                           # instance probabilities reduced to curves and areas (include/ext/isg_curves.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1422,6 +1424,147 @@ def keep_bits_from_mask(mask: Tensor, plan: "GraphPlan", threshold: float = 0.0,
     inside = local < 32 * W
     flags[batch[inside], local[inside]] = ((flat > threshold) != bool(complement))[inside]
     return _pack_bits(flags, W)
+
+
+# ------------------------------------------------------------------------------------------------
+# Fidelity curves: ranked keep bits for every level and side, and the curves' sums
+# ------------------------------------------------------------------------------------------------
+CURVE_LEVELS_MAX = 64       # levels per call (CV_LEVELS_MAX in csrc/isg_curves.hip)
+CURVE_SIDES = ("keep", "remove")
+
+
+def _curve_sides(sides) -> int:
+    names = (sides,) if isinstance(sides, str) else tuple(sides)
+    if not names or len(set(names)) != len(names) or any(s not in CURVE_SIDES for s in names):
+        raise ValueError(f"sides: one or both of {CURVE_SIDES}, each once, got {sides!r}")
+    return sum(1 << CURVE_SIDES.index(s) for s in names)
+
+
+@dataclass
+class CurveBits:
+    """What isg_curve_keep_bits left on the device (include/ext/isg_curves.h): row q = (r L + j) S + s is listed graph r at level
+    j on side s (the keep side first when both are asked for)."""
+    index: Tensor                  # int32 [R L S]: the graph of every row -- ops.induced_instances' index
+    keep: Tensor                   # int32 words [R L S, W]: the keep bits of every row -- ops.induced_instances' keep
+    rank: Tensor                   # int32 [N]: the rank of every node of a listed graph inside its graph (0 = the best); -1 elsewhere
+    level_k: Tensor                # int32 [R, L, S]: the nodes ranked into (keep) or out of (remove) every row
+    status: Tensor                 # int32 [4]: a graph beyond 32 W nodes, a listed graph outside the batch, R L S, 0
+    graphs: Tensor                 # int32 [R] on the device: the listed graphs
+    L: int
+    S: int
+    sides: int                     # the header's bits: 1 keep, 2 remove
+
+    @property
+    def R(self) -> int:
+        return self.graphs.numel()
+
+    def verify(self) -> "CurveBits":
+        """Checks on the host (copies): both status flags are clear, every row holds exactly the bits its level_k promises and
+        none beyond its graph, and the rows of a graph and side are nested along ascending level sizes."""
+        st = self.status.tolist() if self.R and self.L else [0, 0, 0, 0]
+        if st[0] or st[1]:
+            raise _lib.IsgError(f"curve_keep_bits: status {st} (a graph beyond 32 W nodes / a listed graph outside the batch)")
+        if not (self.R and self.L):
+            return self
+        words = self.keep.cpu().long() & 0xFFFFFFFF
+        pop = torch.zeros(words.size(0), dtype=torch.int64)
+        for b in range(32):
+            pop += ((words >> b) & 1).sum(dim=1)
+        k = self.level_k.cpu().long().reshape(self.R, self.L, self.S)
+        pop = pop.view(self.R, self.L, self.S)
+        words = words.view(self.R, self.L, self.S, -1)
+        for s in range(self.S):
+            removal = s == 1 or not (self.sides & 1)
+            n = (pop[:, :, s] + k[:, :, s]) if removal else None
+            if removal and not bool((n == n[:, :1]).all()):
+                raise _lib.IsgError("curve_keep_bits: a remove row's bits and its level size do not add up to the graph's nodes")
+            if not removal and not bool((pop[:, :, s] == k[:, :, s]).all()):
+                raise _lib.IsgError("curve_keep_bits: a keep row does not hold exactly level_k bits")
+            order = torch.argsort(k[:, :, s], dim=1, stable=True)
+            w = torch.gather(words[:, :, s], 1, order.unsqueeze(-1).expand(-1, -1, words.size(-1)))
+            small, large = (w[:, 1:], w[:, :-1]) if removal else (w[:, :-1], w[:, 1:])
+            if bool((small & ~large).any()):
+                raise _lib.IsgError("curve_keep_bits: the rows of a graph are not nested")
+        return self
+
+
+def curve_keep_bits(a: Tensor, plan: "GraphPlan", *, graphs: Optional[Tensor] = None, fractions=None, counts=None,
+                    sides=CURVE_SIDES) -> CurveBits:
+    """The ranking of every listed graph's nodes by the scores a (fp32 [N], higher = more important; ties to the lower node, NaNs
+    last) and the keep rows of all levels and sides in ONE launch (isg_curve_keep_bits, include/ext/isg_curves.h, where the rank
+    relation, the level rule and the row layout are stated).  Exactly one of fractions (shares of a graph's nodes:
+    ceil(fp32(f) * fp32(n)), one fp32 product) and counts (numbers of nodes), at most 64 levels.  A keep row holds
+    min(n, max(1, t)) nodes, a remove row lacks min(n - 1, max(0, t)): no instance is empty.  Rank prefixes hold EXACTLY k
+    nodes -- unlike ops.topk_threshold, under which ties at the k-th value keep more.
+    graphs: int32 / int64 [R], these graphs in this order; None: the graphs with at least one node, which costs one device-to-host
+    copy (R, to size the result), as in keep_bits_leave_one_out.  W = keep_words(plan.nmax)."""
+    import ctypes
+    lib = _ext_curves.load()
+    flat = a.reshape(-1)
+    N, G = plan.N, plan.B
+    p_a = _chk(flat, "a", torch.float32, (N,))
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (G + 1,))
+    if (fractions is None) == (counts is None):
+        raise ValueError("curve_keep_bits: exactly one of fractions and counts")
+    bits = _curve_sides(sides)
+    S = bin(bits).count("1")
+    if fractions is not None:
+        vals = [float(f) for f in fractions]
+        if any(not v >= 0.0 for v in vals):
+            raise ValueError(f"curve_keep_bits: fractions are numbers >= 0, got {vals}")
+        host = (ctypes.c_float * max(len(vals), 1))(*vals)
+        p_frac, p_count = ctypes.addressof(host), 0
+    else:
+        vals = [operator.index(c) for c in counts]
+        if any(v < 0 or v >= 2 ** 31 for v in vals):
+            raise ValueError(f"curve_keep_bits: counts are int32 numbers >= 0, got {vals}")
+        host = (ctypes.c_int32 * max(len(vals), 1))(*vals)
+        p_frac, p_count = 0, ctypes.addressof(host)
+    L = len(vals)
+    if L > CURVE_LEVELS_MAX:
+        raise _lib.IsgError(f"curve_keep_bits: {L} levels (at most {CURVE_LEVELS_MAX})")
+    W = keep_words(plan.nmax)
+    if W > INDUCED_WORDS_MAX:
+        raise _lib.IsgError(f"curve_keep_bits: {W} words per row (at most {INDUCED_WORDS_MAX}: {32 * INDUCED_WORDS_MAX} nodes per graph)")
+    dev = plan.ptr.device
+    if graphs is None:
+        listed = torch.nonzero(plan.ptr[1:] > plan.ptr[:-1]).reshape(-1).to(torch.int32)      # (the copy: the output's length)
+    else:
+        if graphs.dim() != 1 or graphs.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"graphs: expected int32 or int64 [R], got {graphs.dtype} {tuple(graphs.shape)}")
+        listed = graphs.to(device=dev, dtype=torch.int32).contiguous()
+    R = listed.numel()
+    Q = R * L * S
+    i32 = torch.empty(2 * Q + Q * W + 4, dtype=torch.int32, device=dev)
+    level_k, index, keep, status = i32[:Q].view(R, L, S), i32[Q:2 * Q], i32[2 * Q:2 * Q + Q * W].view(Q, W), i32[2 * Q + Q * W:]
+    rank = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    if not Q:
+        status.zero_()
+    COUNTERS["curve_keep_bits"] += 1
+    _lib.check(lib.isg_curve_keep_bits(p_a, p_ptr, listed.data_ptr() if R else 0, p_frac, p_count, N, G, R, L, bits, W,
+                                       rank.data_ptr() if N else 0, level_k.data_ptr(), index.data_ptr(), keep.data_ptr(),
+                                       status.data_ptr(), _stream()), "isg_curve_keep_bits")
+    return CurveBits(index, keep, rank, level_k, status, listed, L, S, bits)
+
+
+def curve_sums(p_inst: Tensor, bits: CurveBits, w: Tensor, totals: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(auc fp32 [R, S], totals float64 [S, L + 3]) of isg_curve_sums (include/ext/isg_curves.h) in ONE launch: p_inst fp32
+    [R L S], the predicted class's probability on every instance of `bits`, in its row order; w fp32 [L] on the device, the
+    quadrature weights over the level axis.  auc[r, s] = the fma chain over ascending levels; totals (ACCUMULATED INTO; None: a
+    fresh buffer of zeros) holds per side the L level sums, the sum of auc, the graphs counted and the graphs skipped.  A graph with
+    a non-finite probability at any level of a side is skipped for that side and its auc is NaN.  Sums run over the rows in order:
+    two calls agree bit for bit."""
+    lib = _ext_curves.load()
+    R, L, S = bits.R, bits.L, bits.S
+    p_p = _chk(p_inst, "p_inst", torch.float32, (R * L * S,))
+    p_w = _chk(w, "w", torch.float32, (L,))
+    if totals is None:
+        totals = torch.zeros(S, L + 3, dtype=torch.float64, device=p_inst.device)
+    p_t = _chk(totals, "totals", torch.float64, (S, L + 3))
+    auc = torch.empty(R, S, dtype=torch.float32, device=p_inst.device)
+    COUNTERS["curve_sums"] += 1
+    _lib.check(lib.isg_curve_sums(p_p, p_w, R, L, bits.sides, auc.data_ptr(), p_t, _stream()), "isg_curve_sums")
+    return auc, totals
 
 
 # ------------------------------------------------------------------------------------------------

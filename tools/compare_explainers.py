@@ -6,10 +6,12 @@ differ on them, not how good an explanation is.
 
   python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048]
                                      [--explainers intrinsic,occlusion,random,attention,integrated_gradients,grad_x_input,mask_optimization]
-                                     [--ig-steps 16] [--mo-steps 100] [--out profiles/<name>.json]
+                                     [--ig-steps 16] [--mo-steps 100] [--curves 0,0.1,0.2,0.3,0.5,0.7,1]
+                                     [--out profiles/<name>.json]
 --explainers: a comma-separated list from explain.EXPLAINERS_ALL + explain.EXPLAINERS_GRADIENT + explain.EXPLAINERS_LEARNED
 (default: explain.EXPLAINERS); --ig-steps: the points of integrated_gradients' path; --mo-steps: the Adam steps
-of mask_optimization."""
+of mask_optimization; --curves: the fractions of every explainer's fidelity curves (without it no
+curve is computed)."""
 import dataclasses
 import json
 import os
@@ -28,6 +30,7 @@ MAX_INSTANCES = int(opt["--max-instances"]) if "--max-instances" in opt else Non
 EXPLAINERS = tuple(n for n in opt["--explainers"].split(",") if n) if "--explainers" in opt else explain.EXPLAINERS
 IG_STEPS = int(opt.get("--ig-steps", 16))
 MO_STEPS = int(opt.get("--mo-steps", 100))
+CURVES = tuple(float(f) for f in opt["--curves"].split(",") if f) if "--curves" in opt else None
 V, A = 2578, 1842
 
 cfg = dataclasses.replace(synthetic.CFG1, num_graphs=GRAPHS, sampler="imle", sample_k=K)
@@ -52,7 +55,7 @@ with torch.no_grad():
         batches.append(explain.EvalBatch(d, label.to(dev), qtok.to(dev), (torch.arange(GRAPHS) % 4 == 0).int().to(dev), names.to(dev),
                                          gold=gold.to(dev)))
 report = explain.compare(model, batches, tables, explainers=EXPLAINERS, k=K, max_instances=MAX_INSTANCES, ig_steps=IG_STEPS,
-                         mo_steps=MO_STEPS)
+                         mo_steps=MO_STEPS, curves=CURVES)
 out = {"device": torch.cuda.get_device_name(0), "graphs_per_batch": GRAPHS, "batches": BATCHES, "k": K, "explainers": {}}
 for name, r in report.items():
     g = r.grounding.sets["any"]["all"]
@@ -61,6 +64,12 @@ for name, r in report.items():
                                "grounding_precision": g.precision, "grounding_recall": g.recall, "grounding_chance": g.chance}
     print(f"{name:10s} fid+ {r.fid_plus:.4f}  fid- {r.fid_minus:.4f}  jaccard {r.jaccard:.3f}  qst coo {r.coo.qst_tok_coo:.3f}  "
           f"grounding p {g.precision:.3f} r {g.recall:.3f} (chance {g.chance:.3f})", flush=True)
+    if r.curves is not None:
+        c = r.curves
+        out["explainers"][name]["curves"] = {"fractions": c.fractions, "p_keep": c.p_keep, "p_remove": c.p_remove, "auc_keep": c.auc_keep,
+                                             "auc_remove": c.auc_remove, "counted": c.counted, "skipped": c.skipped}
+        print(f"{'':10s} area kept {c.auc_keep:.4f}  area removed {c.auc_remove:.4f}  kept " + " ".join(f"{v:.3f}" for v in c.p_keep)
+              + "  removed " + " ".join(f"{v:.3f}" for v in c.p_remove), flush=True)
 if "--out" in opt:
     with open(opt["--out"], "w") as fh:
         fh.write(json.dumps(out, indent=1) + "\n")
