@@ -1069,12 +1069,95 @@ class CurveReport:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# A sampled baseline: Shapley values by permutation sampling
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class ShapleyValues:
+    """Shapley estimates of one batch by permutation sampling (shapley_values())."""
+    pred: Tensor                   # int64 [B]: the class predicted on the whole graph
+    p: Tensor                      # fp32 [B]: its softmax probability on the whole graph
+    attribution: Tensor            # fp32 [N]: the mean marginal contribution of every node over the permutations (phi); NaN in flagged graphs
+    m2: Tensor                     # fp32 [N]: the sum of the squared samples (for stderr())
+    gap: Tensor                    # fp32 [B]: sum of a graph's attributions - (p - v_empty), the completeness gap; NaN in flagged graphs
+    flag: Tensor                   # int32 [B]: 0 fine, 1 a non-finite probability among the graph's instances or its p
+    single: Tensor                 # bool [B]: fewer than 2 nodes -- no instance; a lone node's attribution is p - v_empty
+    bits: "ops.ShapleyBits"        # the permutations (pos) and their prefixes' keep rows
+    p_inst: Tensor                 # fp32 [Q]: the predicted class's probability on every instance
+    logits: Tensor                 # [B, classes] of the whole batch
+    plan: "ops.GraphPlan"
+    chunks: List["ops.InducedInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
+
+    @property
+    def T(self) -> int:
+        """Samples behind every estimate: the permutations, or their antithetic pairs."""
+        return self.bits.T
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift -- the scores of a fidelity curve (fidelity_curves())."""
+        return self.attribution.float().reshape(-1)
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, by the rule of Occlusion.mask: ops.topk_threshold on shifted_attributions."""
+        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+    def stderr(self) -> Tensor:
+        """float64 [N]: the standard error of every estimate, sqrt(max(m2 - T phi^2, 0) / (T (T - 1))); NaN for T = 1."""
+        T = self.T
+        if T < 2:
+            return torch.full_like(self.attribution, float("nan"), dtype=torch.float64)
+        phi, m2 = self.attribution.double(), self.m2.double()
+        return torch.sqrt((m2 - T * phi * phi).clamp_min(0.0) / (T * (T - 1)))
+
+
+def shapley_values(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None, permutations: int = 16,
+                   antithetic: bool = True, perm_seed: int = 0, v_empty: float = 0.0, max_instances: Optional[int] = None,
+                   logits: Optional[Tensor] = None, plan: Optional["ops.GraphPlan"] = None) -> ShapleyValues:
+    """Shapley values of every node by permutation sampling (Castro et al. 2009; Strumbelj and Kononenko 2014): the mean, over
+    `permutations` random orders of a graph's nodes, of the change of the predicted answer's probability when the node joins the
+    nodes before it -- the axiomatic reference point of the post-hoc baselines, of which occlusion() is the one-term truncation
+    (the marginal contribution at the full set alone).  One forward on the batch for `pred` and `p` (or `logits`, with the `plan`
+    of that forward); ONE launch for the seeded permutations and the keep rows of all their prefixes (ops.shapley_keep_bits:
+    permutations * (n - 1) instances per graph of n nodes); the instances cut and forwarded exactly as occlusion() does it
+    (ops.induced_instances, instance_inputs, question rows through the index, noises by graph, chunks of at most max_instances);
+    ONE launch for the estimates (ops.shapley_values).
+
+    The value of the full set is p (not forwarded again), the value of the empty set is `v_empty` (the model never sees an empty
+    graph); with v_empty = 0 a graph's attributions sum to p, and `gap` says how nearly.  antithetic: every other permutation is
+    the one before it reversed (variance reduction; permutations is even).  perm_seed seeds the permutations alone (a graph's
+    depend on it and on the graph's number in the batch); `seed` and `noises` are the sampler's, as in occlusion().  The model
+    must be in eval(); the call runs under torch.no_grad().  A result depends on the composition of its instance batch (quirks
+    Q1 / Q3 / Q4): estimates from different max_instances may differ in the last bits, the permutations never do."""
+    if model.training:
+        raise ValueError("shapley_values scores the model in eval(): in train() dropout and the training samplers would change "
+                         "the answer from instance to instance -- call model.eval()")
+    if max_instances is not None and int(max_instances) < 1:
+        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        if plan is None:
+            plan = _input_plan(inputs, B)
+        if logits is None:
+            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
+                             plan)[0]
+        prob = torch.softmax(logits.float(), dim=1)
+        pred = prob.argmax(dim=1)
+        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
+        bits = ops.shapley_keep_bits(plan, permutations=permutations, antithetic=antithetic, seed=perm_seed)
+        p_inst, chunks = _instance_probabilities(forward, inputs, full, B, plan, bits.index, bits.keep, pred, p, noises, max_instances)
+        phi, m2, gap, flag = ops.shapley_values(p_inst, p.contiguous(), bits, plan, v_empty=v_empty)
+        single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
+    return ShapleyValues(pred, p, phi, m2, gap, flag, single, bits, p_inst, logits, plan, chunks)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The intrinsic mask beside post-hoc baselines
 # ---------------------------------------------------------------------------------------------------------------------
 EXPLAINERS = ("intrinsic", "occlusion", "random")
 EXPLAINERS_ALL = EXPLAINERS + ("attention",)       # what compare() accepts beside the gradient explainers; EXPLAINERS stays its default
 EXPLAINERS_GRADIENT = ("integrated_gradients", "grad_x_input")      # compare() accepts these too (integrated_gradients())
 EXPLAINERS_LEARNED = ("mask_optimization",)                         # ... and this one (mask_optimization(): GNNExplainer)
+EXPLAINERS_SAMPLED = ("shapley",)                                   # ... and this one (shapley_values(): permutation sampling)
 COMPARE_SUMS = 6       # float64 per explainer: sum fid_plus, questions that have one, sum fid_minus, questions that have one,
                        # sum of the Jaccard overlaps with the intrinsic mask, graphs that have one
 
@@ -1114,7 +1197,7 @@ def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: 
 
 def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
             threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16,
-            mo_steps: int = 100, curves: Optional[Sequence[float]] = None) -> Dict[str, ExplainerReport]:
+            mo_steps: int = 100, sv_permutations: int = 16, curves: Optional[Sequence[float]] = None) -> Dict[str, ExplainerReport]:
     """The model's intrinsic mask beside post-hoc baselines, each measured by the same yardsticks over whole batches: per
     explainer the CooReport figures (ops.token_coo), the GroundingReport where every batch carries `gold` (ops.grounding), the
     mean fid_plus / fid_minus (faithfulness_of_mask) and the mean Jaccard overlap with the intrinsic mask.
@@ -1122,7 +1205,9 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
     attention (not among the default): attention_rollout().mask(k); integrated_gradients and grad_x_input (EXPLAINERS_GRADIENT,
     not among the default): integrated_gradients(steps=ig_steps).mask(k) and its one-point case (steps=1, rule="endpoint") --
     autograd records inside those calls only; mask_optimization (EXPLAINERS_LEARNED, not among the default):
-    mask_optimization(steps=mo_steps, init_seed=seed + batch number).mask(k), GNNExplainer with PyG's defaults.
+    mask_optimization(steps=mo_steps, init_seed=seed + batch number).mask(k), GNNExplainer with PyG's defaults; shapley
+    (EXPLAINERS_SAMPLED, not among the default): shapley_values(permutations=sv_permutations, perm_seed=seed + batch
+    number).mask(k), antithetic permutation sampling with v_empty = 0.
     Every total stays on the device, in ONE buffer: the evaluation is one device-to-host copy at the end, as in evaluate().
     curves: a tuple of fractions (CURVE_FRACTIONS, say) -- every explainer's ranking is also scored along the whole curve
     (fidelity_curves on its .scores(); random: its seeded noise; intrinsic: the k-hot mask itself, so the picked nodes come first
@@ -1133,7 +1218,7 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
     if levels is not None:
         curve_weights(levels)                                # (refuses an empty or decreasing axis before any forward)
     cwords = 0 if levels is None else 2 * (len(levels) + 3)  # float64 per explainer: both sides' totals (ops.curve_sums)
-    known = EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED
+    known = EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED + EXPLAINERS_SAMPLED
     unknown = [x for x in names_x if x not in known]
     if unknown or not names_x:
         raise ValueError(f"compare: explainers from {known}, got {names_x}")
@@ -1177,6 +1262,9 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                     res = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances)
                 elif name == "mask_optimization":
                     res = mask_optimization(model, inp, steps=mo_steps, init_seed=seed + number)
+                elif name == "shapley":
+                    res = shapley_values(model, inp, permutations=sv_permutations, perm_seed=seed + number, max_instances=max_instances,
+                                         logits=logits, plan=plan)
                 if res is not None:
                     mask = res.mask(k)
                 elif name == "intrinsic":

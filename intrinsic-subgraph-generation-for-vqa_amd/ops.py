@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import dataclasses
+import math
 import operator
 import os
 import sys
@@ -22,6 +23,7 @@ import torch
 from torch import Tensor
 
 from . import _ext_curves, _ext_ig, _ext_induced, _ext_instances_train, _ext_maskopt, _ext_rollout, _lib, _lib_instances
+from . import _ext_shapley
 
 MAX_NODES_PER_GRAPH = 1024   # LDS strip / sampler row capacity of the kernels
 
@@ -152,6 +154,8 @@ COUNTERS = {"torch_linear": 0, "torch_layer_norm": 0, "torch_attention": 0, "row
             "maskopt_step": 0,                         # mask-optimisation iterations (include/ext/isg_maskopt.h)
             "curve_keep_bits": 0,                      # rankings with their keep rows of all levels (include/ext/isg_curves.h)
             "curve_sums": 0,                           # instance probabilities reduced to curves and areas (include/ext/isg_curves.h)
+            "shapley_keep_bits": 0,                    # seeded permutations with the keep rows of their prefixes (include/ext/isg_shapley.h)
+            "shapley_values": 0,                       # instance probabilities reduced to Shapley estimates (include/ext/isg_shapley.h)
             "eval_groups": 0,                          # grouped meter / grouped co-occurrence calls (include/isg_eval.h)
             "grounding": 0}                            # grounding scores against object annotations (include/isg_grounding.h)
 
@@ -1565,6 +1569,160 @@ def curve_sums(p_inst: Tensor, bits: CurveBits, w: Tensor, totals: Optional[Tens
     COUNTERS["curve_sums"] += 1
     _lib.check(lib.isg_curve_sums(p_p, p_w, R, L, bits.sides, auc.data_ptr(), p_t, _stream()), "isg_curve_sums")
     return auc, totals
+
+
+# ------------------------------------------------------------------------------------------------
+# Shapley sampling: seeded permutations with the keep rows of their prefixes, and the estimates
+# ------------------------------------------------------------------------------------------------
+SHAPLEY_PERMUTATIONS_MAX = 1024     # permutations per call (SV_PERMUTATIONS_MAX in csrc/isg_shapley.hip)
+
+
+@dataclass
+class ShapleyBits:
+    """What isg_shapley_keep_bits left on the device (include/ext/isg_shapley.h): row row_ptr[r] + m (n - 1) + (k - 1) holds the
+    first k nodes of permutation m of listed graph r, for k = 1 .. n - 1."""
+    index: Tensor                  # int32 [Q]: the graph of every row -- ops.induced_instances' index
+    keep: Tensor                   # int32 words [Q, W]: the keep bits of every row -- ops.induced_instances' keep
+    pos: Tensor                    # int32 [M, N]: every node's position in permutation m of its graph; -1 for nodes of unlisted graphs
+    row_ptr: Tensor                # int32 [R + 1]: the first row of every listed graph
+    status: Tensor                 # int32 [4]: a graph beyond 32 W nodes, a listed graph outside the batch, a bad row_ptr, Q
+    graphs: Tensor                 # int32 [R] on the device: the listed graphs
+    M: int                         # permutations per graph
+    antithetic: bool               # permutation 2 t + 1 is permutation 2 t reversed
+
+    @property
+    def R(self) -> int:
+        return self.graphs.numel()
+
+    @property
+    def Q(self) -> int:
+        return self.index.numel()
+
+    @property
+    def T(self) -> int:
+        """Samples per node: M, or M / 2 antithetic pairs."""
+        return self.M // 2 if self.antithetic else self.M
+
+    def verify(self) -> "ShapleyBits":
+        """Checks on the host (copies): the three status flags are clear and status[3] is Q; every graph's pos rows are
+        permutations, an antithetic twin the reversal; row k of a permutation holds exactly its first k nodes (so the rows of a
+        permutation are nested) and no bit beyond its graph."""
+        st = self.status.tolist() if self.R else [0, 0, 0, self.Q]
+        if st[0] or st[1] or st[2] or st[3] != self.Q:
+            raise _lib.IsgError(f"shapley_keep_bits: status {st} (a graph beyond 32 W nodes / a listed graph outside the batch / a bad "
+                                f"row_ptr / Q = {self.Q})")
+        if not self.R:
+            return self
+        words = self.keep.cpu().long() & 0xFFFFFFFF
+        W = words.size(1) if words.dim() == 2 else 1
+        first, index = self.row_ptr.tolist(), self.index.cpu()
+        bit = torch.arange(32 * W, dtype=torch.int64)
+        for r, g in enumerate(self.graphs.tolist()):
+            rows, q0 = first[r + 1] - first[r], first[r]
+            if not rows:
+                continue
+            n = rows // self.M + 1
+            if not bool((index[q0:q0 + rows] == g).all()):
+                raise _lib.IsgError("shapley_keep_bits: a row's index is not its graph")
+            flags = ((words[q0:q0 + rows].view(rows, W, 1) >> torch.arange(32).view(1, 1, 32)) & 1).view(self.M, n - 1, 32 * W)
+            if bool(flags[:, :, n:].any()) or not bool((flags.sum(dim=2) == torch.arange(1, n).view(1, -1)).all()):
+                raise _lib.IsgError("shapley_keep_bits: row k of a permutation does not hold exactly k nodes of its graph")
+            if bool((flags[:, :-1] & ~flags[:, 1:] & 1).any()):
+                raise _lib.IsgError("shapley_keep_bits: the rows of a permutation are not nested")
+            # the positions the rows imply: node i enters at the first k whose row holds it (n - 1 when no row does)
+            implied = (n - 1) - flags[:, :, :n].sum(dim=1)
+            if not bool((implied.sort(dim=1).values == bit[:n].view(1, -1)).all()):
+                raise _lib.IsgError("shapley_keep_bits: a permutation's rows do not order its nodes")
+            if self.antithetic and not bool((implied[1::2] == n - 1 - implied[0::2]).all()):
+                raise _lib.IsgError("shapley_keep_bits: an antithetic twin is not the reversal")
+        return self
+
+
+def shapley_keep_bits(plan: "GraphPlan", *, graphs: Optional[Tensor] = None, permutations: int = 16, antithetic: bool = True,
+                      seed: int = 0) -> ShapleyBits:
+    """`permutations` seeded random permutations of every listed graph's nodes and the keep rows of all their proper prefixes in
+    ONE launch (isg_shapley_keep_bits, include/ext/isg_shapley.h, where the keys, the position relation and the row layout are
+    stated): graph r of n nodes gets permutations * (n - 1) rows, a graph of fewer than 2 nodes none.  antithetic: permutation
+    2 t + 1 is permutation 2 t reversed (permutations is even).  A graph's permutations depend on seed and on its number in the
+    batch alone, not on what is listed beside it.
+    graphs: int32 / int64 [R], these graphs in this order; None: every graph of the batch.  row_ptr is formed with torch ops on
+    the device; Q, its last entry, is the one small device-to-host copy (to size the result), as in keep_bits_leave_one_out.
+    W = keep_words(plan.nmax)."""
+    lib = _ext_shapley.load()
+    N, G = plan.N, plan.B
+    M = operator.index(permutations)
+    anti = bool(antithetic)
+    if not 1 <= M <= SHAPLEY_PERMUTATIONS_MAX:
+        raise _lib.IsgError(f"shapley_keep_bits: {M} permutations (1 to {SHAPLEY_PERMUTATIONS_MAX})")
+    if anti and M & 1:
+        raise ValueError(f"shapley_keep_bits: antithetic permutations come in pairs, got permutations={M}")
+    seed = operator.index(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"shapley_keep_bits: seed is a 64-bit number >= 0, got {seed}")
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (G + 1,))
+    W = keep_words(plan.nmax)
+    if W > INDUCED_WORDS_MAX:
+        raise _lib.IsgError(f"shapley_keep_bits: {W} words per row (at most {INDUCED_WORDS_MAX}: {32 * INDUCED_WORDS_MAX} nodes per graph)")
+    dev = plan.ptr.device
+    if graphs is None:
+        listed = torch.arange(G, dtype=torch.int32, device=dev)
+    else:
+        if graphs.dim() != 1 or graphs.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"graphs: expected int32 or int64 [R], got {graphs.dtype} {tuple(graphs.shape)}")
+        listed = graphs.to(device=dev, dtype=torch.int32).contiguous()
+    R = listed.numel()
+    row_ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    if R and G:
+        inside = (listed >= 0) & (listed < G)
+        gl = listed.long().clamp(0, G - 1)
+        ptr = plan.ptr.long().clamp(0, N)
+        n = (torch.maximum(ptr[1:], ptr[:-1]) - ptr[:-1]).clamp(max=32 * W).index_select(0, gl)
+        row_ptr[1:] = torch.cumsum(torch.where(inside, M * (n - 1).clamp(min=0), torch.zeros_like(n)), 0)
+    Q = int(row_ptr[-1]) if R else 0                              # (the copy: the output's length)
+    if Q >= 2 ** 31 - 1024:
+        raise _lib.IsgError(f"shapley_keep_bits: {Q} rows (fewer than 2^31 - 1024): list fewer graphs per call or lower permutations")
+    row_ptr = row_ptr.to(torch.int32)
+    i32 = torch.empty(Q + Q * W + 4, dtype=torch.int32, device=dev)
+    index, keep, status = i32[:Q], i32[Q:Q + Q * W].view(Q, W), i32[Q + Q * W:]
+    pos = torch.full((M, N), -1, dtype=torch.int32, device=dev)
+    if not R:
+        status.zero_()
+    COUNTERS["shapley_keep_bits"] += 1
+    _lib.check(lib.isg_shapley_keep_bits(p_ptr, listed.data_ptr() if R else 0, row_ptr.data_ptr(), N, G, R, M, Q, int(anti), seed, W,
+                                         pos.data_ptr() if N else 0, index.data_ptr() if Q else 0, keep.data_ptr() if Q else 0,
+                                         status.data_ptr(), _stream()), "isg_shapley_keep_bits")
+    return ShapleyBits(index, keep, pos, row_ptr, status, listed, M, anti)
+
+
+def shapley_values(p_inst: Tensor, p: Tensor, bits: ShapleyBits, plan: "GraphPlan", v_empty: float = 0.0,
+                   want_m2: bool = True) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor]:
+    """(phi fp32 [N], m2 fp32 [N] or None, gap fp32 [R], flag int32 [R]) of isg_shapley_values (include/ext/isg_shapley.h, where
+    the estimator and its arithmetic order are stated) in ONE launch: p_inst fp32 [Q], the predicted class's probability on every
+    instance of `bits`, in its row order; p fp32 [B], that class's probability on the whole graph; v_empty: the value of the empty
+    set (a finite float).  phi is the mean marginal contribution over the bits' permutations, m2 the sum of the squared samples,
+    gap[r] = sum_i phi_i - (p[g] - v_empty); flag[r]: 0 fine, 1 a non-finite probability (phi, m2 and gap NaN), 2 a bad graphs or
+    row_ptr entry (nothing written).  phi and m2 are 0 on the nodes of unlisted graphs.  Two calls agree bit for bit."""
+    lib = _ext_shapley.load()
+    N, G, R, M, Q = plan.N, plan.B, bits.R, bits.M, bits.Q
+    p_pi = _chk(p_inst, "p_inst", torch.float32, (Q,))
+    p_p = _chk(p, "p", torch.float32, (G,))
+    p_ptr = _chk(plan.ptr, "plan.ptr", torch.int32, (G + 1,))
+    p_pos = _chk(bits.pos, "bits.pos", torch.int32, (M, N))
+    p_rp = _chk(bits.row_ptr, "bits.row_ptr", torch.int32, (R + 1,))
+    v = float(v_empty)
+    if not math.isfinite(v):
+        raise ValueError(f"shapley_values: v_empty is a finite number, got {v_empty}")
+    W = bits.keep.size(1) if bits.keep.dim() == 2 and bits.keep.size(1) else keep_words(plan.nmax)
+    dev = p.device
+    f32 = torch.zeros((2 if want_m2 else 1) * N + R, dtype=torch.float32, device=dev)
+    phi, m2, gap = f32[:N], (f32[N:2 * N] if want_m2 else None), f32[(2 if want_m2 else 1) * N:]
+    flag = torch.zeros(R, dtype=torch.int32, device=dev)
+    COUNTERS["shapley_values"] += 1
+    _lib.check(lib.isg_shapley_values(p_pi if Q else 0, p_p if G else 0, p_pos if N else 0, p_ptr, bits.graphs.data_ptr() if R else 0, p_rp,
+                                      N, G, R, M, Q, int(bits.antithetic), v, W, phi.data_ptr() if N else 0,
+                                      m2.data_ptr() if want_m2 and N else 0, gap.data_ptr() if R else 0, flag.data_ptr() if R else 0,
+                                      _stream()), "isg_shapley_values")
+    return phi, m2, gap, flag
 
 
 # ------------------------------------------------------------------------------------------------

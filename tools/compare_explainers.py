@@ -5,12 +5,13 @@ and annotated objects.  An untrained model on random graphs: the figures show th
 differ on them, not how good an explanation is.
 
   python tools/compare_explainers.py [--graphs 64] [--batches 2] [--k 5] [--max-instances 2048]
-                                     [--explainers intrinsic,occlusion,random,attention,integrated_gradients,grad_x_input,mask_optimization]
-                                     [--ig-steps 16] [--mo-steps 100] [--curves 0,0.1,0.2,0.3,0.5,0.7,1]
+                                     [--explainers intrinsic,occlusion,random,attention,integrated_gradients,grad_x_input,mask_optimization,shapley]
+                                     [--ig-steps 16] [--mo-steps 100] [--sv-permutations 16] [--curves 0,0.1,0.2,0.3,0.5,0.7,1]
                                      [--out profiles/<name>.json]
---explainers: a comma-separated list from explain.EXPLAINERS_ALL + explain.EXPLAINERS_GRADIENT + explain.EXPLAINERS_LEARNED
-(default: explain.EXPLAINERS); --ig-steps: the points of integrated_gradients' path; --mo-steps: the Adam steps
-of mask_optimization; --curves: the fractions of every explainer's fidelity curves (without it no
+--explainers: a comma-separated list from explain.EXPLAINERS_ALL + explain.EXPLAINERS_GRADIENT + explain.EXPLAINERS_LEARNED +
+explain.EXPLAINERS_SAMPLED (default: explain.EXPLAINERS); --ig-steps: the points of integrated_gradients' path (DESIGN.md 36);
+--mo-steps: the Adam steps of mask_optimization; --sv-permutations: the antithetic permutations of shapley_values
+(DESIGN.md 39); --curves: the fractions of every explainer's fidelity curves (without it no
 curve is computed)."""
 import dataclasses
 import json
@@ -30,6 +31,7 @@ MAX_INSTANCES = int(opt["--max-instances"]) if "--max-instances" in opt else Non
 EXPLAINERS = tuple(n for n in opt["--explainers"].split(",") if n) if "--explainers" in opt else explain.EXPLAINERS
 IG_STEPS = int(opt.get("--ig-steps", 16))
 MO_STEPS = int(opt.get("--mo-steps", 100))
+SV_PERMUTATIONS = int(opt.get("--sv-permutations", 16))
 CURVES = tuple(float(f) for f in opt["--curves"].split(",") if f) if "--curves" in opt else None
 V, A = 2578, 1842
 
@@ -55,7 +57,7 @@ with torch.no_grad():
         batches.append(explain.EvalBatch(d, label.to(dev), qtok.to(dev), (torch.arange(GRAPHS) % 4 == 0).int().to(dev), names.to(dev),
                                          gold=gold.to(dev)))
 report = explain.compare(model, batches, tables, explainers=EXPLAINERS, k=K, max_instances=MAX_INSTANCES, ig_steps=IG_STEPS,
-                         mo_steps=MO_STEPS, curves=CURVES)
+                         mo_steps=MO_STEPS, sv_permutations=SV_PERMUTATIONS, curves=CURVES)
 out = {"device": torch.cuda.get_device_name(0), "graphs_per_batch": GRAPHS, "batches": BATCHES, "k": K, "explainers": {}}
 for name, r in report.items():
     g = r.grounding.sets["any"]["all"]
