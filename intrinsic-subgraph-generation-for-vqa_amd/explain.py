@@ -17,6 +17,12 @@ node mask, and `compare` reports the model's own mask, the occlusion mask and a 
 `attention_rollout` is the one-forward baseline, `integrated_gradients` (with gradient x input as its one-point case) the gradient
 one: the points of a straight path as one batch of instances, their gradient rows reduced to attributions on the device.
 `mask_optimization` is the learned one (GNNExplainer): a soft node mask optimised by Adam, an iteration's arithmetic in one launch.
+`shapley_values` is the sampled one: permutation sampling, the prefixes of all permutations as one batch of instances.
+`fidelity_curves` scores ANY node ranking along its whole length -- the top-ranked nodes kept alone or removed, level by level --
+and `compare(curves=...)` does so for every explainer.
+
+The frame they share: an explainer starts from `_whole_batch` (the model's answer on the whole batch) or, in row
+space, from `_encoded_rows`; its result owes `scores()` and `mask(k)` (`_Ranked`); it joins `compare` by one entry of `_COMPARE`.
 """
 from __future__ import annotations
 
@@ -57,10 +63,8 @@ class Faithfulness(NamedTuple):
 
 def fidelity_scores(logits: Tensor, logits_keep: Tensor, logits_removed: Tensor, emptied: Tensor) -> Fidelity:
     """The arithmetic of faithfulness() on three [B, classes] logit tensors (any device)."""
-    prob = torch.softmax(logits.float(), dim=1)
-    pred = prob.argmax(dim=1)
+    pred, p = _predicted(logits)
     pick = pred.unsqueeze(1)
-    p = prob.gather(1, pick).squeeze(1)
     p_keep = torch.softmax(logits_keep.float(), dim=1).gather(1, pick).squeeze(1)
     p_removed = torch.softmax(logits_removed.float(), dim=1).gather(1, pick).squeeze(1)
     emptied = emptied.to(device=p.device, dtype=torch.bool)
@@ -121,19 +125,65 @@ def _input_plan(inputs, B: int) -> "ops.GraphPlan":
                                max_edges=inputs.max_edges or None, graph_sizes=inputs.graph_sizes)
 
 
+def _predicted(logits: Tensor, want_p: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """(pred int64 [B]: the predicted class, p fp32 [B]: its softmax probability -- None unless wanted) of [B, classes] logits."""
+    prob = torch.softmax(logits.float(), dim=1)
+    pred = prob.argmax(dim=1)
+    return pred, (prob.gather(1, pred.unsqueeze(1)).squeeze(1) if want_p else None)
+
+
+class _WholeBatch(NamedTuple):
+    """What an explainer starts from: the model's answer on the whole batch (_whole_batch)."""
+    full: bool                     # ISubGVQA (else an AnswerModel)
+    B: int
+    forward: object                # _forwarder's
+    plan: "ops.GraphPlan"
+    sg: object                     # inputs.scene_graphs() for the full model, else None
+    logits: Tensor                 # [B, classes]
+    mask: Optional[Tensor]         # the forward's node mask; None when the caller gave the logits
+
+    def predicted(self) -> Tuple[Tensor, Tensor]:
+        """(pred, p): device work of its own, so only the callers that need them ask."""
+        return _predicted(self.logits)
+
+
+def _whole_batch(model, inputs, noises, seed, logits: Optional[Tensor] = None, plan: Optional["ops.GraphPlan"] = None,
+                 trace=None) -> _WholeBatch:
+    """The plan is built only when not given, the batch is forwarded (under torch.no_grad()) only when the logits are not given."""
+    full, B, forward = _forwarder(model, inputs, noises, seed)
+    with torch.no_grad():
+        if plan is None:
+            plan = _input_plan(inputs, B)
+        sg, mask = inputs.scene_graphs() if full else None, None
+        if logits is None:
+            logits, mask = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan, trace=trace)
+    return _WholeBatch(full, B, forward, plan, sg, logits, mask)
+
+
+def _refuse_training(model, who: str, what_changes: str) -> None:
+    if model.training:
+        raise ValueError(f"{who} the model in eval(): in train() dropout and the training samplers would change {what_changes} -- "
+                         f"call model.eval()")
+
+
+def _refuse_max_instances(max_instances: Optional[int]) -> None:
+    if max_instances is not None and int(max_instances) < 1:
+        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+
+
+def _noise_rows(noises: Optional[Dict[int, Tensor]], B: int, rows: Tensor) -> Optional[Dict[int, Tensor]]:
+    """The noises' rows handed to a batch of instances by their graphs (rows: int64 [Q], the graph of every instance)."""
+    return None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
+
+
 def faithfulness_of_mask(model, inputs, mask: Tensor, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
                          threshold: float = 0.0, logits: Optional[Tensor] = None, plan: Optional["ops.GraphPlan"] = None) -> Faithfulness:
     """faithfulness() for ANY node mask (fp32 [N] or [N, 1]; kept where > threshold): the keep-cut and the removal-cut of the
     mask, one forward on each, scored against the model's answer on the whole batch -- `logits` when the caller has them (with
     the `plan` of that forward), else one forward more.  This is how an explainer other than the model's own sampler (occlusion,
     a random baseline) is measured with the intrinsic mask's yardstick."""
-    full, B, forward = _forwarder(model, inputs, noises, seed)
+    full, B, forward, plan, sg, logits, _ = _whole_batch(model, inputs, noises, seed, logits, plan)
     with torch.no_grad():
-        if plan is None:
-            plan = _input_plan(inputs, B)
-        sg = inputs.scene_graphs() if full else None
-        if logits is None:
-            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan)[0]
         flat = mask.reshape(-1)
         keep = flat > threshold
         has_nodes = (plan.ptr[1:] > plan.ptr[:-1])
@@ -162,12 +212,9 @@ def faithfulness(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, s
     an AnswerModel, a synthetic.FullWorkload (or any object with its fields and scene_graphs()) for ISubGVQA.  A graph that a cut
     would leave without nodes goes through that forward whole (the flags are adjusted before the cut): the model never sees an
     empty graph it was not given.  (The forward, then faithfulness_of_mask on its mask.)"""
-    full, B, forward = _forwarder(model, inputs, noises, seed)
-    with torch.no_grad():
-        plan = _input_plan(inputs, B)
-        logits, mask = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
-                               plan)
-    return faithfulness_of_mask(model, inputs, mask, noises=noises, seed=seed, threshold=threshold, logits=logits, plan=plan)
+    whole = _whole_batch(model, inputs, noises, seed)
+    return faithfulness_of_mask(model, inputs, whole.mask, noises=noises, seed=seed, threshold=threshold, logits=whole.logits,
+                                plan=whole.plan)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -211,28 +258,47 @@ def instance_inputs(inputs, inst: "ops.GraphInstances", full: bool):
     return x, inst.edge_index, ea, inst.batch, sg
 
 
-def _instance_probabilities(forward, inputs, full: bool, B: int, plan: "ops.GraphPlan", index: Tensor, keep: Tensor, pred: Tensor,
-                            p: Tensor, noises, max_instances: Optional[int]):
+def _instance_probabilities(whole: _WholeBatch, inputs, index: Tensor, keep: Tensor, pred: Tensor, p: Tensor, noises,
+                            max_instances: Optional[int]):
     """(fp32 [Q]: the class pred[index[q]]'s probability on instance q, the instance batches in order) of the Q induced-subgraph
     instances that rows of keep bits name (ops.induced_instances), cut at the model's input (instance_inputs), the question rows
     gathered through index, the noises' rows handed to an instance by its graph, forwarded in chunks of at most max_instances
-    instances (None: all at once).  The loop that occlusion() and fidelity_curves() share; the caller holds torch.no_grad()."""
+    instances (None: all at once).  The loop that occlusion(), fidelity_curves() and shapley_values() share; the caller holds
+    torch.no_grad()."""
     Q = index.numel()
     step = Q if max_instances is None else int(max_instances)
     chunks, parts = [], []
     for lo in range(0, Q, max(step, 1)):
         rows = index[lo:lo + step].long()
-        inst = ops.induced_instances(plan, inputs.edge_index, index[lo:lo + step].contiguous(), keep[lo:lo + step].contiguous())
-        nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
-        out = forward(*instance_inputs(inputs, inst, full), inst.plan(), rows, nz)[0]
+        inst = ops.induced_instances(whole.plan, inputs.edge_index, index[lo:lo + step].contiguous(), keep[lo:lo + step].contiguous())
+        out = whole.forward(*instance_inputs(inputs, inst, whole.full), inst.plan(), rows, _noise_rows(noises, whole.B, rows))[0]
         parts.append(torch.softmax(out.float(), dim=1).gather(1, pred.index_select(0, rows).unsqueeze(1)).squeeze(1))
         chunks.append(inst)
     return (torch.cat(parts) if parts else p.new_zeros(0)), chunks
 
 
+class _Ranked:
+    """What a result class owes compare() and fidelity_curves(): scores() and mask(k), over the field that `ranked` names (with
+    a `plan` beside it).  Methods and one class attribute, no dataclass field."""
+    ranked = "attribution"
+
+    def scores(self) -> Tensor:
+        """fp32 [N]: what mask(k) ranks, before the shift -- the scores of a fidelity curve (fidelity_curves()).  The two rules
+        differ at ties: mask(k) keeps its threshold rule, under which ties at the k-th value keep MORE than k nodes; a curve's
+        rank prefixes (ops.curve_keep_bits) keep exactly k, ties going to the lower node."""
+        return getattr(self, self.ranked).float().reshape(-1)
+
+    def mask(self, k) -> Tensor:
+        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k top-ranked nodes of every graph -- ops.topk_threshold on
+        shifted_attributions (the samplers' zero pads compete and lose).  A graph with fewer than k nodes keeps them all; ties
+        at the k-th value are all kept, as the samplers' threshold keeps them."""
+        scores = shifted_attributions(getattr(self, self.ranked), self.plan.batch, self.plan.B).view(-1, 1).contiguous()
+        return ops.topk_threshold(scores, k, plan=self.plan)
+
+
 @dataclass
-class Occlusion:
-    """Leave-one-out attributions of one batch (occlusion())."""
+class Occlusion(_Ranked):
+    """Leave-one-out attributions of one batch (occlusion()): mask(k) keeps the nodes whose removal costs the answer most."""
     pred: Tensor                   # int64 [B]: the class predicted on the whole graph
     p: Tensor                      # fp32 [B]: its softmax probability on the whole graph
     attribution: Tensor            # fp32 [N]: p[g] - (that class's probability with node n removed); 0 on the nodes of `single` graphs
@@ -243,19 +309,6 @@ class Occlusion:
     logits: Tensor                 # [B, classes] of the whole batch
     plan: "ops.GraphPlan"
     chunks: List["ops.InducedInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
-
-    def scores(self) -> Tensor:
-        """fp32 [N]: what mask(k) ranks, before the shift -- the scores of a fidelity curve (fidelity_curves()).  mask(k) keeps
-        its threshold rule, under which ties at the k-th value keep MORE than k nodes; a curve's rank prefixes
-        (ops.curve_keep_bits) keep exactly k, ties going to the lower node."""
-        return self.attribution.float().reshape(-1)
-
-    def mask(self, k) -> Tensor:
-        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph whose removal costs the answer most --
-        ops.topk_threshold on shifted_attributions (the samplers' zero pads compete and lose).  A graph with fewer than k nodes
-        keeps them all; ties at the k-th value are all kept, as the samplers' threshold keeps them."""
-        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
-        return ops.topk_threshold(scores, k, plan=self.plan)
 
 
 def occlusion(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
@@ -271,22 +324,17 @@ def occlusion(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed
     (gumbel, simple; `noises` rows are handed to an instance by its graph, where the columns behind the removed node name the next
     node) the attribution carries sampling noise: the difference of two draws, not of two expectations.  The eval solve of the
     imle / aimle samplers is noise-free."""
-    full, B, forward = _forwarder(model, inputs, noises, seed)
-    if max_instances is not None and int(max_instances) < 1:
-        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    _refuse_max_instances(max_instances)
+    whole = _whole_batch(model, inputs, noises, seed)
+    plan = whole.plan
     with torch.no_grad():
-        plan = _input_plan(inputs, B)
-        sg = inputs.scene_graphs() if full else None
-        logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, sg, plan)[0]
-        prob = torch.softmax(logits.float(), dim=1)
-        pred = prob.argmax(dim=1)
-        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
+        pred, p = whole.predicted()
         index, keep, inst_node = ops.keep_bits_leave_one_out(plan)
-        p_without, chunks = _instance_probabilities(forward, inputs, full, B, plan, index, keep, pred, p, noises, max_instances)
-        attribution = torch.zeros(plan.N, dtype=torch.float32, device=logits.device)
+        p_without, chunks = _instance_probabilities(whole, inputs, index, keep, pred, p, noises, max_instances)
+        attribution = torch.zeros(plan.N, dtype=torch.float32, device=p.device)
         attribution[inst_node] = p.index_select(0, index.long()) - p_without
         single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
-    return Occlusion(pred, p, attribution, single, index, inst_node, p_without, logits, plan, chunks)
+    return Occlusion(pred, p, attribution, single, index, inst_node, p_without, whole.logits, plan, chunks)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -303,24 +351,13 @@ class AttentionTrace:
 
 
 @dataclass
-class Rollout:
-    """Attention-rollout attributions of one batch (attention_rollout())."""
+class Rollout(_Ranked):
+    """Attention-rollout attributions of one batch (attention_rollout()): mask(k) keeps the most relevant nodes."""
     attribution: Tensor            # fp32 [N]: the relevance of every node (include/ext/isg_rollout.h)
     flow: Optional[Tensor]         # fp32 [L, E]: what every edge carried at every layer; None unless asked for
     trace: AttentionTrace          # the forward's attention weights, layer masks, mask and gate
     logits: Tensor                 # [B, classes] of the batch
     plan: "ops.GraphPlan"
-
-    def scores(self) -> Tensor:
-        """fp32 [N]: what mask(k) ranks, before the shift (Occlusion.scores on the difference between the two rules)."""
-        return self.attribution.float().reshape(-1)
-
-    def mask(self, k) -> Tensor:
-        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k most relevant nodes of every graph -- ops.topk_threshold on
-        shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the k-th value are all
-        kept."""
-        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
-        return ops.topk_threshold(scores, k, plan=self.plan)
 
 
 def attention_rollout(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
@@ -330,18 +367,15 @@ def attention_rollout(model, inputs, *, noises: Optional[Dict[int, Tensor]] = No
     trace, under torch.no_grad(), and one launch (ops.attention_rollout); `inputs` as for faithfulness().
     The walk starts from gate * mask (a masked node's pooled term is exactly zero, att_pooling.py), or from the gate alone when
     the forward has no mask.  use_masks=False hands the kernel no layer masks: the attention weights alone decide."""
-    full, B, forward = _forwarder(model, inputs, noises, seed)
     trace = AttentionTrace()
+    whole = _whole_batch(model, inputs, noises, seed, trace=trace)
     with torch.no_grad():
-        plan = _input_plan(inputs, B)
-        logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None, plan,
-                         trace=trace)[0]
         start = trace.gate.float().reshape(-1)
         if trace.mask is not None:
             start = start * trace.mask.float().reshape(-1)
-        relevance, flow = ops.attention_rollout(plan, trace.alphas, start.contiguous(), trace.masks if use_masks else None,
+        relevance, flow = ops.attention_rollout(whole.plan, trace.alphas, start.contiguous(), trace.masks if use_masks else None,
                                                 residual=residual, want_flow=want_flow)
-    return Rollout(relevance, flow, trace, logits, plan)
+    return Rollout(relevance, flow, trace, whole.logits, whole.plan)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -382,8 +416,9 @@ def quadrature(steps: int, rule: str = "gauss_legendre") -> Tuple[Tensor, Tensor
 
 
 @dataclass
-class PathAttributions:
-    """Path (integrated-gradients) attributions of one batch (path_attributions(), integrated_gradients())."""
+class PathAttributions(_Ranked):
+    """Path (integrated-gradients) attributions of one batch (path_attributions(), integrated_gradients()): mask(k) keeps the nodes
+    with the largest attribution."""
     attribution: Tensor                    # fp32 [N]: sum over the channels of (x - baseline) * the path's weighted gradient
     edge_attribution: Optional[Tensor]     # fp32 [E], when the edge rows were on the path
     avg_grad: Optional[Tuple[Tensor, Optional[Tensor]]]    # (fp32 [N, Cx], fp32 [E, Ce] or None): the weighted gradient rows, when asked for
@@ -396,17 +431,6 @@ class PathAttributions:
     chunks: List["ops.GraphInstances"] = field(default_factory=list)      # the instance batches that were forwarded, in order
     pred: Optional[Tensor] = None          # int64 [B]: the class that was explained (integrated_gradients)
     logits: Optional[Tensor] = None        # [B, classes] of the whole batch (integrated_gradients)
-
-    def scores(self) -> Tensor:
-        """fp32 [N]: what mask(k) ranks, before the shift (Occlusion.scores on the difference between the two rules)."""
-        return self.attribution.float().reshape(-1)
-
-    def mask(self, k) -> Tensor:
-        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest attribution --
-        ops.topk_threshold on shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the
-        k-th value are all kept."""
-        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
-        return ops.topk_threshold(scores, k, plan=self.plan)
 
 
 def _step_instances(plan: "ops.GraphPlan", edge_index: Tensor, steps: int) -> "ops.GraphInstances":
@@ -434,8 +458,7 @@ def path_attributions(score, x: Tensor, e: Tensor, plan: "ops.GraphPlan", edge_i
     S, B = int(steps), plan.B
     if plan.batch is None:
         raise ValueError("path_attributions needs a GraphPlan built from the batch vector")
-    if max_instances is not None and int(max_instances) < 1:
-        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    _refuse_max_instances(max_instances)
     per = S if max_instances is None else max(1, min(S, int(max_instances) // max(B, 1)))
     with torch.no_grad():
         x, e = x.detach(), e.detach()
@@ -475,6 +498,35 @@ def _graph_mean_rows(rows: Tensor, graph: Tensor, B: int) -> Tensor:
     return (sums / count.clamp_min(1.0).unsqueeze(1)).index_select(0, graph).contiguous()
 
 
+def _row_answer(model, inputs, full: bool, seed):
+    """answer(x, e, edge_index, batch, instr, glf, plan, noises) -> [B', classes]: the model on rows the MGAT reads, for the row-space
+    explainers -- ISubGVQA.answer_graphs behind the encoder, an AnswerModel as it is."""
+    def answer(x, e, edge_index, batch, instr, glf, plan, noises):
+        if full:
+            return model.answer_graphs(x, edge_index, e, batch, instr, glf, plan, True, noises, seed)[0]
+        return model(synthetic.Workload(x, edge_index, e, batch, instr, glf, glf.size(0), inputs.max_nodes, inputs.max_edges, None),
+                     noises=noises, seed=seed, plan=plan)[0]
+
+    return answer
+
+
+def _encoded_rows(model, inputs, noises, seed, full: bool, plan: "ops.GraphPlan", answer):
+    """(x, e, glf, instr, logits, pred): the fp32 rows the MGAT reads and the question side beside them -- for ISubGVQA the
+    scene-graph encoder's OUTPUT (encode_scene and language_features run once, here), for an AnswerModel the inputs' own rows --
+    with the model's answer on them, under torch.no_grad().  Where integrated_gradients and mask_optimization start."""
+    with torch.no_grad():
+        if full:
+            state = model.encode_scene(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs(), plan)
+            glf, instr = model.language_features(inputs.questions, inputs.att_mask, None, None if seed is None else seed + 7919)
+            x, e = state.x_enc.float().contiguous(), state.e_enc.float().contiguous()
+            logits = answer(x, e, inputs.edge_index, inputs.batch, instr, glf, plan, noises)
+        else:
+            glf, instr = inputs.glf, inputs.instr
+            x, e = inputs.x.float().contiguous(), inputs.edge_attr.float().contiguous()
+            logits = answer(inputs.x, inputs.edge_attr, inputs.edge_index, inputs.batch, instr, glf, plan, noises)
+        return x, e, glf, instr, logits, _predicted(logits, want_p=False)[0]
+
+
 def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None, seed: Optional[int] = None,
                          steps: int = 16, rule: str = "gauss_legendre", baseline="zero", target: str = "prob",
                          edges: bool = False, max_instances: Optional[int] = None) -> PathAttributions:
@@ -494,24 +546,14 @@ def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] =
     constant threshold mask (no gradient through the selection), gumbel is straight-through, simple differentiates its marginals.
     The mask may CHANGE along the path (the score is then not smooth in t); `delta`, the completeness gap, reports what that and
     the quadrature cost.  No parameter's .grad is touched."""
-    if model.training:
-        raise ValueError("integrated_gradients explains the model in eval(): in train() dropout and the training samplers would "
-                         "change the score from point to point -- call model.eval()")
+    _refuse_training(model, "integrated_gradients explains", "the score from point to point")
     if target not in ("prob", "logit"):
         raise ValueError(f"target: 'prob' or 'logit', got {target!r}")
-    full, B, forward = _forwarder(model, inputs, noises, seed)
+    full, B, _ = _forwarder(model, inputs, noises, seed)
+    answer = _row_answer(model, inputs, full, seed)
     with torch.no_grad():
         plan = _input_plan(inputs, B)
-        if full:
-            state = model.encode_scene(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs(), plan)
-            glf, instr = model.language_features(inputs.questions, inputs.att_mask, None, None if seed is None else seed + 7919)
-            x, e = state.x_enc.float().contiguous(), state.e_enc.float().contiguous()
-            logits = model.answer_graphs(x, inputs.edge_index, e, inputs.batch, instr, glf, plan, True, noises, seed)[0]
-        else:
-            glf, instr = inputs.glf, inputs.instr
-            x, e = inputs.x.float().contiguous(), inputs.edge_attr.float().contiguous()
-            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, None, plan)[0]
-        pred = torch.softmax(logits.float(), dim=1).argmax(dim=1)
+        x, e, glf, instr, logits, pred = _encoded_rows(model, inputs, noises, seed, full, plan, answer)
         graph_e = inputs.batch.index_select(0, inputs.edge_index[1])
         if isinstance(baseline, str):
             if baseline not in ("zero", "mean"):
@@ -525,14 +567,9 @@ def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] =
 
     def score(x_inst, e_inst, inst):
         rows = inst.index.long()
-        nz = None if noises is None else {i: n.reshape(B, -1).index_select(0, rows).contiguous() for i, n in noises.items()}
+        nz = _noise_rows(noises, B, rows)
         ins, g = instr.index_select(1, rows).contiguous(), glf.index_select(0, rows)
-        if full:
-            out = model.answer_graphs(x_inst, inst.edge_index, e_inst, inst.batch, ins, g, inst.plan(), True, nz, seed)[0]
-        else:
-            out = model(synthetic.Workload(x_inst, inst.edge_index, e_inst, inst.batch, ins, g, g.size(0), inputs.max_nodes,
-                                           inputs.max_edges, None), noises=nz, seed=seed, plan=inst.plan())[0]
-        out = out.float()
+        out = answer(x_inst, e_inst, inst.edge_index, inst.batch, ins, g, inst.plan(), nz).float()
         pick = pred.index_select(0, rows).unsqueeze(1)
         return (torch.softmax(out, dim=1) if target == "prob" else out).gather(1, pick).squeeze(1)
 
@@ -545,8 +582,9 @@ def integrated_gradients(model, inputs, *, noises: Optional[Dict[int, Tensor]] =
 # A learned baseline: mask optimisation (GNNExplainer)
 # ---------------------------------------------------------------------------------------------------------------------
 @dataclass
-class MaskOptimization:
-    """The learned soft node mask of one batch (mask_optimize(), mask_optimization()): B independent GNNExplainer runs."""
+class MaskOptimization(_Ranked):
+    """The learned soft node mask of one batch (mask_optimize(), mask_optimization()): B independent GNNExplainer runs.  mask(k)
+    keeps the nodes with the largest soft mask."""
     theta: Tensor                          # fp32 [N]: the logit of every node after the last step
     soft: Tensor                           # fp32 [N]: sigmoid(theta), the soft mask
     nll: Tensor                            # fp32 [steps + 1, B] on the device: the score at the mask BEFORE step i (row 0: the initial
@@ -557,18 +595,7 @@ class MaskOptimization:
     edge_soft: Optional[Tensor] = None
     pred: Optional[Tensor] = None          # int64 [B]: the class that was explained
     logits: Optional[Tensor] = None        # [B, classes] of the whole, unmasked batch (mask_optimization)
-
-    def scores(self) -> Tensor:
-        """fp32 [N]: what mask(k) ranks, before the shift: the soft mask (Occlusion.scores on the difference between the two
-        rules)."""
-        return self.soft.float().reshape(-1)
-
-    def mask(self, k) -> Tensor:
-        """fp32 [N, 1], k-hot per graph, in imle_mask's layout: the k nodes of every graph with the largest soft mask --
-        ops.topk_threshold on shifted_attributions, as Occlusion.mask.  A graph with fewer than k nodes keeps them all; ties at the
-        k-th value are all kept."""
-        scores = shifted_attributions(self.soft, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
-        return ops.topk_threshold(scores, k, plan=self.plan)
+    ranked = "soft"                        # (no annotation: not a field)
 
 
 def _edge_ranges(plan: "ops.GraphPlan", edge_index: Tensor) -> Tensor:
@@ -645,30 +672,16 @@ def mask_optimization(model, inputs, *, noises: Optional[Dict[int, Tensor]] = No
     encoder's OUTPUT rows, as integrated_gradients' path lies there: encode_scene and language_features run once, every iteration
     runs answer_graphs.  The model must be in eval(); the samplers behave as integrated_gradients states for eval() under
     autograd, and the model's own mask may change from one iteration to the next.  No parameter's .grad is touched."""
-    if model.training:
-        raise ValueError("mask_optimization explains the model in eval(): in train() dropout and the training samplers would "
-                         "change the score from iteration to iteration -- call model.eval()")
-    full, B, forward = _forwarder(model, inputs, noises, seed)
+    _refuse_training(model, "mask_optimization explains", "the score from iteration to iteration")
+    full, B, _ = _forwarder(model, inputs, noises, seed)
+    answer = _row_answer(model, inputs, full, seed)
     with torch.no_grad():
         plan = _input_plan(inputs, B)
-        if full:
-            state = model.encode_scene(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs(), plan)
-            glf, instr = model.language_features(inputs.questions, inputs.att_mask, None, None if seed is None else seed + 7919)
-            x, e = state.x_enc.float().contiguous(), state.e_enc.float().contiguous()
-            logits = model.answer_graphs(x, inputs.edge_index, e, inputs.batch, instr, glf, plan, True, noises, seed)[0]
-        else:
-            glf, instr = inputs.glf, inputs.instr
-            x, e = inputs.x.float().contiguous(), inputs.edge_attr.float().contiguous()
-            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, None, plan)[0]
-        pred = torch.softmax(logits.float(), dim=1).argmax(dim=1)
+        x, e, glf, instr, logits, pred = _encoded_rows(model, inputs, noises, seed, full, plan, answer)
         pick = pred.unsqueeze(1)
 
     def score(x_m, e_m):
-        if full:
-            out = model.answer_graphs(x_m, inputs.edge_index, e_m, inputs.batch, instr, glf, plan, True, noises, seed)[0]
-        else:
-            out = model(synthetic.Workload(x_m, inputs.edge_index, e_m, inputs.batch, instr, glf, B, inputs.max_nodes,
-                                           inputs.max_edges, None), noises=noises, seed=seed, plan=plan)[0]
+        out = answer(x_m, e_m, inputs.edge_index, inputs.batch, instr, glf, plan, noises)
         return -torch.log_softmax(out.float(), dim=1).gather(1, pick).squeeze(1)
 
     res = mask_optimize(score, x, e, plan, inputs.edge_index, pred_rows=pred, steps=steps, lr=lr, a_size=a_size, a_ent=a_ent,
@@ -856,11 +869,12 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
     GroundingReport of ops.grounding over the same masks and predictions (two launches more per batch), with by_type when types
     is given.  Its totals lie behind the co-occurrence totals in the SAME int64 buffer: still one device-to-host copy."""
     full = not isinstance(model, synthetic.AnswerModel)
-    totals = flat = ground = None
     G = 0 if types is None else int(types.num_groups)
     if types is not None and not 1 <= G <= ops.EVAL_GROUPS_MAX:
         raise ValueError(f"evaluate: {G} groups (1 to {ops.EVAL_GROUPS_MAX})")
-    both = None
+    n_coo = (1 + G) * ops.COO_TOTALS
+    words = n_coo + ((1 + G) * ops.GROUND_TOTALS if grounding else 0)
+    flat = both = ground = None
     with torch.no_grad():
         for b in batches:
             inp = b.inputs
@@ -873,8 +887,7 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
                 out, inst = model.ask(state, inp.questions, inp.att_mask, b.graph_index)
                 plan, names = inst.plan(), inst.gather_nodes(names).contiguous()
             else:
-                plan = ops.GraphPlan.build(inp.batch, inp.edge_index, num_graphs=B, max_nodes=inp.max_nodes or None,
-                                           max_edges=inp.max_edges or None, graph_sizes=inp.graph_sizes)
+                plan = _input_plan(inp, B)
                 if full:
                     out = model(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.questions, inp.att_mask, return_masks=True,
                                 scene_graphs=inp.scene_graphs(), plan=plan)
@@ -882,21 +895,17 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
                     out = model(inp, plan=plan)
             logits, mask = out[0], out[1]
             mask_text = out[4] if full and len(out) > 4 else None
-            if totals is None:
-                if grounding:                       # one buffer, one copy: [1 + G, COO_TOTALS] then [1 + G, GROUND_TOTALS]
-                    flat = torch.zeros((1 + G) * (ops.COO_TOTALS + ops.GROUND_TOTALS), dtype=torch.int64, device=logits.device)
-                    both = flat[:(1 + G) * ops.COO_TOTALS].view(1 + G, ops.COO_TOTALS)
-                    ground = flat[(1 + G) * ops.COO_TOTALS:].view(1 + G, ops.GROUND_TOTALS)
-                else:
-                    both = torch.zeros(1 + G, ops.COO_TOTALS, dtype=torch.int64, device=logits.device)
-                totals = both[0]
+            if flat is None:                        # one buffer, one copy: [1 + G, COO_TOTALS], with grounding then [1 + G, GROUND_TOTALS]
+                flat = torch.zeros(words, dtype=torch.int64, device=logits.device)
+                both = flat[:n_coo].view(1 + G, ops.COO_TOTALS)
+                ground = flat[n_coo:].view(1 + G, ops.GROUND_TOTALS) if grounding else None
             ttok = tkeep = None
             if mask_text is not None:
                 ttok = tables.text_tokens(inp.questions)
                 tkeep = mask_text.reshape(B, -1).float().contiguous()
             pred = logits.argmax(dim=1)
             coo = ops.token_coo(names, mask, plan, pred, b.label,
-                                tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=totals)
+                                tables.on("ans_sg", logits.device), b.qtok, b.qflags, ttok, tkeep, threshold=threshold, totals=both[0])
             groups = None
             if types is not None:
                 groups = getattr(b, "groups", None)
@@ -910,30 +919,22 @@ def evaluate(model, batches: Iterable[EvalBatch], tables: TokenTables, threshold
                     raise ValueError("evaluate(grounding=True): every EvalBatch carries gold (ObjectAnnotations.encode)")
                 ops.grounding(mask, plan, gold.to(logits.device, non_blocking=True), pred, b.label, groups, G, threshold=threshold,
                               totals=ground)
-    if both is None:
-        flat = torch.zeros((1 + G) * (ops.COO_TOTALS + (ops.GROUND_TOTALS if grounding else 0)), dtype=torch.int64)
-        both = flat[:(1 + G) * ops.COO_TOTALS].view(1 + G, ops.COO_TOTALS)
-    if types is None and not grounding:
-        return CooReport.from_totals(both[0])
-    if not grounding:
-        rows = both.tolist()                                 # overall and every group: the evaluation's one device-to-host copy
-        by_type = {f: {} for f in types.facets}
-        for g, (facet, name) in enumerate(types.group_names):
-            by_type[facet][name] = CooReport.from_totals(rows[1 + g])
-        return replace(CooReport.from_totals(rows[0]), by_type=by_type)
-    host = flat.cpu()                                        # both tables, overall and every group: the one device-to-host copy
-    n_coo = (1 + G) * ops.COO_TOTALS
-    rows = host[:n_coo].view(1 + G, ops.COO_TOTALS).tolist()
-    grows = host[n_coo:].view(1 + G, ops.GROUND_TOTALS)     # rows stay tensors: from_totals turns each into ints in one call
-    report, ground_report = CooReport.from_totals(rows[0]), GroundingReport.from_totals(grows[0])
-    if types is not None:
-        by_type, ground_by_type = {f: {} for f in types.facets}, {f: {} for f in types.facets}
-        for g, (facet, name) in enumerate(types.group_names):
-            by_type[facet][name] = CooReport.from_totals(rows[1 + g])
-            ground_by_type[facet][name] = GroundingReport.from_totals(grows[1 + g])
-        report = replace(report, by_type=by_type)
-        ground_report = replace(ground_report, by_type=ground_by_type)
-    return replace(report, grounding=ground_report)
+    if flat is None:                                         # no batch: the same report from zeros on the host
+        flat = torch.zeros(words, dtype=torch.int64)
+    host = flat.cpu()                                        # every table, overall and every group: the one device-to-host copy
+    tables_h = [(CooReport, host[:n_coo].view(1 + G, ops.COO_TOTALS).tolist())]
+    if grounding:                                            # (rows stay tensors: from_totals turns each into ints in one call)
+        tables_h.append((GroundingReport, host[n_coo:].view(1 + G, ops.GROUND_TOTALS)))
+    reports = []
+    for cls, rows in tables_h:                               # row 0: overall; row 1 + g: group g
+        report = cls.from_totals(rows[0])
+        if types is not None:
+            by_type = {f: {} for f in types.facets}
+            for g, (facet, name) in enumerate(types.group_names):
+                by_type[facet][name] = cls.from_totals(rows[1 + g])
+            report = replace(report, by_type=by_type)
+        reports.append(report)
+    return replace(reports[0], grounding=reports[1]) if grounding else reports[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1013,27 +1014,17 @@ def fidelity_curves(model, inputs, scores: Tensor, *, fractions=CURVE_FRACTIONS,
     without nodes have NaN rows and are not counted.  The model must be in eval(); the call runs under torch.no_grad().  A result
     depends on the composition of its instance batch (quirks Q1 / Q3 / Q4): curves from different max_instances may differ in
     the last bits."""
-    if model.training:
-        raise ValueError("fidelity_curves scores the model in eval(): in train() dropout and the training samplers would change "
-                         "the answer from instance to instance -- call model.eval()")
-    if max_instances is not None and int(max_instances) < 1:
-        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
+    _refuse_training(model, "fidelity_curves scores", "the answer from instance to instance")
+    _refuse_max_instances(max_instances)
     fr, cn, x = _curve_levels(fractions, counts)
     weights = curve_weights(x, rule)
-    full, B, forward = _forwarder(model, inputs, noises, seed)
+    whole = _whole_batch(model, inputs, noises, seed, logits, plan)
     with torch.no_grad():
-        if plan is None:
-            plan = _input_plan(inputs, B)
-        if logits is None:
-            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
-                             plan)[0]
-        prob = torch.softmax(logits.float(), dim=1)
-        pred = prob.argmax(dim=1)
-        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
-        bits = ops.curve_keep_bits(scores.detach().float().reshape(-1).contiguous(), plan, fractions=fr, counts=cn, sides=sides)
-        p_inst, chunks = _instance_probabilities(forward, inputs, full, B, plan, bits.index, bits.keep, pred, p, noises, max_instances)
+        pred, p = whole.predicted()
+        bits = ops.curve_keep_bits(scores.detach().float().reshape(-1).contiguous(), whole.plan, fractions=fr, counts=cn, sides=sides)
+        p_inst, chunks = _instance_probabilities(whole, inputs, bits.index, bits.keep, pred, p, noises, max_instances)
         auc, totals = ops.curve_sums(p_inst, bits, weights.float().to(p.device), totals)
-        R, L, S = bits.R, bits.L, bits.S
+        B, R, L, S = whole.B, bits.R, bits.L, bits.S
         listed = bits.graphs.long()
         nan = float("nan")
         per_side = p_inst.view(R, L, S)
@@ -1072,7 +1063,7 @@ class CurveReport:
 # A sampled baseline: Shapley values by permutation sampling
 # ---------------------------------------------------------------------------------------------------------------------
 @dataclass
-class ShapleyValues:
+class ShapleyValues(_Ranked):
     """Shapley estimates of one batch by permutation sampling (shapley_values())."""
     pred: Tensor                   # int64 [B]: the class predicted on the whole graph
     p: Tensor                      # fp32 [B]: its softmax probability on the whole graph
@@ -1091,15 +1082,6 @@ class ShapleyValues:
     def T(self) -> int:
         """Samples behind every estimate: the permutations, or their antithetic pairs."""
         return self.bits.T
-
-    def scores(self) -> Tensor:
-        """fp32 [N]: what mask(k) ranks, before the shift -- the scores of a fidelity curve (fidelity_curves())."""
-        return self.attribution.float().reshape(-1)
-
-    def mask(self, k) -> Tensor:
-        """fp32 [N, 1], k-hot per graph, by the rule of Occlusion.mask: ops.topk_threshold on shifted_attributions."""
-        scores = shifted_attributions(self.attribution, self.plan.batch, self.plan.B).view(-1, 1).contiguous()
-        return ops.topk_threshold(scores, k, plan=self.plan)
 
     def stderr(self) -> Tensor:
         """float64 [N]: the standard error of every estimate, sqrt(max(m2 - T phi^2, 0) / (T (T - 1))); NaN for T = 1."""
@@ -1128,26 +1110,17 @@ def shapley_values(model, inputs, *, noises: Optional[Dict[int, Tensor]] = None,
     depend on it and on the graph's number in the batch); `seed` and `noises` are the sampler's, as in occlusion().  The model
     must be in eval(); the call runs under torch.no_grad().  A result depends on the composition of its instance batch (quirks
     Q1 / Q3 / Q4): estimates from different max_instances may differ in the last bits, the permutations never do."""
-    if model.training:
-        raise ValueError("shapley_values scores the model in eval(): in train() dropout and the training samplers would change "
-                         "the answer from instance to instance -- call model.eval()")
-    if max_instances is not None and int(max_instances) < 1:
-        raise ValueError(f"max_instances must be at least 1, got {max_instances}")
-    full, B, forward = _forwarder(model, inputs, noises, seed)
+    _refuse_training(model, "shapley_values scores", "the answer from instance to instance")
+    _refuse_max_instances(max_instances)
+    whole = _whole_batch(model, inputs, noises, seed, logits, plan)
+    plan = whole.plan
     with torch.no_grad():
-        if plan is None:
-            plan = _input_plan(inputs, B)
-        if logits is None:
-            logits = forward(inputs.x, inputs.edge_index, inputs.edge_attr, inputs.batch, inputs.scene_graphs() if full else None,
-                             plan)[0]
-        prob = torch.softmax(logits.float(), dim=1)
-        pred = prob.argmax(dim=1)
-        p = prob.gather(1, pred.unsqueeze(1)).squeeze(1)
+        pred, p = whole.predicted()
         bits = ops.shapley_keep_bits(plan, permutations=permutations, antithetic=antithetic, seed=perm_seed)
-        p_inst, chunks = _instance_probabilities(forward, inputs, full, B, plan, bits.index, bits.keep, pred, p, noises, max_instances)
+        p_inst, chunks = _instance_probabilities(whole, inputs, bits.index, bits.keep, pred, p, noises, max_instances)
         phi, m2, gap, flag = ops.shapley_values(p_inst, p.contiguous(), bits, plan, v_empty=v_empty)
         single = (plan.ptr[1:] - plan.ptr[:-1]) < 2
-    return ShapleyValues(pred, p, phi, m2, gap, flag, single, bits, p_inst, logits, plan, chunks)
+    return ShapleyValues(pred, p, phi, m2, gap, flag, single, bits, p_inst, whole.logits, plan, chunks)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1195,6 +1168,44 @@ def jaccard_sums(mask: Tensor, other: Tensor, batch: Tensor, B: int, threshold: 
     return torch.stack([torch.where(some, inter / union.clamp_min(1.0), torch.zeros_like(z)).sum(), some.double().sum()])
 
 
+def fidelity_sums(f: Fidelity) -> Tensor:
+    """float64 [4] on the device: (sum of fid_plus, questions that have one, sum of fid_minus, questions that have one)."""
+    has_p, has_m = ~torch.isnan(f.fid_plus), ~torch.isnan(f.fid_minus)
+    return torch.stack([torch.where(has_p, f.fid_plus, torch.zeros_like(f.fid_plus)).double().sum(), has_p.double().sum(),
+                        torch.where(has_m, f.fid_minus, torch.zeros_like(f.fid_minus)).double().sum(), has_m.double().sum()])
+
+
+# name -> (model, inp, ctx) -> a result object (a _Ranked: compare() asks it for mask(k) and, for a curve, scores()), in the order
+# compare() names them when it refuses one.  ctx, per batch: compare()'s k, max_instances, ig_steps, mo_steps and sv_permutations,
+# seed (its seed + the batch's number), and logits, plan and intrinsic (the node mask) of the batch forward it makes once.
+# intrinsic and random have no result object: they give the pair (mask, a function that returns the scores -- random's cost a
+# launch, which only a curve pays).  A new explainer joins compare() by one entry.  Only shapley takes compare()'s batch forward;
+# the others forward the batch themselves (DESIGN.md 40: the follow-up).
+_COMPARE = {
+    "intrinsic": lambda model, inp, c: (c.intrinsic, lambda: c.intrinsic),
+    "occlusion": lambda model, inp, c: occlusion(model, inp, max_instances=c.max_instances),
+    "random": lambda model, inp, c: (random_mask(c.plan, c.k, c.seed), lambda: random_scores(c.plan, c.seed)),
+    "attention": lambda model, inp, c: attention_rollout(model, inp),
+    "integrated_gradients": lambda model, inp, c: integrated_gradients(model, inp, steps=c.ig_steps, max_instances=c.max_instances),
+    "grad_x_input": lambda model, inp, c: integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=c.max_instances),
+    "mask_optimization": lambda model, inp, c: mask_optimization(model, inp, steps=c.mo_steps, init_seed=c.seed),
+    "shapley": lambda model, inp, c: shapley_values(model, inp, permutations=c.sv_permutations, perm_seed=c.seed,
+                                                    max_instances=c.max_instances, logits=c.logits, plan=c.plan),
+}
+assert tuple(_COMPARE) == EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED + EXPLAINERS_SAMPLED      # the public name tuples
+
+
+def _compare_totals(flat: Tensor, X: int, L: int):
+    """The four views of compare()'s totals buffer (int64 [X * (COO_TOTALS + GROUND_TOTALS + COMPARE_SUMS + 2 (L + 3))], with no
+    curve words when L = 0), on the device and on the host alike: coo int64 [X, COO_TOTALS], ground int64 [X, GROUND_TOTALS], sums
+    float64 [X, COMPARE_SUMS] in int64 words, curves float64 [X, 2, L + 3] (both sides' ops.curve_sums totals) or None."""
+    a = X * ops.COO_TOTALS
+    b = a + X * ops.GROUND_TOTALS
+    c = b + X * COMPARE_SUMS
+    return (flat[:a].view(X, ops.COO_TOTALS), flat[a:b].view(X, ops.GROUND_TOTALS), flat[b:c].view(torch.float64).view(X, COMPARE_SUMS),
+            flat[c:].view(torch.float64).view(X, 2, L + 3) if L else None)
+
+
 def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers: Sequence[str] = EXPLAINERS, k: int = 5,
             threshold: float = 0.0, seed: int = 0, max_instances: Optional[int] = None, ig_steps: int = 16,
             mo_steps: int = 100, sv_permutations: int = 16, curves: Optional[Sequence[float]] = None) -> Dict[str, ExplainerReport]:
@@ -1217,63 +1228,37 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
     levels = None if curves is None else tuple(float(f) for f in curves)
     if levels is not None:
         curve_weights(levels)                                # (refuses an empty or decreasing axis before any forward)
-    cwords = 0 if levels is None else 2 * (len(levels) + 3)  # float64 per explainer: both sides' totals (ops.curve_sums)
-    known = EXPLAINERS_ALL + EXPLAINERS_GRADIENT + EXPLAINERS_LEARNED + EXPLAINERS_SAMPLED
+    L = 0 if levels is None else len(levels)
+    known = tuple(_COMPARE)
     unknown = [x for x in names_x if x not in known]
     if unknown or not names_x:
         raise ValueError(f"compare: explainers from {known}, got {names_x}")
     X = len(names_x)
-    full = not isinstance(model, synthetic.AnswerModel)
-    flat = coo = ground = sums = ctot = None
-    with_gold = None
-    per = ops.COO_TOTALS + ops.GROUND_TOTALS + COMPARE_SUMS
+    words = X * (ops.COO_TOTALS + ops.GROUND_TOTALS + COMPARE_SUMS + (2 * (L + 3) if L else 0))   # int64; the sums are float64 in theirs
+    flat = with_gold = None
     with torch.no_grad():
         for number, b in enumerate(batches):
             inp = b.inputs
             if b.graph_index is not None:
                 raise ValueError("compare: one graph per question (occlusion on shared encodings would leave the removed node "
                                  "seen by the encoder)")
-            B = int(inp.questions.size(0) if full else inp.glf.size(0))
-            plan = _input_plan(inp, B)
-            _, _, forward = _forwarder(model, inp, None, None)
-            logits, intrinsic = forward(inp.x, inp.edge_index, inp.edge_attr, inp.batch, inp.scene_graphs() if full else None, plan)
+            _, B, _, plan, _, logits, intrinsic = _whole_batch(model, inp, None, None)
             gold = getattr(b, "gold", None)
             if with_gold is None:
                 with_gold = gold is not None
-                flat = torch.zeros(X * (per + cwords), dtype=torch.int64, device=logits.device)   # int64 words; the sums are float64 in theirs
-                coo = flat[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS)
-                ground = flat[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
-                sums = flat[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):X * per].view(torch.float64).view(X, COMPARE_SUMS)
-                if levels is not None:
-                    ctot = flat[X * per:].view(torch.float64).view(X, 2, len(levels) + 3)
+                flat = torch.zeros(words, dtype=torch.int64, device=logits.device)
+                coo, ground, sums, ctot = _compare_totals(flat, X, L)
             elif with_gold != (gold is not None):
                 raise ValueError("compare: every EvalBatch carries gold, or none does")
             names = inp.x[:, 0] if b.names is None else b.names
             pred = logits.argmax(dim=1)
+            ctx = argparse.Namespace(k=k, seed=seed + number, max_instances=max_instances, ig_steps=ig_steps, mo_steps=mo_steps,
+                                     sv_permutations=sv_permutations, logits=logits, plan=plan, intrinsic=intrinsic)
             for x, name in enumerate(names_x):
-                res = None
-                if name == "occlusion":
-                    res = occlusion(model, inp, max_instances=max_instances)
-                elif name == "attention":
-                    res = attention_rollout(model, inp)
-                elif name == "integrated_gradients":
-                    res = integrated_gradients(model, inp, steps=ig_steps, max_instances=max_instances)
-                elif name == "grad_x_input":
-                    res = integrated_gradients(model, inp, steps=1, rule="endpoint", max_instances=max_instances)
-                elif name == "mask_optimization":
-                    res = mask_optimization(model, inp, steps=mo_steps, init_seed=seed + number)
-                elif name == "shapley":
-                    res = shapley_values(model, inp, permutations=sv_permutations, perm_seed=seed + number, max_instances=max_instances,
-                                         logits=logits, plan=plan)
-                if res is not None:
-                    mask = res.mask(k)
-                elif name == "intrinsic":
-                    mask = intrinsic
-                else:
-                    mask = random_mask(plan, k, seed + number)
-                if levels is not None:
-                    ranked = res.scores() if res is not None else (intrinsic if name == "intrinsic" else random_scores(plan, seed + number))
-                    fidelity_curves(model, inp, ranked, fractions=levels, max_instances=max_instances, logits=logits, plan=plan,
+                res = _COMPARE[name](model, inp, ctx)
+                mask, ranked = res if isinstance(res, tuple) else (res.mask(k), res.scores)
+                if L:
+                    fidelity_curves(model, inp, ranked(), fractions=levels, max_instances=max_instances, logits=logits, plan=plan,
                                     totals=ctot[x])
                 ops.token_coo(names, mask, plan, pred, b.label, tables.on("ans_sg", logits.device), b.qtok, b.qflags, None, None,
                               threshold=threshold, totals=coo[x])
@@ -1281,24 +1266,15 @@ def compare(model, batches: Iterable[EvalBatch], tables: TokenTables, explainers
                     ops.grounding(mask, plan, gold.to(logits.device, non_blocking=True), pred, b.label, threshold=threshold,
                                   totals=ground[x])
                 f = faithfulness_of_mask(model, inp, mask, threshold=threshold, logits=logits, plan=plan).scores
-                has_p, has_m = ~torch.isnan(f.fid_plus), ~torch.isnan(f.fid_minus)
-                sums[x] += torch.cat([torch.stack([torch.where(has_p, f.fid_plus, torch.zeros_like(f.fid_plus)).double().sum(),
-                                                   has_p.double().sum(),
-                                                   torch.where(has_m, f.fid_minus, torch.zeros_like(f.fid_minus)).double().sum(),
-                                                   has_m.double().sum()]),
-                                      jaccard_sums(mask, intrinsic, inp.batch, B, threshold)])
+                sums[x] += torch.cat([fidelity_sums(f), jaccard_sums(mask, intrinsic, inp.batch, B, threshold)])
     if flat is None:
-        flat = torch.zeros(X * (per + cwords), dtype=torch.int64)
-        with_gold = False
-    host = flat.cpu()                                        # every explainer's totals: the one device-to-host copy
-    coo_h = host[:X * ops.COO_TOTALS].view(X, ops.COO_TOTALS).tolist()
-    ground_h = host[X * ops.COO_TOTALS:X * (ops.COO_TOTALS + ops.GROUND_TOTALS)].view(X, ops.GROUND_TOTALS)
-    sums_h = host[X * (ops.COO_TOTALS + ops.GROUND_TOTALS):X * per].view(torch.float64).view(X, COMPARE_SUMS).tolist()
-    curves_h = None if levels is None else host[X * per:].view(torch.float64).view(X, 2, len(levels) + 3).tolist()
+        flat, with_gold = torch.zeros(words, dtype=torch.int64), False
+    coo, ground, sums, ctot = _compare_totals(flat.cpu(), X, L)          # every explainer's totals: the one device-to-host copy
+    coo, sums = coo.tolist(), sums.tolist()
     out = {}
     for x, name in enumerate(names_x):
-        s = tuple(float(v) for v in sums_h[x])
-        out[name] = ExplainerReport(CooReport.from_totals(coo_h[x]), GroundingReport.from_totals(ground_h[x]) if with_gold else None,
+        s = tuple(float(v) for v in sums[x])
+        out[name] = ExplainerReport(CooReport.from_totals(coo[x]), GroundingReport.from_totals(ground[x]) if with_gold else None,
                                     _mean(s[0], s[1]), _mean(s[2], s[3]), _mean(s[4], s[5]), s,
-                                    None if levels is None else CurveReport.from_totals(levels, curves_h[x]))
+                                    CurveReport.from_totals(levels, ctot[x].tolist()) if L else None)
     return out
