@@ -830,8 +830,10 @@ SIMPLE_BWD_KERNEL = True
 def _simple_restatement(scores, k, plan, return_marginals):
     """The differentiable part of simple_topk written with torch ops: (out [, marginals]) = the marginals in both layouts."""
     from .sampling.methods.simple import LARGE_NUMBER, log_marginals
-    if plan is not None:
-        B, nmax, slots = plan.B, plan.nmax, plan.dense_slots()
+    if plan is not None:                               # the forward's row length: the true longest row under a max_nodes hint too
+        B, nmax, slots = plan.B, plan.true_nmax("the SIMPLE sampler"), plan.dense_slots()
+        if nmax != plan.nmax:
+            slots = slots - plan.batch * (plan.nmax - nmax)
     else:
         B, nmax, slots = scores.shape[0], scores.shape[1], None
     n = 1 << max(nmax - 1, 0).bit_length()

@@ -370,7 +370,7 @@ class TilePlan(NamedTuple):
 class _PlanCache:
     """Everything a GraphPlan builds lazily, each on first use.  One object per plan, shared by the views made of it
     (GraphPlan.with_holes): what one of them builds, all of them find."""
-    __slots__ = ("tiles", "edge_planes", "oversize_stats", "oversize", "by_src", "slots", "parent_edge_rows")
+    __slots__ = ("tiles", "edge_planes", "oversize_stats", "oversize", "by_src", "slots", "parent_edge_rows", "nmax_true")
 
     def __init__(self):
         self.tiles = {}                   # (node_cap, edge_cap) -> TilePlan
@@ -380,6 +380,7 @@ class _PlanCache:
         self.by_src = None                # (rowptr_s, eid_s, dst_s)
         self.slots = None                 # int64 [N]
         self.parent_edge_rows = None      # on the plan of a batch's oversize graphs: _from_tensor(the batch's edge_attr, their rows)
+        self.nmax_true = None             # int: the longest row of a plan built with max_nodes= (GraphPlan.true_nmax)
 
 
 def _csr_build(lib, edge_index: Tensor, N: int, E: int, rowptr: Tensor, eid: Tensor, src: Tensor, dst: Optional[Tensor]) -> None:
@@ -425,6 +426,8 @@ class GraphPlan:
     _bounds_dev: Optional[Tensor] = None          # these three: set on a plan built from hints inside a hipGraph capture (build) --
     _bounds_host: Optional[Tensor] = None         # where every replay leaves the true bounds, on the device and in pinned memory,
     _hints: Optional[Tuple[int, Optional[int]]] = None        # and the hinted (max_nodes, max_edges or None) they are held against
+    nmax_hinted: bool = False                     # build() was given max_nodes: nmax is the caller's bound, the true longest row is
+                                                  # nmax_dev (read back once, for the one sampler that needs it on the host: true_nmax)
 
     def memo(self) -> dict:
         return self._memo
@@ -647,6 +650,7 @@ class GraphPlan:
                 raise ValueError("graph_sizes: a HOST tensor [2, num_graphs] (nodes, in-edges per graph)")
             plan.sizes_host = graph_sizes.long()
         host_bounds = bounds_max = None
+        plan.nmax_hinted = max_nodes is not None
         if edge_index is not None:
             _chk(edge_index, "edge_index", torch.int64)
             if edge_index.dim() != 2 or edge_index.size(0) != 2:
@@ -684,6 +688,7 @@ class GraphPlan:
                                                   bounds[1:].data_ptr(), _stream()), "isg_graph_edge_ptr")
         if max_nodes is None or (edge_index is not None and max_edges is None):
             got = bounds.tolist()                   # one D2H sync per batch (to_dense_batch syncs per layer)
+            plan._cache.nmax_true = got[0]
             max_nodes = got[0] if max_nodes is None else max(int(max_nodes), got[0])
             max_edges = got[1] if max_edges is None else max(int(max_edges), got[1])
         elif torch.cuda.is_current_stream_capturing():
@@ -739,6 +744,24 @@ class GraphPlan:
             b = self.batch
             self._cache.slots = b * self.nmax + (torch.arange(self.N, device=b.device) - self.ptr.long()[b])
         return self._cache.slots
+
+    def true_nmax(self, of: str) -> int:
+        """The batch's longest row on the host, for `of` -- an operator whose result depends on it and not only on a bound of it
+        (the SIMPLE sampler: the row length decides its circuit and the number of competing zero pads).  nmax itself unless
+        build() was given max_nodes; then nmax_dev read back, one device-to-host copy per plan, kept in the cache.  A plan built
+        inside a stream capture keeps no such number (every replay rewrites nmax_dev), and during a capture the copy is
+        impossible: IsgError, before anything is launched.  A hint below the true length raises as check_plans() would."""
+        if not self.nmax_hinted:
+            return self.nmax
+        if self._cache.nmax_true is None:
+            if self._bounds_dev is not None or torch.cuda.is_current_stream_capturing():
+                raise _lib.IsgError(f"{of} needs the batch's true longest row on the host; this GraphPlan was built with "
+                                    f"max_nodes={self.nmax}, and nmax_dev cannot be copied back during a stream capture, nor kept for a "
+                                    "plan built inside one: build the plan without max_nodes, outside the capture")
+            self._cache.nmax_true = int(self.nmax_dev.item())
+        if self._cache.nmax_true > self.nmax:
+            raise _hint_error((self._cache.nmax_true, 0), (self.nmax, None), of)
+        return self._cache.nmax_true
 
     def require_csr(self) -> None:
         if self.rowptr is None:
@@ -2919,12 +2942,31 @@ def topk_threshold(scores: Tensor, k, plan: Optional[GraphPlan] = None, noise: O
     return (out, dense) if return_dense else out
 
 
+def _simple_n(nmax: int) -> int:
+    """Variables of the SIMPLE circuit over rows of nmax slots: nmax rounded up to a power of two (simple_scheme.py:88)."""
+    return 1 << max(nmax - 1, 0).bit_length() if nmax > 0 else 0
+
+
+def _simple_rows(scores: Tensor, plan: Optional[GraphPlan]):
+    """_rows for the SIMPLE sampler's forward and backward, (flat, ptr, B, nmax): nmax is the true longest row under a max_nodes
+    hint too (GraphPlan.true_nmax), so that a backward follows the row length of the forward it differentiates."""
+    flat, ptr, B, nmax, _ = _rows(scores, plan)
+    return flat, ptr, B, (nmax if plan is None else plan.true_nmax("the SIMPLE sampler"))
+
+
 def simple_topk(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, uniform: Optional[Tensor] = None,
                 seed: int = 0, return_marginals: bool = False):
     """SIMPLE sampler (simple_scheme.py:44-162): mask = (Gumbel top-k sample - marginals) + marginals, marginals exact
-    through the exactly-k circuit.  Ragged (plan given; plan.nmax must be the batch's true longest row): scores [N] /
-    [N,1]; dense: scores [B,Nmax].  ``uniform``: the [B, n] torch.rand draw (n = Nmax rounded up to a power of two).
-    ``k`` is an int: the circuit and its tables are built per (n, k) for the launch, a k per row is not implemented."""
+    through the exactly-k circuit.  Ragged (plan given): scores [N] / [N,1]; dense: scores [B,Nmax].  ``uniform``: the [B, n]
+    torch.rand draw (n = Nmax rounded up to a power of two).  ``k`` is an int: the circuit and its tables are built per (n, k)
+    for the launch, a k per row is not implemented.
+
+    Nmax is the batch's TRUE longest row, never a bound of it: the number of zero pads and of -1e10 pads behind a row decides
+    its marginals, so a plan built with ``max_nodes=`` (plan.nmax is then the hint) gives the un-hinted plan's bits.  The
+    length is read from plan.nmax_dev -- one device-to-host copy per hinted plan (GraphPlan.true_nmax), none on other plans;
+    during a stream capture, where that copy is impossible, IsgError is raised before any launch.  The marginals are
+    [B, true Nmax].  On a hinted plan ``uniform`` may also be [B, n(hint)], the draw of a caller who knows the hint alone: its
+    first n(true) columns are the draw, the rule Gumbel noise follows under a hint."""
     if isinstance(k, Tensor):
         raise NotImplementedError("simple_topk takes one k for the batch: the SIMPLE sampler's circuit and tables are built per "
                                   "(n, k) for the launch, so a per-graph budget (a k per row) is out of its scope")
@@ -2932,14 +2974,21 @@ def simple_topk(scores: Tensor, k: int, plan: Optional[GraphPlan] = None, unifor
         from . import autograd
         return autograd.simple_topk(scores, k, plan, uniform, seed, return_marginals)
     lib = _lib.load()
-    flat, ptr, B, nmax, _ = _rows(scores, plan)
+    flat, ptr, B, nmax = _simple_rows(scores, plan)
     out = torch.empty_like(flat)
-    n = 1 << max(nmax - 1, 0).bit_length() if nmax > 0 else 0
-    if uniform is not None and uniform.numel() != B * n:
-        raise ValueError(f"uniform must hold B*n = {B}*{n} values, got {tuple(uniform.shape)}")
+    n = _simple_n(nmax)
+    if uniform is not None:
+        n_hint = n if plan is None else _simple_n(plan.nmax)
+        if uniform.numel() == B * n:
+            uniform = uniform.reshape(B, n)
+        elif uniform.numel() == B * n_hint:
+            uniform = uniform.reshape(B, n_hint)[:, :n].contiguous()     # the kernel strides the draw by n
+        else:
+            raise ValueError(f"uniform must hold B*n = {B}*{n} values" + (f" (or {B}*{n_hint}, by the plan's max_nodes hint)"
+                                                                          if n_hint != n else "") + f", got {tuple(uniform.shape)}")
     marg = torch.empty(B, nmax, dtype=torch.float32, device=scores.device) if return_marginals else None
     _lib.check(lib.isg_simple_topk(_chk(flat, "scores", torch.float32), ptr, B, nmax,
-                                   0 if uniform is None else _chk(uniform.reshape(B, n), "uniform", torch.float32),
+                                   0 if uniform is None else _chk(uniform, "uniform", torch.float32),
                                    int(seed) & (2 ** 64 - 1), _gid_ptr(plan), int(k), out.data_ptr(),
                                    0 if marg is None else marg.data_ptr(), _stream()), "isg_simple_topk")
     out = out.view(scores.shape)
@@ -2951,11 +3000,12 @@ def simple_topk_backward(scores: Tensor, k: int, plan: Optional[GraphPlan] = Non
     """d scores of simple_topk for d out = g_out (the layout of scores) and d marginals = g_marg ([B, Nmax]); either may be None
     (= 0).  One launch of isg_simple_topk_bwd, which rebuilds the circuit's trees from the scores alone: the sample carries no
     gradient, so neither ``uniform`` nor ``seed`` is an argument.  None when the library refuses the shape (a row whose four trees
-    exceed the LDS rule of isg_simple_topk_bwd_row_bytes): the caller differentiates the torch restatement instead."""
+    exceed the LDS rule of isg_simple_topk_bwd_row_bytes): the caller differentiates the torch restatement instead.
+    Nmax is the forward's: the batch's true longest row, on a plan built with ``max_nodes=`` too (see simple_topk)."""
     from . import _lib_sampler_train
     lib = _lib_sampler_train.load()
     scores = scores.detach()
-    flat, ptr, B, nmax, _ = _rows(scores, plan)
+    flat, ptr, B, nmax = _simple_rows(scores, plan)
     go = None if g_out is None else g_out.detach().reshape(flat.shape)          # held until the launch is queued
     gm = None if g_marg is None else g_marg.detach().reshape(B, nmax)
     d = torch.empty_like(flat)

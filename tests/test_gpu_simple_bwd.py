@@ -127,6 +127,35 @@ def test_ragged_and_dense_layouts_give_the_same_bits(dev, name):
         assert torch.equal(d.cpu()[real], r.cpu()), (name, grads)
 
 
+@pytest.mark.parametrize("hint", [64, 100])
+def test_hinted_plan_gives_the_unhinted_plans_bits(dev, hint):
+    """A plan built with max_nodes= above the longest row (33): the backward follows the forward's row length, the device's true
+    longest row, so d scores are the un-hinted plan's bit for bit -- at 64 the circuit has the same n and the hint would only add
+    zero pads, at 100 it would double n.  g_marg is [B, true nmax] on both."""
+    from isubgvqa_amd import ops
+    name = "nmax=33 k=3"
+    dense, lens, k, g_out, g_marg, real = inputs(name)
+    sc, plain, _ = ragged(dev, name)
+    batch = torch.repeat_interleave(torch.arange(len(lens)), lens)
+    hinted = ops.GraphPlan.build(batch.to(dev), None, num_graphs=len(lens), max_nodes=hint)
+    assert plain.nmax == 33 and hinted.nmax == hint
+    go, gm = g_out[real].view(-1, 1).to(dev), g_marg.to(dev)
+    for a_out, a_marg in ((go, None), (None, gm), (go, gm)):
+        a = ops.simple_topk_backward(sc, k, plain, a_out, a_marg)
+        b = ops.simple_topk_backward(sc, k, hinted, a_out, a_marg)
+        assert a is not None and b is not None and float(a.abs().max()) > 0
+        assert torch.equal(a, b), f"max_nodes={hint}: max difference {float((a - b).abs().max()):.3e}"
+    leaves = []
+    for plan in (plain, hinted):                         # and through autograd, forward and backward on the same plan
+        leaf = sc.clone().requires_grad_(True)
+        out, marg = ops.simple_topk(leaf, k, plan=plan, seed=11, return_marginals=True)
+        ((out * go).sum() + (marg * gm).sum()).backward()
+        leaves.append((out.detach(), marg.detach(), leaf.grad))
+    for x, y in zip(*leaves):
+        assert torch.equal(x, y)
+    ops.check_plans()
+
+
 def test_every_row_is_its_own(dev):
     from isubgvqa_amd import ops
     dense, lens, k, g_out, g_marg, real = inputs("nmax=65")
