@@ -1,46 +1,30 @@
-"""ctypes binding of the induced-subgraph instances of libisg_hip.so (include/ext/isg_induced.h), derived from the header like
-_lib's.
+"""ctypes binding of the induced-subgraph instances of libisg_hip.so (include/ext/isg_induced.h), derived from the header like _lib's.
 
-An EXTENSION header: it lies under include/ext/, outside _lib.HEADERS, so _lib.load() / _lib.checked() neither bind nor check
-it.  load() here does both on whatever handle _lib.load() returns, the first time it sees that handle -- the product library, the
-strict twin or a variant build swapped in through `_lib._lib` / _lib.using() alike -- and `load() is _lib.load()` holds as for the
-_lib_<name> modules.  The header has an ABI version of its own (ISG_INDUCED_ABI_VERSION).
+The second extension header has an ABI version of its own (ISG_INDUCED_ABI_VERSION).  The symbols live in the same shared library.
+
+One of the headers of _lib.EXTENSIONS: parsed there once and held against every other header; outside _lib.HEADERS, so it is
+bound and version-checked by _lib.load_extension, on whatever handle _lib.load() returns, the first time that handle is seen --
+`load() is _lib.load()`, always, and a library swapped in through `_lib._lib` is the library here too.
 """
 from __future__ import annotations
 
-import os
-
 from . import _lib
 
-HEADER_PATH = os.path.join(_lib.INCLUDE, "ext", "isg_induced.h")
-# name -> (restype, argtypes) of every symbol the header declares; ISG_INDUCED_ABI_VERSION
-SIGNATURES, ABI_VERSION = _lib.read_header(HEADER_PATH)
-VERSION_SYMBOL = "isg_induced_abi_version"
-
-
-def refuse_redeclared(signatures, declared_in) -> None:
-    """A symbol of this header that a device header of the table declares as well is refused, by name."""
-    for name in signatures:
-        if name in declared_in:
-            raise _lib.IsgError(f"`{name}` is declared in include/{declared_in[name]} and in include/ext/isg_induced.h")
-
-
-refuse_redeclared(SIGNATURES, _lib._declared_in)
-
-_checked = {}       # id(handle) -> the handle (kept, so that an id is never handed to another object): bound and version-checked
+# name -> (restype, argtypes) of every symbol include/ext/isg_induced.h declares; ISG_INDUCED_ABI_VERSION
+HEADER_PATH, SIGNATURES, ABI_VERSION = _lib.extension("isg_induced.h")
+VERSION_SYMBOL = _lib.EXTENSIONS["isg_induced.h"][0]
 
 
 def load():
-    """The package's handle (_lib.load(), looked up when called) with this header's symbols bound and its version checked: once
-    per handle; raises IsgError (never falls back) when the handle lacks a symbol or answers another version."""
-    lib = _lib.load()
-    if _checked.get(id(lib)) is not lib:
-        try:
-            _lib.bind(lib, SIGNATURES)
-        except AttributeError as e:
-            raise _lib.IsgError(f"{_lib.LIB_PATH} lacks a symbol of include/ext/isg_induced.h ({e}): rebuild it (build())") from None
-        v = getattr(lib, VERSION_SYMBOL)()
-        if v != ABI_VERSION:
-            raise _lib.IsgError(f"libisg_hip.so induced-instance ABI version {v}, binding expects {ABI_VERSION}")
-        _checked[id(lib)] = lib
-    return lib
+    """The package's handle (_lib.load(), looked up when called) with this header's symbols bound and its version checked."""
+    return _lib.load_extension("isg_induced.h")
+
+
+def refuse_redeclared(signatures, declared_in) -> None:
+    """_lib.refuse_redeclared for this header.  declared_in: symbol -> the file under include/ that declares it."""
+    _lib.refuse_redeclared("isg_induced.h", signatures, declared_in)
+
+
+def declared_elsewhere() -> dict:
+    """symbol -> file under include/ of every device header and of every other extension header."""
+    return _lib.declared_elsewhere("isg_induced.h")

@@ -1,4 +1,5 @@
-"""ctypes binding of libisg_hip.so (C ABI declared in include/isg.h and the include/isg_*.h of HEADERS).
+"""ctypes binding of libisg_hip.so (C ABI declared in include/isg.h, the include/isg_*.h of HEADERS and the include/ext/isg_*.h of
+EXTENSIONS).
 
 The product path has no CPU fallback: if the shared library is missing or a tensor is not on
 an MI355X, the ops raise.  Build the library with ``python -c "import __graft_entry__ as g; g.build()"``.
@@ -133,6 +134,56 @@ HEADER_PATH, SIGNATURES, ABI_VERSION = header("isg.h")
 for _file in HEADERS:
     header(_file)
 
+# Every extension header (include/ext/) of the same library, in the order they were added: file -> (its version symbol, the
+# noun its messages use).  Outside HEADERS: bind() without signatures, checked() and load() neither bind nor check them, so a
+# variant build that lacks one extension's symbols still serves everything else; load_extension() does both, per header, on
+# whatever handle load() returns.
+EXTENSIONS = {
+    "isg_instances_train.h": ("isg_instances_train_abi_version", "instance-training "),
+    "isg_induced.h": ("isg_induced_abi_version", "induced-instance "),
+    "isg_rollout.h": ("isg_rollout_abi_version", "attention-rollout "),
+    "isg_ig.h": ("isg_ig_abi_version", "integrated-gradients "),
+    "isg_maskopt.h": ("isg_maskopt_abi_version", "mask-optimisation "),
+    "isg_curves.h": ("isg_curve_abi_version", "fidelity-curve "),
+    "isg_shapley.h": ("isg_shapley_abi_version", "Shapley-sampling "),
+}
+_extensions = {}                                    # file -> extension(file)
+_bound = {}         # (id(handle), file) -> the handle (kept, so that an id is never handed to another object): bound and checked
+
+
+def refuse_redeclared(file: str, signatures, declared_in) -> None:
+    """A symbol of the extension header `file` that another header declares as well is refused, by name.  declared_in: symbol ->
+    the file under include/ that declares it."""
+    for name in signatures:
+        if name in declared_in:
+            raise IsgError(f"`{name}` is declared in include/{declared_in[name]} and in include/ext/{file}")
+
+
+def declared_elsewhere(file: str) -> dict:
+    """symbol -> file under include/ of every device header and of every extension header read so far but `file` (all of
+    EXTENSIONS, once this module is imported)."""
+    where = dict(_declared_in)
+    for other, (_, signatures, _) in _extensions.items():
+        if other != file:
+            for name in signatures:
+                where.setdefault(name, "ext/" + other)
+    return where
+
+
+def extension(file: str):
+    """(path, {name: (restype, argtypes)}, ABI version) of one header of EXTENSIONS, read once and held against every device header
+    and every extension read before it: between them, each pair of headers is compared."""
+    if file not in _extensions:
+        path = os.path.join(INCLUDE, "ext", file)
+        signatures, abi = read_header(path)
+        refuse_redeclared(file, signatures, declared_elsewhere(file))
+        _extensions[file] = (path, signatures, abi)
+    return _extensions[file]
+
+
+for _file in EXTENSIONS:
+    extension(_file)
+
 _lib = None
 
 
@@ -147,17 +198,22 @@ def bind(lib, signatures=None):
     return lib
 
 
+def _check_one(lib, where: str, parsed, version: str, noun: str) -> None:
+    """bind() one header's symbols (where: its file under include/), then its version check."""
+    _, signatures, abi = parsed
+    try:
+        bind(lib, signatures)
+    except AttributeError as e:
+        raise IsgError(f"{LIB_PATH} lacks a symbol of include/{where} ({e}): rebuild it (build())") from None
+    v = getattr(lib, version)()
+    if v != abi:
+        raise IsgError(f"libisg_hip.so {noun}ABI version {v}, binding expects {abi}")
+
+
 def checked(lib):
     """bind() header by header, each followed by its version check: the handle, or the IsgError that names the header at fault."""
     for file, (version, noun) in HEADERS.items():
-        _, signatures, abi = header(file)
-        try:
-            bind(lib, signatures)
-        except AttributeError as e:
-            raise IsgError(f"{LIB_PATH} lacks a symbol of include/{file} ({e}): rebuild it (build())") from None
-        v = getattr(lib, version)()
-        if v != abi:
-            raise IsgError(f"libisg_hip.so {noun}ABI version {v}, binding expects {abi}")
+        _check_one(lib, file, header(file), version, noun)
     return lib
 
 
@@ -174,6 +230,18 @@ def load():
             "g.build()\"` (hipcc --offload-arch=gfx950). There is no CPU fallback for this path.")
     _lib = checked(ctypes.CDLL(LIB_PATH))
     return _lib
+
+
+def load_extension(file: str):
+    """The package's handle (load(), looked up when called) with the symbols of one header of EXTENSIONS bound and its version
+    checked: once per handle and header -- the product library, the strict twin or a variant build swapped in through `_lib` /
+    using() alike; raises IsgError (never falls back) when the handle lacks a symbol or answers another version.  Every
+    _ext_<name>.load() is this."""
+    lib = load()
+    if _bound.get((id(lib), file)) is not lib:
+        _check_one(lib, "ext/" + file, extension(file), *EXTENSIONS[file])
+        _bound[id(lib), file] = lib
+    return lib
 
 
 @contextlib.contextmanager

@@ -10,6 +10,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 import curves_restated as CR
@@ -76,8 +77,7 @@ def test_curves_header_parses_binds_and_is_exported():
         with pytest.raises(_lib.IsgError, match=f"`{name}` is declared in include/ext/{file} and in include/ext/isg_curves.h"):
             X.refuse_redeclared({name: None}, X.declared_elsewhere())
     # the build lists the header and checks the version, the counters exist, smoke() runs the known answer
-    src = inspect.getsource(ge.build)
-    assert '"ext", "isg_curves.h")' in src.split("hipcc =")[0] and "isg_curve_abi_version() == _ext_curves.ABI_VERSION" in src
+    build_checks("isg_curves.h")
     assert ops.COUNTERS["curve_keep_bits"] >= 0 and ops.COUNTERS["curve_sums"] >= 0
     assert "_smoke_curves(dev)" in inspect.getsource(ge.smoke) and "counts=(1, 2)" in inspect.getsource(ge._smoke_curves)
 

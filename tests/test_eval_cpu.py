@@ -11,6 +11,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 from eval_restated import add_coo_groups, add_group_meters, bad_ids, restate_rank, restate_top
 from token_coo_restated import HIST, TOTALS, add_totals
@@ -46,9 +47,7 @@ def test_eval_header_parses_binds_and_is_exported():
     assert _lib_eval.SIGNATURES["isg_group_meters"] == (ctypes.c_int, [ptr, ptr, ptr, i32, i32, i32, ptr, ptr, ptr, i64, ptr, i64, ptr])
     # (table, qflags, groups, F, G, totals, status, B, stream)
     assert _lib_eval.SIGNATURES["isg_token_coo_groups"] == (ctypes.c_int, [ptr, ptr, ptr, i32, i32, ptr, ptr, i64, ptr])
-    src = inspect.getsource(ge.build)
-    assert '"isg_eval.h")' in src.split("hipcc =")[0], "include/isg_eval.h is not among build()'s header dependencies"
-    assert "isg_eval_abi_version() == _lib_eval.ABI_VERSION" in src
+    build_checks("isg_eval.h")
     assert "_smoke_eval(dev)" in inspect.getsource(ge.smoke)
     assert "eval_groups" in ops.COUNTERS
     assert (ops.EVAL_TOPK_MAX, ops.EVAL_FACETS_MAX, ops.EVAL_GROUPS_MAX, ops.GROUP_SLOTS) == (8, 4, 256, 8)

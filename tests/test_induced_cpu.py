@@ -11,6 +11,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 import induced_cases as C
@@ -73,9 +74,7 @@ def test_induced_header_parses_binds_and_is_exported():
     with pytest.raises(_lib.IsgError, match="`isg_induced_size` is declared in include/isg_x.h and in include/ext/isg_induced.h"):
         X.refuse_redeclared(X.SIGNATURES, {"isg_induced_size": "isg_x.h"})
     # the build checks the version, the smoke run has its case, the counter exists, the kernels use no atomic, printf or assert
-    src = inspect.getsource(ge.build)
-    assert '"ext", "isg_induced.h")' in src.split("hipcc =")[0]
-    assert "isg_induced_abi_version() == _ext_induced.ABI_VERSION" in src
+    build_checks("isg_induced.h")
     assert "isg_induced_abi_version()" in inspect.getsource(ge._smoke_induced)
     assert ops.COUNTERS["induced_instances"] >= 0
     text = re.sub(r"//[^\n]*", "", open(os.path.join(ge.CSRC, "isg_induced.hip")).read()).lower()

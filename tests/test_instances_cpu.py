@@ -11,6 +11,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT, load_golden
 
 EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -4
@@ -59,9 +60,7 @@ def test_instances_header_parses_binds_and_is_exported():
     # (x, ldx, x_rows, node_src, n_out, x_out, ldxo, Cx, e, lde, e_rows, edge_src, m_out, e_out, ldeo, Ce, stream)
     assert _lib_instances.SIGNATURES["isg_instance_rows"] == (
         ctypes.c_int, [ptr, i32, i64, ptr, i64, ptr, i32, i32, ptr, i32, i64, ptr, i64, ptr, i32, i32, ptr])
-    src = inspect.getsource(ge.build)
-    assert '"isg_instances.h")' in src.split("hipcc =")[0], "include/isg_instances.h is not among build()'s header dependencies"
-    assert "isg_instances_abi_version() == _lib_instances.ABI_VERSION" in src
+    build_checks("isg_instances.h")
     assert "_smoke_graph_instances(dev)" in inspect.getsource(ge.smoke)
     smoke = inspect.getsource(ge._smoke_graph_instances)
     assert "isg_instances_abi_version()" in smoke and "graph_instances(" in smoke

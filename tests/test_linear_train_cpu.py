@@ -2,13 +2,13 @@
 need no GPU: the header binds and both libraries export it, the entry points refuse what their comments say before they touch a
 device, the host-only sizes stay inside their ranges, and with the switch off _Linear.backward reaches neither new operator."""
 import ctypes
-import inspect
 import os
 import re
 
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 EINVAL, EUNSUPPORTED = -1, -2
@@ -48,9 +48,7 @@ def test_linear_train_header_parses_binds_and_is_exported():
     assert sig["isg_linear_bwd_prep"] == (ctypes.c_int, [V, I32, V, I32, I32, V, I32, V, I64, I32, V])
     assert sig["isg_linear_wgrad_bf16x6_splits"] == (I64, [I64, I32, I32])
     assert sig["isg_linear_wgrad_bf16x6"] == (ctypes.c_int, [V, V, V, I64, I32, I32, I32, I32, I64, V])
-    src = inspect.getsource(ge.build)
-    assert '"isg_linear_train.h")' in src.split("hipcc =")[0], "include/isg_linear_train.h is not among build()'s header dependencies"
-    assert "isg_linear_train_abi_version() == _lib_linear_train.ABI_VERSION" in src
+    build_checks("isg_linear_train.h")
     assert os.path.exists(os.path.join(ge.CSRC, "isg_linear_bwd.hip"))
     # the strict twin is a second build of the new source, not the fast object linked twice
     assert any(m in open(os.path.join(ge.CSRC, "isg_linear_bwd.hip")).read() for m in ("ISG_WAIT(", "ISG_BARRIER("))

@@ -10,6 +10,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 import maskopt_restated as MR
@@ -74,9 +75,8 @@ def test_maskopt_header_parses_binds_and_is_exported():
         with pytest.raises(_lib.IsgError, match=f"`{name}` is declared in include/ext/{file} and in include/ext/isg_maskopt.h"):
             X.refuse_redeclared({name: None}, X.declared_elsewhere())
     # the build lists the header and checks the version, the counter exists, the kernel is plain HIP
-    src = inspect.getsource(ge.build)
-    assert '"ext", "isg_maskopt.h")' in src.split("hipcc =")[0] and '"ext", "isg_ig.h")' in src.split("hipcc =")[0]
-    assert "isg_maskopt_abi_version() == _ext_maskopt.ABI_VERSION" in src
+    build_checks("isg_maskopt.h")
+    build_checks("isg_ig.h")
     assert ops.COUNTERS["maskopt_step"] >= 0
     text = re.sub(r"//[^\n]*", "", open(os.path.join(ge.CSRC, "isg_maskopt.hip")).read()).lower()
     assert "atomic" not in text and "printf" not in text and "assert" not in text and "asm" not in text

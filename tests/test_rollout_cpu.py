@@ -11,6 +11,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 import rollout_restated as RR
@@ -146,9 +147,7 @@ def test_rollout_header_parses_binds_and_is_exported():
     with pytest.raises(_lib.IsgError, match="include/ext/isg_induced.h and in include/ext/isg_rollout.h"):
         X.refuse_redeclared({"isg_induced_size": None}, X.declared_elsewhere())
     # the build checks the version, the counter exists, the kernel uses no atomic, printf, assert or inline assembly
-    src = inspect.getsource(ge.build)
-    assert '"ext", "isg_rollout.h")' in src.split("hipcc =")[0]
-    assert "isg_rollout_abi_version() == _ext_rollout.ABI_VERSION" in src
+    build_checks("isg_rollout.h")
     assert ops.COUNTERS["attention_rollout"] >= 0
     text = re.sub(r"//[^\n]*", "", open(os.path.join(ge.CSRC, "isg_rollout.hip")).read()).lower()
     assert "atomic" not in text and "printf" not in text and "assert" not in text and "asm" not in text

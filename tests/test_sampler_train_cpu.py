@@ -4,12 +4,12 @@ agree on the version, the LDS rule is the one restated here, the entry point ref
 device, and -- the algorithm before any kernel -- the explicit two-sweep reverse pass of tests/simple_bwd_restated.py equals
 autograd through sampling/methods/simple.py::log_marginals in fp64."""
 import ctypes
-import inspect
 import os
 import re
 
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT, load_golden
 
 EINVAL, EUNSUPPORTED = -1, -2
@@ -59,9 +59,7 @@ def test_sampler_train_header_parses_binds_and_is_exported():
     assert sig["isg_simple_topk_bwd_row_bytes"] == (I64, [I32, I32])
     #                                                     scores ptr B  nmax k   g_out g_marg d_scores stream
     assert sig["isg_simple_topk_bwd"] == (ctypes.c_int, [V, V, I64, I32, I32, V, V, V, V])
-    src = inspect.getsource(ge.build)
-    assert '"isg_sampler_train.h")' in src.split("hipcc =")[0], "include/isg_sampler_train.h is not among build()'s header dependencies"
-    assert "isg_sampler_train_abi_version() == _lib_sampler_train.ABI_VERSION" in src
+    build_checks("isg_sampler_train.h")
     assert os.path.exists(os.path.join(ge.CSRC, "isg_simple_bwd.hip")) and os.path.exists(os.path.join(ge.CSRC, "isg_simple.hpp"))
     # the backward rebuilds the trees with the forward's code: both sources take it from the one shared header
     for f in ("isg_simple.hip", "isg_simple_bwd.hip"):

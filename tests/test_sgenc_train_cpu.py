@@ -7,6 +7,7 @@ import re
 import torch
 
 import sgenc_bwd_restated as R
+from binding_checks import build_checks
 from conftest import ROOT
 
 ENTRY_POINTS = {"isg_sgenc_train_abi_version", "isg_segment_rows_sum", "isg_segment_rows_chunk", "isg_segment_rows_ws_bytes",
@@ -36,7 +37,7 @@ def test_fifth_header_declares_the_entry_points_and_the_binding_follows_it():
     assert lib.isg_gather_add_bwd_parts(0) == 0 and lib.isg_gather_add_bwd_parts(1) == 1
     assert 1 <= lib.isg_gather_add_bwd_parts(1 << 20) <= 4096
     # every source that is compiled is listed for staleness with the header
-    assert "isg_sgenc_train.h" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    build_checks("isg_sgenc_train.h")
 
 
 def test_token_csr_on_cpu_tensors():

@@ -12,6 +12,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 import shapley_restated as SR
@@ -78,9 +79,7 @@ def test_shapley_header_parses_binds_and_is_exported():
         with pytest.raises(_lib.IsgError, match=f"`{name}` is declared in include/ext/{file} and in include/ext/isg_shapley.h"):
             X.refuse_redeclared({name: None}, X.declared_elsewhere())
     # the build lists the header and checks the version, the counters exist, smoke() runs the known answer
-    src = inspect.getsource(ge.build)
-    assert '"ext", "isg_shapley.h")' in src.split("hipcc =")[0] and "isg_shapley_abi_version() == _ext_shapley.ABI_VERSION" in src
-    assert "len(_ext_shapley.SIGNATURES)" in src
+    build_checks("isg_shapley.h")
     assert ops.COUNTERS["shapley_keep_bits"] >= 0 and ops.COUNTERS["shapley_values"] >= 0
     assert "_smoke_shapley(dev)" in inspect.getsource(ge.smoke) and "seed=0x100000007" in inspect.getsource(ge._smoke_shapley)
 

@@ -6,6 +6,8 @@ import itertools
 
 import torch
 
+from binding_checks import build_checks
+
 P = 4096                        # any non-null 16-byte aligned address; nothing dereferences it on the paths tested here
 EINVAL = -1
 
@@ -122,9 +124,7 @@ def test_sparse_out_header_parses_binds_and_is_exported():
     res, args = _lib_masked.SIGNATURES["isg_gatv2_layer_conv_tables"]
     assert _lib_sparse_out.SIGNATURES["isg_gatv2_layer_conv_sparse"] == (res, args[:26] + [ctypes.c_int32] + args[26:])
     import inspect
-    src = inspect.getsource(ge.build)
-    assert '"isg_sparse_out.h")' in src.split("hipcc =")[0], "include/isg_sparse_out.h is not among build()'s header dependencies"
-    assert "isg_sparse_out_abi_version() == _lib_sparse_out.ABI_VERSION" in src
+    build_checks("isg_sparse_out.h")
 
 
 def test_sparse_entry_point_refuses_bad_flags_before_any_launch():

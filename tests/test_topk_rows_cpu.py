@@ -13,6 +13,7 @@ import re
 import pytest
 import torch
 
+from binding_checks import build_checks
 from conftest import ROOT
 
 EINVAL, EUNSUPPORTED = -1, -2
@@ -58,9 +59,7 @@ def test_topk_rows_header_parses_binds_and_is_exported():
     assert sig["isg_topk_gumbel_rows"] == (I, with_rows(old["isg_topk_gumbel"][1], 8))
     assert sig["isg_topk_gumbel_rows_bwd"] == (I, with_rows(old["isg_topk_gumbel_bwd"][1], 8))
     assert old["isg_topk_threshold"][1][6] is F and old["isg_topk_gumbel"][1][6] is U64
-    src = inspect.getsource(ge.build)
-    assert '"isg_topk_rows.h")' in src.split("hipcc =")[0], "include/isg_topk_rows.h is not among build()'s header dependencies"
-    assert "isg_topk_rows_abi_version() == _lib_topk_rows.ABI_VERSION" in src
+    build_checks("isg_topk_rows.h")
     assert "ops.topk_budget(" in inspect.getsource(ge.smoke)
     # the scalar entry points and the per-row ones run the same kernels: both sources take them from the one shared header
     for f in ("isg_sampler.hip", "isg_topk_rows.hip"):
